@@ -10,8 +10,12 @@ every reported component on rank 0 (builder.rs:841-930). On N > 1 GPUs the defau
 the 10,000 replicates of a step are sharded over the ranks (strong scaling); --weak gives each rank
 its own 10,000 replicate ids per step.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line. --full adds the legs that
+take runs of their own: the CPU baseline on the host cores and the end-to-end run() from a fresh
+panel. --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 
 Rank 0 prints one JSON line (contract in the task brief); see DESIGN.md §5 for the roofline.
 """
@@ -56,6 +60,24 @@ def synthetic(rows, preds, weighted, seed=20260424):
         out["y" + g] = beta[0] + x @ beta[1:] + rng.normal(0.0, 0.5, ng)
         out["w" + g] = rng.uniform(0.5, 2.0, ng) if weighted else None
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files of one run together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64 (float32 where the dict says so).
+    An array over its share of DUMP_BUDGET_BYTES is cut to a fixed, seeded sample of its rows
+    (sorted, so replicate order is kept): the same rows in every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays)) - 4096  # the .npy header
+    for name, (a, dtype) in arrays.items():
+        a = np.ascontiguousarray(a, dtype=dtype)
+        row_bytes = max(1, a.nbytes // max(1, a.shape[0]))
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(20260424).choice(a.shape[0], share // row_bytes, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 @contextlib.contextmanager
@@ -244,8 +266,10 @@ def bench_mm(args, world, rank, local, dist):
                      "tflops": fit_rows * flops_row / (asm_ms * 1e-3) / 1e12, "max_ipm_iterations": iters},
     }
     out["cpu_baseline"] = cpu_baseline_mm(d, args.sims, args.cpu_seconds, args.cpu_threads) \
-        if world == 1 and args.cpu_seconds > 0 else None
+        if args.full and world == 1 and args.cpu_seconds > 0 else None
     rows, ok = last
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rows": (rows, np.float64), "ok": (ok, np.float32)})
     out["check"] = {"ok_replicates": int(ok.sum()), "q50_gap_mean": float(np.nanmean(rows[:, 6]))}
     print(json.dumps(out), flush=True)
 
@@ -345,7 +369,9 @@ def bench_heckman(args, world, rank, local, dist):
         "cpu_baseline": None,
         "check": {"ok_replicates": int(okh.sum()), "explained_mean": float(rows[:, 0].mean().item())},
     }
-    if world == 1 and args.cpu_seconds > 0:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rows": (rows.cpu().numpy(), np.float64), "ok": (okh, np.float32)})
+    if args.full and world == 1 and args.cpu_seconds > 0:
         out["cpu_baseline"] = cpu_baseline_heckman(frame, names, zs, args.cpu_seconds, args.cpu_threads)
     pr.close()
     print(json.dumps(out), flush=True)
@@ -580,9 +606,18 @@ def parse_args(argv):
     ap.add_argument("--preds", type=int, default=20)
     ap.add_argument("--ref", type=int, default=0, help="ReferenceCoefficients (0 = GroupA)")
     ap.add_argument("--unweighted", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="0 disables the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU baseline (cpu_baseline) and, on "
+                         "the default workload, the end-to-end run() from a fresh panel (end_to_end)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy: rows "
+                         "(the gathered component columns of every replicate, f64), ok (f32) and, on the default "
+                         "workload, stats (ob_aggregate of those rows, f64)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="--full: seconds the CPU baseline leg aims at; 0 disables it")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every core this process may use (host_cores())")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end configs[1] run from a fresh panel")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="--full: skip the end-to-end configs[1] run from a fresh panel")
     ap.add_argument("--taus", type=str, default="",
                     help="configs[3]: comma-separated RIF quantiles sharing one bootstrap (e.g. 0.1,0.5,0.9); "
                          "reports replicate-quantiles/s instead of the headline metric")
@@ -736,8 +771,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, gram_launch_ms = float(t[0]), float(t[1])
 
+    if rank == 0 and args.dump_outputs:  # the last timed step's buffers, as aggregate() read them
+        b = (args.warmup + args.steps - 1) % 2
+        dump_outputs(args.dump_outputs, {"rows": (h_rows[b].numpy(), np.float64), "ok": (h_ok[b].numpy(), np.float32),
+                                         "stats": (stats, np.float64)})
+
     e2e = None
-    if not args.no_e2e and not taus and world == 1:
+    if args.full and not args.no_e2e and not taus and world == 1:
         e2e = end_to_end(ob, ctx, d, ya, yb, total, args.ref, stat_cols, dev)
 
     if rank == 0:
@@ -803,7 +843,7 @@ def main():
             "breakdown_ms_per_step_rank0": {k_: v / args.steps for k_, v in sums.items()},
             "end_to_end": e2e,
         }
-        if world == 1 and args.cpu_seconds > 0 and not taus:
+        if args.full and world == 1 and args.cpu_seconds > 0 and not taus:
             # every usable core (the reference's Rayon pool); when the box's per-GPU share
             # (OMP_NUM_THREADS) is smaller, that share too, and the faster of the two is the value
             runs = [cpu_baseline(d, args.preds, weighted, args.ref, args.cpu_seconds, args.cpu_threads)]

@@ -110,3 +110,35 @@ def test_one_gpu_line_is_labelled_single():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.count('"weak" if world > 1 else "single"') == 2  # the --mm and --heckman lines
 
+
+def test_plain_run_leaves_the_extra_legs_to_full():
+    """The driver's `--gpus 1 --steps N --warmup W` runs neither the CPU baseline nor the end-to-end
+    run(): both sit behind --full, off by default, in every mode of the bench."""
+    b = _bench()
+    args = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 2)
+    assert b.parse_args(["--full"]).full is True
+    assert b.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    guards = src.count("if args.full and world == 1 and args.cpu_seconds > 0")
+    assert guards == 3, "the default, --mm and --heckman CPU baselines each run only under --full"
+    assert "if args.full and not args.no_e2e and not taus and world == 1:" in src
+
+
+def test_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: float32/float64 .npy files, at most 64 MB together; an array over its share is
+    cut to the same seeded, ordered sample of rows in every run."""
+    import numpy as np
+
+    b = _bench()
+    big = np.arange(3_000_000 * 4, dtype=np.float64).reshape(-1, 4)  # 96 MB
+    arrays = {"rows": (big, np.float64), "ok": (np.ones(10, dtype=np.uint8), np.float32)}
+    b.dump_outputs(str(tmp_path / "a"), arrays)
+    b.dump_outputs(str(tmp_path / "b"), arrays)
+    size = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert size <= 64 << 20
+    ra, rb = np.load(tmp_path / "a" / "rows.npy"), np.load(tmp_path / "b" / "rows.npy")
+    assert ra.dtype == np.float64 and np.array_equal(ra, rb)
+    assert np.all(np.diff(ra[:, 0]) > 0) and np.array_equal(ra[:, 1], ra[:, 0] + 1)  # whole rows, in order
+    ok = np.load(tmp_path / "a" / "ok.npy")
+    assert ok.dtype == np.float32 and ok.shape == (10,)

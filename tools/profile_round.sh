@@ -10,7 +10,7 @@ OUT=$PWD/gpurun_out
 mkdir -p "$OUT"
 REPO=$PWD
 if [ -z "${SKIP_BENCH:-}" ]; then
-  timeout -k 10 300 python bench.py > "$OUT/${TAG}_bench.json"
+  timeout -k 10 300 python bench.py --full > "$OUT/${TAG}_bench.json"
 fi
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_stats" -o run -- \

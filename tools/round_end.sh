@@ -17,7 +17,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smok
   || { tail -30 $O/${TAG}_smoke.txt; exit 1; }
 tail -1 $O/${TAG}_smoke.txt
 step bench
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err \
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err \
   || { tail -30 $O/${TAG}_bench.err; exit 1; }
 python -c "import json;d=json.loads(open('$O/${TAG}_bench.json').read().strip().splitlines()[-1]);print(round(d['value']),d['roofline']['frac'],d['breakdown_ms_per_step_rank0'])"
 step profile
