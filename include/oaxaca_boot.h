@@ -464,6 +464,71 @@ int ob_qd_results_get(const ob_qd_results* r, int32_t i, const char** key, ob_co
 int64_t ob_qd_results_n_failed(const ob_qd_results* r);
 void ob_qd_results_free(ob_qd_results* r);
 
+/* ---- DFL reweighting (dfl.rs:34-195, math/logit.rs:31-118, math/kde.rs:20-59) ----------------
+ * The distributional companion of the mean decomposition: a logit propensity score of group
+ * membership reweights group B to group A's characteristics, then Gaussian kernel densities of the
+ * outcome are evaluated on a grid for A, B and B's counterfactual. The n x K Newton passes and the
+ * density sums run on the GPU; sums are f64 with a fixed reduction order (no atomics), so a call
+ * repeated on the same input returns the same bytes. */
+
+/* logit(): Newton-Raphson from beta = 0. x: column-major n x k with the intercept column supplied
+   by the caller, ldx >= n; y: 0/1. p = sigmoid(x beta) clamped to [1e-10, 1 - 1e-10]; each step
+   solves X^T diag(p (1 - p)) X step = X^T (y - p) by Cholesky; converged when ||step||_2 < tol.
+   beta[k]; probs[n] (may be NULL) are the probabilities at the START of the last iteration when
+   converged (the reference does not recompute them with the final beta) and those at the final
+   beta after max_iter unconverged iterations. A Cholesky failure is OB_E_LINALG "Failed to solve
+   Information Matrix in Logit. Perfect separation?". k <= OB_LOGIT_MAX_K, else OB_E_UNSUPPORTED
+   before any work. */
+#define OB_LOGIT_MAX_K 64
+int ob_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int32_t k, int32_t max_iter,
+             double tol, double* beta, double* probs, int32_t* converged, int32_t* iterations);
+/* kde(): density[g] = sum_i w_i phi((grid[g] - data[i]) / bandwidth) / bandwidth with phi the
+   standard normal pdf and w the weights over their sum (weights NULL: 1 / n). A grid point whose
+   every term underflows gets exactly 0. */
+int ob_kde(ob_ctx* ctx, const double* data, const double* weights, int64_t n, const double* grid, int64_t n_grid,
+           double bandwidth, double* density);
+/* silverman_bandwidth() of math/kde.rs:44-59 (not the RIF one): 0.9 min(sd, iqr / 1.34) n^-0.2 with
+   the (n - 1) variance and quartiles sorted[(size_t)(n 0.25)], sorted[(size_t)(n 0.75)]. Host only. */
+int ob_silverman_bandwidth(const double* data, int64_t n, double* out);
+
+typedef struct {
+  const char* outcome;
+  const char* group;
+  const char* reference_group;
+  const char* const* predictors;
+  int32_t n_predictors;
+  int32_t grid_size; /* 0: the reference's 100 */
+} ob_dfl_config;
+
+typedef struct ob_dfl_results ob_dfl_results;
+/* run_dfl over a column frame. Group A is the first sorted unique value of the group column that
+   is not the reference; the logit target is 1 on A's rows and 0 on EVERY other row (a null group
+   reads as ""), while n_b counts the reference's rows only. OB_COL_STR predictors become dummies
+   "{col}_{val}" over the sorted levels without the first; numeric ones are cast to f64. No rows are
+   dropped (no clean_dataframe). logit(y, X, 100, 1e-6); B's rows get psi = p / (1 - p) * (n_b / n) /
+   (n_a / n) with p clamped to [1e-4, 0.9999]; grid[i] = min + i (max - min) / grid_size for
+   i < grid_size; Silverman bandwidths of A's and of the non-A outcomes (the counterfactual uses the
+   latter). Errors: a missing column, a non-string group column or a non-f64 outcome is OB_E_POLARS;
+   a null outcome is OB_E_GROUP "Null outcome encountered in DFL".
+   Stricter than the reference (which would carry NaNs or panic): an empty group A or an empty
+   reference group is OB_E_GROUP, a null in a predictor column is OB_E_POLARS. */
+int ob_dfl_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_dfl_config* cfg,
+               ob_dfl_results** out);
+/* DflResult (dfl.rs:10-19): *n_grid points; the arrays stay valid until ob_dfl_results_free. */
+int ob_dfl_results_get(const ob_dfl_results* r, int64_t* n_grid, const double** grid, const double** density_a,
+                       const double** density_b, const double** density_b_counterfactual);
+typedef struct {
+  int64_t n_a, n_b;          /* rows equal to A / to the reference */
+  int32_t logit_iterations;
+  int32_t logit_converged;
+  double bandwidth_a, bandwidth_b;
+  const char* group_a;       /* valid until ob_dfl_results_free */
+  double logit_ms;           /* HIP-event ms of the Newton-pass launches, summed */
+  double kde_ms;             /* HIP-event ms of the three KDE launches, summed */
+} ob_dfl_info;
+int ob_dfl_results_info(const ob_dfl_results* r, ob_dfl_info* out);
+void ob_dfl_results_free(ob_dfl_results* r);
+
 #ifdef __cplusplus
 }
 #endif

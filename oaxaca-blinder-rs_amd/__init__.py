@@ -6,10 +6,12 @@ hyphen). See DESIGN.md for the kernels and INTEGRATION.md for the Rust/C binding
 """
 from . import _native
 from ._native import OaxacaError
-from .api import (BudgetAdjustment, ComponentResult, DecompositionDetail, OaxacaBlinder, OaxacaBuilder,
+from .api import (BudgetAdjustment, ComponentResult, DecompositionDetail, DflResult, OaxacaBlinder, OaxacaBuilder,
                   OaxacaResults, PreparedRun, QuantileDecompositionBuilder, QuantileDecompositionDetail,
-                  QuantileDecompositionResults, ReferenceCoefficients, TwoFoldResults, parse_formula)
-from .engine import Panel, aggregate, boot_multi, bootstrap_stats, rif, row_layout
+                  QuantileDecompositionResults, ReferenceCoefficients, TwoFoldResults, parse_formula, run_dfl,
+                  run_dfl_from_csv)
+from .engine import (Panel, aggregate, boot_multi, bootstrap_stats, kde, logit, rif, row_layout,
+                     silverman_bandwidth)
 from .frame import Frame, read_csv
 
 __all__ = [
@@ -17,4 +19,5 @@ __all__ = [
     "ComponentResult", "BudgetAdjustment", "ReferenceCoefficients", "OaxacaError", "PreparedRun",
     "Panel", "boot_multi", "Frame", "read_csv", "aggregate", "bootstrap_stats", "rif", "row_layout", "parse_formula",
     "QuantileDecompositionBuilder", "QuantileDecompositionDetail", "QuantileDecompositionResults",
+    "DflResult", "run_dfl", "run_dfl_from_csv", "logit", "kde", "silverman_bandwidth",
 ]

@@ -45,7 +45,11 @@ EXPORTED = (
     "ob_debug_gram_exceptions", "ob_panel_set_gather_columns", "ob_debug_shard_sim", "ob_debug_mm_fail",
     "ob_debug_chunks", "ob_debug_mm_betas", "ob_set_option", "ob_get_option", "ob_tuning_build",
     "ob_debug_normal",
+    "ob_logit", "ob_kde", "ob_silverman_bandwidth", "ob_dfl_run", "ob_dfl_results_get", "ob_dfl_results_info",
+    "ob_dfl_results_free",
 )
+
+OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
 
 
 class OaxacaError(RuntimeError):
@@ -113,6 +117,17 @@ class ob_qd_config(C.Structure):
                 ("quantiles", C.POINTER(C.c_double)), ("n_quantiles", C.c_int32),
                 ("simulations", C.c_int32), ("bootstrap_reps", C.c_uint64),
                 ("has_seed", C.c_int32), ("seed", C.c_uint64)]
+
+
+class ob_dfl_config(C.Structure):
+    _fields_ = [("outcome", C.c_char_p), ("group", C.c_char_p), ("reference_group", C.c_char_p),
+                ("predictors", C.POINTER(C.c_char_p)), ("n_predictors", C.c_int32), ("grid_size", C.c_int32)]
+
+
+class ob_dfl_info(C.Structure):
+    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("logit_iterations", C.c_int32),
+                ("logit_converged", C.c_int32), ("bandwidth_a", C.c_double), ("bandwidth_b", C.c_double),
+                ("group_a", C.c_char_p), ("logit_ms", C.c_double), ("kde_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -205,6 +220,16 @@ _SIGS = {
     "ob_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]),
     "ob_tuning_build": (C.c_int, []),
     "ob_debug_normal": (C.c_int, [C.c_int, _D, C.c_int64, _D, _D]),
+    "ob_logit": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int32, C.c_int32, C.c_double, _D, _D,
+                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ob_kde": (C.c_int, [_P, _D, _D, C.c_int64, _D, C.c_int64, C.c_double, _D]),
+    "ob_silverman_bandwidth": (C.c_int, [_D, C.c_int64, _D]),
+    "ob_dfl_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_dfl_config),
+                             C.POINTER(_P)]),
+    "ob_dfl_results_get": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D),
+                                     C.POINTER(_D)]),
+    "ob_dfl_results_info": (C.c_int, [_P, C.POINTER(ob_dfl_info)]),
+    "ob_dfl_results_free": (None, [_P]),
 }
 
 _lib = None

@@ -606,3 +606,82 @@ class QuantileDecompositionBuilder:
         finally:
             lib.ob_qd_results_free(h)
             del pa, ca
+
+
+@dataclass
+class DflResult:
+    """dfl.rs:10-19 / python.rs:348-382 (``PyDflResult``): the grid and the three densities. The
+    remaining fields are what ``ob_dfl_results_info`` reports about the run."""
+    grid: np.ndarray
+    density_a: np.ndarray
+    density_b: np.ndarray
+    density_b_counterfactual: np.ndarray
+    n_a: int = 0
+    n_b: int = 0
+    group_a: str = ""
+    logit_iterations: int = 0
+    logit_converged: bool = False
+    bandwidth_a: float = float("nan")
+    bandwidth_b: float = float("nan")
+    logit_ms: float = 0.0
+    kde_ms: float = 0.0
+
+    def to_json(self) -> str:
+        """The reference's ``#[derive(Serialize)]`` fields, in its order."""
+        return json.dumps({"grid": self.grid.tolist(), "density_a": self.density_a.tolist(),
+                           "density_b": self.density_b.tolist(),
+                           "density_b_counterfactual": self.density_b_counterfactual.tolist()})
+
+    def plot(self):
+        """python.rs:362-381: the three densities on one matplotlib figure (returned)."""
+        try:
+            import matplotlib.pyplot as plt
+        except ImportError as e:
+            raise ImportError("DflResult.plot() needs matplotlib, which is not installed") from e
+        fig = plt.figure()
+        ax = fig.gca()
+        ax.plot(self.grid, self.density_a)
+        ax.plot(self.grid, self.density_b)
+        ax.plot(self.grid, self.density_b_counterfactual)
+        ax.legend(["Group A", "Group B", "Group B (Counterfactual)"])
+        ax.set_title("DFL Decomposition: Density Estimates")
+        return fig
+
+
+def run_dfl(dataframe, outcome: str, group: str, reference_group: str, predictors, device: int | None = None,
+            grid_size: int = 0) -> DflResult:
+    """dfl.rs:34-195 on the MI355X engine (``ob_dfl_run``). ``dataframe`` is what ``OaxacaBuilder``
+    takes; ``grid_size`` 0 is the reference's 100 points."""
+    lib = N.lib()
+    frame = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
+    cols, ncol, nrow = frame.as_c()
+    predictors = [str(p) for p in predictors]
+    cfg = N.ob_dfl_config()
+    cfg.outcome, cfg.group, cfg.reference_group = outcome.encode(), group.encode(), reference_group.encode()
+    pp, pa = _strs(predictors)
+    cfg.predictors, cfg.n_predictors, cfg.grid_size = pp, len(predictors), int(grid_size)
+    h = C.c_void_p()
+    N.check(lib.ob_dfl_run(N.context(device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+    try:
+        ng = C.c_int64()
+        ptrs = [C.POINTER(C.c_double)() for _ in range(4)]
+        N.check(lib.ob_dfl_results_get(h, C.byref(ng), *[C.byref(p) for p in ptrs]))
+        arrs = [np.ctypeslib.as_array(p, shape=(ng.value,)).copy() if ng.value else np.zeros(0) for p in ptrs]
+        info = N.ob_dfl_info()
+        N.check(lib.ob_dfl_results_info(h, C.byref(info)))
+        return DflResult(*arrs, n_a=int(info.n_a), n_b=int(info.n_b), group_a=info.group_a.decode(),
+                         logit_iterations=int(info.logit_iterations), logit_converged=bool(info.logit_converged),
+                         bandwidth_a=info.bandwidth_a, bandwidth_b=info.bandwidth_b, logit_ms=info.logit_ms,
+                         kde_ms=info.kde_ms)
+    finally:
+        lib.ob_dfl_results_free(h)
+        del pa
+
+
+def run_dfl_from_csv(csv_path, outcome: str, group: str, reference_group: str, predictors,
+                     device: int | None = None, grid_size: int = 0) -> DflResult:
+    """python.rs:316-346: the CSV read by the native reader (``ob_csv_read``), then ``run_dfl``."""
+    from .frame import read_csv
+
+    return run_dfl(read_csv(csv_path), outcome, group, reference_group, predictors, device=device,
+                   grid_size=grid_size)

@@ -23,30 +23,12 @@
 
 #include "ob_common.hpp"
 #include "ob_engine.hpp"
+#include "ob_frame.hpp"
 #include "ob_host.hpp"
 #include "ob_mm.hpp"
 #include "ob_spec.h"
 
 namespace ob {
-
-struct Col {
-  std::string name;
-  int kind = OB_COL_F64;
-  std::vector<double> f;       // OB_COL_F64 values (OB_COL_I64 values cast on use)
-  std::vector<int64_t> i;      // OB_COL_I64
-  std::vector<std::string> s;  // OB_COL_STR
-  std::vector<uint8_t> valid;  // 1 = non-null
-};
-
-struct Frame {
-  int64_t nrows = 0;
-  std::vector<Col> cols;
-  int find(const std::string& n) const {
-    for (size_t c = 0; c < cols.size(); ++c)
-      if (cols[c].name == n) return (int)c;
-    return -1;
-  }
-};
 
 struct Config {
   std::string outcome, group, reference_group;
@@ -63,7 +45,7 @@ struct Config {
   uint64_t seed = 0;
 };
 
-static const char* dtype_name(int kind) {
+const char* dtype_name(int kind) {
   switch (kind) {
     case OB_COL_F64: return "f64";
     case OB_COL_I64: return "i64";
@@ -71,7 +53,7 @@ static const char* dtype_name(int kind) {
   }
 }
 
-static int load_frame(const ob_column* cols, int n_cols, int64_t n_rows, Frame& out) {
+int load_frame(const ob_column* cols, int n_cols, int64_t n_rows, Frame& out) {
   if (n_cols < 0 || n_rows < 0 || (n_cols > 0 && !cols)) return fail(OB_E_INVALID, "bad frame arguments");
   out.nrows = n_rows;
   out.cols.clear();

@@ -264,3 +264,44 @@ def rif(y, quantile: float):
     out = np.empty_like(y)
     N.check(N.lib().ob_rif(_dp(y), len(y), float(quantile), _dp(out)))
     return out
+
+
+def logit(y, x, max_iter: int = 100, tol: float = 1e-6, device: int | None = None):
+    """math/logit.rs:31-118 with the Newton passes on the GPU (``ob_logit``). ``x``: (n, k) with the
+    intercept column included, ``k <= OB_LOGIT_MAX_K``. Returns (coefficients, predicted_probs,
+    converged, iterations); on convergence the probabilities are those of the last iteration's
+    start, as in the reference."""
+    xf = np.asfortranarray(x, dtype=np.float64)
+    if xf.ndim != 2:
+        raise ValueError("x must be (n, k)")
+    n, k = xf.shape
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.shape != (n,):
+        raise ValueError("y must have one entry per row of x")
+    beta, probs = np.empty(k), np.empty(n)
+    conv, iters = C.c_int32(0), C.c_int32(0)
+    N.check(N.lib().ob_logit(N.context(device), _dp(xf), max(n, 1), _dp(y), n, k, int(max_iter), float(tol),
+                             _dp(beta), _dp(probs), C.byref(conv), C.byref(iters)))
+    return beta, probs, bool(conv.value), int(iters.value)
+
+
+def kde(data, grid, bandwidth: float, weights=None, device: int | None = None):
+    """math/kde.rs:20-41 on the GPU (``ob_kde``): the weighted Gaussian kernel density of ``data``
+    at the ``grid`` points."""
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w is not None and w.shape != data.shape:
+        raise ValueError("weights must match data")
+    out = np.empty(len(grid))
+    N.check(N.lib().ob_kde(N.context(device), _dp(data), _dp(w), len(data), _dp(grid), len(grid), float(bandwidth),
+                           _dp(out)))
+    return out
+
+
+def silverman_bandwidth(data) -> float:
+    """math/kde.rs:44-59 via the native host routine (not the RIF bandwidth of math/rif.rs)."""
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    out = C.c_double()
+    N.check(N.lib().ob_silverman_bandwidth(_dp(data), len(data), C.byref(out)))
+    return out.value
