@@ -1,5 +1,6 @@
 """NumPy f64 restatement of the reference's DFL reweighting, used only as the checker of the
-engine's DFL path (tests/test_dfl_host.py, tests/test_gpu_dfl.py, tools/dfl_time.py). Paths are
+engine's DFL path (tests/test_dfl_host.py, tests/test_gpu_dfl.py, tests/test_gpu_dfl_passes.py,
+tools/dfl_time.py), and the case table and extended-precision trajectory of the latter. Paths are
 relative to oaxaca_blinder/src/ of dot-comma-hyphen/oaxaca-blinder-rs.
 
     logit                math/logit.rs:31-118
@@ -84,6 +85,155 @@ def logit(y, x, max_iter=100, tol=1e-6):
                         step_norms=norms)
     return dict(coefficients=beta, predicted_probs=_probs(x, beta), converged=False,  # logit.rs:108-117
                 iterations=max_iter, step_norms=norms)
+
+
+# ---- extended-precision Newton trajectory (tests/test_dfl_host.py, tests/test_gpu_dfl_passes.py) ----
+
+EXTENDED = bool(np.finfo(np.longdouble).eps < 1e-18)  # x87 80-bit: eps 1.08e-19
+EPS = 2.0 ** -52
+
+
+def _solve_spd(m, b, dtype):
+    """_cholesky_solve with every operation in ``dtype``."""
+    k = len(b)
+    l = np.array(m, dtype=dtype)
+    for j in range(k):
+        for c in range(j):
+            l[j:, j] -= l[j, c] * l[j:, c]
+        if not l[j, j] > 0:
+            raise LinalgError(LINALG_MESSAGE)
+        l[j, j] = np.sqrt(l[j, j])
+        l[j + 1:, j] /= l[j, j]
+    z = np.array(b, dtype=dtype)
+    for i in range(k):
+        z[i] /= l[i, i]
+        z[i + 1:] -= z[i] * l[i + 1:, i]
+    for i in range(k - 1, -1, -1):
+        z[i] = (z[i] - l[i + 1:, i] @ z[i + 1:]) / l[i, i]
+    return z
+
+
+def _fsum_tn(a, b):
+    """a^T b with every entry an exact sum of the f64 products (the 64-bit longdouble fallback)."""
+    a2, b2 = a.reshape(len(a), -1), b.reshape(len(b), -1)
+    out = np.array([[math.fsum((a2[:, i] * b2[:, j]).tolist()) for j in range(b2.shape[1])]
+                    for i in range(a2.shape[1])])
+    return out.reshape(a.shape[1:] + b.shape[1:])
+
+
+def logit_trajectory(y, x, iters, dtype=np.longdouble):
+    """The Newton recursion of ``logit`` (clamp included), exactly ``iters`` iterations from beta = 0,
+    with the sums, the probabilities and the solve carried in ``dtype``. Returns dict(betas: beta_t
+    for t = 1 .. iters, probs_start: the probabilities at each iteration's start, conds: the 2-norm
+    condition number of each iteration's information matrix, final_probs: the probabilities at the
+    last beta, step_norms). The probabilities at beta_t are probs_start[t] (final_probs for
+    t = iters). Where longdouble is 64 bits wide the sums are exact (fsum) sums of f64 products."""
+    dtype = np.dtype(dtype)
+    wide = EXTENDED or dtype != np.dtype(np.longdouble)
+    xe, ye = np.asarray(x, dtype=dtype), np.asarray(y, dtype=dtype)
+    lo, hi = dtype.type(1e-10), dtype.type(1.0 - 1e-10)  # the f64 constants of logit.rs:45
+    # a^T b with the long axis contiguous in both operands (numpy's longdouble matmul is a plain loop)
+    tn = (lambda a, b: np.ascontiguousarray(a.T) @ np.ascontiguousarray(b.T).T) if wide else _fsum_tn
+
+    def probs_at(beta):
+        eta = xe @ beta if wide else _fsum_tn(xe.T, beta)
+        with np.errstate(over="ignore"):
+            return np.clip(1 / (1 + np.exp(-eta)), lo, hi)
+
+    beta = np.zeros(xe.shape[1], dtype=dtype)
+    betas, starts, conds, norms = [], [], [], []
+    for _ in range(iters):
+        p = probs_at(beta)
+        info = tn(xe, xe * (p * (1 - p))[:, None])
+        step = _solve_spd(info, tn(xe, ye - p), dtype)
+        beta = beta + step
+        betas.append(beta)
+        starts.append(p)
+        conds.append(float(np.linalg.cond(info.astype(np.float64))))
+        norms.append(float(np.sqrt(step @ step)))
+    return dict(betas=betas, probs_start=starts, conds=conds, final_probs=probs_at(beta), step_norms=norms)
+
+
+def beta_bar(cond):
+    """The bar on max|beta_t - ref_t| / max|ref_t| of one Newton iterate: 512 cond(H_t) 2^-52. The
+    f64 restatement sits within 6.4 cond eps of the extended recursion, the device's fixed-order sum
+    of up to 4096 per-wave partials adds the same order, and about 64x is margin."""
+    return 512.0 * cond * EPS
+
+
+def panel(n, k, seed):
+    """Random normal design with an intercept, beta ~ 0.5 / sqrt(K) (test_gpu_dfl.py's _panel)."""
+    rng = np.random.default_rng(seed)
+    x = np.column_stack([np.ones(n), rng.normal(size=(n, k - 1))])
+    beta = rng.normal(size=k) * 0.5 / np.sqrt(k)
+    y = (rng.random(n) < 1.0 / (1.0 + np.exp(-(x @ beta)))).astype(np.float64)
+    return x, y
+
+
+def saturated_panel(n, k, seed):
+    """``panel`` with eight rows of column 1 at +-55 .. +-70 and that column's true coefficient 0.6,
+    y drawn from the model: from the third iteration on, those rows' probabilities sit on both
+    clamps of logit.rs:45 at the iteration's start, and |x beta| stays under 45."""
+    rng = np.random.default_rng(seed)
+    x = np.column_stack([np.ones(n), rng.normal(size=(n, k - 1))])
+    x[:8, 1] = [55.0, -55.0, 60.0, -60.0, 65.0, -65.0, 70.0, -70.0]
+    beta = rng.normal(size=k) * 0.5 / np.sqrt(k)
+    beta[1] = 0.6
+    y = (rng.random(n) < 1.0 / (1.0 + np.exp(-(x @ beta)))).astype(np.float64)
+    return x, y
+
+
+class PassCase:
+    """One row of the Newton-pass case table, with its data and references computed once."""
+
+    def __init__(self, n, k, seed, ldx=None, saturated=False, max_t=4, converges=True, note=""):
+        self.n, self.k, self.seed, self.ldx, self.saturated = n, k, seed, ldx, saturated
+        self.max_t, self.converges, self.note = max_t, converges, note
+        self.big = n > 100000
+        self.id = f"{n}x{k}"
+        self._data = self._conv = self._traj = None
+
+    def data(self):
+        if self._data is None:
+            self._data = (saturated_panel if self.saturated else panel)(self.n, self.k, self.seed)
+        return self._data
+
+    def converged(self):
+        """``logit`` at the reference's own tol = 1e-6, max_iter = 100 (None for the one-row case)."""
+        if self._conv is None and self.converges:
+            x, y = self.data()
+            self._conv = logit(y, x, 100, 1e-6)
+        return self._conv
+
+    def steps(self):
+        """The iterations t = 1 .. steps() held to the bar: min(iterations to converge, 4)."""
+        return min(self.converged()["iterations"], self.max_t) if self.converges else self.max_t
+
+    def trajectory(self):
+        """The extended trajectory over every iteration of the converged run (at least steps())."""
+        if self._traj is None:
+            x, y = self.data()
+            iters = max(self.steps(), self.converged()["iterations"] if self.converges else 0)
+            self._traj = logit_trajectory(y, x, iters)
+        return self._traj
+
+
+PASS_CASES = [
+    PassCase(64, 1, 44, note="intercept only, one exactly full sub-tile"),
+    PassCase(1, 1, 32, max_t=2, converges=False, note="one row, max_iter = 2 only"),
+    PassCase(128, 16, 33, note="one full column block, two full sub-tiles"),
+    PassCase(1000, 17, 45, note="first NCB = 2"),
+    PassCase(2000, 32, 35),
+    PassCase(3000, 48, 36),
+    PassCase(3000, 49, 37, note="first NCB = 4"),
+    PassCase(3000, 64, 38, note="K_max"),
+    PassCase(1000, 5, 39, ldx=1037, note="ldx = 1037"),
+    PassCase(4099, 9, 40, saturated=True, note="both clamps bind"),
+    PassCase(262145, 3, 41, note="spu = 2, units = 2049, the last unit has one sub-tile with one live row"),
+    PassCase(262145, 17, 42, note="spu = 2 with NCB = 2"),
+    PassCase(600001, 2, 43, note="spu = 3, units = 3126, short last unit"),
+]
+BIG_SKIP = "longdouble is 64 bits wide here: the fsum fallback is too slow for the n > 100000 cases"
 
 
 def gaussian_kernel(u):

@@ -1,6 +1,7 @@
 """DFL reweighting, host side: the NumPy restatement (tests/dfl_ref.py) against the reference's own
 inline tests (tests/golden/dfl_kat.json), and the native Silverman bandwidth against the
-restatement. No GPU here."""
+restatement; the restatement against its own extended-precision trajectory on the Newton-pass
+case table, which proves the bar of tests/test_gpu_dfl_passes.py. No GPU here."""
 import json
 import math
 import os
@@ -122,6 +123,68 @@ def test_ref_dfl_third_group_and_errors():
     with pytest.raises(R.DflError) as e:
         R.run_dfl(f, "y", "g", "zz", ["x"])
     assert e.value.kind == "group"
+
+
+# ---- the Newton-pass case table (dfl_ref.PASS_CASES) and its bar ---------------------------------
+
+def _case_params():
+    return [pytest.param(c, id=c.id, marks=[] if R.EXTENDED or not c.big else pytest.mark.skip(reason=R.BIG_SKIP))
+            for c in R.PASS_CASES]
+
+
+def test_logit_trajectory_f64_is_the_restatement():
+    """In f64 the trajectory is ``logit`` itself up to the order of its sums."""
+    x, y = R.panel(257, 4, 3)
+    tr = R.logit_trajectory(y, x, 3, np.float64)
+    for t in (1, 2, 3):
+        r = R.logit(y, x, t, 0.0)
+        assert not r["converged"] and r["iterations"] == t
+        assert np.allclose(tr["betas"][t - 1], r["coefficients"], rtol=1e-13, atol=0)
+        assert np.allclose(tr["step_norms"][:t], r["step_norms"], rtol=1e-10, atol=0)
+        p_t = tr["probs_start"][t] if t < 3 else tr["final_probs"]
+        assert np.allclose(p_t, r["predicted_probs"], rtol=0, atol=1e-14)
+    assert np.array_equal(tr["probs_start"][0], np.full(257, 0.5)) and len(tr["conds"]) == 3
+
+
+@pytest.mark.parametrize("case", _case_params())
+def test_restatement_within_an_eighth_of_the_bar(case):
+    """The f64 restatement against the extended trajectory, every case and every t: beta within 1/8
+    of 512 cond(H_t) 2^-52 and the probabilities within 1.25e-13, so the reference alone sits well
+    inside the bars tests/test_gpu_dfl_passes.py holds the device to. Worst seen: 0.012 of the bar
+    (3000 x 48) and 6.5e-16 (262145 x 17)."""
+    x, y = case.data()
+    tr = case.trajectory()
+    assert len(tr["betas"]) >= case.steps() >= 1
+    if case.converges:
+        conv, norms = case.converged(), case.converged()["step_norms"]
+        # the iteration count cannot hinge on rounding: the deciding norms are far from tol
+        assert conv["converged"] and norms[-1] <= 1e-6 / 2 and norms[-2] >= 2 * 1e-6, norms
+        assert len(tr["betas"]) == conv["iterations"]
+    worst_b = worst_p = 0.0
+    for t in range(1, case.steps() + 1):
+        r = R.logit(y, x, t, 0.0)  # tol = 0: never converges early
+        assert not r["converged"] and r["iterations"] == t
+        ref = tr["betas"][t - 1]
+        err = float(np.max(np.abs(r["coefficients"] - ref)) / np.max(np.abs(ref)))
+        bar = R.beta_bar(tr["conds"][t - 1])
+        p_t = tr["probs_start"][t] if t < len(tr["betas"]) else tr["final_probs"]
+        perr = float(np.max(np.abs(r["predicted_probs"] - p_t)))
+        worst_b, worst_p = max(worst_b, err / bar), max(worst_p, perr)
+        assert err <= bar / 8, (case.id, t, err, bar)
+        assert perr <= 1.25e-13, (case.id, t, perr)
+    print(f"{case.id}: restatement at {worst_b:.4f} of the bar, probabilities off by {worst_p:.2e}")
+    assert float(np.max(np.abs(x @ tr["betas"][-1].astype(np.float64)))) < 45.0  # the 1e-12 bar's premise
+
+
+def test_saturated_case_binds_both_clamps():
+    case = next(c for c in R.PASS_CASES if c.saturated)
+    tr = case.trajectory()
+    lo = [int(np.sum(p == np.longdouble(1e-10))) for p in tr["probs_start"]]
+    hi = [int(np.sum(p == np.longdouble(1.0 - 1e-10))) for p in tr["probs_start"]]
+    print("saturated case: rows on the lower / upper clamp per iteration", lo, hi)
+    assert any(a > 0 and b > 0 for a, b in zip(lo, hi))
+    held = range(case.steps())  # ... within the iterations held to the bar, not only later ones
+    assert any(lo[t] > 0 and hi[t] > 0 for t in held)
 
 
 def _silverman_cases():
