@@ -529,6 +529,89 @@ typedef struct {
 int ob_dfl_results_info(const ob_dfl_results* r, ob_dfl_info* out);
 void ob_dfl_results_free(ob_dfl_results* r);
 
+/* ---- Matching (matching/engine.rs, matching/distance.rs, matching/logistic.rs) -----------------
+ * Nearest-neighbour matching with replacement on raw covariates, on Mahalanobis-transformed ones or
+ * on a propensity score. The all-pairs distance pass, the control covariance, the transform and the
+ * logistic's n x K sums run on the GPU; counts are integer atomics and every f64 sum has a fixed
+ * order, so a call repeated on the same input returns the same bytes.
+ *
+ * The one deliberate difference from the reference: among exactly equidistant controls its choice
+ * depends on the shape of its k-d tree. Here the k nearest are the k smallest by the lexicographic
+ * key (squared distance, control position), whatever the launch shape. */
+
+#define OB_MATCH_MAX_DIM 64 /* covariates */
+#define OB_MATCH_MAX_K 16   /* neighbours */
+/* The min(k, n_c) nearest controls of each query. queries: column-major n_q x dim, ldq >= n_q;
+   controls: column-major n_c x dim, ldc >= n_c (entries past n_q / n_c of a column are never read).
+   The squared distance is 0 + t_0 t_0 + t_1 t_1 + ... with t_j = q_j - c_j in covariate order, each
+   product and sum rounded on its own (no FMA), which is the kdtree crate's squared_euclidean bit
+   for bit. idx[n_q][k] (control positions) and dist2[n_q][k] are ascending by (dist2, position);
+   entries past min(k, n_c) hold -1 / +inf. dim > OB_MATCH_MAX_DIM or k > OB_MATCH_MAX_K is
+   OB_E_UNSUPPORTED before any device work; a non-finite coordinate is OB_E_DIAG. */
+int ob_knn(ob_ctx* ctx, const double* queries, int64_t ldq, int64_t n_q, const double* controls, int64_t ldc,
+           int64_t n_c, int32_t dim, int32_t k, int64_t* idx, double* dist2);
+/* LogisticRegression::fit + predict_proba of matching/logistic.rs (not math/logit.rs, which
+   ob_logit restates): Newton-Raphson from beta = 0 with p = 1 / (1 + e^-x beta) unclamped, 1e-6
+   added to the Hessian's diagonal, an LU solve with partial pivoting (a zero pivot is OB_E_DIAG
+   "Hessian is singular"), beta += delta, stop when ||delta||_2 < tol; running out of iterations is
+   not an error. x: column-major n x k with the intercept supplied by the caller, ldx >= n; y: the
+   target as given. beta[k]; probs[n] (may be NULL) are the scores at the final beta. *converged:
+   whether the last step was under tol; *iterations: the steps taken. k <= OB_LOGIT_MAX_K. */
+int ob_match_logistic(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int32_t k,
+                      int32_t max_iter, double tol, double* beta, double* probs, int32_t* converged,
+                      int32_t* iterations);
+
+enum { OB_MATCH_EUCLIDEAN = 0, OB_MATCH_MAHALANOBIS = 1, OB_MATCH_PSM = 2 };
+typedef struct {
+  const char* treatment;
+  const char* outcome; /* read by OB_MATCH_PSM only; the other methods never look at it */
+  const char* const* covariates;
+  int32_t n_covariates;
+  int32_t k;
+  int32_t method; /* OB_MATCH_* */
+} ob_match_config;
+
+typedef struct ob_match_results ob_match_results;
+/* run_matching(k, use_mahalanobis) / match_psm(k) over a column frame.
+   Groups: treated rows have a treatment value equal to 1, controls one equal to 0 (any numeric
+   column); every other row, a null included, is in neither and gets weight 0. A string treatment
+   column is OB_E_POLARS. Covariates are cast to f64.
+   Mahalanobis: S is the covariance of the CONTROL rows (centred, n - 1 divisor; fewer than 2 controls
+   is OB_E_DIAG "Not enough data points to calculate covariance"), S^-1 a general inverse (adjugate
+   up to dimension 4, LU with partial pivoting beyond; OB_E_DIAG "Covariance matrix is singular and
+   cannot be inverted"), L its lower Cholesky factor (OB_E_DIAG "Cholesky decomposition failed"),
+   and both groups become X L.
+   Each treated row takes its min(k, n_c) nearest controls (ob_knn's distance and key); k = 0 or no
+   controls selects nothing. A treated row's weight is 1; a control matched m times gets 0.0 with the
+   f64 value 1.0 / k added m times in sequence (not m / k).
+   PSM first makes prepare_data's checks: an empty treated or control group is OB_E_GROUP "One group
+   is empty", a missing or non-f64 outcome OB_E_POLARS, a null outcome in a treated or control row
+   OB_E_GROUP "Null values in outcomes"; a non-f64 treatment column is OB_E_POLARS here. The design
+   is an intercept and the covariates of ALL rows, the target the raw treatment value (null: 0.0),
+   fitted by ob_match_logistic(.., 100, 1e-6); the scores are then the single covariate of a
+   Euclidean match.
+   Stricter than the reference (which would carry NaNs into its tree): a null in a covariate column
+   is OB_E_POLARS, a non-finite coordinate of a treated or control row after the transform is
+   OB_E_DIAG. n_covariates > OB_MATCH_MAX_DIM or k > OB_MATCH_MAX_K is OB_E_UNSUPPORTED. */
+int ob_match_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_match_config* cfg,
+                 ob_match_results** out);
+/* weights[*n_rows]: the reference's return value. An extension: treated_rows[*n_treated] are the
+   treated rows' frame positions, and neighbor_rows / neighbor_dist2 [*n_treated][*k_out] their
+   neighbours' frame positions and squared distances in ob_knn's order (-1 / +inf past
+   min(k, n_control)). Any out pointer may be NULL; the arrays live until ob_match_results_free. */
+int ob_match_results_get(const ob_match_results* r, int64_t* n_rows, const double** weights, int64_t* n_treated,
+                         int32_t* k_out, const int64_t** treated_rows, const int64_t** neighbor_rows,
+                         const double** neighbor_dist2);
+typedef struct {
+  int64_t n_treated, n_control;
+  int32_t logistic_iterations; /* OB_MATCH_PSM, else 0 */
+  int32_t logistic_converged;
+  double knn_ms;  /* HIP-event ms of the distance pass and its merge */
+  double prep_ms; /* HIP-event ms of everything else on the device: covariance, transform, logistic, packing */
+} ob_match_info;
+int ob_match_results_info(const ob_match_results* r, ob_match_info* out);
+void ob_match_results_free(ob_match_results* r);
+
 #ifdef __cplusplus
 }
 #endif

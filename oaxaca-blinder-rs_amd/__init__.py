@@ -6,11 +6,11 @@ hyphen). See DESIGN.md for the kernels and INTEGRATION.md for the Rust/C binding
 """
 from . import _native
 from ._native import OaxacaError
-from .api import (BudgetAdjustment, ComponentResult, DecompositionDetail, DflResult, OaxacaBlinder, OaxacaBuilder,
-                  OaxacaResults, PreparedRun, QuantileDecompositionBuilder, QuantileDecompositionDetail,
-                  QuantileDecompositionResults, ReferenceCoefficients, TwoFoldResults, parse_formula, run_dfl,
-                  run_dfl_from_csv)
-from .engine import (Panel, aggregate, boot_multi, bootstrap_stats, kde, logit, rif, row_layout,
+from .api import (BudgetAdjustment, ComponentResult, DecompositionDetail, DflResult, MatchingEngine, MatchResult,
+                  OaxacaBlinder, OaxacaBuilder, OaxacaResults, PreparedRun, QuantileDecompositionBuilder,
+                  QuantileDecompositionDetail, QuantileDecompositionResults, ReferenceCoefficients, TwoFoldResults,
+                  match_units, parse_formula, run_dfl, run_dfl_from_csv)
+from .engine import (Panel, aggregate, boot_multi, bootstrap_stats, kde, knn, logit, match_logistic, rif, row_layout,
                      silverman_bandwidth)
 from .frame import Frame, read_csv
 
@@ -20,4 +20,5 @@ __all__ = [
     "Panel", "boot_multi", "Frame", "read_csv", "aggregate", "bootstrap_stats", "rif", "row_layout", "parse_formula",
     "QuantileDecompositionBuilder", "QuantileDecompositionDetail", "QuantileDecompositionResults",
     "DflResult", "run_dfl", "run_dfl_from_csv", "logit", "kde", "silverman_bandwidth",
+    "MatchingEngine", "MatchResult", "match_units", "knn", "match_logistic",
 ]

@@ -47,9 +47,13 @@ EXPORTED = (
     "ob_debug_normal",
     "ob_logit", "ob_kde", "ob_silverman_bandwidth", "ob_dfl_run", "ob_dfl_results_get", "ob_dfl_results_info",
     "ob_dfl_results_free",
+    "ob_knn", "ob_match_logistic", "ob_match_run", "ob_match_results_get", "ob_match_results_info",
+    "ob_match_results_free",
 )
 
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
+OB_MATCH_MAX_DIM, OB_MATCH_MAX_K = 64, 16
+OB_MATCH_EUCLIDEAN, OB_MATCH_MAHALANOBIS, OB_MATCH_PSM = 0, 1, 2
 
 
 class OaxacaError(RuntimeError):
@@ -128,6 +132,16 @@ class ob_dfl_info(C.Structure):
     _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("logit_iterations", C.c_int32),
                 ("logit_converged", C.c_int32), ("bandwidth_a", C.c_double), ("bandwidth_b", C.c_double),
                 ("group_a", C.c_char_p), ("logit_ms", C.c_double), ("kde_ms", C.c_double)]
+
+
+class ob_match_config(C.Structure):
+    _fields_ = [("treatment", C.c_char_p), ("outcome", C.c_char_p), ("covariates", C.POINTER(C.c_char_p)),
+                ("n_covariates", C.c_int32), ("k", C.c_int32), ("method", C.c_int32)]
+
+
+class ob_match_info(C.Structure):
+    _fields_ = [("n_treated", C.c_int64), ("n_control", C.c_int64), ("logistic_iterations", C.c_int32),
+                ("logistic_converged", C.c_int32), ("knn_ms", C.c_double), ("prep_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -230,6 +244,17 @@ _SIGS = {
                                      C.POINTER(_D)]),
     "ob_dfl_results_info": (C.c_int, [_P, C.POINTER(ob_dfl_info)]),
     "ob_dfl_results_free": (None, [_P]),
+    "ob_knn": (C.c_int, [_P, _D, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                         C.POINTER(C.c_int64), _D]),
+    "ob_match_logistic": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int32, C.c_int32, C.c_double, _D, _D,
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ob_match_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_match_config),
+                               C.POINTER(_P)]),
+    "ob_match_results_get": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(_D), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int64)),
+                                       C.POINTER(C.POINTER(C.c_int64)), C.POINTER(_D)]),
+    "ob_match_results_info": (C.c_int, [_P, C.POINTER(ob_match_info)]),
+    "ob_match_results_free": (None, [_P]),
 }
 
 _lib = None

@@ -685,3 +685,94 @@ def run_dfl_from_csv(csv_path, outcome: str, group: str, reference_group: str, p
 
     return run_dfl(read_csv(csv_path), outcome, group, reference_group, predictors, device=device,
                    grid_size=grid_size)
+
+
+@dataclass
+class MatchResult:
+    """What ``ob_match_run`` returns: the reference's weights, and as an extension each treated
+    row's neighbours (frame positions, -1 past min(k, n_control)) and their squared distances."""
+    weights: np.ndarray
+    treated_rows: np.ndarray
+    neighbor_rows: np.ndarray
+    neighbor_dist2: np.ndarray
+    n_treated: int = 0
+    n_control: int = 0
+    logistic_iterations: int = 0
+    logistic_converged: bool = False
+    knn_ms: float = 0.0
+    prep_ms: float = 0.0
+
+
+_MATCH_METHODS = {"mahalanobis": N.OB_MATCH_MAHALANOBIS, "psm": N.OB_MATCH_PSM}
+
+
+class MatchingEngine:
+    """matching/engine.rs:10-284 on the MI355X engine (``ob_match_run``). ``dataframe`` is what
+    ``OaxacaBuilder`` takes. Ties among exactly equidistant controls go to the smaller control
+    position (the reference's depend on its tree's shape)."""
+
+    def __init__(self, dataframe, treatment_col: str, outcome_col: str, covariates, device: int | None = None):
+        self._frame = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
+        self._treatment, self._outcome = str(treatment_col), str(outcome_col)
+        self._covariates = [str(c) for c in covariates]
+        self._device = device
+
+    def run(self, k: int, method: int) -> MatchResult:
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg = N.ob_match_config()
+        cfg.treatment, cfg.outcome = self._treatment.encode(), self._outcome.encode()
+        pp, pa = _strs(self._covariates)
+        cfg.covariates, cfg.n_covariates, cfg.k, cfg.method = pp, len(self._covariates), int(k), int(method)
+        h = C.c_void_p()
+        N.check(lib.ob_match_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+        try:
+            n, nt, kk = C.c_int64(), C.c_int64(), C.c_int32()
+            w, d2 = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+            tr, nb = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)()
+            N.check(lib.ob_match_results_get(h, C.byref(n), C.byref(w), C.byref(nt), C.byref(kk), C.byref(tr),
+                                             C.byref(nb), C.byref(d2)))
+
+            def arr(p, shape, dtype):
+                size = int(np.prod(shape))
+                return np.ctypeslib.as_array(p, shape=(size,)).copy().reshape(shape) if size else np.zeros(shape, dtype)
+
+            info = N.ob_match_info()
+            N.check(lib.ob_match_results_info(h, C.byref(info)))
+            return MatchResult(arr(w, (n.value,), np.float64), arr(tr, (nt.value,), np.int64),
+                               arr(nb, (nt.value, kk.value), np.int64), arr(d2, (nt.value, kk.value), np.float64),
+                               n_treated=int(info.n_treated), n_control=int(info.n_control),
+                               logistic_iterations=int(info.logistic_iterations),
+                               logistic_converged=bool(info.logistic_converged), knn_ms=info.knn_ms,
+                               prep_ms=info.prep_ms)
+        finally:
+            lib.ob_match_results_free(h)
+            del pa
+
+    def run_matching(self, k: int, use_mahalanobis: bool = False) -> list:
+        """engine.rs:113-229: the weight of every row."""
+        return self.match_nearest_neighbor(k, use_mahalanobis).tolist()
+
+    def match_nearest_neighbor(self, k: int, use_mahalanobis: bool = False) -> np.ndarray:
+        """engine.rs:103-110."""
+        return self.run(k, N.OB_MATCH_MAHALANOBIS if use_mahalanobis else N.OB_MATCH_EUCLIDEAN).weights
+
+    def match_psm(self, k: int) -> list:
+        """engine.rs:232-283."""
+        return self.run(k, N.OB_MATCH_PSM).weights.tolist()
+
+    def neighbors(self, k: int, use_mahalanobis: bool = False):
+        """(idx, dist2), both (n_treated, k): each treated row's neighbours as frame positions and
+        their squared distances (an extension; the reference returns the weights only)."""
+        r = self.run(k, N.OB_MATCH_MAHALANOBIS if use_mahalanobis else N.OB_MATCH_EUCLIDEAN)
+        return r.neighbor_rows, r.neighbor_dist2
+
+
+def match_units(csv_path, treatment: str, outcome: str, covariates, k: int = 1, method: str = "euclidean",
+                device: int | None = None) -> list:
+    """python.rs:387-423: the CSV read by the native reader, then the weights. Any method other than
+    "psm" or "mahalanobis" is Euclidean (python.rs:411-420)."""
+    from .frame import read_csv
+
+    eng = MatchingEngine(read_csv(csv_path), treatment, outcome, covariates, device=device)
+    return eng.run(k, _MATCH_METHODS.get(method, N.OB_MATCH_EUCLIDEAN)).weights.tolist()

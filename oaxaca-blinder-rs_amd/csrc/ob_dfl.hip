@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ob_dfl.hpp"
+#include "ob_match.hpp"
 
 namespace {
 
@@ -64,13 +65,16 @@ struct LogitArgs {
 // lane = row writes before the operand-shaped reads of other lanes (and back).
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// logit.rs:15-17,45: sigmoid then clamp (a NaN stays a NaN, as f64::clamp keeps it)
+// logit.rs:15-17,45: sigmoid then clamp (a NaN stays a NaN, as f64::clamp keeps it). CLAMP = false is
+// matching/logistic.rs:51,111, which has no clamp.
+template <bool CLAMP = true>
 __device__ __forceinline__ double logit_prob(double z) {
   const double p = 1.0 / (1.0 + exp(-z));
+  if (!CLAMP) return p;
   return p < 1e-10 ? 1e-10 : (p > 1.0 - 1e-10 ? 1.0 - 1e-10 : p);
 }
 
-template <int NCB>
+template <int NCB, bool CLAMP = true>
 __global__ __launch_bounds__(kBlock) void ob_logit_pass_kernel(const LogitArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   constexpr int NC = 16 * NCB;
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void ob_logit_pass_kernel(const LogitArgs a
       xs[c * kLgStride + lane] = v;
       eta = fma(v, a.beta[c], eta);
     }
-    const double p = logit_prob(eta);
+    const double p = logit_prob<CLAMP>(eta);
     ws[lane] = live ? p * (1.0 - p) : 0.0;
     rs[lane] = live ? a.y[row] - p : 0.0;
     if (live && a.probs) a.probs[row] = p;
@@ -168,13 +172,14 @@ __global__ __launch_bounds__(kBlock) void ob_dfl_reduce_kernel(const double* par
   if (tid == 0) out[blockIdx.x] = red[0];
 }
 
+template <bool CLAMP = true>
 __global__ __launch_bounds__(kBlock) void ob_logit_probs_kernel(const double* x, int64_t ldx, const double* beta,
                                                                  int64_t n, int k, double* probs) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (row >= n) return;
   double eta = 0.0;
   for (int c = 0; c < k; ++c) eta = fma(x[(size_t)c * ldx + row], beta[c], eta);
-  probs[row] = logit_prob(eta);
+  probs[row] = logit_prob<CLAMP>(eta);
 }
 
 // blockIdx.x: group of kKdeGp grid points, blockIdx.y: data chunk. partial: [n_grid][nchunks].
@@ -242,12 +247,12 @@ struct Events {
   }
 };
 
-template <int NCB>
+template <int NCB, bool CLAMP = true>
 int launch_logit_pass(const LogitArgs& a, hipStream_t s) {
   const size_t lds = sizeof(double) * kLgWaves * (16 * NCB * kLgStride + kLgRowVecs);
-  DFL_OK(hipFuncSetAttribute((const void*)ob_logit_pass_kernel<NCB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)lds));
-  hipLaunchKernelGGL(ob_logit_pass_kernel<NCB>, dim3((a.units + kLgWaves - 1) / kLgWaves), dim3(kBlock), lds, s, a);
+  DFL_OK(hipFuncSetAttribute((const void*)ob_logit_pass_kernel<NCB, CLAMP>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((ob_logit_pass_kernel<NCB, CLAMP>), dim3((a.units + kLgWaves - 1) / kLgWaves), dim3(kBlock), lds, s, a);
   DFL_OK(hipGetLastError());
   return OB_OK;
 }
@@ -279,12 +284,62 @@ bool host_chol_solve(std::vector<double>& m, int k, std::vector<double>& b) {
   return true;
 }
 
+// nalgebra LU::new (partial pivoting by the largest |entry|; a zero pivot column is skipped) + solve on
+// the host: m is k x k column-major, full; false iff a diagonal entry of U is zero (logistic.rs:95).
+bool host_lu_solve(std::vector<double>& m, int k, std::vector<double>& b) {
+  for (int i = 0; i < k; ++i) {
+    int piv = i;
+    for (int r = i + 1; r < k; ++r)
+      if (std::fabs(m[r + (size_t)i * k]) > std::fabs(m[piv + (size_t)i * k])) piv = r;
+    if (m[piv + (size_t)i * k] == 0.0) continue;
+    if (piv != i) {
+      for (int c = 0; c < k; ++c) std::swap(m[i + (size_t)c * k], m[piv + (size_t)c * k]);
+      std::swap(b[i], b[piv]);
+    }
+    for (int r = i + 1; r < k; ++r) {
+      const double f = m[r + (size_t)i * k] / m[i + (size_t)i * k];
+      for (int c = i + 1; c < k; ++c) m[r + (size_t)c * k] -= f * m[i + (size_t)c * k];
+      b[r] -= f * b[i];
+    }
+  }
+  for (int i = k - 1; i >= 0; --i) {
+    const double diag = m[i + (size_t)i * k];
+    if (diag == 0.0) return false;
+    double part = b[i];
+    for (int c = i + 1; c < k; ++c) part -= m[i + (size_t)c * k] * b[c];
+    b[i] = part / diag;
+  }
+  return true;
+}
+
+// The Newton loop of both logits. MATCH = false: math/logit.rs:31-118 (dfl_logit). MATCH = true:
+// matching/logistic.rs:31-113 (match_logistic): no clamp, a 1e-6 ridge, LU, scores at the final beta.
+template <bool MATCH>
+int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter, double tol,
+                 double* beta, double* probs, ob::LogitInfo* info);
+
 }  // namespace
 
 namespace ob {
 
 int dfl_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter, double tol,
               double* beta, double* probs, LogitInfo* info) {
+  return logit_newton<false>(ctx, x, ldx, y, n, k, max_iter, tol, beta, probs, info);
+}
+
+int match_logistic(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter,
+                   double tol, double* beta, double* probs, LogitInfo* info) {
+  return logit_newton<true>(ctx, x, ldx, y, n, k, max_iter, tol, beta, probs, info);
+}
+
+}  // namespace ob
+
+namespace {
+
+template <bool MATCH>
+int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter, double tol,
+                 double* beta, double* probs, ob::LogitInfo* info) {
+  using namespace ob;
   if (!ctx || !x || !y || !beta || !info) return fail(OB_E_INVALID, "null pointer");
   if (n <= 0 || k <= 0 || ldx < n || max_iter < 0) return fail(OB_E_INVALID, "bad logit dimensions");
   if (k > kLogitMaxK)
@@ -327,10 +382,10 @@ int dfl_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_
     DFL_OK(hipMemcpyAsync(db.p, b.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
     DFL_OK(hipEventRecord(ev.a, st));
     switch (ncb) {
-      case 1: OB_TRY(launch_logit_pass<1>(a, st)); break;
-      case 2: OB_TRY(launch_logit_pass<2>(a, st)); break;
-      case 3: OB_TRY(launch_logit_pass<3>(a, st)); break;
-      default: OB_TRY(launch_logit_pass<4>(a, st)); break;
+      case 1: OB_TRY((launch_logit_pass<1, !MATCH>(a, st))); break;
+      case 2: OB_TRY((launch_logit_pass<2, !MATCH>(a, st))); break;
+      case 3: OB_TRY((launch_logit_pass<3, !MATCH>(a, st))); break;
+      default: OB_TRY((launch_logit_pass<4, !MATCH>(a, st))); break;
     }
     hipLaunchKernelGGL(ob_dfl_reduce_kernel, dim3(ne), dim3(kBlock), 0, st, dpart.d(), a.units, dsum.d());
     DFL_OK(hipGetLastError());
@@ -344,9 +399,17 @@ int dfl_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_
     for (int c = 0; c < k; ++c)
       for (int r = c; r < k; ++r) m[r + (size_t)c * k] = sums[c * k - c * (c - 1) / 2 + (r - c)];
     for (int c = 0; c < k; ++c) step[c] = sums[k * (k + 1) / 2 + c];
-    if (!host_chol_solve(m, k, step))  // logit.rs:88-95
+    if (MATCH) {
+      for (int c = 0; c < k; ++c) {
+        for (int r = 0; r < c; ++r) m[r + (size_t)c * k] = m[c + (size_t)r * k];
+        m[c + (size_t)c * k] += 1e-6;  // logistic.rs:89-91
+      }
+      if (!host_lu_solve(m, k, step))  // logistic.rs:95
+        return fail(OB_E_DIAG, "%sHessian is singular", error_prefix(OB_E_DIAG));
+    } else if (!host_chol_solve(m, k, step)) {  // logit.rs:88-95
       return fail(OB_E_LINALG, "%sFailed to solve Information Matrix in Logit. Perfect separation?",
                   error_prefix(OB_E_LINALG));
+    }
     double nrm = 0.0;
     for (int c = 0; c < k; ++c) {
       b[c] += step[c];
@@ -358,9 +421,9 @@ int dfl_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_
       break;
     }
   }
-  if (!converged && probs) {  // logit.rs:108-110
+  if ((MATCH || !converged) && probs) {  // logit.rs:108-110; logistic.rs:109-112 always scores at the final beta
     DFL_OK(hipMemcpyAsync(db.p, b.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(ob_logit_probs_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, dx.d(),
+    hipLaunchKernelGGL(ob_logit_probs_kernel<!MATCH>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, dx.d(),
                        n, db.d(), n, k, dp.d());
     DFL_OK(hipGetLastError());
   }
@@ -371,6 +434,10 @@ int dfl_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_
   info->iterations = iterations;
   return OB_OK;
 }
+
+}  // namespace
+
+namespace ob {
 
 int dfl_kde(ob_ctx* ctx, const double* data, const double* wnorm, int64_t n, const double* grid, int64_t n_grid,
             double bandwidth, double* density, double* ms_out) {

@@ -41,6 +41,8 @@ enum class Opt : int {
                 // beside level 1 of piece k + 1 (1: one launch each); unset: the engine's rule
   TailStream,   // 1: a boot's reduce / solve on a stream of their own, so the next segment's Gram
                 // need not wait for them (two partial buffers); 0: on the caller's stream; unset: rule
+  MatchChunks,  // the matching distance pass splits the controls into this many chunks (1: no split);
+                // unset: the rule of match_knn, a function of the input sizes (results do not depend on it)
   Count
 };
 

@@ -285,6 +285,39 @@ def logit(y, x, max_iter: int = 100, tol: float = 1e-6, device: int | None = Non
     return beta, probs, bool(conv.value), int(iters.value)
 
 
+def knn(queries, controls, k: int, device: int | None = None):
+    """The min(k, n_c) nearest controls of each query (``ob_knn``): squared Euclidean distance summed
+    in covariate order without FMA, ties by control position. ``queries``: (n_q, d), ``controls``:
+    (n_c, d). Returns (idx int64 (n_q, k), dist2 (n_q, k)), ascending, -1 / +inf past min(k, n_c)."""
+    q = np.asfortranarray(queries, dtype=np.float64)
+    c = np.asfortranarray(controls, dtype=np.float64)
+    if q.ndim != 2 or c.ndim != 2 or q.shape[1] != c.shape[1]:
+        raise ValueError("queries and controls must be (n, d) with the same d")
+    (n_q, d), n_c, k = q.shape, c.shape[0], int(k)
+    idx, dist2 = np.empty((n_q, max(k, 0)), dtype=np.int64), np.empty((n_q, max(k, 0)))
+    N.check(N.lib().ob_knn(N.context(device), _dp(q), max(n_q, 1), n_q, _dp(c), max(n_c, 1), n_c, d, k,
+                           idx.ctypes.data_as(C.POINTER(C.c_int64)), _dp(dist2)))
+    return idx, dist2
+
+
+def match_logistic(x, y, max_iter: int = 100, tol: float = 1e-6, device: int | None = None):
+    """matching/logistic.rs:31-113 with the Newton passes on the GPU (``ob_match_logistic``): no
+    probability clamp, a 1e-6 ridge, an LU solve. ``x``: (n, k) with the intercept column included.
+    Returns (coefficients, scores at the final coefficients, converged, iterations)."""
+    xf = np.asfortranarray(x, dtype=np.float64)
+    if xf.ndim != 2:
+        raise ValueError("x must be (n, k)")
+    n, k = xf.shape
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.shape != (n,):
+        raise ValueError("y must have one entry per row of x")
+    beta, probs = np.empty(k), np.empty(n)
+    conv, iters = C.c_int32(0), C.c_int32(0)
+    N.check(N.lib().ob_match_logistic(N.context(device), _dp(xf), max(n, 1), _dp(y), n, k, int(max_iter), float(tol),
+                                      _dp(beta), _dp(probs), C.byref(conv), C.byref(iters)))
+    return beta, probs, bool(conv.value), int(iters.value)
+
+
 def kde(data, grid, bandwidth: float, weights=None, device: int | None = None):
     """math/kde.rs:20-41 on the GPU (``ob_kde``): the weighted Gaussian kernel density of ``data``
     at the ``grid`` points."""
