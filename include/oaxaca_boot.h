@@ -39,6 +39,8 @@ extern "C" {
 #define OB_E_OVERFLOW 10     /* a resample count exceeded the Gram's range in one row: 127 on the default i8
                                 path (probability ~1e-215 per row and replicate), 255 on the f64 path */
 #define OB_E_RCCL 11         /* RCCL missing or a collective failed (multi-GPU entry points) */
+#define OB_E_CONVERGENCE 12  /* AkmError::ConvergenceFailed (akm.rs:11): an AKM loop ran out of iterations, or
+                                the OLS of the demeaned controls is singular */
 
 const char* ob_last_error(void);
 const char* ob_version(void);
@@ -276,6 +278,8 @@ int ob_debug_mm_betas(ob_panel* panel, uint64_t seed, int32_t simulations, uint6
                    the next piece's level 1 (default 1; rows bitwise unchanged)
      "tail_stream" 1: the Gram and the reduce / solve on engine streams, the caller's stream waiting for
                    them at the end of the call (default 0; rows bitwise unchanged)
+     "akm_poll"    n >= 1: the AKM loops read their device-side done flags every n iterations (default 8;
+                   results and iteration counts bitwise unchanged)
    Unknown names are OB_E_INVALID. ob_get_option reads back what ob_set_option stored (NaN: unset). ob_tuning_build() is 1 in a -DOB_TUNING=1 build (`make tuning`),
    which also reads OB_<NAME> from the environment for options nobody set. */
 int ob_set_option(const char* name, double value);
@@ -611,6 +615,96 @@ typedef struct {
 } ob_match_info;
 int ob_match_results_info(const ob_match_results* r, ob_match_info* out);
 void ob_match_results_free(ob_match_results* r);
+
+/* ---- AKM two-way fixed effects (akm.rs:47-621) -------------------------------------------------
+ * y = x beta + alpha[worker] + psi[firm] + e on the largest connected set of the worker-firm graph:
+ * the outcome and every control are demeaned by alternating worker and firm means until a fixed
+ * point (demean_vector), beta is the OLS of the demeaned outcome on the demeaned controls, and the
+ * effects come from alternating means of the residual (recover_fe). The group means, the Gram and
+ * the R^2 sums run on the GPU as segmented reductions over the rows grouped by worker and by firm;
+ * every sum is f64 in a fixed order that depends only on the input's sizes and group layout (no
+ * floating atomics), so a call repeated on the same input returns the same bytes, and a column gives
+ * the same bytes and iteration count demeaned alone or in any batch.
+ *
+ * The one deliberate difference from the reference: among components with equally many nodes its
+ * choice follows HashMap iteration order. Here the component holding the smallest sorted worker id
+ * wins. */
+#define OB_AKM_MAX_CONTROLS 64
+
+typedef struct ob_akm_set ob_akm_set;
+/* find_largest_connected_set (akm.rs:151-234) and the dense indices of solve_akm (akm.rs:246-303).
+   Host only: needs no GPU. Id columns are OB_COL_STR or OB_COL_I64 (cast to decimal strings, so they
+   sort as strings: "10" < "9"); an OB_COL_F64 id column is OB_E_UNSUPPORTED. Nodes are the distinct
+   non-null worker and firm ids, edges the rows with both ids non-null; the component with the most
+   nodes (workers + firms, not rows) is kept. Rows outside it or with a null id are dropped; no kept
+   row is OB_E_INSUFFICIENT "No connected set found". A missing column is OB_E_COLUMN. */
+int ob_akm_connected_set(const ob_column* cols, int32_t n_cols, int64_t n_rows, const char* worker_col,
+                         const char* firm_col, ob_akm_set** out);
+/* keep[*n_rows]: 1 for a kept row; worker_idx / firm_idx[*n_kept]: the dense index of each kept row, in
+   row order, over the kept ids in sorted string order; *n_components counts every component of the
+   graph. Any out pointer may be NULL; the arrays live until ob_akm_set_free. */
+int ob_akm_set_get(const ob_akm_set* s, int64_t* n_rows, const uint8_t** keep, int64_t* n_kept,
+                   const int32_t** worker_idx, const int32_t** firm_idx, int64_t* n_workers, int64_t* n_firms,
+                   int64_t* n_components);
+/* The i-th sorted kept id: which = 0 worker, 1 firm. NULL when out of range. */
+const char* ob_akm_set_id(const ob_akm_set* s, int32_t which, int64_t i);
+void ob_akm_set_free(ob_akm_set* s);
+
+/* demean_vector (akm.rs:452-527) of n_cols columns in one batch. v and out: column-major n x n_cols
+   with leading dimension ldv >= n (entries past n of a column are never read or written). Each
+   iteration subtracts every worker's mean, then every firm's mean of the result, and a column stops
+   at the first iteration whose change ||v - prev||_2 is not above tol, or after max_iters; the rule is
+   evaluated on the device per column and a stopped column is frozen. iterations[n_cols]; converged[c]
+   = iterations[c] < max_iters, the reference's own test, so a column that converges in its last
+   allowed iteration, or max_iters = 0, reads as not converged. That is reported, not an error.
+   worker_idx / firm_idx: n dense indices in [0, n_workers) / [0, n_firms), else OB_E_INVALID. */
+int ob_akm_demean(ob_ctx* ctx, const double* v, int64_t ldv, int64_t n, int32_t n_cols, const int32_t* worker_idx,
+                  const int32_t* firm_idx, int64_t n_workers, int64_t n_firms, double tol, int64_t max_iters,
+                  double* out, int32_t* iterations, int32_t* converged);
+/* recover_fe (akm.rs:530-621): from alpha = psi = 0, alpha_w = mean(r - psi[firm] | w), then psi_f =
+   mean(r - alpha[worker] | f) with the new alpha, until the 2-norm of the change of (alpha, psi) is
+   not above tol; then psi[0] is subtracted from every psi and added to every alpha (skipped when not
+   converged, where the reference returns nothing). The same converged rule as ob_akm_demean. */
+int ob_akm_recover_fe(ob_ctx* ctx, const double* r, int64_t n, const int32_t* worker_idx, const int32_t* firm_idx,
+                      int64_t n_workers, int64_t n_firms, double tol, int64_t max_iters, double* alpha, double* psi,
+                      int32_t* iterations, int32_t* converged);
+
+typedef struct {
+  const char* outcome;
+  const char* worker_col;
+  const char* firm_col;
+  const char* const* controls;
+  int32_t n_controls;
+  double tolerance;  /* 0: the reference's 1e-8 */
+  int64_t max_iters; /* negative: the reference's 1000 (0 stays 0, which fails at once as there) */
+} ob_akm_config;
+
+typedef struct ob_akm_results ob_akm_results;
+/* AkmBuilder::run over a column frame. The outcome and the controls must be OB_COL_F64 (else
+   OB_E_POLARS); a null outcome in a kept row is OB_E_INSUFFICIENT "Null outcome encountered", a null
+   control reads as 0.0. A loop that ends with iterations >= max_iters is OB_E_CONVERGENCE
+   "demean_vector failed to converge within N iterations" / "recover_fe failed ...", a failed Cholesky
+   of X'X OB_E_CONVERGENCE "OLS design matrix is singular". More than OB_AKM_MAX_CONTROLS controls, or
+   2^31 or more rows or nodes, is OB_E_UNSUPPORTED before any device work. r2 = 1 - rss / tss. */
+int ob_akm_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_akm_config* cfg,
+               ob_akm_results** out);
+/* AkmResult (akm.rs:39-44): beta[*n_controls]; the sorted worker ids and their effects, the sorted firm
+   ids and theirs. Any out pointer may be NULL; everything lives until ob_akm_results_free. */
+int ob_akm_results_get(const ob_akm_results* r, int32_t* n_controls, const double** beta, int64_t* n_workers,
+                       const char* const** worker_ids, const double** worker_effects, int64_t* n_firms,
+                       const char* const** firm_ids, const double** firm_effects, double* r2);
+typedef struct {
+  int64_t n_rows_kept, n_workers, n_firms, n_components;
+  const int32_t* demean_iterations; /* 1 + n_controls entries: the outcome, then the controls */
+  int32_t n_demean;
+  int32_t recover_iterations;
+  int32_t launches_per_iteration; /* kernel launches of one demean iteration */
+  double demean_ms;  /* HIP-event ms of the demean loop */
+  double ols_ms;     /* the Gram, the residual and the R^2 sums */
+  double recover_ms; /* the recover_fe loop and the normalisation */
+} ob_akm_info;
+int ob_akm_results_info(const ob_akm_results* r, ob_akm_info* out);
+void ob_akm_results_free(ob_akm_results* r);
 
 #ifdef __cplusplus
 }

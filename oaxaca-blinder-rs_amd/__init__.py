@@ -6,12 +6,13 @@ hyphen). See DESIGN.md for the kernels and INTEGRATION.md for the Rust/C binding
 """
 from . import _native
 from ._native import OaxacaError
-from .api import (BudgetAdjustment, ComponentResult, DecompositionDetail, DflResult, MatchingEngine, MatchResult,
-                  OaxacaBlinder, OaxacaBuilder, OaxacaResults, PreparedRun, QuantileDecompositionBuilder,
-                  QuantileDecompositionDetail, QuantileDecompositionResults, ReferenceCoefficients, TwoFoldResults,
-                  match_units, parse_formula, run_dfl, run_dfl_from_csv)
-from .engine import (Panel, aggregate, boot_multi, bootstrap_stats, kde, knn, logit, match_logistic, rif, row_layout,
-                     silverman_bandwidth)
+from .api import (AkmBuilder, AkmResult, BudgetAdjustment, ComponentResult, DecompositionDetail, DflResult,
+                  MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder, OaxacaResults, PreparedRun,
+                  QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
+                  ReferenceCoefficients, TwoFoldResults, estimate_akm, match_units, parse_formula, run_dfl,
+                  run_dfl_from_csv)
+from .engine import (Panel, aggregate, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
+                     knn, logit, match_logistic, rif, row_layout, silverman_bandwidth)
 from .frame import Frame, read_csv
 
 __all__ = [
@@ -21,4 +22,5 @@ __all__ = [
     "QuantileDecompositionBuilder", "QuantileDecompositionDetail", "QuantileDecompositionResults",
     "DflResult", "run_dfl", "run_dfl_from_csv", "logit", "kde", "silverman_bandwidth",
     "MatchingEngine", "MatchResult", "match_units", "knn", "match_logistic",
+    "AkmBuilder", "AkmResult", "estimate_akm", "akm_connected_set", "akm_demean", "akm_recover_fe",
 ]

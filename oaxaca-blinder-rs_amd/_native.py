@@ -49,9 +49,13 @@ EXPORTED = (
     "ob_dfl_results_free",
     "ob_knn", "ob_match_logistic", "ob_match_run", "ob_match_results_get", "ob_match_results_info",
     "ob_match_results_free",
+    "ob_akm_connected_set", "ob_akm_set_get", "ob_akm_set_id", "ob_akm_set_free", "ob_akm_demean",
+    "ob_akm_recover_fe", "ob_akm_run", "ob_akm_results_get", "ob_akm_results_info", "ob_akm_results_free",
 )
 
+OB_E_CONVERGENCE = 12
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
+OB_AKM_MAX_CONTROLS = 64
 OB_MATCH_MAX_DIM, OB_MATCH_MAX_K = 64, 16
 OB_MATCH_EUCLIDEAN, OB_MATCH_MAHALANOBIS, OB_MATCH_PSM = 0, 1, 2
 
@@ -142,6 +146,19 @@ class ob_match_config(C.Structure):
 class ob_match_info(C.Structure):
     _fields_ = [("n_treated", C.c_int64), ("n_control", C.c_int64), ("logistic_iterations", C.c_int32),
                 ("logistic_converged", C.c_int32), ("knn_ms", C.c_double), ("prep_ms", C.c_double)]
+
+
+class ob_akm_config(C.Structure):
+    _fields_ = [("outcome", C.c_char_p), ("worker_col", C.c_char_p), ("firm_col", C.c_char_p),
+                ("controls", C.POINTER(C.c_char_p)), ("n_controls", C.c_int32), ("tolerance", C.c_double),
+                ("max_iters", C.c_int64)]
+
+
+class ob_akm_info(C.Structure):
+    _fields_ = [("n_rows_kept", C.c_int64), ("n_workers", C.c_int64), ("n_firms", C.c_int64),
+                ("n_components", C.c_int64), ("demean_iterations", C.POINTER(C.c_int32)), ("n_demean", C.c_int32),
+                ("recover_iterations", C.c_int32), ("launches_per_iteration", C.c_int32),
+                ("demean_ms", C.c_double), ("ols_ms", C.c_double), ("recover_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -255,6 +272,26 @@ _SIGS = {
                                        C.POINTER(C.POINTER(C.c_int64)), C.POINTER(_D)]),
     "ob_match_results_info": (C.c_int, [_P, C.POINTER(ob_match_info)]),
     "ob_match_results_free": (None, [_P]),
+    "ob_akm_connected_set": (C.c_int, [C.POINTER(ob_column), C.c_int32, C.c_int64, C.c_char_p, C.c_char_p,
+                                       C.POINTER(_P)]),
+    "ob_akm_set_get": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(_U8), C.POINTER(C.c_int64),
+                                 C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ob_akm_set_id": (C.c_char_p, [_P, C.c_int32, C.c_int64]),
+    "ob_akm_set_free": (None, [_P]),
+    "ob_akm_demean": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.c_int64, C.c_int64, C.c_double, C.c_int64, _D, C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32)]),
+    "ob_akm_recover_fe": (C.c_int, [_P, _D, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64,
+                                    C.c_int64, C.c_double, C.c_int64, _D, _D, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32)]),
+    "ob_akm_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_akm_config),
+                             C.POINTER(_P)]),
+    "ob_akm_results_get": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(_D), C.POINTER(C.c_int64),
+                                     C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(_D), C.POINTER(C.c_int64),
+                                     C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(_D), C.POINTER(C.c_double)]),
+    "ob_akm_results_info": (C.c_int, [_P, C.POINTER(ob_akm_info)]),
+    "ob_akm_results_free": (None, [_P]),
 }
 
 _lib = None

@@ -776,3 +776,83 @@ def match_units(csv_path, treatment: str, outcome: str, covariates, k: int = 1, 
 
     eng = MatchingEngine(read_csv(csv_path), treatment, outcome, covariates, device=device)
     return eng.run(k, _MATCH_METHODS.get(method, N.OB_MATCH_EUCLIDEAN)).weights.tolist()
+
+
+@dataclass
+class AkmResult:
+    """akm.rs:39-44 as python.rs exposes it (``PyAkmResult``): ``beta`` in control order, the worker and
+    firm effects as dicts from id string to effect, ``r2``; ``info`` is what ``ob_akm_results_info``
+    reports (rows kept, counts, per-column demean iterations, recover_fe iterations, HIP-event ms)."""
+    beta: list
+    worker_effects: dict
+    firm_effects: dict
+    r2: float
+    info: dict = field(default_factory=dict)
+
+
+class AkmBuilder:
+    """akm.rs:47-111 on the MI355X engine (``ob_akm_run``). ``dataframe`` is what ``OaxacaBuilder``
+    takes. Among components with equally many nodes the one holding the smallest sorted worker id is
+    kept (the reference's pick follows its HashMap's iteration order)."""
+
+    def __init__(self, dataframe, outcome: str, worker_col: str, firm_col: str, device: int | None = None):
+        self._frame = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
+        self._outcome, self._worker, self._firm = str(outcome), str(worker_col), str(firm_col)
+        self._controls: list = []
+        self._tolerance, self._max_iters = 1e-8, 1000
+        self._device = device
+
+    def controls(self, controls):
+        self._controls = [str(c) for c in controls]
+        return self
+
+    def tolerance(self, tol: float):
+        self._tolerance = float(tol)
+        return self
+
+    def max_iters(self, iters: int):
+        if int(iters) < 0:
+            raise ValueError("max_iters is unsigned")
+        self._max_iters = int(iters)
+        return self
+
+    def run(self) -> AkmResult:
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg = N.ob_akm_config()
+        cfg.outcome, cfg.worker_col, cfg.firm_col = self._outcome.encode(), self._worker.encode(), self._firm.encode()
+        pp, pa = _strs(self._controls)
+        cfg.controls, cfg.n_controls = pp, len(self._controls)
+        cfg.tolerance, cfg.max_iters = self._tolerance, self._max_iters
+        h = C.c_void_p()
+        N.check(lib.ob_akm_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+        try:
+            k, nw, nf, r2 = C.c_int32(), C.c_int64(), C.c_int64(), C.c_double()
+            beta, alpha, psi = (C.POINTER(C.c_double)() for _ in range(3))
+            wid, fid = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
+            N.check(lib.ob_akm_results_get(h, C.byref(k), C.byref(beta), C.byref(nw), C.byref(wid), C.byref(alpha),
+                                           C.byref(nf), C.byref(fid), C.byref(psi), C.byref(r2)))
+            info = N.ob_akm_info()
+            N.check(lib.ob_akm_results_info(h, C.byref(info)))
+            return AkmResult(
+                [beta[j] for j in range(k.value)],
+                {wid[i].decode(): alpha[i] for i in range(nw.value)},
+                {fid[i].decode(): psi[i] for i in range(nf.value)}, r2.value,
+                {"n_rows_kept": int(info.n_rows_kept), "n_workers": int(info.n_workers),
+                 "n_firms": int(info.n_firms), "n_components": int(info.n_components),
+                 "demean_iterations": [int(info.demean_iterations[j]) for j in range(info.n_demean)],
+                 "recover_iterations": int(info.recover_iterations),
+                 "launches_per_iteration": int(info.launches_per_iteration), "demean_ms": info.demean_ms,
+                 "ols_ms": info.ols_ms, "recover_ms": info.recover_ms})
+        finally:
+            lib.ob_akm_results_free(h)
+            del pa
+
+
+def estimate_akm(csv_path, outcome: str, worker_col: str, firm_col: str, controls=None, tolerance: float = 1e-8,
+                 max_iters: int = 1000, device: int | None = None) -> AkmResult:
+    """python.rs ``estimate_akm``: the CSV read by the native reader, then ``AkmBuilder.run``."""
+    from .frame import read_csv
+
+    b = AkmBuilder(read_csv(csv_path), outcome, worker_col, firm_col, device=device)
+    return b.controls(controls or []).tolerance(tolerance).max_iters(max_iters).run()

@@ -43,6 +43,8 @@ enum class Opt : int {
                 // need not wait for them (two partial buffers); 0: on the caller's stream; unset: rule
   MatchChunks,  // the matching distance pass splits the controls into this many chunks (1: no split);
                 // unset: the rule of match_knn, a function of the input sizes (results do not depend on it)
+  AkmPoll,      // the AKM loops read their done flags every this many iterations (results and iteration
+                // counts do not depend on it); unset: kAkmPollDefault
   Count
 };
 

@@ -338,3 +338,81 @@ def silverman_bandwidth(data) -> float:
     out = C.c_double()
     N.check(N.lib().ob_silverman_bandwidth(_dp(data), len(data), C.byref(out)))
     return out.value
+
+
+def _i32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def akm_connected_set(dataframe, worker_col: str, firm_col: str) -> dict:
+    """akm.rs:151-303 on the host (``ob_akm_connected_set``, no GPU needed): the largest connected set
+    of the worker-firm graph by node count; among equally large components the one holding the
+    smallest sorted worker id. Returns ``keep`` (bool per row), ``worker_idx`` / ``firm_idx`` (int32
+    per kept row, dense over the kept ids in sorted string order), ``worker_ids`` / ``firm_ids`` (the
+    sorted id strings) and ``n_components``."""
+    from .frame import Frame
+
+    lib = N.lib()
+    frame = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
+    cols, ncol, nrow = frame.as_c()
+    h = C.c_void_p()
+    N.check(lib.ob_akm_connected_set(cols, ncol, nrow, worker_col.encode(), firm_col.encode(), C.byref(h)))
+    try:
+        n, kept, nw, nf, comps = (C.c_int64() for _ in range(5))
+        keep = C.POINTER(C.c_uint8)()
+        wi, fi = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+        N.check(lib.ob_akm_set_get(h, C.byref(n), C.byref(keep), C.byref(kept), C.byref(wi), C.byref(fi),
+                                   C.byref(nw), C.byref(nf), C.byref(comps)))
+
+        def arr(p, m, dtype):
+            return np.ctypeslib.as_array(p, shape=(m,)).astype(dtype) if m else np.zeros(0, dtype)
+
+        return {"keep": arr(keep, n.value, bool), "worker_idx": arr(wi, kept.value, np.int32),
+                "firm_idx": arr(fi, kept.value, np.int32),
+                "worker_ids": [lib.ob_akm_set_id(h, 0, i).decode() for i in range(nw.value)],
+                "firm_ids": [lib.ob_akm_set_id(h, 1, i).decode() for i in range(nf.value)],
+                "n_components": int(comps.value)}
+    finally:
+        lib.ob_akm_set_free(h)
+
+
+def akm_demean(v, worker_idx, firm_idx, n_workers: int, n_firms: int, tol: float = 1e-8, max_iters: int = 1000,
+               device: int | None = None):
+    """akm.rs:452-527 for a batch of columns on the GPU (``ob_akm_demean``). ``v``: (n,) or (n, c); a
+    Fortran-ordered view with a longer leading dimension is passed as it is. Returns (demeaned,
+    iterations int32 (c,), converged bool (c,)); a column is the same bytes alone or in a batch."""
+    v = np.asarray(v, dtype=np.float64)
+    one = v.ndim == 1
+    v2 = v.reshape(-1, 1) if one else v
+    if v2.ndim != 2:
+        raise ValueError("v must be (n,) or (n, c)")
+    n, c = v2.shape
+    if not (v2.strides[0] == 8 and v2.strides[1] % 8 == 0 and v2.strides[1] >= 8 * max(n, 1)):
+        v2 = np.asfortranarray(v2)
+    ldv = v2.strides[1] // 8 if c > 1 and n > 0 else max(n, 1)
+    wi = np.ascontiguousarray(worker_idx, dtype=np.int32)
+    fi = np.ascontiguousarray(firm_idx, dtype=np.int32)
+    if wi.shape != (n,) or fi.shape != (n,):
+        raise ValueError("one worker and one firm index per row")
+    out = np.full((c, ldv), np.nan).T[:n]  # the same leading dimension; the padding is never written
+    iters, conv = np.zeros(c, np.int32), np.zeros(c, np.int32)
+    N.check(N.lib().ob_akm_demean(N.context(device), _dp(v2), ldv, n, c, _i32(wi), _i32(fi), int(n_workers),
+                                  int(n_firms), float(tol), int(max_iters), _dp(out), _i32(iters), _i32(conv)))
+    return (out[:, 0] if one else out), iters, conv.astype(bool)
+
+
+def akm_recover_fe(r, worker_idx, firm_idx, n_workers: int, n_firms: int, tol: float = 1e-8, max_iters: int = 1000,
+                   device: int | None = None):
+    """akm.rs:530-621 on the GPU (``ob_akm_recover_fe``), the psi[0] normalisation included. Returns
+    (alpha, psi, iterations, converged)."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    n = len(r)
+    wi = np.ascontiguousarray(worker_idx, dtype=np.int32)
+    fi = np.ascontiguousarray(firm_idx, dtype=np.int32)
+    if wi.shape != (n,) or fi.shape != (n,):
+        raise ValueError("one worker and one firm index per row")
+    alpha, psi = np.zeros(int(n_workers)), np.zeros(int(n_firms))
+    iters, conv = C.c_int32(0), C.c_int32(0)
+    N.check(N.lib().ob_akm_recover_fe(N.context(device), _dp(r), n, _i32(wi), _i32(fi), int(n_workers), int(n_firms),
+                                      float(tol), int(max_iters), _dp(alpha), _dp(psi), C.byref(iters), C.byref(conv)))
+    return alpha, psi, int(iters.value), bool(conv.value)
