@@ -19,6 +19,7 @@
 #include "ob_akm.hpp"
 #include "ob_common.hpp"
 #include "ob_frame.hpp"
+#include "ob_linalg.hpp"
 
 struct ob_akm_set {
   std::vector<uint8_t> keep;
@@ -201,33 +202,6 @@ struct PlanHolder {
   ~PlanHolder() { akm_plan_free(p); }
 };
 
-// nalgebra Cholesky::new (left-looking, the lower triangle) and solve; false on a pivot that is zero,
-// negative or NaN. a: k x k column-major, overwritten; b: the right side, then the solution.
-bool cholesky_solve(std::vector<double>& a, int k, std::vector<double>& b) {
-  for (int j = 0; j < k; ++j) {
-    for (int i = j; i < k; ++i) {
-      double v = a[i + (size_t)j * k];
-      for (int c = 0; c < j; ++c) v -= a[j + (size_t)c * k] * a[i + (size_t)c * k];
-      a[i + (size_t)j * k] = v;
-    }
-    const double diag = a[j + (size_t)j * k];
-    if (!(diag != 0.0 && diag >= 0.0)) return false;
-    const double den = std::sqrt(diag);
-    for (int i = j; i < k; ++i) a[i + (size_t)j * k] = (i == j) ? den : a[i + (size_t)j * k] / den;
-  }
-  for (int i = 0; i < k; ++i) {
-    double v = b[i];
-    for (int c = 0; c < i; ++c) v -= a[i + (size_t)c * k] * b[c];
-    b[i] = v / a[i + (size_t)i * k];
-  }
-  for (int i = k - 1; i >= 0; --i) {
-    double v = b[i];
-    for (int c = i + 1; c < k; ++c) v -= a[c + (size_t)i * k] * b[c];
-    b[i] = v / a[i + (size_t)i * k];
-  }
-  return true;
-}
-
 int akm_run(ob_ctx* ctx, const Frame& f, const ob_akm_config* cfg, ob_akm_results* res) {
   const int k = cfg->n_controls;
   if (k < 0 || (k > 0 && !cfg->controls)) return fail(OB_E_INVALID, "bad name list");
@@ -284,7 +258,9 @@ int akm_run(ob_ctx* ctx, const Frame& f, const ob_akm_config* cfg, ob_akm_result
       res->beta[a] = g[(size_t)(a + 1) * nc];
       for (int b = 0; b < k; ++b) xtx[a + (size_t)b * k] = g[(size_t)(a + 1) * nc + b + 1];
     }
-    if (!cholesky_solve(xtx, k, res->beta)) return convergence_failed("OLS design matrix is singular");
+    // the back substitution subtracts term by term, which is not nalgebra's order
+    if (!chol_factor_solve(xtx.data(), k, res->beta.data(), BackSub::Sequential))
+      return convergence_failed("OLS design matrix is singular");
   }
   OB_TRY(akm_residual(plan.p, res->beta.data(), &ms));
   res->ols_ms += ms;

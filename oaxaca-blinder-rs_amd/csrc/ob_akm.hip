@@ -9,7 +9,7 @@
 //   akm_shift_kernel         the psi[0] normalisation
 //   akm_gram_kernel          V'V of the demeaned batch, per-block partials
 //   akm_rowsum_kernel        sum y, tss and rss terms, per-block partials
-//   akm_reduce_kernel        partials added in a fixed order
+//   ob_ordered_sum_kernel    partials added in a fixed order (ob_device.hpp)
 //   akm_resid_kernel         r = y - X beta
 //
 // Rows are grouped twice, by worker and by firm, as CSR lists of row positions (ascending inside a
@@ -25,18 +25,12 @@
 #include <vector>
 
 #include "ob_akm.hpp"
+#include "ob_device.hpp"
 #include "ob_engine.hpp"
+#include "ob_hip.hpp"
 #include "ob_options.hpp"
 
 namespace {
-
-#define AKM_OK(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, \
-                      __LINE__);                                                         \
-  } while (0)
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
@@ -75,12 +69,6 @@ __device__ __forceinline__ int seg_role(const Seg& s, int* group) {
   const int64_t slot = (int64_t)(b - s.n_large - mblocks) * kBlock + tid;
   *group = slot < s.n_small ? s.order[(int64_t)s.n_large + s.n_medium + slot] : -1;
   return kRoleLane;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 // Every thread receives the waves' sums added in wave order. red: kWaves doubles of LDS.
@@ -304,21 +292,6 @@ __global__ __launch_bounds__(kBlock) void akm_gram_kernel(const double* __restri
   }
 }
 
-// out[e] = partial[e][0 .. m) added by thread in stride order, then a fixed LDS tree. One block per sum.
-__global__ __launch_bounds__(kBlock) void akm_reduce_kernel(const double* partial, uint32_t m, double* out) {
-  __shared__ double red[kBlock];
-  const int tid = threadIdx.x;
-  double s = 0.0;
-  for (uint32_t b = tid; b < m; b += kBlock) s += partial[(size_t)blockIdx.x * m + b];
-  red[tid] = s;
-  __syncthreads();
-  for (int h = kBlock / 2; h > 0; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[blockIdx.x] = red[0];
-}
-
 enum { kSumY = 0, kSumTss = 1, kSumRss = 2 };
 
 // partial[block] = this block's rows (block-strided) of y, (y - mean)^2 or (y - pred)^2 with
@@ -367,46 +340,21 @@ __global__ __launch_bounds__(kBlock) void akm_resid_kernel(const double* __restr
   r[row] = v;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) {
-    bytes = std::max<size_t>(bytes, 16);
-    if (p && cap >= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  double* d() const { return static_cast<double*>(p); }
-  int32_t* i() const { return static_cast<int32_t*>(p); }
-};
-
+// The elapsed time of a stretch of one stream.
 struct Timer {
-  hipEvent_t a = nullptr, b = nullptr;
+  Events<2> ev;
   hipStream_t st = nullptr;
-  ~Timer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
   hipError_t start(hipStream_t s) {
     st = s;
-    hipError_t e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = hipEventRecord(a, st);
-    return e;
+    const hipError_t e = ev.create();
+    return e == hipSuccess ? hipEventRecord(ev.e[0], st) : e;
   }
   // the stream must be idle after this
   hipError_t stop(double* ms) {
-    hipError_t e = hipEventRecord(b, st);
-    if (e == hipSuccess) e = hipEventSynchronize(b);
+    hipError_t e = hipEventRecord(ev.e[1], st);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.e[1]);
     float f = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, ev.e[0], ev.e[1]);
     if (ms) *ms = f;
     return e;
   }
@@ -417,8 +365,6 @@ struct Grouping {
   Seg seg = {};
   unsigned blocks = 0;
 };
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
 
@@ -458,17 +404,17 @@ int build_grouping(hipStream_t st, int64_t n, const int32_t* idx, int64_t n_grou
   order.insert(order.end(), small.begin(), small.end());
   const int64_t blocks = (int64_t)large.size() + ((int64_t)medium.size() + kWaves - 1) / kWaves +
                          ((int64_t)small.size() + kBlock - 1) / kBlock;
-  AKM_OK(g.ptr.alloc(sizeof(int32_t) * ptr.size()));
-  AKM_OK(g.rows.alloc(sizeof(int32_t) * rows.size()));
-  AKM_OK(g.order.alloc(sizeof(int32_t) * order.size()));
-  AKM_OK(hipMemcpyAsync(g.ptr.p, ptr.data(), sizeof(int32_t) * ptr.size(), hipMemcpyHostToDevice, st));
-  if (n) AKM_OK(hipMemcpyAsync(g.rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, st));
+  OB_HIP(g.ptr.alloc(sizeof(int32_t) * ptr.size()));
+  OB_HIP(g.rows.alloc(sizeof(int32_t) * rows.size()));
+  OB_HIP(g.order.alloc(sizeof(int32_t) * order.size()));
+  OB_HIP(hipMemcpyAsync(g.ptr.p, ptr.data(), sizeof(int32_t) * ptr.size(), hipMemcpyHostToDevice, st));
+  if (n) OB_HIP(hipMemcpyAsync(g.rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, st));
   if (n_groups)
-    AKM_OK(hipMemcpyAsync(g.order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, st));
-  AKM_OK(hipStreamSynchronize(st));  // the host vectors go away
-  g.seg.ptr = g.ptr.i();
-  g.seg.rows = g.rows.i();
-  g.seg.order = g.order.i();
+    OB_HIP(hipMemcpyAsync(g.order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, st));
+  OB_HIP(hipStreamSynchronize(st));  // the host vectors go away
+  g.seg.ptr = g.ptr.as<int32_t>();
+  g.seg.rows = g.rows.as<int32_t>();
+  g.seg.order = g.order.as<int32_t>();
   g.seg.n_large = (int32_t)large.size();
   g.seg.n_medium = (int32_t)medium.size();
   g.seg.n_small = (int32_t)small.size();
@@ -480,11 +426,11 @@ int poll_interval() { return std::max(1, opt_int(Opt::AkmPoll, kAkmPollDefault))
 
 // state: [iters[m], done[m]] as int32; zeroed, then max_iters = 0 marks every loop done at once
 int init_state(AkmPlan* p, int m, int64_t max_iters, hipStream_t st) {
-  AKM_OK(p->state.alloc(sizeof(int32_t) * 2 * (size_t)m));
+  OB_HIP(p->state.alloc(sizeof(int32_t) * 2 * (size_t)m));
   std::vector<int32_t> h(2 * (size_t)m, 0);
   if (max_iters <= 0) std::fill(h.begin() + m, h.end(), 1);
-  AKM_OK(hipMemcpyAsync(p->state.p, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice, st));
-  AKM_OK(hipStreamSynchronize(st));
+  OB_HIP(hipMemcpyAsync(p->state.p, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice, st));
+  OB_HIP(hipStreamSynchronize(st));
   return OB_OK;
 }
 
@@ -493,7 +439,7 @@ int init_state(AkmPlan* p, int m, int64_t max_iters, hipStream_t st) {
 int akm_plan_create(ob_ctx* ctx, int64_t n, const int32_t* widx, const int32_t* fidx, int64_t n_workers,
                     int64_t n_firms, AkmPlan** out) {
   *out = nullptr;
-  AKM_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   AkmPlan* p = new AkmPlan();
   p->ctx = ctx;
@@ -503,9 +449,9 @@ int akm_plan_create(ob_ctx* ctx, int64_t n, const int32_t* widx, const int32_t* 
   int rc = build_grouping(st, n, widx, n_workers, p->w);
   if (rc == OB_OK) rc = build_grouping(st, n, fidx, n_firms, p->f);
   auto upload = [&](DevBuf& b, const int32_t* src) -> int {
-    AKM_OK(b.alloc(sizeof(int32_t) * (size_t)n));
-    if (n) AKM_OK(hipMemcpyAsync(b.p, src, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    AKM_OK(hipStreamSynchronize(st));
+    OB_HIP(b.alloc(sizeof(int32_t) * (size_t)n));
+    if (n) OB_HIP(hipMemcpyAsync(b.p, src, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    OB_HIP(hipStreamSynchronize(st));
     return OB_OK;
   };
   if (rc == OB_OK) rc = upload(p->widx, widx);
@@ -526,26 +472,26 @@ void akm_plan_free(AkmPlan* p) {
 
 int akm_demean(AkmPlan* p, const double* v, int n_cols, double tol, int64_t max_iters, double* out,
                int32_t* iterations, int32_t* converged, double* ms, int* launches) {
-  AKM_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int64_t n = p->n;
   const size_t bytes = sizeof(double) * (size_t)n * n_cols;
   p->ncols = n_cols;
   if (launches) *launches = 3;
   const int32_t cap = (int32_t)std::min<int64_t>(std::max<int64_t>(max_iters, 0), INT32_MAX);
-  AKM_OK(p->raw.alloc(bytes));
-  AKM_OK(p->v.alloc(bytes));
-  AKM_OK(p->mid.alloc(bytes));
-  AKM_OK(p->dpart.alloc(sizeof(double) * (size_t)std::max(p->f.blocks, 1u) * n_cols));
-  if (n) AKM_OK(hipMemcpyAsync(p->raw.p, v, bytes, hipMemcpyHostToDevice, st));
-  if (n) AKM_OK(hipMemcpyAsync(p->v.p, p->raw.p, bytes, hipMemcpyDeviceToDevice, st));
+  OB_HIP(p->raw.alloc(bytes));
+  OB_HIP(p->v.alloc(bytes));
+  OB_HIP(p->mid.alloc(bytes));
+  OB_HIP(p->dpart.alloc(sizeof(double) * (size_t)std::max(p->f.blocks, 1u) * n_cols));
+  if (n) OB_HIP(hipMemcpyAsync(p->raw.p, v, bytes, hipMemcpyHostToDevice, st));
+  if (n) OB_HIP(hipMemcpyAsync(p->v.p, p->raw.p, bytes, hipMemcpyDeviceToDevice, st));
   // mid holds the worker pass's output; a frozen column of it is neither written nor read again
-  AKM_OK(hipMemsetAsync(p->dpart.p, 0, p->dpart.cap, st));
+  OB_HIP(hipMemsetAsync(p->dpart.p, 0, p->dpart.cap, st));
   OB_TRY(init_state(p, n_cols, cap, st));
-  int32_t* iters = p->state.i();
+  int32_t* iters = p->state.as<int32_t>();
   int32_t* done = iters + n_cols;
   Timer tm;
-  AKM_OK(tm.start(st));
+  OB_HIP(tm.start(st));
   std::vector<int32_t> h(2 * (size_t)n_cols, 0);
   const int poll = poll_interval();
   for (int64_t it = 0; it < cap;) {
@@ -560,39 +506,39 @@ int akm_demean(AkmPlan* p, const double* v, int n_cols, double tol, int64_t max_
       hipLaunchKernelGGL(akm_flag_kernel, dim3(n_cols), dim3(kBlock), 0, st, p->dpart.d(), (int)p->f.blocks, n_cols,
                          tol, cap, iters, done);
     }
-    AKM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     it += burst;
-    AKM_OK(hipMemcpyAsync(h.data(), p->state.p, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, st));
-    AKM_OK(hipStreamSynchronize(st));
+    OB_HIP(hipMemcpyAsync(h.data(), p->state.p, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, st));
+    OB_HIP(hipStreamSynchronize(st));
     if (std::all_of(h.begin() + n_cols, h.end(), [](int32_t d) { return d != 0; })) break;
   }
-  AKM_OK(tm.stop(ms));
+  OB_HIP(tm.stop(ms));
   for (int c = 0; c < n_cols; ++c) {
     if (iterations) iterations[c] = h[c];
     if (converged) converged[c] = (int64_t)h[c] < max_iters ? 1 : 0;  // akm.rs:519
   }
   if (out && n) {
-    AKM_OK(hipMemcpyAsync(out, p->v.p, bytes, hipMemcpyDeviceToHost, st));
-    AKM_OK(hipStreamSynchronize(st));
+    OB_HIP(hipMemcpyAsync(out, p->v.p, bytes, hipMemcpyDeviceToHost, st));
+    OB_HIP(hipStreamSynchronize(st));
   }
   return OB_OK;
 }
 
 int akm_gram(AkmPlan* p, double* g, double* ms) {
-  AKM_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int c = p->ncols;
   if (c < 1 || c > kGramMaxC) return fail(OB_E_INVALID, "akm_gram: bad column count");
   const unsigned nblk = (unsigned)std::max<int64_t>(1, std::min<int64_t>((p->n + kGramRows - 1) / kGramRows, kGramMaxBlocks));
-  AKM_OK(p->scratch.alloc(sizeof(double) * (size_t)c * c * nblk));
-  AKM_OK(p->small.alloc(sizeof(double) * (size_t)c * c));
+  OB_HIP(p->scratch.alloc(sizeof(double) * (size_t)c * c * nblk));
+  OB_HIP(p->small.alloc(sizeof(double) * (size_t)c * c));
   Timer tm;
-  AKM_OK(tm.start(st));
+  OB_HIP(tm.start(st));
   hipLaunchKernelGGL(akm_gram_kernel, dim3(nblk), dim3(kBlock), 0, st, p->v.d(), p->n, c, p->scratch.d());
-  hipLaunchKernelGGL(akm_reduce_kernel, dim3(c * c), dim3(kBlock), 0, st, p->scratch.d(), nblk, p->small.d());
-  AKM_OK(hipGetLastError());
-  AKM_OK(hipMemcpyAsync(g, p->small.p, sizeof(double) * (size_t)c * c, hipMemcpyDeviceToHost, st));
-  AKM_OK(tm.stop(ms));
+  hipLaunchKernelGGL(ob_ordered_sum_kernel<>, dim3(c * c), dim3(kSumBlock), 0, st, p->scratch.d(), nblk, p->small.d());
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipMemcpyAsync(g, p->small.p, sizeof(double) * (size_t)c * c, hipMemcpyDeviceToHost, st));
+  OB_HIP(tm.stop(ms));
   return OB_OK;
 }
 
@@ -601,9 +547,9 @@ namespace {
 // beta on the device, after alpha and psi in no buffer of theirs: the tail of `small`
 int upload_beta(AkmPlan* p, const double* beta, hipStream_t st, double** dbeta) {
   const int k = p->ncols - 1;
-  AKM_OK(p->small.alloc(sizeof(double) * (size_t)kGramMaxC * kGramMaxC));
-  if (k > 0) AKM_OK(hipMemcpyAsync(p->small.p, beta, sizeof(double) * k, hipMemcpyHostToDevice, st));
-  AKM_OK(hipStreamSynchronize(st));
+  OB_HIP(p->small.alloc(sizeof(double) * (size_t)kGramMaxC * kGramMaxC));
+  if (k > 0) OB_HIP(hipMemcpyAsync(p->small.p, beta, sizeof(double) * k, hipMemcpyHostToDevice, st));
+  OB_HIP(hipStreamSynchronize(st));
   *dbeta = p->small.d();
   return OB_OK;
 }
@@ -611,111 +557,111 @@ int upload_beta(AkmPlan* p, const double* beta, hipStream_t st, double** dbeta) 
 }  // namespace
 
 int akm_residual(AkmPlan* p, const double* beta, double* ms) {
-  AKM_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   double* dbeta = nullptr;
   OB_TRY(upload_beta(p, beta, st, &dbeta));
-  AKM_OK(p->r.alloc(sizeof(double) * (size_t)p->n));
+  OB_HIP(p->r.alloc(sizeof(double) * (size_t)p->n));
   Timer tm;
-  AKM_OK(tm.start(st));
+  OB_HIP(tm.start(st));
   if (p->n)
     hipLaunchKernelGGL(akm_resid_kernel, dim3(blocks_for(p->n)), dim3(kBlock), 0, st, p->raw.d(), p->n, p->ncols, dbeta,
                        p->r.d());
-  AKM_OK(hipGetLastError());
-  AKM_OK(tm.stop(ms));
+  OB_HIP(hipGetLastError());
+  OB_HIP(tm.stop(ms));
   return OB_OK;
 }
 
 int akm_recover(AkmPlan* p, const double* r, double tol, int64_t max_iters, double* alpha, double* psi,
                 int32_t* iterations, int32_t* converged, double* ms) {
-  AKM_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int64_t n = p->n, nw = p->n_workers, nf = p->n_firms;
   const int32_t cap = (int32_t)std::min<int64_t>(std::max<int64_t>(max_iters, 0), INT32_MAX);
-  AKM_OK(p->r.alloc(sizeof(double) * (size_t)n));
-  if (r && n) AKM_OK(hipMemcpyAsync(p->r.p, r, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  AKM_OK(p->alpha.alloc(sizeof(double) * (size_t)nw));
-  AKM_OK(p->psi.alloc(sizeof(double) * (size_t)nf));
-  AKM_OK(hipMemsetAsync(p->alpha.p, 0, p->alpha.cap, st));
-  AKM_OK(hipMemsetAsync(p->psi.p, 0, p->psi.cap, st));
+  OB_HIP(p->r.alloc(sizeof(double) * (size_t)n));
+  if (r && n) OB_HIP(hipMemcpyAsync(p->r.p, r, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  OB_HIP(p->alpha.alloc(sizeof(double) * (size_t)nw));
+  OB_HIP(p->psi.alloc(sizeof(double) * (size_t)nf));
+  OB_HIP(hipMemsetAsync(p->alpha.p, 0, p->alpha.cap, st));
+  OB_HIP(hipMemsetAsync(p->psi.p, 0, p->psi.cap, st));
   const unsigned nb = p->w.blocks + p->f.blocks;
-  AKM_OK(p->dpart.alloc(sizeof(double) * (size_t)std::max(nb, 1u)));
-  AKM_OK(hipMemsetAsync(p->dpart.p, 0, p->dpart.cap, st));
+  OB_HIP(p->dpart.alloc(sizeof(double) * (size_t)std::max(nb, 1u)));
+  OB_HIP(hipMemsetAsync(p->dpart.p, 0, p->dpart.cap, st));
   OB_TRY(init_state(p, 1, cap, st));
-  int32_t* iters = p->state.i();
+  int32_t* iters = p->state.as<int32_t>();
   int32_t* done = iters + 1;
   Timer tm;
-  AKM_OK(tm.start(st));
+  OB_HIP(tm.start(st));
   int32_t h[2] = {0, cap <= 0 ? 1 : 0};
   const int poll = poll_interval();
   for (int64_t it = 0; it < cap;) {
     const int64_t burst = std::min<int64_t>(poll, cap - it);
     for (int64_t b = 0; b < burst; ++b) {
       if (p->w.blocks)
-        hipLaunchKernelGGL(akm_fe_kernel, dim3(p->w.blocks), dim3(kBlock), 0, st, p->w.seg, p->r.d(), p->fidx.i(),
-                           p->psi.d(), p->alpha.d(), done, p->dpart.d());
+        hipLaunchKernelGGL(akm_fe_kernel, dim3(p->w.blocks), dim3(kBlock), 0, st, p->w.seg, p->r.d(),
+                           p->fidx.as<int32_t>(), p->psi.d(), p->alpha.d(), done, p->dpart.d());
       if (p->f.blocks)
-        hipLaunchKernelGGL(akm_fe_kernel, dim3(p->f.blocks), dim3(kBlock), 0, st, p->f.seg, p->r.d(), p->widx.i(),
-                           p->alpha.d(), p->psi.d(), done, p->dpart.d() + p->w.blocks);
+        hipLaunchKernelGGL(akm_fe_kernel, dim3(p->f.blocks), dim3(kBlock), 0, st, p->f.seg, p->r.d(),
+                           p->widx.as<int32_t>(), p->alpha.d(), p->psi.d(), done, p->dpart.d() + p->w.blocks);
       hipLaunchKernelGGL(akm_fe_flag_kernel, dim3(1), dim3(kBlock), 0, st, p->dpart.d(), (int)nb, tol, cap, iters, done);
     }
-    AKM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     it += burst;
-    AKM_OK(hipMemcpyAsync(h, p->state.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    AKM_OK(hipStreamSynchronize(st));
+    OB_HIP(hipMemcpyAsync(h, p->state.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    OB_HIP(hipStreamSynchronize(st));
     if (h[1] != 0) break;
   }
   if (iterations) *iterations = h[0];
   const bool ok = (int64_t)h[0] < max_iters;  // akm.rs:604
   if (converged) *converged = ok ? 1 : 0;
   if (ok && nf > 0) {  // akm.rs:611-618
-    AKM_OK(p->scratch.alloc(sizeof(double)));
-    AKM_OK(hipMemcpyAsync(p->scratch.p, p->psi.p, sizeof(double), hipMemcpyDeviceToDevice, st));
+    OB_HIP(p->scratch.alloc(sizeof(double)));
+    OB_HIP(hipMemcpyAsync(p->scratch.p, p->psi.p, sizeof(double), hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(akm_shift_kernel, dim3(blocks_for(nf)), dim3(kBlock), 0, st, p->psi.d(), nf, p->scratch.d(), -1.0);
     if (nw)
       hipLaunchKernelGGL(akm_shift_kernel, dim3(blocks_for(nw)), dim3(kBlock), 0, st, p->alpha.d(), nw, p->scratch.d(),
                          1.0);
-    AKM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
   }
-  AKM_OK(tm.stop(ms));
-  if (alpha && nw) AKM_OK(hipMemcpyAsync(alpha, p->alpha.p, sizeof(double) * (size_t)nw, hipMemcpyDeviceToHost, st));
-  if (psi && nf) AKM_OK(hipMemcpyAsync(psi, p->psi.p, sizeof(double) * (size_t)nf, hipMemcpyDeviceToHost, st));
-  AKM_OK(hipStreamSynchronize(st));
+  OB_HIP(tm.stop(ms));
+  if (alpha && nw) OB_HIP(hipMemcpyAsync(alpha, p->alpha.p, sizeof(double) * (size_t)nw, hipMemcpyDeviceToHost, st));
+  if (psi && nf) OB_HIP(hipMemcpyAsync(psi, p->psi.p, sizeof(double) * (size_t)nf, hipMemcpyDeviceToHost, st));
+  OB_HIP(hipStreamSynchronize(st));
   return OB_OK;
 }
 
 int akm_r2(AkmPlan* p, const double* beta, double* tss, double* rss, double* ms) {
-  AKM_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int64_t n = p->n;
   const int c = p->ncols;
   double* dbeta = nullptr;
   OB_TRY(upload_beta(p, beta, st, &dbeta));
   const unsigned nblk = (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_for(n), kSumMaxBlocks));
-  AKM_OK(p->scratch.alloc(sizeof(double) * ((size_t)nblk + 1)));
+  OB_HIP(p->scratch.alloc(sizeof(double) * ((size_t)nblk + 1)));
   double* part = p->scratch.d();
   double* total = part + nblk;
   Timer tm;
-  AKM_OK(tm.start(st));
+  OB_HIP(tm.start(st));
   auto finish = [&](double* host) -> int {
-    hipLaunchKernelGGL(akm_reduce_kernel, dim3(1), dim3(kBlock), 0, st, part, nblk, total);
-    AKM_OK(hipGetLastError());
-    AKM_OK(hipMemcpyAsync(host, total, sizeof(double), hipMemcpyDeviceToHost, st));
-    AKM_OK(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(ob_ordered_sum_kernel<>, dim3(1), dim3(kSumBlock), 0, st, part, nblk, total);
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipMemcpyAsync(host, total, sizeof(double), hipMemcpyDeviceToHost, st));
+    OB_HIP(hipStreamSynchronize(st));
     return OB_OK;
   };
   double ysum = 0.0;
   hipLaunchKernelGGL(akm_rowsum_kernel<kSumY>, dim3(nblk), dim3(kBlock), 0, st, p->raw.d(), n, c, 0.0, dbeta,
-                     p->widx.i(), p->fidx.i(), p->alpha.d(), p->psi.d(), part);
+                     p->widx.as<int32_t>(), p->fidx.as<int32_t>(), p->alpha.d(), p->psi.d(), part);
   OB_TRY(finish(&ysum));
   const double mean = ysum / (double)n;
   hipLaunchKernelGGL(akm_rowsum_kernel<kSumTss>, dim3(nblk), dim3(kBlock), 0, st, p->raw.d(), n, c, mean, dbeta,
-                     p->widx.i(), p->fidx.i(), p->alpha.d(), p->psi.d(), part);
+                     p->widx.as<int32_t>(), p->fidx.as<int32_t>(), p->alpha.d(), p->psi.d(), part);
   OB_TRY(finish(tss));
   hipLaunchKernelGGL(akm_rowsum_kernel<kSumRss>, dim3(nblk), dim3(kBlock), 0, st, p->raw.d(), n, c, mean, dbeta,
-                     p->widx.i(), p->fidx.i(), p->alpha.d(), p->psi.d(), part);
+                     p->widx.as<int32_t>(), p->fidx.as<int32_t>(), p->alpha.d(), p->psi.d(), part);
   OB_TRY(finish(rss));
-  AKM_OK(tm.stop(ms));
+  OB_HIP(tm.stop(ms));
   return OB_OK;
 }
 

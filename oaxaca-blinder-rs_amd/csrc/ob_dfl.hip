@@ -3,7 +3,8 @@
 //   ob_logit_pass_kernel   one Newton pass of math/logit.rs:43-82 over column-major X: p = clamp(
 //                          sigmoid(x beta)), the information matrix X^T diag(p (1 - p)) X and the
 //                          gradient X^T (y - p), as per-wave partial sums
-//   ob_dfl_reduce_kernel   the partials of one sum added in unit order, then a fixed LDS tree
+//   ob_ordered_sum_kernel  the partials of one sum added in unit order, then a fixed LDS tree
+//                          (ob_device.hpp)
 //   ob_logit_probs_kernel  p at a given beta (logit.rs:108-110, the unconverged exit)
 //   ob_kde_kernel          sum_i w_i exp(-u^2 / 2), u = (x_g - d_i) / h (math/kde.rs:31-38), four
 //                          grid points per thread over one chunk of the data
@@ -23,20 +24,15 @@
 #include <cmath>
 #include <vector>
 
+#include "ob_device.hpp"
 #include "ob_dfl.hpp"
+#include "ob_hip.hpp"
+#include "ob_linalg.hpp"
 #include "ob_match.hpp"
 
 namespace {
 
 typedef double ob_d4 __attribute__((ext_vector_type(4)));
-
-#define DFL_OK(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, \
-                      __LINE__);                                                         \
-  } while (0)
 
 constexpr int kBlock = 256;
 constexpr int kLgWaves = kBlock / 64;
@@ -157,21 +153,6 @@ __global__ __launch_bounds__(kBlock) void ob_logit_pass_kernel(const LogitArgs a
   }
 }
 
-// out[e] = partial[e][0 .. m) added by thread in stride order, then a fixed LDS tree. One block per sum.
-__global__ __launch_bounds__(kBlock) void ob_dfl_reduce_kernel(const double* partial, uint32_t m, double* out) {
-  __shared__ double red[kBlock];
-  const int tid = threadIdx.x;
-  double s = 0.0;
-  for (uint32_t b = tid; b < m; b += kBlock) s += partial[(size_t)blockIdx.x * m + b];
-  red[tid] = s;
-  __syncthreads();
-  for (int h = kBlock / 2; h > 0; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[blockIdx.x] = red[0];
-}
-
 template <bool CLAMP = true>
 __global__ __launch_bounds__(kBlock) void ob_logit_probs_kernel(const double* x, int64_t ldx, const double* beta,
                                                                  int64_t n, int k, double* probs) {
@@ -207,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void ob_kde_kernel(const double* data, cons
   }
 #pragma unroll
   for (int q = 0; q < kKdeGp; ++q) {
-    double v = acc[q];
+    double v = acc[q];  // not wave_sum(): the call schedules this kernel differently
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if (lane == 0) red[wave][q] = v;
@@ -229,113 +210,18 @@ __global__ __launch_bounds__(kBlock) void ob_kde_finish_kernel(const double* par
   density[g] = s * 0.3989422804014327 / h;  // 1 / sqrt(2 pi): gaussian_kernel's factor (kde.rs:4-6)
 }
 
-// One hipMalloc that frees itself.
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-  double* d() const { return static_cast<double*>(p); }
-};
-
-struct Events {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Events() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 template <int NCB, bool CLAMP = true>
 int launch_logit_pass(const LogitArgs& a, hipStream_t s) {
   const size_t lds = sizeof(double) * kLgWaves * (16 * NCB * kLgStride + kLgRowVecs);
-  DFL_OK(hipFuncSetAttribute((const void*)ob_logit_pass_kernel<NCB, CLAMP>,
+  OB_HIP(hipFuncSetAttribute((const void*)ob_logit_pass_kernel<NCB, CLAMP>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((ob_logit_pass_kernel<NCB, CLAMP>), dim3((a.units + kLgWaves - 1) / kLgWaves), dim3(kBlock), lds, s, a);
-  DFL_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   return OB_OK;
-}
-
-// nalgebra Cholesky::new + solve on the host (the order of ob_device.hpp's wave_cholesky): m is
-// k x k column-major, lower triangle filled; false iff a pivot is zero, negative or NaN.
-bool host_chol_solve(std::vector<double>& m, int k, std::vector<double>& b) {
-  for (int j = 0; j < k; ++j) {
-    for (int i = j; i < k; ++i) {
-      double v = m[i + (size_t)j * k];
-      for (int c = 0; c < j; ++c) v = -m[j + (size_t)c * k] * m[i + (size_t)c * k] + v;
-      m[i + (size_t)j * k] = v;
-    }
-    const double diag = m[j + (size_t)j * k];
-    if (!(diag != 0.0 && diag >= 0.0)) return false;
-    const double den = std::sqrt(diag);
-    for (int i = j; i < k; ++i) m[i + (size_t)j * k] = (i == j) ? den : m[i + (size_t)j * k] / den;
-  }
-  for (int i = 0; i < k; ++i) {
-    const double coeff = b[i] / m[i + (size_t)i * k];
-    for (int r = i + 1; r < k; ++r) b[r] -= coeff * m[r + (size_t)i * k];
-    b[i] = coeff;
-  }
-  for (int i = k - 1; i >= 0; --i) {
-    double part = 0.0;
-    for (int r = i + 1; r < k; ++r) part += m[r + (size_t)i * k] * b[r];
-    b[i] = (b[i] - part) / m[i + (size_t)i * k];
-  }
-  return true;
-}
-
-// nalgebra LU::new (partial pivoting by the largest |entry|; a zero pivot column is skipped) + solve on
-// the host: m is k x k column-major, full; false iff a diagonal entry of U is zero (logistic.rs:95).
-bool host_lu_solve(std::vector<double>& m, int k, std::vector<double>& b) {
-  for (int i = 0; i < k; ++i) {
-    int piv = i;
-    for (int r = i + 1; r < k; ++r)
-      if (std::fabs(m[r + (size_t)i * k]) > std::fabs(m[piv + (size_t)i * k])) piv = r;
-    if (m[piv + (size_t)i * k] == 0.0) continue;
-    if (piv != i) {
-      for (int c = 0; c < k; ++c) std::swap(m[i + (size_t)c * k], m[piv + (size_t)c * k]);
-      std::swap(b[i], b[piv]);
-    }
-    for (int r = i + 1; r < k; ++r) {
-      const double f = m[r + (size_t)i * k] / m[i + (size_t)i * k];
-      for (int c = i + 1; c < k; ++c) m[r + (size_t)c * k] -= f * m[i + (size_t)c * k];
-      b[r] -= f * b[i];
-    }
-  }
-  for (int i = k - 1; i >= 0; --i) {
-    const double diag = m[i + (size_t)i * k];
-    if (diag == 0.0) return false;
-    double part = b[i];
-    for (int c = i + 1; c < k; ++c) part -= m[i + (size_t)c * k] * b[c];
-    b[i] = part / diag;
-  }
-  return true;
 }
 
 // The Newton loop of both logits. MATCH = false: math/logit.rs:31-118 (dfl_logit). MATCH = true:
 // matching/logistic.rs:31-113 (match_logistic): no clamp, a 1e-6 ridge, LU, scores at the final beta.
-template <bool MATCH>
-int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter, double tol,
-                 double* beta, double* probs, ob::LogitInfo* info);
-
-}  // namespace
-
-namespace ob {
-
-int dfl_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter, double tol,
-              double* beta, double* probs, LogitInfo* info) {
-  return logit_newton<false>(ctx, x, ldx, y, n, k, max_iter, tol, beta, probs, info);
-}
-
-int match_logistic(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter,
-                   double tol, double* beta, double* probs, LogitInfo* info) {
-  return logit_newton<true>(ctx, x, ldx, y, n, k, max_iter, tol, beta, probs, info);
-}
-
-}  // namespace ob
-
-namespace {
-
 template <bool MATCH>
 int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter, double tol,
                  double* beta, double* probs, ob::LogitInfo* info) {
@@ -346,7 +232,7 @@ int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int
     return fail(OB_E_UNSUPPORTED, "logit: %d columns, the kernel takes at most %d (intercept included)", k, kLogitMaxK);
   if ((n + 63) / 64 > (int64_t)0x7fffffff) return fail(OB_E_UNSUPPORTED, "logit: too many rows");
   *info = LogitInfo();
-  DFL_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int ne = k * (k + 1) / 2 + k;
   LogitArgs a = {};
@@ -354,18 +240,17 @@ int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int
   a.spu = (a.nsub + kLgMaxUnits - 1) / kLgMaxUnits;
   a.units = (a.nsub + a.spu - 1) / a.spu;
   DevBuf dx, dy, db, dp, dpart, dsum;
-  DFL_OK(dx.alloc(sizeof(double) * (size_t)n * k));
-  DFL_OK(dy.alloc(sizeof(double) * (size_t)n));
-  DFL_OK(db.alloc(sizeof(double) * k));
-  DFL_OK(dp.alloc(sizeof(double) * (size_t)n));
-  DFL_OK(dpart.alloc(sizeof(double) * (size_t)ne * a.units));
-  DFL_OK(dsum.alloc(sizeof(double) * ne));
-  Events ev;
-  DFL_OK(hipEventCreate(&ev.a));
-  DFL_OK(hipEventCreate(&ev.b));
-  DFL_OK(hipMemcpy2DAsync(dx.p, sizeof(double) * (size_t)n, x, sizeof(double) * (size_t)ldx, sizeof(double) * (size_t)n,
+  OB_HIP(dx.alloc(sizeof(double) * (size_t)n * k));
+  OB_HIP(dy.alloc(sizeof(double) * (size_t)n));
+  OB_HIP(db.alloc(sizeof(double) * k));
+  OB_HIP(dp.alloc(sizeof(double) * (size_t)n));
+  OB_HIP(dpart.alloc(sizeof(double) * (size_t)ne * a.units));
+  OB_HIP(dsum.alloc(sizeof(double) * ne));
+  Events<2> ev;
+  OB_HIP(ev.create());
+  OB_HIP(hipMemcpy2DAsync(dx.p, sizeof(double) * (size_t)n, x, sizeof(double) * (size_t)ldx, sizeof(double) * (size_t)n,
                           (size_t)k, hipMemcpyHostToDevice, st));
-  DFL_OK(hipMemcpyAsync(dy.p, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  OB_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
   a.x = dx.d();
   a.ldx = n;
   a.y = dy.d();
@@ -379,21 +264,21 @@ int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int
   bool converged = false;
   int iterations = max_iter;
   for (int iter = 0; iter < max_iter; ++iter) {
-    DFL_OK(hipMemcpyAsync(db.p, b.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
-    DFL_OK(hipEventRecord(ev.a, st));
+    OB_HIP(hipMemcpyAsync(db.p, b.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+    OB_HIP(hipEventRecord(ev.e[0], st));
     switch (ncb) {
       case 1: OB_TRY((launch_logit_pass<1, !MATCH>(a, st))); break;
       case 2: OB_TRY((launch_logit_pass<2, !MATCH>(a, st))); break;
       case 3: OB_TRY((launch_logit_pass<3, !MATCH>(a, st))); break;
       default: OB_TRY((launch_logit_pass<4, !MATCH>(a, st))); break;
     }
-    hipLaunchKernelGGL(ob_dfl_reduce_kernel, dim3(ne), dim3(kBlock), 0, st, dpart.d(), a.units, dsum.d());
-    DFL_OK(hipGetLastError());
-    DFL_OK(hipEventRecord(ev.b, st));
-    DFL_OK(hipMemcpyAsync(sums.data(), dsum.p, sizeof(double) * ne, hipMemcpyDeviceToHost, st));
-    DFL_OK(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(ob_ordered_sum_kernel<>, dim3(ne), dim3(kSumBlock), 0, st, dpart.d(), a.units, dsum.d());
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipEventRecord(ev.e[1], st));
+    OB_HIP(hipMemcpyAsync(sums.data(), dsum.p, sizeof(double) * ne, hipMemcpyDeviceToHost, st));
+    OB_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
-    DFL_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
     info->ms += ms;
     // information matrix X^T W X (lower triangle from the upper-triangle pair sums) and gradient
     for (int c = 0; c < k; ++c)
@@ -406,7 +291,7 @@ int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int
       }
       if (!host_lu_solve(m, k, step))  // logistic.rs:95
         return fail(OB_E_DIAG, "%sHessian is singular", error_prefix(OB_E_DIAG));
-    } else if (!host_chol_solve(m, k, step)) {  // logit.rs:88-95
+    } else if (!chol_factor_solve(m.data(), k, step.data(), BackSub::Dot)) {  // logit.rs:88-95
       return fail(OB_E_LINALG, "%sFailed to solve Information Matrix in Logit. Perfect separation?",
                   error_prefix(OB_E_LINALG));
     }
@@ -422,13 +307,13 @@ int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int
     }
   }
   if ((MATCH || !converged) && probs) {  // logit.rs:108-110; logistic.rs:109-112 always scores at the final beta
-    DFL_OK(hipMemcpyAsync(db.p, b.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+    OB_HIP(hipMemcpyAsync(db.p, b.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(ob_logit_probs_kernel<!MATCH>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, dx.d(),
                        n, db.d(), n, k, dp.d());
-    DFL_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
   }
-  if (probs) DFL_OK(hipMemcpyAsync(probs, dp.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-  DFL_OK(hipStreamSynchronize(st));
+  if (probs) OB_HIP(hipMemcpyAsync(probs, dp.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+  OB_HIP(hipStreamSynchronize(st));
   std::copy(b.begin(), b.end(), beta);
   info->converged = converged ? 1 : 0;
   info->iterations = iterations;
@@ -438,6 +323,16 @@ int logit_newton(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int
 }  // namespace
 
 namespace ob {
+
+int dfl_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter, double tol,
+              double* beta, double* probs, LogitInfo* info) {
+  return logit_newton<false>(ctx, x, ldx, y, n, k, max_iter, tol, beta, probs, info);
+}
+
+int match_logistic(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int k, int max_iter,
+                   double tol, double* beta, double* probs, LogitInfo* info) {
+  return logit_newton<true>(ctx, x, ldx, y, n, k, max_iter, tol, beta, probs, info);
+}
 
 int dfl_kde(ob_ctx* ctx, const double* data, const double* wnorm, int64_t n, const double* grid, int64_t n_grid,
             double bandwidth, double* density, double* ms_out) {
@@ -456,33 +351,32 @@ int dfl_kde(ob_ctx* ctx, const double* data, const double* wnorm, int64_t n, con
   const uint32_t nchunks0 = (uint32_t)std::min<int64_t>(std::min<int64_t>((n + kBlock - 1) / kBlock, want), kKdeMaxChunks);
   const int64_t chunk = (n + nchunks0 - 1) / nchunks0;
   const uint32_t nchunks = (uint32_t)((n + chunk - 1) / chunk);
-  DFL_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf dd, dw, dg, dpart, dout;
-  DFL_OK(dd.alloc(sizeof(double) * (size_t)n));
-  if (wnorm) DFL_OK(dw.alloc(sizeof(double) * (size_t)n));
-  DFL_OK(dg.alloc(sizeof(double) * (size_t)n_grid));
-  DFL_OK(dpart.alloc(sizeof(double) * (size_t)n_grid * nchunks));
-  DFL_OK(dout.alloc(sizeof(double) * (size_t)n_grid));
-  Events ev;
-  DFL_OK(hipEventCreate(&ev.a));
-  DFL_OK(hipEventCreate(&ev.b));
-  DFL_OK(hipMemcpyAsync(dd.p, data, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  if (wnorm) DFL_OK(hipMemcpyAsync(dw.p, wnorm, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  DFL_OK(hipMemcpyAsync(dg.p, grid, sizeof(double) * (size_t)n_grid, hipMemcpyHostToDevice, st));
-  DFL_OK(hipEventRecord(ev.a, st));
+  OB_HIP(dd.alloc(sizeof(double) * (size_t)n));
+  if (wnorm) OB_HIP(dw.alloc(sizeof(double) * (size_t)n));
+  OB_HIP(dg.alloc(sizeof(double) * (size_t)n_grid));
+  OB_HIP(dpart.alloc(sizeof(double) * (size_t)n_grid * nchunks));
+  OB_HIP(dout.alloc(sizeof(double) * (size_t)n_grid));
+  Events<2> ev;
+  OB_HIP(ev.create());
+  OB_HIP(hipMemcpyAsync(dd.p, data, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  if (wnorm) OB_HIP(hipMemcpyAsync(dw.p, wnorm, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  OB_HIP(hipMemcpyAsync(dg.p, grid, sizeof(double) * (size_t)n_grid, hipMemcpyHostToDevice, st));
+  OB_HIP(hipEventRecord(ev.e[0], st));
   hipLaunchKernelGGL(ob_kde_kernel, dim3((unsigned)ggroups, nchunks), dim3(kBlock), 0, st, dd.d(),
                      wnorm ? dw.d() : (const double*)nullptr, 1.0 / (double)n, n, dg.d(), n_grid, bandwidth, chunk,
                      nchunks, dpart.d());
-  DFL_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   hipLaunchKernelGGL(ob_kde_finish_kernel, dim3((unsigned)((n_grid + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                      dpart.d(), nchunks, n_grid, bandwidth, dout.d());
-  DFL_OK(hipGetLastError());
-  DFL_OK(hipEventRecord(ev.b, st));
-  DFL_OK(hipMemcpyAsync(density, dout.p, sizeof(double) * (size_t)n_grid, hipMemcpyDeviceToHost, st));
-  DFL_OK(hipStreamSynchronize(st));
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipEventRecord(ev.e[1], st));
+  OB_HIP(hipMemcpyAsync(density, dout.p, sizeof(double) * (size_t)n_grid, hipMemcpyDeviceToHost, st));
+  OB_HIP(hipStreamSynchronize(st));
   float ms = 0.f;
-  DFL_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
+  OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
   if (ms_out) *ms_out = ms;
   return OB_OK;
 }

@@ -29,6 +29,7 @@
 
 #include "ob_device.hpp"
 #include "ob_engine.hpp"
+#include "ob_hip.hpp"
 #include "ob_heckman.hpp"
 #include "ob_options.hpp"
 #include "ob_spec.h"
@@ -53,14 +54,6 @@ constexpr int64_t kMaxGroupRows = (int64_t)1 << 28;
 #endif
 constexpr size_t kSegEvents = 7;  // level-1 start / end, counts end (resample stream), Gram start / end, reduce end, solve end
 constexpr int kColStride = 96;  // doubles per staged column: 64 rows rotated by (c mod 32), wrap duplicated
-
-#define HIP_OK(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, \
-                      __LINE__);                                                         \
-  } while (0)
 
 struct GramArgs {
   const double* gcols0;  // Gram panel of group A (ob_panel_kernel layout: [sub-tile][c_first..k1-1][96])
@@ -1416,12 +1409,12 @@ int ky_device(int device, ob_ky_tables* out) {
     ob_ky_tables t{};
     uint32_t *off = nullptr, *hot = nullptr;
     uint16_t* list = nullptr;
-    HIP_OK(hipMalloc(&off, sizeof(uint32_t) * h.off.size()));
-    HIP_OK(hipMalloc(&list, sizeof(uint16_t) * h.list.size()));
-    HIP_OK(hipMalloc(&hot, sizeof(uint32_t) * h.hot.size()));
-    HIP_OK(hipMemcpy(off, h.off.data(), sizeof(uint32_t) * h.off.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(list, h.list.data(), sizeof(uint16_t) * h.list.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(hot, h.hot.data(), sizeof(uint32_t) * h.hot.size(), hipMemcpyHostToDevice));
+    OB_HIP(hipMalloc(&off, sizeof(uint32_t) * h.off.size()));
+    OB_HIP(hipMalloc(&list, sizeof(uint16_t) * h.list.size()));
+    OB_HIP(hipMalloc(&hot, sizeof(uint32_t) * h.hot.size()));
+    OB_HIP(hipMemcpy(off, h.off.data(), sizeof(uint32_t) * h.off.size(), hipMemcpyHostToDevice));
+    OB_HIP(hipMemcpy(list, h.list.data(), sizeof(uint16_t) * h.list.size(), hipMemcpyHostToDevice));
+    OB_HIP(hipMemcpy(hot, h.hot.data(), sizeof(uint32_t) * h.hot.size(), hipMemcpyHostToDevice));
     t.off = off;
     t.list = list;
     t.hot = hot;
@@ -1570,7 +1563,7 @@ int ensure_buf(T** ptr, size_t& cap_elems, size_t need_elems) {
   if (*ptr) (void)hipFree(*ptr);
   *ptr = nullptr;
   cap_elems = 0;
-  HIP_OK(hipMalloc((void**)ptr, std::max<size_t>(need_elems, 1) * sizeof(T)));
+  OB_HIP(hipMalloc((void**)ptr, std::max<size_t>(need_elems, 1) * sizeof(T)));
   cap_elems = need_elems;
   return OB_OK;
 }
@@ -1626,7 +1619,7 @@ int ensure_heck(ob_panel* p, const Plan& pl) {
   OB_TRY(ensure_buf(&p->d_hgamma, p->cap_hgamma, (size_t)2 * pl.rep_pad * p->ks));
   OB_TRY(ensure_buf(&p->d_hflags, p->cap_hflags, (size_t)2 * pl.rep_pad));
   OB_TRY(ensure_buf(&p->d_hpartial, p->cap_hpartial, (size_t)pl.n_chunks() * pl.rep_pad * vals));
-  if (!p->d_hactive) HIP_OK(hipMalloc(&p->d_hactive, sizeof(uint32_t)));
+  if (!p->d_hactive) OB_HIP(hipMalloc(&p->d_hactive, sizeof(uint32_t)));
   return OB_OK;
 }
 
@@ -1665,7 +1658,7 @@ namespace ob {
 
 int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_b) {
   ob_ctx* ctx = p->ctx;
-  HIP_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   Plan pl = make_plan(p, 1, true);
   // the unit Gram's blocks: a run of sub-tiles per block, at most kUgMaxBlocks per group
@@ -1702,19 +1695,19 @@ int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_
   uint8_t* d_ok = p->d_pe_ok;
   ua.partial = p->d_pe + o_part;
   const size_t lds = sizeof(double) * (size_t)p->k1 * kColStride;
-  HIP_OK(hipFuncSetAttribute((const void*)ob_unit_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  OB_HIP(hipFuncSetAttribute((const void*)ob_unit_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   if (ua.nblocks) {
     hipLaunchKernelGGL(ob_unit_gram_kernel, dim3(ua.nblocks), dim3(kBlock), lds, s, ua);
-    HIP_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(ob_unit_reduce_kernel, dim3(2 * p->e_pad), dim3(kBlock), 0, s, (const double*)ua.partial,
                      ua.nblocks, ua.blocks0, p->e, p->e_pad, d_gram);
-  HIP_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   if (p->heckman) {  // estimation.rs:114-172 on the whole groups (every row once)
     if (!p->chunks_ready) {  // the probit/IMR passes walk the panel's chunk table
       p->chunks = pl.chunks;
       OB_TRY(ensure_buf(&p->d_chunks, p->cap_chunks, p->chunks.size()));
-      HIP_OK(hipMemcpyAsync(p->d_chunks, p->chunks.data(), sizeof(uint32_t) * p->chunks.size(), hipMemcpyHostToDevice, s));
+      OB_HIP(hipMemcpyAsync(p->d_chunks, p->chunks.data(), sizeof(uint32_t) * p->chunks.size(), hipMemcpyHostToDevice, s));
       p->chunks_ready = true;
     }
     OB_TRY(ensure_heck(p, pl));
@@ -1727,9 +1720,9 @@ int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_
     int it = 0;
     OB_TRY(ob::heckman_segment(hs, s, &it));
     uint8_t okh = 0;
-    HIP_OK(hipMemcpyAsync(row, d_row, sizeof(double) * p->row_len, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(&okh, d_ok, 1, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
+    OB_HIP(hipMemcpyAsync(row, d_row, sizeof(double) * p->row_len, hipMemcpyDeviceToHost, s));
+    OB_HIP(hipMemcpyAsync(&okh, d_ok, 1, hipMemcpyDeviceToHost, s));
+    OB_HIP(hipStreamSynchronize(s));
     p->timing.probit_iterations = it;
     switch (okh) {
       case OB_HS_OK: return OB_OK;  // residuals: zeros over B's selected rows (estimation.rs:152-153), the caller's
@@ -1759,7 +1752,7 @@ int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_
     sa.gram_out = t == 0 ? d_gout : nullptr;
     sa.raw_status = 1;
     sa.raw_beta_b = d_beta + (size_t)t * p->k;
-    HIP_OK(launch_solve(p, sa, 1, s));
+    OB_HIP(launch_solve(p, sa, 1, s));
   }
   // the residuals (only when asked for) are computed before the one host synchronization
   if (resid_b && p->n[1] > 0) {
@@ -1768,14 +1761,14 @@ int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_
       hipLaunchKernelGGL(ob_residual_kernel, dim3((p->n[1] + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
                          (const double*)p->d_cols[1], p->ld[1], p->n[1], p->p, p->p + t,
                          (const double*)(d_beta + (size_t)t * p->k), d_res);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipMemcpyAsync(resid_b + (size_t)t * p->n[1], d_res, sizeof(double) * p->n[1], hipMemcpyDeviceToHost, s));
+      OB_HIP(hipGetLastError());
+      OB_HIP(hipMemcpyAsync(resid_b + (size_t)t * p->n[1], d_res, sizeof(double) * p->n[1], hipMemcpyDeviceToHost, s));
     }
   }
   uint8_t okh = 0;
-  HIP_OK(hipMemcpyAsync(row, d_row, sizeof(double) * p->row_len * p->n_y, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(&okh, d_ok, 1, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
+  OB_HIP(hipMemcpyAsync(row, d_row, sizeof(double) * p->row_len * p->n_y, hipMemcpyDeviceToHost, s));
+  OB_HIP(hipMemcpyAsync(&okh, d_ok, 1, hipMemcpyDeviceToHost, s));
+  OB_HIP(hipStreamSynchronize(s));
   if (okh == 2) return ob::fail(OB_E_GROUP, "%sNo data in groups for weighted coefficients.", error_prefix(OB_E_GROUP));
   if (okh != 1)
     return ob::fail(OB_E_LINALG,
@@ -1790,7 +1783,7 @@ int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_
 // ob_engine.hpp layout, replicate batches of 64). Used by the Machado-Mata driver (ob_mm.hip).
 int engine_counts(ob_panel* p, uint64_t seed, uint64_t first_rep, uint32_t n_reps, hipStream_t s,
                   uint32_t* nb_rep, uint32_t* rep_pad) {
-  HIP_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   if (n_reps == 0) return OB_OK;
   if (first_rep + n_reps > 0xFFFFFFFFull)
     return ob::fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 / MM-1 counter word)");
@@ -1803,12 +1796,12 @@ int engine_counts(ob_panel* p, uint64_t seed, uint64_t first_rep, uint32_t n_rep
   // count kernel only ever ORs into it, so an overflow in any segment survives to the check.
   const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);
   const size_t lds_l1 = sizeof(uint32_t) * std::max(l1_lds_words(p->ntiles[0]), l1_lds_words(p->ntiles[1]));
-  HIP_OK(hipFuncSetAttribute((const void*)ob_level1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l1));
+  OB_HIP(hipFuncSetAttribute((const void*)ob_level1_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l1));
   ob_ky_tables ky{};
   OB_TRY(ky_device(p->ctx->device, &ky));
   hipLaunchKernelGGL(ob_level1_kernel<0>, dim3(n_reps, 2), dim3(kBlock), lds_l1, s, p->n[0], p->n[1], p->ntiles[0],
                      (uint32_t)first_rep, tiles, key0, key1, p->d_m1, ky);
-  HIP_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   GramArgs ga = gram_args(p, pl);
   ga.flags = p->d_flags + 2;
   ga.m1 = p->d_m1;
@@ -1820,26 +1813,26 @@ int engine_counts(ob_panel* p, uint64_t seed, uint64_t first_rep, uint32_t n_rep
   ga.tiles_total = tiles;
   hipLaunchKernelGGL(ob_count_kernel<false>, dim3((tiles + kCntTilesPerBlock - 1) / kCntTilesPerBlock, pl.nb_rep),
                      dim3(kBlock), 0, s, ga);
-  HIP_OK(hipGetLastError());
-  if (opt_int(Opt::DebugCountOverflow, 0)) HIP_OK(hipMemsetAsync(p->d_flags + 2, 0xFF, sizeof(uint32_t), s));
+  OB_HIP(hipGetLastError());
+  if (opt_int(Opt::DebugCountOverflow, 0)) OB_HIP(hipMemsetAsync(p->d_flags + 2, 0xFF, sizeof(uint32_t), s));
   *nb_rep = pl.nb_rep;
   *rep_pad = pl.rep_pad;
   return OB_OK;
 }
 
 int engine_order(ob_panel* p, hipStream_t s) {
-  if (p->order_stream && p->order_stream != s) HIP_OK(hipStreamWaitEvent(s, p->order_ev, 0));
+  if (p->order_stream && p->order_stream != s) OB_HIP(hipStreamWaitEvent(s, p->order_ev, 0));
   return OB_OK;
 }
 
 int engine_mark(ob_panel* p, hipStream_t s, bool scratch) {
-  if (!p->order_ev) HIP_OK(hipEventCreateWithFlags(&p->order_ev, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(p->order_ev, s));
+  if (!p->order_ev) OB_HIP(hipEventCreateWithFlags(&p->order_ev, hipEventDisableTiming));
+  OB_HIP(hipEventRecord(p->order_ev, s));
   p->order_stream = s;
   if (scratch) {
-    if (!p->scratch_ev) HIP_OK(hipEventCreateWithFlags(&p->scratch_ev, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(p->scratch_ev, s));
-    if (p->scratch_ev2) HIP_OK(hipEventRecord(p->scratch_ev2, s));
+    if (!p->scratch_ev) OB_HIP(hipEventCreateWithFlags(&p->scratch_ev, hipEventDisableTiming));
+    OB_HIP(hipEventRecord(p->scratch_ev, s));
+    if (p->scratch_ev2) OB_HIP(hipEventRecord(p->scratch_ev2, s));
     p->scratch_recorded = true;
   }
   return OB_OK;
@@ -1848,7 +1841,7 @@ int engine_mark(ob_panel* p, hipStream_t s, bool scratch) {
 int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps, int ref_mode, double* d_rows,
                 uint8_t* d_ok, hipStream_t stream) {
   ob_ctx* ctx = p->ctx;
-  HIP_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   if (n_reps == 0) return OB_OK;
   if (first_rep + n_reps > 0x100000000ull)
     return ob::fail(OB_E_INVALID, "replicate ids must stay below 2^32 (OBRS-3 counter word)");
@@ -1873,7 +1866,7 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
     s_work = true;
     p->chunks = pl.chunks;
     OB_TRY(ensure_buf(&p->d_chunks, p->cap_chunks, p->chunks.size()));
-    HIP_OK(hipMemcpyAsync(p->d_chunks, p->chunks.data(), sizeof(uint32_t) * p->chunks.size(), hipMemcpyHostToDevice, s));
+    OB_HIP(hipMemcpyAsync(p->d_chunks, p->chunks.data(), sizeof(uint32_t) * p->chunks.size(), hipMemcpyHostToDevice, s));
     p->chunks_ready = true;
   }
   if (pl.chunks != p->chunks || pl_tail.chunks != p->chunks)
@@ -1918,7 +1911,7 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
 #else
   const L1Kernel l1k = ob_level1_kernel<0>;
 #endif
-  HIP_OK(hipFuncSetAttribute((const void*)l1k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l1));
+  OB_HIP(hipFuncSetAttribute((const void*)l1k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l1));
   p->timing.chunks = nch;
   p->timing.blocks = use_i8 ? (int32_t)((uint32_t)nch * ((pl.nb_rep + 3) / 4) * (uint32_t)p->oz_n_ct)
                             : (int32_t)(pl.nb_rep * pl.n_cg * (uint32_t)nch);
@@ -1927,18 +1920,18 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
   const size_t nseg = (size_t)((n_reps + seg - 1) / seg);
   while (p->seg_events.size() < kSegEvents * (nseg + (size_t)p->pending_segments)) {
     hipEvent_t e;
-    HIP_OK(hipEventCreate(&e));
+    OB_HIP(hipEventCreate(&e));
     p->seg_events.push_back(e);
   }
   // the resample stream (ob_engine.hpp): level 1 and counts wait only for the previous call's last
   // read of the count images, not for its reduce / solve / gather
   const bool overlap = OB_BOOT_OVERLAP && !p->heckman;
   if (overlap) {
-    if (!p->rs_stream) HIP_OK(hipStreamCreateWithFlags(&p->rs_stream, hipStreamNonBlocking));
-    if (!p->rs_ev) HIP_OK(hipEventCreateWithFlags(&p->rs_ev, hipEventDisableTiming));
-    if (!p->scratch_ev) HIP_OK(hipEventCreateWithFlags(&p->scratch_ev, hipEventDisableTiming));
+    if (!p->rs_stream) OB_HIP(hipStreamCreateWithFlags(&p->rs_stream, hipStreamNonBlocking));
+    if (!p->rs_ev) OB_HIP(hipEventCreateWithFlags(&p->rs_ev, hipEventDisableTiming));
+    if (!p->scratch_ev) OB_HIP(hipEventCreateWithFlags(&p->scratch_ev, hipEventDisableTiming));
     if (!p->scratch_recorded) {  // no engine call on this panel yet: start where s is
-      HIP_OK(hipEventRecord(p->scratch_ev, s));
+      OB_HIP(hipEventRecord(p->scratch_ev, s));
       p->scratch_recorded = true;
     }
   }
@@ -1951,9 +1944,9 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
   // profiles/r06_ab_rs_double.txt)
   const int rs_pieces = ob::opt_int(ob::Opt::RsPieces, 1);
   if (overlap && rs_pieces > 1) {
-    if (!p->cnt_stream) HIP_OK(hipStreamCreateWithFlags(&p->cnt_stream, hipStreamNonBlocking));
+    if (!p->cnt_stream) OB_HIP(hipStreamCreateWithFlags(&p->cnt_stream, hipStreamNonBlocking));
     for (hipEvent_t& e : p->cnt_ev)
-      if (!e) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      if (!e) OB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   const int rs_opt = ob::opt_int(ob::Opt::RsDouble, -1);
   const bool dbl = overlap && (rs_opt == 1 || (rs_opt < 0 && use_i8 && !ob::oz_wide(p, nch, pl.nb_rep)));
@@ -1961,26 +1954,26 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
     OB_TRY(ensure_buf(&p->d_m1b, p->cap_m1b, (size_t)tiles * pl.rep_pad));
     OB_TRY(ensure_buf(&p->d_countsb, p->cap_countsb, (size_t)tiles * pl.nb_rep * 4 * kCimgWords));
     if (!p->scratch_ev2) {
-      HIP_OK(hipEventCreateWithFlags(&p->scratch_ev2, hipEventDisableTiming));
-      HIP_OK(hipEventRecord(p->scratch_ev2, s));
+      OB_HIP(hipEventCreateWithFlags(&p->scratch_ev2, hipEventDisableTiming));
+      OB_HIP(hipEventRecord(p->scratch_ev2, s));
     }
   }
   const bool tov = overlap && ob::opt_int(ob::Opt::TailStream, 0) == 1;
   if (tov) {
-    if (!p->g_stream) HIP_OK(hipStreamCreateWithFlags(&p->g_stream, hipStreamNonBlocking));
-    if (!p->t_stream) HIP_OK(hipStreamCreateWithFlags(&p->t_stream, hipStreamNonBlocking));
+    if (!p->g_stream) OB_HIP(hipStreamCreateWithFlags(&p->g_stream, hipStreamNonBlocking));
+    if (!p->t_stream) OB_HIP(hipStreamCreateWithFlags(&p->t_stream, hipStreamNonBlocking));
     for (hipEvent_t* e : {&p->g_ev, &p->t_ev, &p->user_ev, &p->prep_ev})
-      if (!*e) HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      if (!*e) OB_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     for (hipEvent_t& e : p->red_ev)
       if (!e) {
-        HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(e, s));
+        OB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        OB_HIP(hipEventRecord(e, s));
       }
     OB_TRY(ensure_buf(&p->d_partialb, p->cap_partialb, need_partial * p->e_pad));
-    HIP_OK(hipEventRecord(p->user_ev, s));
+    OB_HIP(hipEventRecord(p->user_ev, s));
     if (s_work) {
-      HIP_OK(hipEventRecord(p->prep_ev, s));
-      HIP_OK(hipStreamWaitEvent(p->g_stream, p->prep_ev, 0));
+      OB_HIP(hipEventRecord(p->prep_ev, s));
+      OB_HIP(hipStreamWaitEvent(p->g_stream, p->prep_ev, 0));
     }
   }
   const hipStream_t sg = tov ? p->g_stream : s;  // the Gram
@@ -2000,8 +1993,8 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
     const int pb = tov ? p->part_parity : 0;
     if (tov) p->part_parity ^= 1;
     double* const partial = pb ? p->d_partialb : p->d_partial;
-    if (overlap) HIP_OK(hipStreamWaitEvent(sr, sev, 0));
-    if (timed) HIP_OK(hipEventRecord(ev[0], sr));
+    if (overlap) OB_HIP(hipStreamWaitEvent(sr, sev, 0));
+    if (timed) OB_HIP(hipEventRecord(ev[0], sr));
     // pieces (option rs_pieces): level 1 over replicate batches [b0, b1) of piece k, then (below) the
     // count kernel of each piece on cnt_stream once its level 1 is done, beside the next piece's
     const int npc = overlap ? std::max(1, std::min({rs_pieces, 8, (int)plx.nb_rep})) : 1;
@@ -2011,10 +2004,10 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
       if (r1 > r0)
         hipLaunchKernelGGL(l1k, dim3(r1 - r0, 2), dim3(kBlock), lds_l1, sr, p->n[0], p->n[1], p->ntiles[0],
                            frep + r0, tiles, key0, key1, m1 + (size_t)r0 * tiles, ky);
-      HIP_OK(hipGetLastError());
-      if (npc > 1) HIP_OK(hipEventRecord(p->cnt_ev[k], sr));
+      OB_HIP(hipGetLastError());
+      if (npc > 1) OB_HIP(hipEventRecord(p->cnt_ev[k], sr));
     }
-    if (timed) HIP_OK(hipEventRecord(ev[1], sr));
+    if (timed) OB_HIP(hipEventRecord(ev[1], sr));
     GramArgs ga = gram_args(p, plx);
     ga.chunks = p->d_chunks;
     ga.m1 = m1;
@@ -2029,47 +2022,47 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
     const hipStream_t sc = npc > 1 ? p->cnt_stream : sr;
     for (int k = 0; k < npc; ++k) {
       const uint32_t b0 = plx.nb_rep * k / npc, b1 = plx.nb_rep * (k + 1) / npc;
-      if (npc > 1) HIP_OK(hipStreamWaitEvent(sc, p->cnt_ev[k], 0));
+      if (npc > 1) OB_HIP(hipStreamWaitEvent(sc, p->cnt_ev[k], 0));
       if (b1 == b0) continue;
       ga.rb0 = b0;
       const dim3 cgrid((tiles + kCntTilesPerBlock - 1) / kCntTilesPerBlock, b1 - b0);
       if (use_i8) hipLaunchKernelGGL(ob_count_kernel<true>, cgrid, dim3(kBlock), 0, sc, ga);
       else hipLaunchKernelGGL(ob_count_kernel<false>, cgrid, dim3(kBlock), 0, sc, ga);
-      HIP_OK(hipGetLastError());
+      OB_HIP(hipGetLastError());
     }
     ga.rb0 = 0;
-    if (timed) HIP_OK(hipEventRecord(ev[2], sc));
+    if (timed) OB_HIP(hipEventRecord(ev[2], sc));
     if (overlap) {
-      HIP_OK(hipEventRecord(p->rs_ev, sc));
-      HIP_OK(hipStreamWaitEvent(sg, p->rs_ev, 0));
+      OB_HIP(hipEventRecord(p->rs_ev, sc));
+      OB_HIP(hipStreamWaitEvent(sg, p->rs_ev, 0));
     }
-    if (tov) HIP_OK(hipStreamWaitEvent(sg, p->red_ev[pb], 0));  // the reduce two segments back read it
-    if (timed) HIP_OK(hipEventRecord(ev[3], sg));
+    if (tov) OB_HIP(hipStreamWaitEvent(sg, p->red_ev[pb], 0));  // the reduce two segments back read it
+    if (timed) OB_HIP(hipEventRecord(ev[3], sg));
     if (use_i8) {
       OB_TRY(ob::oz_gram(p, p->d_chunks, nchx, counts, plx.nb_rep, plx.rep_pad, ns, partial, sg));
     } else {
       const uint32_t blocks = plx.nb_rep * plx.n_cg * (uint32_t)nchx;
-      HIP_OK(launch_gram(p, plx.cb, false, ga, blocks, sg));
+      OB_HIP(launch_gram(p, plx.cb, false, ga, blocks, sg));
     }
-    if (timed) HIP_OK(hipEventRecord(ev[4], sg));
+    if (timed) OB_HIP(hipEventRecord(ev[4], sg));
     const bool exc = use_i8 && ob::oz_exceptions_pending(p);
-    if (overlap && !exc) HIP_OK(hipEventRecord(sev, sg));  // the count images are free again
+    if (overlap && !exc) OB_HIP(hipEventRecord(sev, sg));  // the count images are free again
     if (tov) {
-      HIP_OK(hipEventRecord(p->g_ev, sg));
-      HIP_OK(hipStreamWaitEvent(st, p->g_ev, 0));
-      HIP_OK(hipStreamWaitEvent(st, p->user_ev, 0));  // the caller's use of the rows buffers so far
+      OB_HIP(hipEventRecord(p->g_ev, sg));
+      OB_HIP(hipStreamWaitEvent(st, p->g_ev, 0));
+      OB_HIP(hipStreamWaitEvent(st, p->user_ev, 0));  // the caller's use of the rows buffers so far
     }
     const size_t nred = (size_t)ns * p->e_pad;
     hipLaunchKernelGGL(ob_reduce_kernel, dim3((unsigned)((nred + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        (const double*)partial, (const uint32_t*)p->d_chunks, nchx, plx.rep_pad, p->e_pad, ns,
                        p->d_gram);
-    HIP_OK(hipGetLastError());
-    if (tov) HIP_OK(hipEventRecord(p->red_ev[pb], st));
+    OB_HIP(hipGetLastError());
+    if (tov) OB_HIP(hipEventRecord(p->red_ev[pb], st));
     if (exc) {
       OB_TRY(ob::oz_exceptions(p, counts, plx.nb_rep, ns, p->d_gram, st));
-      if (overlap) HIP_OK(hipEventRecord(sev, st));
+      if (overlap) OB_HIP(hipEventRecord(sev, st));
     }
-    if (timed) HIP_OK(hipEventRecord(ev[5], st));
+    if (timed) OB_HIP(hipEventRecord(ev[5], st));
     if (p->heckman) {  // probit iterations + IMR sums + two-step solve (synchronizes the stream)
       ob_heck_seg hs = heck_seg(p, plx, p->d_chunks, p->d_gram, ref_mode);
       hs.counts = counts;
@@ -2096,15 +2089,15 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
       sa.gram_out = nullptr;
       sa.raw_beta_b = nullptr;
       sa.raw_status = 0;
-      HIP_OK(launch_solve(p, sa, ns, st));
+      OB_HIP(launch_solve(p, sa, ns, st));
     }
-    if (timed) HIP_OK(hipEventRecord(ev[6], st));
+    if (timed) OB_HIP(hipEventRecord(ev[6], st));
     p->timing.gram_launches += 1;
     p->pending_segments += 1;
   }
   if (tov) {  // the caller's stream sees the rows complete, as without the tail stream
-    HIP_OK(hipEventRecord(p->t_ev, st));
-    HIP_OK(hipStreamWaitEvent(s, p->t_ev, 0));
+    OB_HIP(hipEventRecord(p->t_ev, st));
+    OB_HIP(hipStreamWaitEvent(s, p->t_ev, 0));
   }
   p->timing_pending = true;
   p->last_stream = s;
@@ -2115,8 +2108,8 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
 // count-overflow flag.
 int engine_collect(ob_panel* p) {
   if (!p->timing_pending) return OB_OK;
-  HIP_OK(hipSetDevice(p->ctx->device));
-  HIP_OK(hipStreamSynchronize(p->last_stream));
+  OB_HIP(hipSetDevice(p->ctx->device));
+  OB_HIP(hipStreamSynchronize(p->last_stream));
   p->timing_pending = false;
   // (ev[2] -> ev[3] is the Gram's wait for the previous call's tail on the boot stream: not a kernel)
   double* dst[kSegEvents - 1] = {&p->timing.level1_ms, &p->timing.counts_ms, nullptr, &p->timing.gram_ms,
@@ -2126,22 +2119,22 @@ int engine_collect(ob_panel* p) {
     for (size_t i = 0; i + 1 < kSegEvents; ++i) {
       if (!dst[i]) continue;
       float t = 0.f;
-      HIP_OK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+      OB_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
       *dst[i] += t;
     }
   }
   if (p->heckman) p->timing.heckman_ms = p->timing.solve_ms;
   for (int k = 0; k < p->pending_gathers; ++k) {  // ob_shard.cpp: the RCCL all-gathers
     float t = 0.f;
-    HIP_OK(hipEventElapsedTime(&t, p->gather_evs[2 * k], p->gather_evs[2 * k + 1]));
+    OB_HIP(hipEventElapsedTime(&t, p->gather_evs[2 * k], p->gather_evs[2 * k + 1]));
     p->timing.gather_ms += t;
   }
   p->pending_gathers = 0;
   p->pending_segments = 0;
   if (p->timing.gram_path == 2) OB_TRY(ob::oz_collect(p));
   uint32_t flag = 0;
-  HIP_OK(hipMemcpy(&flag, p->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (flag) HIP_OK(hipMemset(p->d_flags, 0, sizeof(uint32_t)));  // collected: the next calls start clean
+  OB_HIP(hipMemcpy(&flag, p->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (flag) OB_HIP(hipMemset(p->d_flags, 0, sizeof(uint32_t)));  // collected: the next calls start clean
   // a count of 256+ wraps its byte (bit 0: byte sums differ from the tile counts); on the i8 path
   // the bound is 127 either way
   if ((flag & 1u) && p->timing.gram_path != 2)
@@ -2177,9 +2170,9 @@ int ob_ctx_create(int device, ob_ctx** out) {
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
     return ob::fail(OB_E_HIP, "no HIP device visible: the MI355X engine has no CPU fallback");
   if (device < 0 || device >= n) return ob::fail(OB_E_INVALID, "device %d out of range (%d devices)", device, n);
-  HIP_OK(hipSetDevice(device));
+  OB_HIP(hipSetDevice(device));
   hipDeviceProp_t prop;
-  HIP_OK(hipGetDeviceProperties(&prop, device));
+  OB_HIP(hipGetDeviceProperties(&prop, device));
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return ob::fail(OB_E_HIP, "device %d is %s; this engine is built for gfx950 (MI355X) only", device,
                     prop.gcnArchName);
@@ -2237,7 +2230,7 @@ int ob_panel_create(ob_ctx* ctx, const ob_panel_desc* d, ob_panel** out) {
         if (gd[g]->w[i] < 0.0)
           return ob::fail(OB_E_GROUP, "%sWeights cannot be negative", ob::error_prefix(OB_E_GROUP));
   }
-  HIP_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   ob_panel* p = new ob_panel();
   p->ctx = ctx;
   p->p = d->p;
@@ -2422,7 +2415,7 @@ int ob_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_b) {
   }
   // ordered after any call on this panel from another stream (an async boot on a user
   // stream may still read the buffers the point estimate rewrites), and marked for the next one
-  HIP_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t s = p->ctx->stream;
   OB_TRY(ob::engine_order(p, s));
   const int rc = ob::engine_point_estimate(p, ref_mode, row, resid_b);
@@ -2446,21 +2439,21 @@ int ob_boot_run(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
                 uint8_t* ok) {
   if (!p || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
   if (n_reps == 0) return OB_OK;
-  HIP_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   if (p->tmp_reps < n_reps) {
     (void)hipFree(p->d_rows_tmp);
     (void)hipFree(p->d_ok_tmp);
     p->d_rows_tmp = nullptr;
     p->d_ok_tmp = nullptr;
     p->tmp_reps = 0;
-    HIP_OK(hipMalloc(&p->d_rows_tmp, sizeof(double) * n_reps * p->row_len * p->n_y));
-    HIP_OK(hipMalloc(&p->d_ok_tmp, n_reps * p->n_y));
+    OB_HIP(hipMalloc(&p->d_rows_tmp, sizeof(double) * n_reps * p->row_len * p->n_y));
+    OB_HIP(hipMalloc(&p->d_ok_tmp, n_reps * p->n_y));
     p->tmp_reps = n_reps;
   }
   OB_TRY(ob_boot_run_device(p, seed, first_rep, n_reps, ref_mode, p->d_rows_tmp, p->d_ok_tmp, nullptr));
   OB_TRY(ob::engine_collect(p));
-  HIP_OK(hipMemcpy(rows, p->d_rows_tmp, sizeof(double) * n_reps * p->row_len * p->n_y, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(ok, p->d_ok_tmp, n_reps * p->n_y, hipMemcpyDeviceToHost));
+  OB_HIP(hipMemcpy(rows, p->d_rows_tmp, sizeof(double) * n_reps * p->row_len * p->n_y, hipMemcpyDeviceToHost));
+  OB_HIP(hipMemcpy(ok, p->d_ok_tmp, n_reps * p->n_y, hipMemcpyDeviceToHost));
   return OB_OK;
 }
 
@@ -2480,30 +2473,30 @@ int ob_debug_counts(ob_panel* p, uint64_t seed, uint64_t first_rep, uint32_t n_r
   if (!p || (group != 0 && group != 1)) return ob::fail(OB_E_INVALID, "bad arguments");
   if (n_reps == 0) return OB_OK;
   if (n_reps > 16384) return ob::fail(OB_E_INVALID, "at most 16384 replicates per call");
-  HIP_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t s = p->ctx->stream;
   uint32_t nb = 0, rep_pad = 0;
   OB_TRY(ob::engine_order(p, s));  // after any call on this panel from another stream
-  HIP_OK(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
+  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
   const int rc = ob::engine_counts(p, seed, first_rep, n_reps, s, &nb, &rep_pad);
   OB_TRY(ob::engine_mark(p, s));
   OB_TRY(rc);
-  HIP_OK(hipStreamSynchronize(s));
+  OB_HIP(hipStreamSynchronize(s));
   uint32_t flag = 0;
-  HIP_OK(hipMemcpy(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost));  // engine_counts' word
+  OB_HIP(hipMemcpy(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost));  // engine_counts' word
   if (flag & 1u) return ob::fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
   const uint32_t tiles = p->ntiles[0] + p->ntiles[1], tg = p->ntiles[group], t0 = group ? p->ntiles[0] : 0u;
   const uint32_t n = p->n[group];
   if (level1) {
     std::vector<uint32_t> m1((size_t)tiles * n_reps);
-    HIP_OK(hipMemcpy(m1.data(), p->d_m1, sizeof(uint32_t) * m1.size(), hipMemcpyDeviceToHost));
+    OB_HIP(hipMemcpy(m1.data(), p->d_m1, sizeof(uint32_t) * m1.size(), hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < n_reps; ++r)
       for (uint32_t t = 0; t < tg; ++t) level1[(size_t)r * tg + t] = m1[(size_t)r * tiles + t0 + t];
   }
   if (row_counts && n) {
     const size_t per_tile = (size_t)nb * 4 * kCimgWords;
     std::vector<uint32_t> img((size_t)tg * per_tile);
-    HIP_OK(hipMemcpy(img.data(), p->d_counts + (size_t)t0 * per_tile, sizeof(uint32_t) * img.size(),
+    OB_HIP(hipMemcpy(img.data(), p->d_counts + (size_t)t0 * per_tile, sizeof(uint32_t) * img.size(),
                      hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < n_reps; ++r) {
       const uint32_t b = r >> 6, lr = r & 63u;
@@ -2524,11 +2517,11 @@ int ob_debug_gram(ob_panel* p, int path, uint64_t seed, uint64_t first_rep, uint
   if (n_reps == 0) return OB_OK;
   if (n_reps > 16384) return ob::fail(OB_E_INVALID, "at most 16384 replicates per call (one segment)");
   if (p->heckman) return ob::fail(OB_E_UNSUPPORTED, "Heckman panels use the f64 Gram only");
-  HIP_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   double* d_rows = nullptr;
   uint8_t* d_ok = nullptr;
-  HIP_OK(hipMalloc(&d_rows, sizeof(double) * n_reps * p->row_len * p->n_y));
-  HIP_OK(hipMalloc(&d_ok, (size_t)n_reps * p->n_y));
+  OB_HIP(hipMalloc(&d_rows, sizeof(double) * n_reps * p->row_len * p->n_y));
+  OB_HIP(hipMalloc(&d_ok, (size_t)n_reps * p->n_y));
   const int saved = p->gram_force;
   p->gram_force = path;
   int rc = ob_boot_run_device(p, seed, first_rep, n_reps, OB_REF_GROUP_A, d_rows, d_ok, nullptr);

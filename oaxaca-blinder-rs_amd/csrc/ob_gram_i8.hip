@@ -41,6 +41,7 @@
 
 #include "ob_common.hpp"
 #include "ob_engine.hpp"
+#include "ob_hip.hpp"
 #include "ob_options.hpp"
 #include "ob_spec.h"
 
@@ -64,13 +65,6 @@ constexpr int kSix0 = OB_OZ_SIX0;      // six-slice blocks: slices of group 0 (g
 // tools/build_alt.sh) measured 14.6 ms per Gram launch against 13.4 ms at configs[1].
 #define OB_OZ_A_NT 0
 #endif
-
-#define OZ_HIP(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 // v_c of a row (ob_panel_kernel's formula): weighted sqrt(w) [1, x, y], else [1, x, y].
 __device__ __forceinline__ double oz_v(const double* cols, int64_t ld, int nxy, int weighted, size_t row, int c) {
@@ -1196,41 +1190,41 @@ int oz_prepare(ob_panel* p, hipStream_t s) {
   size_t bytes = 0;
   for (int g = 0; g < 2; ++g) bytes += (size_t)(p->ld[g] >> 6) * n_ct * kSubUnits * 16;
   size_t free_b = 0, total_b = 0;
-  OZ_HIP(hipSetDevice(p->ctx->device));
-  OZ_HIP(hipMemGetInfo(&free_b, &total_b));
+  OB_HIP(hipSetDevice(p->ctx->device));
+  OB_HIP(hipMemGetInfo(&free_b, &total_b));
   if (bytes > free_b / 2 || bytes > (96ull << 30)) {
     p->oz_state = -1;
     return OB_OK;
   }
   for (int g = 0; g < 2; ++g) {
     if (!p->d_oz_b[g])
-      OZ_HIP(hipMalloc(&p->d_oz_b[g], std::max<size_t>((size_t)(p->ld[g] >> 6) * n_ct * kSubUnits * 16, 16)));
-    if (!p->d_oz_dev[g]) OZ_HIP(hipMalloc(&p->d_oz_dev[g], std::max<size_t>((size_t)p->ld[g], 1)));
-    if (!p->d_oz_tile_chunk[g]) OZ_HIP(hipMalloc(&p->d_oz_tile_chunk[g], sizeof(int32_t) * std::max(p->ntiles[g], 1u)));
+      OB_HIP(hipMalloc(&p->d_oz_b[g], std::max<size_t>((size_t)(p->ld[g] >> 6) * n_ct * kSubUnits * 16, 16)));
+    if (!p->d_oz_dev[g]) OB_HIP(hipMalloc(&p->d_oz_dev[g], std::max<size_t>((size_t)p->ld[g], 1)));
+    if (!p->d_oz_tile_chunk[g]) OB_HIP(hipMalloc(&p->d_oz_tile_chunk[g], sizeof(int32_t) * std::max(p->ntiles[g], 1u)));
     p->oz_tile_chunk[g].assign(std::max(p->ntiles[g], 1u), 0);
   }
-  if (!p->d_oz_pexp) OZ_HIP(hipMalloc(&p->d_oz_pexp, sizeof(int32_t) * (size_t)n_chunks * npp));
-  if (!p->d_oz_psum) OZ_HIP(hipMalloc(&p->d_oz_psum, sizeof(int64_t) * 2 * (size_t)n_chunks * npp));
-  if (!p->d_oz_nsl) OZ_HIP(hipMalloc(&p->d_oz_nsl, (size_t)n_chunks * n_ct));
-  if (!p->d_oz_pnsl) OZ_HIP(hipMalloc(&p->d_oz_pnsl, (size_t)n_chunks * npp));
-  if (!p->d_oz_acc) OZ_HIP(hipMalloc(&p->d_oz_acc, sizeof(int64_t) * 2 * (size_t)n_chunks * p->k1));
-  if (!p->d_oz_meta) OZ_HIP(hipMalloc(&p->d_oz_meta, sizeof(int32_t) * kMetaWords));
-  if (!p->d_oz_exc) OZ_HIP(hipMalloc(&p->d_oz_exc, sizeof(uint32_t) * kOzExcCap));
-  if (!p->d_oz_excp) OZ_HIP(hipMalloc(&p->d_oz_excp, sizeof(double) * kOzExcCap * (size_t)p->e_pad));
+  if (!p->d_oz_pexp) OB_HIP(hipMalloc(&p->d_oz_pexp, sizeof(int32_t) * (size_t)n_chunks * npp));
+  if (!p->d_oz_psum) OB_HIP(hipMalloc(&p->d_oz_psum, sizeof(int64_t) * 2 * (size_t)n_chunks * npp));
+  if (!p->d_oz_nsl) OB_HIP(hipMalloc(&p->d_oz_nsl, (size_t)n_chunks * n_ct));
+  if (!p->d_oz_pnsl) OB_HIP(hipMalloc(&p->d_oz_pnsl, (size_t)n_chunks * npp));
+  if (!p->d_oz_acc) OB_HIP(hipMalloc(&p->d_oz_acc, sizeof(int64_t) * 2 * (size_t)n_chunks * p->k1));
+  if (!p->d_oz_meta) OB_HIP(hipMalloc(&p->d_oz_meta, sizeof(int32_t) * kMetaWords));
+  if (!p->d_oz_exc) OB_HIP(hipMalloc(&p->d_oz_exc, sizeof(uint32_t) * kOzExcCap));
+  if (!p->d_oz_excp) OB_HIP(hipMalloc(&p->d_oz_excp, sizeof(double) * kOzExcCap * (size_t)p->e_pad));
   for (int i = 0; i < 2; ++i)
-    if (!p->oz_ev[i]) OZ_HIP(hipEventCreate(&p->oz_ev[i]));
+    if (!p->oz_ev[i]) OB_HIP(hipEventCreate(&p->oz_ev[i]));
   for (int c = 0; c < n_chunks; ++c)
     for (uint32_t t = chunks[3 * c + 1]; t < chunks[3 * c + 2]; ++t) p->oz_tile_chunk[chunks[3 * c]][t] = c;
 
-  OZ_HIP(hipEventRecord(p->oz_ev[0], s));
+  OB_HIP(hipEventRecord(p->oz_ev[0], s));
   for (int g = 0; g < 2; ++g)
-    OZ_HIP(hipMemcpyAsync(p->d_oz_tile_chunk[g], p->oz_tile_chunk[g].data(), sizeof(int32_t) * p->oz_tile_chunk[g].size(),
+    OB_HIP(hipMemcpyAsync(p->d_oz_tile_chunk[g], p->oz_tile_chunk[g].data(), sizeof(int32_t) * p->oz_tile_chunk[g].size(),
                           hipMemcpyHostToDevice, s));
-  OZ_HIP(hipMemsetAsync(p->d_oz_acc, 0, sizeof(int64_t) * 2 * (size_t)n_chunks * p->k1, s));
-  OZ_HIP(hipMemsetAsync(p->d_oz_meta, 0, sizeof(int32_t) * kMetaWords, s));
-  OZ_HIP(hipMemsetAsync(p->d_oz_pexp, 0, sizeof(int32_t) * (size_t)n_chunks * npp, s));
-  OZ_HIP(hipMemsetAsync(p->d_oz_psum, 0, sizeof(int64_t) * 2 * (size_t)n_chunks * npp, s));
-  OZ_HIP(hipMemsetAsync(p->d_oz_exc, 0xFF, sizeof(uint32_t) * kOzExcCap, s));
+  OB_HIP(hipMemsetAsync(p->d_oz_acc, 0, sizeof(int64_t) * 2 * (size_t)n_chunks * p->k1, s));
+  OB_HIP(hipMemsetAsync(p->d_oz_meta, 0, sizeof(int32_t) * kMetaWords, s));
+  OB_HIP(hipMemsetAsync(p->d_oz_pexp, 0, sizeof(int32_t) * (size_t)n_chunks * npp, s));
+  OB_HIP(hipMemsetAsync(p->d_oz_psum, 0, sizeof(int64_t) * 2 * (size_t)n_chunks * npp, s));
+  OB_HIP(hipMemsetAsync(p->d_oz_exc, 0xFF, sizeof(uint32_t) * kOzExcCap, s));
   const int nxy = p->p + p->n_y;
   const double* cols[2] = {p->d_cols[0], p->d_cols[1]};
   for (int g = 0; g < 2; ++g)
@@ -1238,36 +1232,36 @@ int oz_prepare(ob_panel* p, hipStream_t s) {
       hipLaunchKernelGGL(oz_scale_kernel, dim3(p->ntiles[g]), dim3(256), 0, s, cols[g], p->ld[g], p->n[g], nxy,
                          p->weighted, p->k1, (const int32_t*)p->d_oz_tile_chunk[g],
                          reinterpret_cast<unsigned long long*>(p->d_oz_acc));
-      OZ_HIP(hipGetLastError());
+      OB_HIP(hipGetLastError());
     }
   for (int g = 0; g < 2; ++g)
     if (p->ntiles[g]) {
       hipLaunchKernelGGL(oz_dev_kernel, dim3(p->ntiles[g]), dim3(256), 0, s, cols[g], p->ld[g], p->n[g], nxy,
                          p->weighted, p->k1, (const int32_t*)p->d_oz_tile_chunk[g], (const long long*)p->d_oz_acc,
                          p->d_oz_dev[g], p->d_oz_meta);
-      OZ_HIP(hipGetLastError());
+      OB_HIP(hipGetLastError());
     }
   hipLaunchKernelGGL(oz_choose_kernel, dim3(1), dim3(64), 0, s, p->d_oz_meta);
-  OZ_HIP(hipGetLastError());
+  OB_HIP(hipGetLastError());
   for (int g = 0; g < 2; ++g)
     if (p->ntiles[g]) {
       hipLaunchKernelGGL(oz_collect_kernel, dim3(p->ntiles[g]), dim3(256), 0, s, (const int8_t*)p->d_oz_dev[g], p->n[g],
                          (uint32_t)g, p->d_oz_meta, p->d_oz_exc);
-      OZ_HIP(hipGetLastError());
+      OB_HIP(hipGetLastError());
     }
   hipLaunchKernelGGL(oz_sort_kernel, dim3(1), dim3(1024), 0, s, p->d_oz_exc, p->d_oz_meta);
-  OZ_HIP(hipGetLastError());
+  OB_HIP(hipGetLastError());
   hipLaunchKernelGGL(oz_excp_kernel, dim3(kOzExcCap), dim3(256), 0, s, cols[0], cols[1], p->ld[0], p->ld[1], nxy,
                      p->weighted, p->k1, p->e, p->e_pad, (const uint32_t*)p->d_oz_exc, (const int32_t*)p->d_oz_meta,
                      p->d_oz_excp);
-  OZ_HIP(hipGetLastError());
+  OB_HIP(hipGetLastError());
   const int k1p = p->k1 | 1;
   const int pexp_pairs = std::min(p->e, kPexpPairs), pexp_blocks = (p->e + kPexpPairs - 1) / kPexpPairs;
   const size_t lds_pexp =
       sizeof(double) * ((size_t)64 * k1p + pexp_pairs) + (2 * sizeof(int32_t) + 2) * (size_t)pexp_pairs;
   const size_t lds_dig = sizeof(double) * (size_t)64 * k1p;
-  OZ_HIP(hipFuncSetAttribute((const void*)oz_pexp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pexp));
-  OZ_HIP(hipFuncSetAttribute((const void*)oz_digits_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dig));
+  OB_HIP(hipFuncSetAttribute((const void*)oz_pexp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pexp));
+  OB_HIP(hipFuncSetAttribute((const void*)oz_digits_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dig));
   for (int g = 0; g < 2; ++g)
     if (p->ntiles[g]) {
       hipLaunchKernelGGL(oz_pexp_kernel, dim3(p->ntiles[g], pexp_blocks), dim3(256), lds_pexp, s, cols[g], p->ld[g],
@@ -1275,17 +1269,17 @@ int oz_prepare(ob_panel* p, hipStream_t s) {
                          p->weighted, p->k1, p->e, npp, (const int32_t*)p->d_oz_tile_chunk[g],
                          (const int8_t*)p->d_oz_dev[g], (const int32_t*)p->d_oz_meta, p->d_oz_pexp,
                          reinterpret_cast<unsigned long long*>(p->d_oz_psum));
-      OZ_HIP(hipGetLastError());
+      OB_HIP(hipGetLastError());
     }
   const int npe = n_chunks * npp;
   hipLaunchKernelGGL(oz_pexp_finish_kernel, dim3((npe + 255) / 256), dim3(256), 0, s, p->d_oz_pexp, npe);
-  OZ_HIP(hipGetLastError());
+  OB_HIP(hipGetLastError());
   const int force7 = ob::opt_int(ob::Opt::GramDigits, 0) == 7 ? 1 : 0;
   const int nct_all = n_chunks * n_ct;
   hipLaunchKernelGGL(oz_nsl_kernel, dim3((nct_all + 255) / 256), dim3(256), 0, s, (const int32_t*)p->d_oz_pexp,
                      (const long long*)p->d_oz_psum, (const uint32_t*)p->d_chunks, p->n[0], p->n[1], p->e, n_ct, npp,
                      n_chunks, force7, p->d_oz_pnsl, p->d_oz_nsl, p->d_oz_meta);
-  OZ_HIP(hipGetLastError());
+  OB_HIP(hipGetLastError());
   p->oz_tiles = nct_all;
   for (int g = 0; g < 2; ++g) {
     const uint32_t nsub = (uint32_t)(p->ld[g] >> 6);
@@ -1294,9 +1288,9 @@ int oz_prepare(ob_panel* p, hipStream_t s) {
                        p->weighted, p->k1, p->e, n_ct, npp, (const int32_t*)p->d_oz_tile_chunk[g],
                        (const int8_t*)p->d_oz_dev[g], (const int32_t*)p->d_oz_meta, (const int32_t*)p->d_oz_pexp,
                        (const uint8_t*)p->d_oz_pnsl, reinterpret_cast<ob_v4i*>(p->d_oz_b[g]));
-    OZ_HIP(hipGetLastError());
+    OB_HIP(hipGetLastError());
   }
-  OZ_HIP(hipEventRecord(p->oz_ev[1], s));
+  OB_HIP(hipEventRecord(p->oz_ev[1], s));
   p->oz_timed = true;
   p->oz_nexc = -1;
   p->oz_n_ct = n_ct;
@@ -1314,7 +1308,7 @@ int oz_exceptions(ob_panel* p, const uint32_t* counts, uint32_t nb_rep, uint32_t
   hipLaunchKernelGGL(oz_exc_kernel, dim3(nb_rep, 2), dim3(256), 0, s, reinterpret_cast<const uint8_t*>(counts), nb_rep,
                      p->ntiles[0], (const uint32_t*)p->d_oz_exc, (const double*)p->d_oz_excp,
                      (const int32_t*)p->d_oz_meta, p->e, p->e_pad, n_reps, gram);
-  OZ_HIP(hipGetLastError());
+  OB_HIP(hipGetLastError());
   return OB_OK;
 }
 
@@ -1325,13 +1319,13 @@ int oz_collect(ob_panel* p) {
   if (p->oz_state != 1) return OB_OK;
   if (p->oz_timed) {
     float t = 0.f;
-    OZ_HIP(hipEventElapsedTime(&t, p->oz_ev[0], p->oz_ev[1]));
+    OB_HIP(hipEventElapsedTime(&t, p->oz_ev[0], p->oz_ev[1]));
     p->timing.prep_ms = t;
     p->oz_timed = false;
   }
   if (p->oz_nexc < 0) {
     int32_t meta[6] = {0, 0, 0, 0, 0, 0};
-    OZ_HIP(hipMemcpy(meta, p->d_oz_meta, sizeof(meta), hipMemcpyDeviceToHost));
+    OB_HIP(hipMemcpy(meta, p->d_oz_meta, sizeof(meta), hipMemcpyDeviceToHost));
     p->oz_bits = meta[0];
     p->oz_nexc = meta[1];
     p->oz_overflow = meta[3] != 0;
@@ -1450,7 +1444,7 @@ int oz_gram(ob_panel* p, const uint32_t* d_chunks, int n_chunks, const uint32_t*
         (void)hipFree(p->d_oz_pint);
         p->d_oz_pint = nullptr;
         p->cap_oz_pint = 0;
-        OZ_HIP(hipMalloc(&p->d_oz_pint, need * sizeof(long long)));
+        OB_HIP(hipMalloc(&p->d_oz_pint, need * sizeof(long long)));
         p->cap_oz_pint = need;
       }
       a.pint = p->d_oz_pint;
@@ -1467,17 +1461,17 @@ int oz_gram(ob_panel* p, const uint32_t* d_chunks, int n_chunks, const uint32_t*
     };
 #if OB_TUNING  // timing ablations (gram_diag): wrong results by design
     switch (ob::opt_int(ob::Opt::GramDiag, 0) & 398) {
-      case 2: OZ_HIP(wlaunch(oz_gram_w_kernel<2>)); break;
-      case 128: OZ_HIP(wlaunch(oz_gram_w_kernel<128>)); break;
-      case 256: OZ_HIP(wlaunch(oz_gram_w_kernel<256>)); break;
-      case 384: OZ_HIP(wlaunch(oz_gram_w_kernel<384>)); break;
-      case 4: OZ_HIP(wlaunch(oz_gram_w_kernel<4>)); break;
-      case 8: OZ_HIP(wlaunch(oz_gram_w_kernel<8>)); break;
-      case 6: OZ_HIP(wlaunch(oz_gram_w_kernel<6>)); break;
-      default: OZ_HIP(wlaunch(oz_gram_w_kernel<0>)); break;
+      case 2: OB_HIP(wlaunch(oz_gram_w_kernel<2>)); break;
+      case 128: OB_HIP(wlaunch(oz_gram_w_kernel<128>)); break;
+      case 256: OB_HIP(wlaunch(oz_gram_w_kernel<256>)); break;
+      case 384: OB_HIP(wlaunch(oz_gram_w_kernel<384>)); break;
+      case 4: OB_HIP(wlaunch(oz_gram_w_kernel<4>)); break;
+      case 8: OB_HIP(wlaunch(oz_gram_w_kernel<8>)); break;
+      case 6: OB_HIP(wlaunch(oz_gram_w_kernel<6>)); break;
+      default: OB_HIP(wlaunch(oz_gram_w_kernel<0>)); break;
     }
 #else
-    OZ_HIP(wlaunch(oz_gram_w_kernel<0>));
+    OB_HIP(wlaunch(oz_gram_w_kernel<0>));
 #endif
     return OB_OK;
   }
@@ -1490,15 +1484,15 @@ int oz_gram(ob_panel* p, const uint32_t* d_chunks, int n_chunks, const uint32_t*
   };
 #if OB_TUNING  // timing ablations (gram_diag): wrong results by design
   switch (ob::opt_int(ob::Opt::GramDiag, 0) & 30) {
-    case 2: OZ_HIP(launch(oz_gram_kernel<2>)); break;
-    case 4: OZ_HIP(launch(oz_gram_kernel<4>)); break;
-    case 6: OZ_HIP(launch(oz_gram_kernel<6>)); break;
-    case 8: OZ_HIP(launch(oz_gram_kernel<8>)); break;
-    case 16: OZ_HIP(launch(oz_gram_kernel<16>)); break;
-    default: OZ_HIP(launch(oz_gram_kernel<0>)); break;
+    case 2: OB_HIP(launch(oz_gram_kernel<2>)); break;
+    case 4: OB_HIP(launch(oz_gram_kernel<4>)); break;
+    case 6: OB_HIP(launch(oz_gram_kernel<6>)); break;
+    case 8: OB_HIP(launch(oz_gram_kernel<8>)); break;
+    case 16: OB_HIP(launch(oz_gram_kernel<16>)); break;
+    default: OB_HIP(launch(oz_gram_kernel<0>)); break;
   }
 #else
-  OZ_HIP(launch(oz_gram_kernel<0>));
+  OB_HIP(launch(oz_gram_kernel<0>));
 #endif
   return OB_OK;
 }
@@ -1511,14 +1505,14 @@ extern "C" {
 int ob_debug_gram_exceptions(ob_panel* p, int32_t* bits, int32_t* n_exc, uint32_t* rows, int32_t cap) {
   if (!p || !bits || !n_exc) return ob::fail(OB_E_INVALID, "null pointer");
   if (p->oz_state != 1) return ob::fail(OB_E_INVALID, "the panel's i8 Gram is not built (run a boot on the i8 path first)");
-  OZ_HIP(hipSetDevice(p->ctx->device));
-  OZ_HIP(hipDeviceSynchronize());
+  OB_HIP(hipSetDevice(p->ctx->device));
+  OB_HIP(hipDeviceSynchronize());
   int32_t meta[4] = {0, 0, 0, 0};
-  OZ_HIP(hipMemcpy(meta, p->d_oz_meta, sizeof(meta), hipMemcpyDeviceToHost));
+  OB_HIP(hipMemcpy(meta, p->d_oz_meta, sizeof(meta), hipMemcpyDeviceToHost));
   *bits = meta[0];
   *n_exc = meta[1];
   if (rows && cap > 0 && meta[1] > 0)
-    OZ_HIP(hipMemcpy(rows, p->d_oz_exc, sizeof(uint32_t) * (size_t)std::min(cap, meta[1]), hipMemcpyDeviceToHost));
+    OB_HIP(hipMemcpy(rows, p->d_oz_exc, sizeof(uint32_t) * (size_t)std::min(cap, meta[1]), hipMemcpyDeviceToHost));
   return meta[3] ? ob::fail(OB_E_UNSUPPORTED, "more than %d non-finite rows", kOzExcCap) : OB_OK;
 }
 

@@ -27,6 +27,7 @@
 
 #include "ob_device.hpp"
 #include "ob_engine.hpp"
+#include "ob_hip.hpp"
 #include "ob_heckman.hpp"
 #include "ob_options.hpp"
 #include "ob_spec.h"
@@ -35,14 +36,6 @@ namespace {
 
 constexpr int kHB = 256;
 constexpr uint32_t kDone = 1u, kFailed = 2u;
-
-#define HK_OK(expr)                                                                      \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, \
-                      __LINE__);                                                         \
-  } while (0)
 
 // statrs Normal(0, 1): pdf = exp(-z^2 / 2) / sqrt(2 pi), cdf = erfc(-z / sqrt 2) / 2.
 // (The constant divisions are multiplications by the reciprocals: a last-bit difference.)
@@ -671,20 +664,20 @@ int heckman_segment(const ob_heck_seg& a, hipStream_t s, int* iters, ob_heck_tim
     }
   } ev;
   if (tm)
-    for (hipEvent_t& x : ev.e) HK_OK(hipEventCreate(&x));
-  HK_OK(hipMemsetAsync(a.gamma, 0, sizeof(double) * 2 * a.rep_pad * a.ks, s));
-  HK_OK(hipMemsetAsync(a.hflags, 0, sizeof(uint32_t) * 2 * a.rep_pad, s));
+    for (hipEvent_t& x : ev.e) OB_HIP(hipEventCreate(&x));
+  OB_HIP(hipMemsetAsync(a.gamma, 0, sizeof(double) * 2 * a.rep_pad * a.ks, s));
+  OB_HIP(hipMemsetAsync(a.hflags, 0, sizeof(uint32_t) * 2 * a.rep_pad, s));
   int it = 0;
   while (it < a.max_iter) {  // probit.rs:48-147, each replicate stopping on its own
-    HK_OK(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
-    HK_OK(probit_iter(a, s, tm ? ev.e : nullptr));
+    OB_HIP(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
+    OB_HIP(probit_iter(a, s, tm ? ev.e : nullptr));
     ++it;
     uint32_t active = 0;
-    HK_OK(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HK_OK(hipStreamSynchronize(s));
+    OB_HIP(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    OB_HIP(hipStreamSynchronize(s));
     if (tm) {
       float ms = 0.f;
-      HK_OK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+      OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
       tm->probit_ms += ms;
       tm->probit_launches += 1;
     }
@@ -707,20 +700,20 @@ int heckman_segment(const ob_heck_seg& a, hipStream_t s, int* iters, ob_heck_tim
   const void* fn = nb == 32   ? (cody ? sums(std::integral_constant<int, 32>{}, T{}) : sums(std::integral_constant<int, 32>{}, F{}))
                    : nb == 40 ? (cody ? sums(std::integral_constant<int, 40>{}, T{}) : sums(std::integral_constant<int, 40>{}, F{}))
                               : (cody ? sums(std::integral_constant<int, 64>{}, T{}) : sums(std::integral_constant<int, 64>{}, F{}));
-  HK_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sums));
-  if (tm) HK_OK(hipEventRecord(ev.e[2], s));
+  OB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sums));
+  if (tm) OB_HIP(hipEventRecord(ev.e[2], s));
   void* args[] = {const_cast<ob_heck_seg*>(&a)};
-  HK_OK(hipLaunchKernel(fn, grid, dim3(kHB), args, lds_sums, s));
-  HK_OK(hipGetLastError());
-  if (tm) HK_OK(hipEventRecord(ev.e[3], s));
+  OB_HIP(hipLaunchKernel(fn, grid, dim3(kHB), args, lds_sums, s));
+  OB_HIP(hipGetLastError());
+  if (tm) OB_HIP(hipEventRecord(ev.e[3], s));
   const size_t lds = heck_solve_lds(a);
-  HK_OK(hipFuncSetAttribute((const void*)ob_heck_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  OB_HIP(hipFuncSetAttribute((const void*)ob_heck_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(ob_heck_solve_kernel, dim3(a.n_reps), dim3(64), lds, s, a);
-  HK_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   if (tm) {  // the events die with this call: read the sums pass now
     float ms = 0.f;
-    HK_OK(hipEventSynchronize(ev.e[3]));
-    HK_OK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+    OB_HIP(hipEventSynchronize(ev.e[3]));
+    OB_HIP(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
     tm->sums_ms += ms;
   }
   return OB_OK;
@@ -744,9 +737,9 @@ __global__ void ob_normal_kernel(const double* z, int64_t n, double* pdf, double
 extern "C" int ob_debug_normal(int device, const double* z, int64_t n, double* pdf, double* cdf) {
   if (n < 0 || (n && (!z || !pdf || !cdf))) return ob::fail(OB_E_INVALID, "bad arguments");
   if (n == 0) return OB_OK;
-  HK_OK(hipSetDevice(device));
+  OB_HIP(hipSetDevice(device));
   double* d = nullptr;
-  HK_OK(hipMalloc(&d, sizeof(double) * 3 * (size_t)n));
+  OB_HIP(hipMalloc(&d, sizeof(double) * 3 * (size_t)n));
   int rc = OB_OK;
   do {
     if (hipMemcpy(d, z, sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) { rc = ob::fail(OB_E_HIP, "copy"); break; }

@@ -14,6 +14,7 @@
 
 #include "ob_common.hpp"
 #include "ob_frame.hpp"
+#include "ob_linalg.hpp"
 #include "ob_match.hpp"
 
 struct ob_match_results {
@@ -33,74 +34,6 @@ int polars_not_found(const std::string& name) {
 }
 
 double col_value(const Col& c, int64_t r) { return c.kind == OB_COL_I64 ? (double)c.i[r] : c.f[r]; }
-
-// determinant of the (d - 1) x (d - 1) minor of m (d <= 4, column-major) without row sr and column sc
-double minor_det(const std::vector<double>& m, int d, int sr, int sc) {
-  double a[3][3];
-  int ri = 0;
-  for (int r = 0; r < d; ++r) {
-    if (r == sr) continue;
-    int ci = 0;
-    for (int c = 0; c < d; ++c) {
-      if (c == sc) continue;
-      a[ri][ci++] = m[r + (size_t)c * d];
-    }
-    ++ri;
-  }
-  switch (d - 1) {
-    case 0: return 1.0;
-    case 1: return a[0][0];
-    case 2: return a[0][0] * a[1][1] - a[1][0] * a[0][1];
-    default:
-      return a[0][0] * (a[1][1] * a[2][2] - a[2][1] * a[1][2]) - a[0][1] * (a[1][0] * a[2][2] - a[2][0] * a[1][2]) +
-             a[0][2] * (a[1][0] * a[2][1] - a[2][0] * a[1][1]);
-  }
-}
-
-// nalgebra try_inverse: the adjugate over the determinant up to dimension 4 (false when the
-// determinant is exactly zero), LU with partial pivoting beyond (false on a zero pivot).
-bool try_inverse(const std::vector<double>& m, int d, std::vector<double>& inv) {
-  inv.assign((size_t)d * d, 0.0);
-  if (d <= 4) {
-    std::vector<double> cof((size_t)d * d);
-    for (int r = 0; r < d; ++r)
-      for (int c = 0; c < d; ++c) cof[r + (size_t)c * d] = (((r + c) & 1) ? -1.0 : 1.0) * minor_det(m, d, r, c);
-    double det = 0.0;
-    for (int c = 0; c < d; ++c) det += m[(size_t)c * d] * cof[(size_t)c * d];
-    if (det == 0.0) return false;
-    for (int r = 0; r < d; ++r)
-      for (int c = 0; c < d; ++c) inv[r + (size_t)c * d] = cof[c + (size_t)r * d] / det;
-    return true;
-  }
-  std::vector<double> a(m);
-  for (int i = 0; i < d; ++i) inv[i + (size_t)i * d] = 1.0;
-  for (int i = 0; i < d; ++i) {
-    int piv = i;
-    for (int r = i + 1; r < d; ++r)
-      if (std::fabs(a[r + (size_t)i * d]) > std::fabs(a[piv + (size_t)i * d])) piv = r;
-    if (a[piv + (size_t)i * d] == 0.0) continue;
-    if (piv != i)
-      for (int c = 0; c < d; ++c) {
-        std::swap(a[i + (size_t)c * d], a[piv + (size_t)c * d]);
-        std::swap(inv[i + (size_t)c * d], inv[piv + (size_t)c * d]);
-      }
-    for (int r = i + 1; r < d; ++r) {
-      const double f = a[r + (size_t)i * d] / a[i + (size_t)i * d];
-      for (int c = i + 1; c < d; ++c) a[r + (size_t)c * d] -= f * a[i + (size_t)c * d];
-      for (int c = 0; c < d; ++c) inv[r + (size_t)c * d] -= f * inv[i + (size_t)c * d];
-    }
-  }
-  for (int i = d - 1; i >= 0; --i) {
-    const double diag = a[i + (size_t)i * d];
-    if (diag == 0.0) return false;
-    for (int c = 0; c < d; ++c) {
-      double part = inv[i + (size_t)c * d];
-      for (int j = i + 1; j < d; ++j) part -= a[i + (size_t)j * d] * inv[j + (size_t)c * d];
-      inv[i + (size_t)c * d] = part / diag;
-    }
-  }
-  return true;
-}
 
 // 0.0 with the f64 value 1.0 / k added m times in sequence (engine.rs:206-208), for m = 0 .. m_max
 std::vector<double> weight_table(int k, uint32_t m_max) {
@@ -248,19 +181,9 @@ int mahalanobis_factor(const std::vector<double>& s, int d, std::vector<double>&
     return fail(OB_E_DIAG, "%sCovariance matrix is singular and cannot be inverted", error_prefix(OB_E_DIAG));
   // nalgebra Cholesky::new on the lower triangle, then l() (engine.rs:163-167)
   l = inv;
-  for (int j = 0; j < d; ++j) {
-    for (int i = j; i < d; ++i) {
-      double v = l[i + (size_t)j * d];
-      for (int c = 0; c < j; ++c) v -= l[j + (size_t)c * d] * l[i + (size_t)c * d];
-      l[i + (size_t)j * d] = v;
-    }
-    const double diag = l[j + (size_t)j * d];
-    if (!(diag != 0.0 && diag >= 0.0))
-      return fail(OB_E_DIAG, "%sCholesky decomposition failed", error_prefix(OB_E_DIAG));
-    const double den = std::sqrt(diag);
-    for (int i = j; i < d; ++i) l[i + (size_t)j * d] = (i == j) ? den : l[i + (size_t)j * d] / den;
+  if (!chol_factor(l.data(), d)) return fail(OB_E_DIAG, "%sCholesky decomposition failed", error_prefix(OB_E_DIAG));
+  for (int j = 0; j < d; ++j)
     for (int i = 0; i < j; ++i) l[i + (size_t)j * d] = 0.0;
-  }
   return OB_OK;
 }
 

@@ -6,7 +6,8 @@
 //   ob_knn_merge_kernel     the chunks' lists of one query merged by the same key
 //   ob_match_count_kernel   how often each control was chosen (integer atomics)
 //   ob_match_cov_kernel     centred cross-products of the control rows (distance.rs:36-44), per-block
-//   ob_match_reduce_kernel  partials into their own slots, then added in a fixed order
+//   ob_ordered_sum_kernel   the blocks' partials of one cross-product added in a fixed order
+//                           (ob_device.hpp)
 //   ob_match_xl_kernel      X L, the Mahalanobis transform (engine.rs:174-175)
 //   ob_match_pack_kernel    controls to row-major rows padded to the kernel's dimension bucket
 //   ob_match_finite_kernel  the stricter rule: a non-finite coordinate is an error
@@ -22,20 +23,15 @@
 #include <climits>
 #include <cmath>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
+#include "ob_device.hpp"
+#include "ob_hip.hpp"
 #include "ob_match.hpp"
 #include "ob_options.hpp"
 
 namespace {
-
-#define MATCH_OK(expr)                                                                   \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, \
-                      __LINE__);                                                         \
-  } while (0)
 
 constexpr int kBlock = 256;
 constexpr int kKnnFill = 2048;       // blocks wanted before the controls are split into chunks
@@ -205,21 +201,6 @@ __global__ __launch_bounds__(kBlock) void ob_match_cov_kernel(const double* x, i
   }
 }
 
-// out[e] = partial[e][0 .. m) added by thread in stride order, then a fixed LDS tree. One block per sum.
-__global__ __launch_bounds__(kBlock) void ob_match_reduce_kernel(const double* partial, uint32_t m, double* out) {
-  __shared__ double red[kBlock];
-  const int tid = threadIdx.x;
-  double s = 0.0;
-  for (uint32_t b = tid; b < m; b += kBlock) s += partial[(size_t)blockIdx.x * m + b];
-  red[tid] = s;
-  __syncthreads();
-  for (int h = kBlock / 2; h > 0; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[blockIdx.x] = red[0];
-}
-
 // out[c][row] = sum_j x[j][row] l[j][c] (both column-major, l is d x d). blockIdx.y: the column c.
 __global__ __launch_bounds__(kBlock) void ob_match_xl_kernel(const double* x, int64_t n, int d, const double* l,
                                                               double* out) {
@@ -231,32 +212,21 @@ __global__ __launch_bounds__(kBlock) void ob_match_xl_kernel(const double* x, in
   out[(size_t)c * n + row] = s;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-  double* d() const { return static_cast<double*>(p); }
-};
-
-struct Events {
-  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-  ~Events() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+// Calls f with k's bucket of the neighbour list, 1, 4, 8 or 16, as a compile-time constant.
+template <class F>
+void with_k_bucket(int k, F f) {
+  if (k <= 1) f(std::integral_constant<int, 1>());
+  else if (k <= 4) f(std::integral_constant<int, 4>());
+  else if (k <= 8) f(std::integral_constant<int, 8>());
+  else f(std::integral_constant<int, 16>());
+}
 
 template <int DP>
 int launch_knn(const KnnArgs& a, dim3 grid, hipStream_t s) {
-  if (a.k <= 1) hipLaunchKernelGGL((ob_knn_kernel<DP, 1>), grid, dim3(kBlock), 0, s, a);
-  else if (a.k <= 4) hipLaunchKernelGGL((ob_knn_kernel<DP, 4>), grid, dim3(kBlock), 0, s, a);
-  else if (a.k <= 8) hipLaunchKernelGGL((ob_knn_kernel<DP, 8>), grid, dim3(kBlock), 0, s, a);
-  else hipLaunchKernelGGL((ob_knn_kernel<DP, 16>), grid, dim3(kBlock), 0, s, a);
-  MATCH_OK(hipGetLastError());
+  with_k_bucket(a.k, [&](auto kb) {
+    hipLaunchKernelGGL((ob_knn_kernel<DP, decltype(kb)::value>), grid, dim3(kBlock), 0, s, a);
+  });
+  OB_HIP(hipGetLastError());
   return OB_OK;
 }
 
@@ -270,11 +240,12 @@ int dim_bucket(int dim) {
 int transform(hipStream_t st, DevBuf& x, int64_t n, int d, const double* dl) {
   if (n == 0) return OB_OK;
   DevBuf out;
-  MATCH_OK(out.alloc(sizeof(double) * (size_t)n * d));
+  OB_HIP(out.alloc(sizeof(double) * (size_t)n * d));
   hipLaunchKernelGGL(ob_match_xl_kernel, dim3(blocks_for(n), d), dim3(kBlock), 0, st, x.d(), n, d, dl, out.d());
-  MATCH_OK(hipGetLastError());
-  MATCH_OK(hipStreamSynchronize(st));
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipStreamSynchronize(st));
   std::swap(x.p, out.p);
+  std::swap(x.cap, out.cap);
   return OB_OK;
 }
 
@@ -301,21 +272,21 @@ int match_knn(ob_ctx* ctx, const double* q, int64_t ldq, int64_t n_q, const doub
     dist2[i] = std::numeric_limits<double>::infinity();
   }
   if (counts) std::fill(counts, counts + n_c, 0u);
-  MATCH_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  Events ev;
-  for (hipEvent_t& e : ev.e) MATCH_OK(hipEventCreate(&e));
+  Events<3> ev;
+  OB_HIP(ev.create());
   DevBuf dq, dc, dflag;
-  MATCH_OK(dq.alloc(sizeof(double) * (size_t)n_q * dim));
-  MATCH_OK(dc.alloc(sizeof(double) * (size_t)n_c * dim));
-  MATCH_OK(dflag.alloc(sizeof(uint32_t)));
-  MATCH_OK(hipEventRecord(ev.e[0], st));
-  MATCH_OK(hipMemsetAsync(dflag.p, 0, sizeof(uint32_t), st));
+  OB_HIP(dq.alloc(sizeof(double) * (size_t)n_q * dim));
+  OB_HIP(dc.alloc(sizeof(double) * (size_t)n_c * dim));
+  OB_HIP(dflag.alloc(sizeof(uint32_t)));
+  OB_HIP(hipEventRecord(ev.e[0], st));
+  OB_HIP(hipMemsetAsync(dflag.p, 0, sizeof(uint32_t), st));
   if (n_q)
-    MATCH_OK(hipMemcpy2DAsync(dq.p, sizeof(double) * (size_t)n_q, q, sizeof(double) * (size_t)ldq,
+    OB_HIP(hipMemcpy2DAsync(dq.p, sizeof(double) * (size_t)n_q, q, sizeof(double) * (size_t)ldq,
                               sizeof(double) * (size_t)n_q, (size_t)dim, hipMemcpyHostToDevice, st));
   if (n_c)
-    MATCH_OK(hipMemcpy2DAsync(dc.p, sizeof(double) * (size_t)n_c, c, sizeof(double) * (size_t)ldc,
+    OB_HIP(hipMemcpy2DAsync(dc.p, sizeof(double) * (size_t)n_c, c, sizeof(double) * (size_t)ldc,
                               sizeof(double) * (size_t)n_c, (size_t)dim, hipMemcpyHostToDevice, st));
   if (mahalanobis) {
     // mean on the host in row order, centred cross-products on the device (distance.rs:36-44)
@@ -327,33 +298,33 @@ int match_knn(ob_ctx* ctx, const double* q, int64_t ldq, int64_t n_q, const doub
     }
     const unsigned nblk = (unsigned)std::min<int64_t>((n_c + kCovRows - 1) / kCovRows, kCovMaxBlocks);
     DevBuf dmean, dpart, dsum, dl;
-    MATCH_OK(dmean.alloc(sizeof(double) * dim));
-    MATCH_OK(dpart.alloc(sizeof(double) * (size_t)dim * dim * nblk));
-    MATCH_OK(dsum.alloc(sizeof(double) * (size_t)dim * dim));
-    MATCH_OK(dl.alloc(sizeof(double) * (size_t)dim * dim));
-    MATCH_OK(hipMemcpyAsync(dmean.p, mean.data(), sizeof(double) * dim, hipMemcpyHostToDevice, st));
+    OB_HIP(dmean.alloc(sizeof(double) * dim));
+    OB_HIP(dpart.alloc(sizeof(double) * (size_t)dim * dim * nblk));
+    OB_HIP(dsum.alloc(sizeof(double) * (size_t)dim * dim));
+    OB_HIP(dl.alloc(sizeof(double) * (size_t)dim * dim));
+    OB_HIP(hipMemcpyAsync(dmean.p, mean.data(), sizeof(double) * dim, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(ob_match_cov_kernel, dim3(nblk), dim3(kBlock), 0, st, dc.d(), n_c, dim, dmean.d(), dpart.d());
-    MATCH_OK(hipGetLastError());
-    hipLaunchKernelGGL(ob_match_reduce_kernel, dim3(dim * dim), dim3(kBlock), 0, st, dpart.d(), nblk, dsum.d());
-    MATCH_OK(hipGetLastError());
-    MATCH_OK(hipMemcpyAsync(s.data(), dsum.p, sizeof(double) * (size_t)dim * dim, hipMemcpyDeviceToHost, st));
-    MATCH_OK(hipStreamSynchronize(st));
+    OB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ob_ordered_sum_kernel<>, dim3(dim * dim), dim3(kSumBlock), 0, st, dpart.d(), nblk, dsum.d());
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipMemcpyAsync(s.data(), dsum.p, sizeof(double) * (size_t)dim * dim, hipMemcpyDeviceToHost, st));
+    OB_HIP(hipStreamSynchronize(st));
     for (double& v : s) v /= (double)(n_c - 1);
     OB_TRY(mahalanobis_factor(s, dim, l));
-    MATCH_OK(hipMemcpyAsync(dl.p, l.data(), sizeof(double) * (size_t)dim * dim, hipMemcpyHostToDevice, st));
+    OB_HIP(hipMemcpyAsync(dl.p, l.data(), sizeof(double) * (size_t)dim * dim, hipMemcpyHostToDevice, st));
     OB_TRY(transform(st, dq, n_q, dim, dl.d()));
     OB_TRY(transform(st, dc, n_c, dim, dl.d()));
   }
   if (n_q * dim)
     hipLaunchKernelGGL(ob_match_finite_kernel, dim3(blocks_for(n_q * dim)), dim3(kBlock), 0, st, dq.d(), n_q * dim,
-                       static_cast<uint32_t*>(dflag.p));
+                       dflag.as<uint32_t>());
   if (n_c * dim)
     hipLaunchKernelGGL(ob_match_finite_kernel, dim3(blocks_for(n_c * dim)), dim3(kBlock), 0, st, dc.d(), n_c * dim,
-                       static_cast<uint32_t*>(dflag.p));
-  MATCH_OK(hipGetLastError());
+                       dflag.as<uint32_t>());
+  OB_HIP(hipGetLastError());
   uint32_t flag = 0;
-  MATCH_OK(hipMemcpyAsync(&flag, dflag.p, sizeof(flag), hipMemcpyDeviceToHost, st));
-  MATCH_OK(hipStreamSynchronize(st));
+  OB_HIP(hipMemcpyAsync(&flag, dflag.p, sizeof(flag), hipMemcpyDeviceToHost, st));
+  OB_HIP(hipStreamSynchronize(st));
   if (flag)
     return fail(OB_E_DIAG, "%snon-finite covariate in a treated or control row%s", error_prefix(OB_E_DIAG),
                 mahalanobis ? " after the Mahalanobis transform" : "");
@@ -370,15 +341,15 @@ int match_knn(ob_ctx* ctx, const double* q, int64_t ldq, int64_t n_q, const doub
   const uint32_t nchunks = (uint32_t)((n_c + chunk - 1) / chunk);
   const int dp = dim_bucket(dim);
   DevBuf dpack, dpd, dpi, didx, ddist, dcnt;
-  MATCH_OK(dpack.alloc(sizeof(double) * (size_t)n_c * dp));
-  MATCH_OK(dpd.alloc(sizeof(double) * (size_t)nchunks * k * n_q));
-  MATCH_OK(dpi.alloc(sizeof(int32_t) * (size_t)nchunks * k * n_q));
-  MATCH_OK(didx.alloc(sizeof(int64_t) * (size_t)n_q * k));
-  MATCH_OK(ddist.alloc(sizeof(double) * (size_t)n_q * k));
+  OB_HIP(dpack.alloc(sizeof(double) * (size_t)n_c * dp));
+  OB_HIP(dpd.alloc(sizeof(double) * (size_t)nchunks * k * n_q));
+  OB_HIP(dpi.alloc(sizeof(int32_t) * (size_t)nchunks * k * n_q));
+  OB_HIP(didx.alloc(sizeof(int64_t) * (size_t)n_q * k));
+  OB_HIP(ddist.alloc(sizeof(double) * (size_t)n_q * k));
   hipLaunchKernelGGL(ob_match_pack_kernel, dim3(blocks_for(n_c * dp)), dim3(kBlock), 0, st, dc.d(), n_c, dim, dp,
                      dpack.d());
-  MATCH_OK(hipGetLastError());
-  MATCH_OK(hipEventRecord(ev.e[1], st));
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipEventRecord(ev.e[1], st));
   KnnArgs a = {};
   a.q = dq.d();
   a.c = dpack.d();
@@ -389,7 +360,7 @@ int match_knn(ob_ctx* ctx, const double* q, int64_t ldq, int64_t n_q, const doub
   a.chunk = (int32_t)chunk;
   a.nchunks = nchunks;
   a.pd = dpd.d();
-  a.pi = static_cast<int32_t*>(dpi.p);
+  a.pi = dpi.as<int32_t>();
   const dim3 grid((unsigned)qblocks, nchunks);
   switch (dp) {
     case 4: OB_TRY(launch_knn<4>(a, grid, st)); break;
@@ -400,37 +371,29 @@ int match_knn(ob_ctx* ctx, const double* q, int64_t ldq, int64_t n_q, const doub
     case 48: OB_TRY(launch_knn<48>(a, grid, st)); break;
     default: OB_TRY(launch_knn<64>(a, grid, st)); break;
   }
-  int64_t* oidx = static_cast<int64_t*>(didx.p);
-  if (k <= 1)
-    hipLaunchKernelGGL(ob_knn_merge_kernel<1>, dim3((unsigned)qblocks), dim3(kBlock), 0, st, a.pd, a.pi, nchunks, n_q, k,
-                       oidx, ddist.d());
-  else if (k <= 4)
-    hipLaunchKernelGGL(ob_knn_merge_kernel<4>, dim3((unsigned)qblocks), dim3(kBlock), 0, st, a.pd, a.pi, nchunks, n_q, k,
-                       oidx, ddist.d());
-  else if (k <= 8)
-    hipLaunchKernelGGL(ob_knn_merge_kernel<8>, dim3((unsigned)qblocks), dim3(kBlock), 0, st, a.pd, a.pi, nchunks, n_q, k,
-                       oidx, ddist.d());
-  else
-    hipLaunchKernelGGL(ob_knn_merge_kernel<16>, dim3((unsigned)qblocks), dim3(kBlock), 0, st, a.pd, a.pi, nchunks, n_q,
-                       k, oidx, ddist.d());
-  MATCH_OK(hipGetLastError());
-  MATCH_OK(hipEventRecord(ev.e[2], st));
+  int64_t* oidx = didx.as<int64_t>();
+  with_k_bucket(k, [&](auto kb) {
+    hipLaunchKernelGGL(ob_knn_merge_kernel<decltype(kb)::value>, dim3((unsigned)qblocks), dim3(kBlock), 0, st, a.pd,
+                       a.pi, nchunks, n_q, k, oidx, ddist.d());
+  });
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipEventRecord(ev.e[2], st));
   if (counts) {
-    MATCH_OK(dcnt.alloc(sizeof(uint32_t) * (size_t)n_c));
-    MATCH_OK(hipMemsetAsync(dcnt.p, 0, sizeof(uint32_t) * (size_t)n_c, st));
+    OB_HIP(dcnt.alloc(sizeof(uint32_t) * (size_t)n_c));
+    OB_HIP(hipMemsetAsync(dcnt.p, 0, sizeof(uint32_t) * (size_t)n_c, st));
     hipLaunchKernelGGL(ob_match_count_kernel, dim3(blocks_for(n_q * k)), dim3(kBlock), 0, st, oidx, n_q * k, n_c,
-                       static_cast<uint32_t*>(dcnt.p));
-    MATCH_OK(hipGetLastError());
-    MATCH_OK(hipMemcpyAsync(counts, dcnt.p, sizeof(uint32_t) * (size_t)n_c, hipMemcpyDeviceToHost, st));
+                       dcnt.as<uint32_t>());
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipMemcpyAsync(counts, dcnt.p, sizeof(uint32_t) * (size_t)n_c, hipMemcpyDeviceToHost, st));
   }
-  MATCH_OK(hipMemcpyAsync(idx, didx.p, sizeof(int64_t) * (size_t)n_q * k, hipMemcpyDeviceToHost, st));
-  MATCH_OK(hipMemcpyAsync(dist2, ddist.p, sizeof(double) * (size_t)n_q * k, hipMemcpyDeviceToHost, st));
-  MATCH_OK(hipStreamSynchronize(st));
+  OB_HIP(hipMemcpyAsync(idx, didx.p, sizeof(int64_t) * (size_t)n_q * k, hipMemcpyDeviceToHost, st));
+  OB_HIP(hipMemcpyAsync(dist2, ddist.p, sizeof(double) * (size_t)n_q * k, hipMemcpyDeviceToHost, st));
+  OB_HIP(hipStreamSynchronize(st));
   if (timing) {
     float ms = 0.f;
-    MATCH_OK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
     timing->prep_ms = ms;
-    MATCH_OK(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+    OB_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
     timing->knn_ms = ms;
   }
   return OB_OK;

@@ -42,6 +42,7 @@
 
 #include "ob_device.hpp"
 #include "ob_engine.hpp"
+#include "ob_hip.hpp"
 #include "ob_mm.hpp"
 #include "ob_options.hpp"
 #include "ob_spec.h"
@@ -83,14 +84,6 @@ enum { FS_TAU, FS_GAP, FS_OBJ, FS_MU, FS_SIGMU, FS_AP, FS_AD, FS_NACT, FS_DELTA,
 __host__ __device__ constexpr int nv_asm(int K) { return K * (K + 1) / 2 + 2 * K + 2; }
 // Classify partial layout per fit: sum_above c x (K), sum_all c x (K), sum_above c y, kept rows.
 __host__ __device__ constexpr int nv_cls(int K) { return 2 * K + 2; }
-
-#define MM_OK(expr)                                                                      \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess)                                                                \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, \
-                      __LINE__);                                                         \
-  } while (0)
 
 struct MmArgs {
   const double* cols[2];  // [col][ld]: x_1..x_p, y (intercept implicit)
@@ -1778,27 +1771,27 @@ int start_fits(const MmArgs& a, int K, hipStream_t s, const MmArgs* full = nullp
   const uint32_t nch = a.nch[0] + a.nch[1];
   const size_t lds_solve = sizeof(double) * ((size_t)K * K + K);
   hipLaunchKernelGGL(mm_rows_kernel, dim3(nch, 1, a.n_rb), dim3(256), 0, s, a);
-  MM_OK(hipGetLastError());
-  MM_OK(hipMemsetAsync(a.active_rows, 0, sizeof(unsigned long long), s));
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipMemsetAsync(a.active_rows, 0, sizeof(unsigned long long), s));
   pass(K, 0, a, dim3(nch, 1, a.n_rb), 0, s);
-  MM_OK(hipGetLastError());
-  MM_OK(reduce_partials(a, nv_asm(K), 0, 0, s));  // the OLS sums sit in fit 0 (the statuses are not set yet)
+  OB_HIP(hipGetLastError());
+  OB_HIP(reduce_partials(a, nv_asm(K), 0, 0, s));  // the OLS sums sit in fit 0 (the statuses are not set yet)
   hipLaunchKernelGGL(mm_start_kernel, dim3(a.n_rb * 2), dim3(64), lds_solve, s, a, K);
-  MM_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   const MmArgs& ao = full ? *full : a;
   int m2 = 1;
   while (m2 < ao.S) m2 <<= 1;
   const size_t lds_ord = (size_t)m2 * (sizeof(double) + sizeof(uint32_t));
-  MM_OK(hipFuncSetAttribute((const void*)mm_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ord));
+  OB_HIP(hipFuncSetAttribute((const void*)mm_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ord));
   hipLaunchKernelGGL(mm_order_kernel, dim3(ao.n_rb * 2), dim3(256), lds_ord, s, ao, m2);
-  MM_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   if (full) {
     hipLaunchKernelGGL(mm_subtau_kernel, dim3((unsigned)(((size_t)a.n_rb * 2 * a.S_pad + 255) / 256)), dim3(256), 0, s,
                        *full, a, f);
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(mm_shift_kernel, dim3(a.n_rb * 2), dim3(1024), 0, s, a, K);
-  MM_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   return OB_OK;
 }
 
@@ -1813,31 +1806,31 @@ int ipm(const MmArgs& a, int K, int first_mode, hipStream_t s, MmStats& st) {
   const size_t n_fits = (size_t)a.n_rb * 2 * a.S_pad;
   const dim3 grid(nch, a.S_pad / 64, a.n_rb);
   const size_t lds_solve = sizeof(double) * ((size_t)K * K + K);
-  MM_OK(st.events(2 * (size_t)ob::kMmMaxIter));
+  OB_HIP(st.events(2 * (size_t)ob::kMmMaxIter));
   int it = 0;
   for (it = 1; it <= ob::kMmMaxIter; ++it) {
-    MM_OK(hipEventRecord(st.ev[2 * (it - 1)], s));
+    OB_HIP(hipEventRecord(st.ev[2 * (it - 1)], s));
     pass(K, 0, a, grid, it == 1 ? first_mode : 2, s);
-    MM_OK(hipGetLastError());
-    MM_OK(hipEventRecord(st.ev[2 * (it - 1) + 1], s));
-    MM_OK(reduce_partials(a, nv1, 0, 1, s));
-    MM_OK(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipEventRecord(st.ev[2 * (it - 1) + 1], s));
+    OB_HIP(reduce_partials(a, nv1, 0, 1, s));
+    OB_HIP(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
     hipLaunchKernelGGL(mm_solve_affine_kernel, dim3((unsigned)n_fits), dim3(64), lds_solve, s, a, K,
                        a.rp ? (it == 1 ? 1 : 2) : 0);
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     if (it % kCheckEvery == 0 || it == ob::kMmMaxIter) {
       uint32_t active = 0;
-      MM_OK(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      OB_HIP(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       const auto ts = std::chrono::steady_clock::now();
-      MM_OK(hipStreamSynchronize(s));
+      OB_HIP(hipStreamSynchronize(s));
       st.sync_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
       if (trace()) {
         fprintf(stderr, "[mm] iteration %d: %u of %zu fits active\n", it, active, n_fits);
         if (active && active <= 4) {  // the last live fits: where they stand
           std::vector<uint32_t> fst(n_fits);
           std::vector<double> fsh(n_fits * kFs);
-          MM_OK(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * n_fits, hipMemcpyDeviceToHost));
-          MM_OK(hipMemcpy(fsh.data(), a.fs, sizeof(double) * n_fits * kFs, hipMemcpyDeviceToHost));
+          OB_HIP(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * n_fits, hipMemcpyDeviceToHost));
+          OB_HIP(hipMemcpy(fsh.data(), a.fs, sizeof(double) * n_fits * kFs, hipMemcpyDeviceToHost));
           for (size_t f = 0; f < n_fits; ++f)
             if ((int)(f % a.S_pad) < a.S && !(fst[f] & (kDone | kFailed))) {
               const double* q = fsh.data() + f * kFs;
@@ -1850,33 +1843,33 @@ int ipm(const MmArgs& a, int K, int first_mode, hipStream_t s, MmStats& st) {
       if (active == 0) break;
     }
     pass(K, 1, a, grid, 0, s);
-    MM_OK(hipGetLastError());
-    MM_OK(reduce_partials(a, nv2, 2, 1, s));
+    OB_HIP(hipGetLastError());
+    OB_HIP(reduce_partials(a, nv2, 2, 1, s));
     hipLaunchKernelGGL(mm_solve_corrector_kernel, dim3((unsigned)n_fits), dim3(64), lds_solve, s, a, K);
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     pass(K, 2, a, grid, 0, s);
-    MM_OK(hipGetLastError());
-    MM_OK(reduce_partials(a, 2, 2, 1, s));
+    OB_HIP(hipGetLastError());
+    OB_HIP(reduce_partials(a, 2, 2, 1, s));
     hipLaunchKernelGGL(mm_step_kernel, dim3((unsigned)((n_fits + 255) / 256)), dim3(256), 0, s, a, K, n_fits);
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
   }
   {
     unsigned long long rows = 0;
-    MM_OK(hipMemcpyAsync(&rows, a.active_rows, sizeof(rows), hipMemcpyDeviceToHost, s));
-    MM_OK(hipStreamSynchronize(s));
+    OB_HIP(hipMemcpyAsync(&rows, a.active_rows, sizeof(rows), hipMemcpyDeviceToHost, s));
+    OB_HIP(hipStreamSynchronize(s));
     st.fit_rows += (double)rows;
     for (int i = 0; i < std::min(it, ob::kMmMaxIter); ++i) {
       float ms = 0.f;
-      MM_OK(hipEventElapsedTime(&ms, st.ev[2 * i], st.ev[2 * i + 1]));
+      OB_HIP(hipEventElapsedTime(&ms, st.ev[2 * i], st.ev[2 * i + 1]));
       st.assemble_ms += ms;
     }
   }
   if (trace()) {
-    MM_OK(hipStreamSynchronize(s));
+    OB_HIP(hipStreamSynchronize(s));
     std::vector<uint32_t> fst(n_fits);
     std::vector<double> fsh(n_fits * kFs);
-    MM_OK(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * n_fits, hipMemcpyDeviceToHost));
-    MM_OK(hipMemcpy(fsh.data(), a.fs, sizeof(double) * n_fits * kFs, hipMemcpyDeviceToHost));
+    OB_HIP(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * n_fits, hipMemcpyDeviceToHost));
+    OB_HIP(hipMemcpy(fsh.data(), a.fs, sizeof(double) * n_fits * kFs, hipMemcpyDeviceToHost));
     size_t done = 0, failed = 0, live = 0;
     for (size_t f = 0; f < n_fits; ++f) {
       if ((int)(f % a.S_pad) >= a.S) continue;
@@ -1892,7 +1885,7 @@ int ipm(const MmArgs& a, int K, int first_mode, hipStream_t s, MmStats& st) {
     fprintf(stderr, "[mm] after %d iterations: %zu converged, %zu failed, %zu still live\n", it, done, failed, live);
   }
   hipLaunchKernelGGL(mm_expire_kernel, dim3((unsigned)((n_fits + 255) / 256)), dim3(256), 0, s, a, n_fits);
-  MM_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   st.iterations = std::max(st.iterations, std::min(it, ob::kMmMaxIter));
   return OB_OK;
 }
@@ -1903,25 +1896,25 @@ int reduced_round(const MmArgs& a, int K, int round, hipStream_t s, MmStats& st)
   const size_t n_fits = (size_t)a.n_rb * 2 * a.S_pad;
   const dim3 grid(nch, a.S_pad / 64, a.n_rb);
   const unsigned fit_blocks = (unsigned)((n_fits + 255) / 256);
-  MM_OK(hipMemsetAsync(a.active_rows, 0, sizeof(unsigned long long), s));
+  OB_HIP(hipMemsetAsync(a.active_rows, 0, sizeof(unsigned long long), s));
   MmArgs ac = a;
   ac.list_stat = trace() && round == 0;
   if (ac.list_stat) {
     const unsigned long long z[2] = {0ull, 0ull};
-    MM_OK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mm_list_stat), z, sizeof(z), 0, hipMemcpyHostToDevice, s));
+    OB_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mm_list_stat), z, sizeof(z), 0, hipMemcpyHostToDevice, s));
   }
   pass(K, 3, ac, grid, 0, s);  // classify: block lists + fixed-row sums
-  MM_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   if (ac.list_stat) {
     unsigned long long v[2];
-    MM_OK(hipMemcpyFromSymbolAsync(v, HIP_SYMBOL(g_mm_list_stat), sizeof(v), 0, hipMemcpyDeviceToHost, s));
-    MM_OK(hipStreamSynchronize(s));
+    OB_HIP(hipMemcpyFromSymbolAsync(v, HIP_SYMBOL(g_mm_list_stat), sizeof(v), 0, hipMemcpyDeviceToHost, s));
+    OB_HIP(hipStreamSynchronize(s));
     fprintf(stderr, "[mm] block lists: %llu (wave, entry) pairs, %llu (%.1f %%) needed by a fit of the wave\n", v[0],
             v[1], v[0] ? 100.0 * (double)v[1] / (double)v[0] : 0.0);
   }
-  MM_OK(reduce_partials(a, nv_cls(K), 0, 0, s));
+  OB_HIP(reduce_partials(a, nv_cls(K), 0, 0, s));
   hipLaunchKernelGGL(mm_bvec_kernel, dim3(fit_blocks), dim3(256), 0, s, a, K, n_fits, round == 0 ? 1 : 0);
-  MM_OK(hipGetLastError());
+  OB_HIP(hipGetLastError());
   MmArgs a2 = a;
   a2.block_lists = 1;
   a2.rowlist = a.blist;
@@ -1945,10 +1938,10 @@ int capture_fits(const MmArgs& a, int K, hipStream_t s) {
   const size_t nf = (size_t)2 * a.S_pad;  // slot 0: fit_index(a, 0, g, j) = g S_pad + j
   std::vector<uint32_t> lane(nf), fst(nf);
   std::vector<double> beta(nf * K);
-  MM_OK(hipStreamSynchronize(s));
-  MM_OK(hipMemcpy(lane.data(), a.lane_of, sizeof(uint32_t) * nf, hipMemcpyDeviceToHost));
-  MM_OK(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * nf, hipMemcpyDeviceToHost));
-  MM_OK(hipMemcpy(beta.data(), a.beta, sizeof(double) * nf * K, hipMemcpyDeviceToHost));
+  OB_HIP(hipStreamSynchronize(s));
+  OB_HIP(hipMemcpy(lane.data(), a.lane_of, sizeof(uint32_t) * nf, hipMemcpyDeviceToHost));
+  OB_HIP(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * nf, hipMemcpyDeviceToHost));
+  OB_HIP(hipMemcpy(beta.data(), a.beta, sizeof(double) * nf * K, hipMemcpyDeviceToHost));
   for (int g = 0; g < 2; ++g)
     for (int sm = 0; sm < a.S; ++sm) {
       const size_t f = (size_t)g * a.S_pad + lane[(size_t)g * a.S_pad + sm];
@@ -1974,7 +1967,7 @@ int run_batch(MmArgs a, int K, hipStream_t s, double* rows_h, uint8_t* ok_h, MmS
     OB_TRY(ipm(a, K, 1, s, st));
   } else {
     hipLaunchKernelGGL(mm_rows_kernel, dim3(nch, 1, a.n_rb), dim3(256), 0, s, a);  // the full lists
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     MmArgs a1 = a;  // phase 1: every kSubStride-th row, chunks of kRc1 rows
     a1.rc = kRc1;
     a1.cap = kRc1 / kSubStride;
@@ -2005,38 +1998,38 @@ int run_batch(MmArgs a, int K, hipStream_t s, double* rows_h, uint8_t* ok_h, MmS
     OB_TRY(start_fits(a1, K, s, &a, f));
     OB_TRY(ipm(a1, K, 1, s, st));
     hipLaunchKernelGGL(mm_interp_kernel, dim3((unsigned)((n_fits + 255) / 256)), dim3(256), 0, s, a, a1, K, f);
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     if (trace()) {
-      MM_OK(hipStreamSynchronize(s));
+      OB_HIP(hipStreamSynchronize(s));
       fprintf(stderr, "[mm] phase 1 done at %.1f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count());
     }
     hipLaunchKernelGGL(mm_sample_kernel, dim3(a.n_rb * 2), dim3(1024), 0, s, a);
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     MmArgs al = a;
     al.gchol = rd.gchol;
     hipLaunchKernelGGL(mm_lev_kernel, dim3(nch, 1, a.n_rb), dim3(256), 0, s, al, K);
-    MM_OK(hipGetLastError());
+    OB_HIP(hipGetLastError());
     const double kappa_opt = ob::opt_double(ob::Opt::MmKappa, 0.0);  // options mm_kappa, mm_band0: tuning
     const double kappa = kappa_opt > 0.0 ? kappa_opt : kBandKappa;
     const double band0 = ob::opt_double(ob::Opt::MmBand0, kBand0);
     hipLaunchKernelGGL(mm_band_kernel, dim3((unsigned)n_fits), dim3(256), 0, s, a, K, kappa, band0);
-    MM_OK(hipGetLastError());
-    MM_OK(hipMemsetAsync(a.xmask, 0, sizeof(uint32_t) * (size_t)a.n_rb * nch * (a.S_pad / 64) * (a.cap / 32), s));
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipMemsetAsync(a.xmask, 0, sizeof(uint32_t) * (size_t)a.n_rb * nch * (a.S_pad / 64) * (a.cap / 32), s));
     // round 0: the bands; round 1: flagged fits, their bands plus the wrong-signed rows; round 2:
     // fits flagged again, on all rows (no verification: nothing is fixed)
     for (int round = 0; round < 3; ++round) {
       OB_TRY(reduced_round(a, K, round, s, st));
       if (round == 2) break;
-      MM_OK(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
+      OB_HIP(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
       pass(K, 4, a, dim3(nch, a.S_pad / 64, a.n_rb), 0, s);  // verify the fixed rows' signs
-      MM_OK(hipGetLastError());
+      OB_HIP(hipGetLastError());
       if (trace()) {  // why fits go to the next round: wrong-signed fixed rows or failures (with tau)
-        MM_OK(hipStreamSynchronize(s));
+        OB_HIP(hipStreamSynchronize(s));
         std::vector<uint32_t> fst(n_fits);
         std::vector<double> fsh(n_fits * kFs);
-        MM_OK(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * n_fits, hipMemcpyDeviceToHost));
-        MM_OK(hipMemcpy(fsh.data(), a.fs, sizeof(double) * n_fits * kFs, hipMemcpyDeviceToHost));
+        OB_HIP(hipMemcpy(fst.data(), a.fstat, sizeof(uint32_t) * n_fits, hipMemcpyDeviceToHost));
+        OB_HIP(hipMemcpy(fsh.data(), a.fs, sizeof(double) * n_fits * kFs, hipMemcpyDeviceToHost));
         int nv = 0, nf = 0;
         for (size_t f = 0; f < n_fits; ++f) {
           if ((int)(f % a.S_pad) >= a.S || fst[f] == kDone) continue;
@@ -2053,26 +2046,26 @@ int run_batch(MmArgs a, int K, hipStream_t s, double* rows_h, uint8_t* ok_h, MmS
       }
       hipLaunchKernelGGL(mm_retry_kernel, dim3((unsigned)((n_fits + 255) / 256)), dim3(256), 0, s, a, K, n_fits,
                          round == 1 ? 1 : 0);
-      MM_OK(hipGetLastError());
+      OB_HIP(hipGetLastError());
       uint32_t retry = 0;
-      MM_OK(hipMemcpyAsync(&retry, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      MM_OK(hipStreamSynchronize(s));
+      OB_HIP(hipMemcpyAsync(&retry, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      OB_HIP(hipStreamSynchronize(s));
       st.retried += retry;
       if (!retry) break;
     }
     if (trace()) {
-      MM_OK(hipStreamSynchronize(s));
+      OB_HIP(hipStreamSynchronize(s));
       fprintf(stderr, "[mm] batch done at %.1f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count());
     }
   }
   const size_t lds_fin = (size_t)m2 * (3 * sizeof(double) + 2 * sizeof(uint16_t));
-  MM_OK(hipFuncSetAttribute((const void*)mm_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin));
+  OB_HIP(hipFuncSetAttribute((const void*)mm_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin));
   hipLaunchKernelGGL(mm_finish_kernel, dim3(a.n_rb), dim3(256), lds_fin, s, a, K, m2);
-  MM_OK(hipGetLastError());
-  MM_OK(hipMemcpyAsync(rows_h, a.rows, sizeof(double) * a.n_rb * 3 * a.n_q, hipMemcpyDeviceToHost, s));
-  MM_OK(hipMemcpyAsync(ok_h, a.ok, a.n_rb, hipMemcpyDeviceToHost, s));
-  MM_OK(hipStreamSynchronize(s));
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipMemcpyAsync(rows_h, a.rows, sizeof(double) * a.n_rb * 3 * a.n_q, hipMemcpyDeviceToHost, s));
+  OB_HIP(hipMemcpyAsync(ok_h, a.ok, a.n_rb, hipMemcpyDeviceToHost, s));
+  OB_HIP(hipStreamSynchronize(s));
   if (g_capture.on) OB_TRY(capture_fits(a, K, s));
   return OB_OK;
 }
@@ -2089,7 +2082,7 @@ static int mm_run_impl(ob_panel* p, uint64_t seed, int sims, const double* quant
 // run rewrites) and marked so that the next call on another stream waits for it.
 int mm_run(ob_panel* p, uint64_t seed, int sims, const double* quantiles, int n_q, uint64_t first_rep,
            uint64_t n_reps, bool with_point, double* rows, uint8_t* ok, int* max_iters) {
-  MM_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   OB_TRY(ob::engine_order(p, p->ctx->stream));
   const int rc = mm_run_impl(p, seed, sims, quantiles, n_q, first_rep, n_reps, with_point, rows, ok, max_iters);
   const int rm = ob::engine_mark(p, p->ctx->stream);
@@ -2099,7 +2092,7 @@ int mm_run(ob_panel* p, uint64_t seed, int sims, const double* quantiles, int n_
 static int mm_run_impl(ob_panel* p, uint64_t seed, int sims, const double* quantiles, int n_q, uint64_t first_rep,
                        uint64_t n_reps, bool with_point, double* rows, uint8_t* ok, int* max_iters) {
   ob_ctx* ctx = p->ctx;
-  MM_OK(hipSetDevice(ctx->device));
+  OB_HIP(hipSetDevice(ctx->device));
   const int K = p->k;
   if (K > kMmMaxK) return ob::fail(OB_E_UNSUPPORTED, "Machado-Mata takes at most %d columns (intercept included), got %d", kMmMaxK, K);
   if (p->weighted || p->heckman || p->n_y != 1) return ob::fail(OB_E_INVALID, "Machado-Mata panels are unweighted, one outcome");
@@ -2130,7 +2123,7 @@ static int mm_run_impl(ob_panel* p, uint64_t seed, int sims, const double* quant
   const size_t state_per_rep = 3 * state_rows * S_pad * sizeof(double);
   const uint64_t want = std::max<uint64_t>(n_reps, 1);
   size_t free_b = 0, total_b = 0;
-  MM_OK(hipMemGetInfo(&free_b, &total_b));
+  OB_HIP(hipMemGetInfo(&free_b, &total_b));
   size_t held = 0;  // this panel's state slots from an earlier call count as free
   if (p->mm_ws)
     for (int i = 0; i < 3; ++i) held += static_cast<Buffers*>(p->mm_ws)->cap[i];
@@ -2166,12 +2159,12 @@ static int mm_run_impl(ob_panel* p, uint64_t seed, int sims, const double* quant
                            d8 * fits * K, u4 * (size_t)rb_cap * 2 * 2 * kBandSamples, u4 * (size_t)rb_cap * 2,
                            d8 * (size_t)rb_cap * 2 * (K * K + 1), d8 * lists_full * rcF,
                            u4 * (lists_blk ? lists_blk : 1) * (rcF / 32)};
-  MM_OK(b.reserve(need));
-  MM_OK(hipMemcpy(b.quant, quantiles, sizeof(double) * n_q, hipMemcpyHostToDevice));
+  OB_HIP(b.reserve(need));
+  OB_HIP(hipMemcpy(b.quant, quantiles, sizeof(double) * n_q, hipMemcpyHostToDevice));
 
   // the overflow word of this call's count images (engine_counts ORs into d_flags[2] over every
   // segment; word 0 is the boot calls' and may belong to an async boot not yet collected)
-  MM_OK(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));
+  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));
   MmArgs a{};
   for (int g = 0; g < 2; ++g) {
     a.cols[g] = p->d_cols[g];
@@ -2265,7 +2258,7 @@ static int mm_run_impl(ob_panel* p, uint64_t seed, int sims, const double* quant
     }
   }
   uint32_t flag = 0;
-  MM_OK(hipMemcpy(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  OB_HIP(hipMemcpy(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (flag) return ob::fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
   p->timing.mm_assemble_ms = st.assemble_ms;
   p->timing.mm_fit_rows = st.fit_rows;
@@ -2309,13 +2302,13 @@ extern "C" int ob_debug_mm_betas(ob_panel* p, uint64_t seed, int32_t simulations
 
 extern "C" int ob_debug_mm_fail(ob_panel* p, const uint8_t* mask, int32_t sims) {
   if (!p || sims < 0 || (sims && !mask)) return ob::fail(OB_E_INVALID, "bad arguments");
-  MM_OK(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   (void)hipFree(p->d_mm_fail);
   p->d_mm_fail = nullptr;
   p->mm_fail_sims = 0;
   if (sims == 0) return OB_OK;
-  MM_OK(hipMalloc(&p->d_mm_fail, 2 * (size_t)sims));
-  MM_OK(hipMemcpy(p->d_mm_fail, mask, 2 * (size_t)sims, hipMemcpyHostToDevice));
+  OB_HIP(hipMalloc(&p->d_mm_fail, 2 * (size_t)sims));
+  OB_HIP(hipMemcpy(p->d_mm_fail, mask, 2 * (size_t)sims, hipMemcpyHostToDevice));
   p->mm_fail_sims = sims;
   return OB_OK;
 }

@@ -22,18 +22,12 @@
 
 #include "ob_common.hpp"
 #include "ob_engine.hpp"
+#include "ob_hip.hpp"
 #include "ob_shard_layout.h"
 
 static_assert(sizeof(ob_unique_id) == sizeof(ncclUniqueId), "ob_unique_id mirrors ncclUniqueId");
 
 namespace {
-
-#define SH_HIP(expr)                                                                                      \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess)                                                                                 \
-      return ob::fail(OB_E_HIP, "HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__);     \
-  } while (0)
 
 struct Rccl {
   void* h = nullptr;
@@ -109,7 +103,7 @@ int ensure_dev(T** buf, size_t* cap, size_t elems) {
   (void)hipFree(*buf);
   *buf = nullptr;
   *cap = 0;
-  SH_HIP(hipMalloc(buf, sizeof(T) * std::max<size_t>(elems, 1)));
+  OB_HIP(hipMalloc(buf, sizeof(T) * std::max<size_t>(elems, 1)));
   *cap = elems;
   return OB_OK;
 }
@@ -127,8 +121,8 @@ int ensure_gather_map(ob_panel* p) {
     m[c] = q;
     m[(size_t)rl + q] = c;
   }
-  if (!p->d_gather_map) SH_HIP(hipMalloc(&p->d_gather_map, sizeof(int32_t) * (size_t)(2 * rl)));
-  SH_HIP(hipMemcpy(p->d_gather_map, m.data(), sizeof(int32_t) * m.size(), hipMemcpyHostToDevice));
+  if (!p->d_gather_map) OB_HIP(hipMalloc(&p->d_gather_map, sizeof(int32_t) * (size_t)(2 * rl)));
+  OB_HIP(hipMemcpy(p->d_gather_map, m.data(), sizeof(int32_t) * m.size(), hipMemcpyHostToDevice));
   p->gather_map_ready = true;
   return OB_OK;
 }
@@ -139,7 +133,7 @@ int ensure_gather_map(ob_panel* p) {
 int shard_compute(ob_panel* p, uint64_t seed, const Shard& sh, int world, int ref_mode, hipStream_t s) {
   const size_t rl = (size_t)p->row_len, ny = (size_t)p->n_y;
   const int nc = n_gather_cols(p);
-  SH_HIP(hipSetDevice(p->ctx->device));
+  OB_HIP(hipSetDevice(p->ctx->device));
   OB_TRY(ob::engine_order(p, s));  // the previous call's gather buffers, on another stream
   OB_TRY(ensure_gather_map(p));
   const size_t slots = ny * std::max<uint64_t>(sh.per, 1);
@@ -158,10 +152,10 @@ int shard_compute(ob_panel* p, uint64_t seed, const Shard& sh, int world, int re
   }
   while (p->gather_evs.size() < 2 * (size_t)(p->pending_gathers + 1)) {
     hipEvent_t e;
-    SH_HIP(hipEventCreate(&e));
+    OB_HIP(hipEventCreate(&e));
     p->gather_evs.push_back(e);
   }
-  SH_HIP(hipEventRecord(p->gather_evs[2 * (size_t)p->pending_gathers], s));
+  OB_HIP(hipEventRecord(p->gather_evs[2 * (size_t)p->pending_gathers], s));
   OB_TRY(ob::shard_pack(p->d_shard_rows, p->d_shard_ok, sh, (int)rl, nc, p->d_gather_map + rl, (int)ny, p->d_send,
                         p->d_send_ok, s));
   return OB_OK;
@@ -188,8 +182,8 @@ int shard_gather(const Rccl* r, ob_panel* p, ncclComm_t comm, const Shard& sh, i
 int shard_deliver(ob_panel* p, const Shard& sh, int world, uint64_t n_reps, double* rows, uint8_t* ok, bool host,
                   const double* own, hipStream_t s) {
   const size_t rl = (size_t)p->row_len, ny = (size_t)p->n_y;
-  SH_HIP(hipSetDevice(p->ctx->device));
-  SH_HIP(hipEventRecord(p->gather_evs[2 * (size_t)p->pending_gathers + 1], s));
+  OB_HIP(hipSetDevice(p->ctx->device));
+  OB_HIP(hipEventRecord(p->gather_evs[2 * (size_t)p->pending_gathers + 1], s));
   p->pending_gathers += 1;
   p->timing_pending = true;  // ob_panel_sync waits on s and reads the gather's events
   p->last_stream = s;
@@ -204,8 +198,8 @@ int shard_deliver(ob_panel* p, const Shard& sh, int world, uint64_t n_reps, doub
   OB_TRY(ob::shard_unpack(p->d_gather_rows, p->d_gather_ok, sh, world, n_reps, (int)rl, n_gather_cols(p),
                           p->d_gather_map, (int)ny, own, drows, dok, s));
   if (host) {
-    SH_HIP(hipMemcpyAsync(rows, drows, sizeof(double) * ny * n_reps * rl, hipMemcpyDeviceToHost, s));
-    SH_HIP(hipMemcpyAsync(ok, dok, ny * n_reps, hipMemcpyDeviceToHost, s));
+    OB_HIP(hipMemcpyAsync(rows, drows, sizeof(double) * ny * n_reps * rl, hipMemcpyDeviceToHost, s));
+    OB_HIP(hipMemcpyAsync(ok, dok, ny * n_reps, hipMemcpyDeviceToHost, s));
   }
   return ob::engine_mark(p, s, false);  // the gather reads no count image: scratch stays as the boot left it
 }
@@ -264,7 +258,7 @@ int ob_ctx_create_rank(int device, int rank, int world, const ob_unique_id* id, 
   ncclUniqueId u;
   std::memcpy(u.internal, id->internal, sizeof(u.internal));
   ncclComm_t comm = nullptr;
-  SH_HIP(hipSetDevice(device));
+  OB_HIP(hipSetDevice(device));
   const ncclResult_t e = r->comm_init_rank(&comm, world, u, rank);
   if (e != ncclSuccess) {
     ob_ctx_destroy(c);
@@ -389,16 +383,16 @@ int ob_debug_shard_sim(ob_panel* p, int world, int self_rank, uint64_t seed, uin
     OB_TRY(shard_compute(p, seed, sh, world, ref_mode, s));
     OB_TRY(ob::engine_collect(p));  // this rank's shard has finished (its ok / overflow checks)
     for (int t = 0; t < p->n_y; ++t) {  // the all-gather's placement of rank r's blocks
-      SH_HIP(hipMemcpyAsync(p->d_gather_rows + ob_recv_block_off(sh, world, t, r, nc), p->d_send + ob_send_off(sh, t, 0, nc, 0),
+      OB_HIP(hipMemcpyAsync(p->d_gather_rows + ob_recv_block_off(sh, world, t, r, nc), p->d_send + ob_send_off(sh, t, 0, nc, 0),
                             sizeof(double) * ob_send_elems(sh, nc), hipMemcpyDeviceToDevice, s));
-      SH_HIP(hipMemcpyAsync(p->d_gather_ok + ob_recv_block_off(sh, world, t, r, 1), p->d_send_ok + ob_send_ok_off(sh, t, 0),
+      OB_HIP(hipMemcpyAsync(p->d_gather_ok + ob_recv_block_off(sh, world, t, r, 1), p->d_send_ok + ob_send_ok_off(sh, t, 0),
                             sh.per, hipMemcpyDeviceToDevice, s));
     }
     if (r == self_rank) {
       self = sh;
       OB_TRY(ensure_dev(&p->d_own_rows, &p->cap_own, std::max<size_t>(ny * sh.count * rl, 1)));
       if (sh.count)
-        SH_HIP(hipMemcpyAsync(p->d_own_rows, p->d_shard_rows, sizeof(double) * ny * sh.count * rl, hipMemcpyDeviceToDevice, s));
+        OB_HIP(hipMemcpyAsync(p->d_own_rows, p->d_shard_rows, sizeof(double) * ny * sh.count * rl, hipMemcpyDeviceToDevice, s));
     }
   }
   OB_TRY(shard_deliver(p, self, world, n_reps, rows, ok, true, p->d_own_rows, s));

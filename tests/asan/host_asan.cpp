@@ -1,7 +1,8 @@
 // Host-side sanitizer driver: the C-ABI host paths of liboaxaca_boot -- CSV front
 // end (ob_csv.cpp), frame logic of the builder (ob_builder.cpp: clean_dataframe, dummies,
-// split_groups, prepare_data via ob_builder_data_matrices), inference (ob_host.cpp) and the
-// no-GPU failure of the device entry points -- built with -fsanitize=address,undefined on the
+// split_groups, prepare_data via ob_builder_data_matrices), inference (ob_host.cpp), the host
+// linear algebra of the estimators (ob_linalg.hpp) and the no-GPU failure of the device entry
+// points -- built with -fsanitize=address,undefined on the
 // host side (tests/asan/Makefile) and run by tests/test_asan.py. Exit code 0 = every check held;
 // the sanitizers abort on the first finding.
 #include <cmath>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/oaxaca_boot.h"
+#include "../../oaxaca-blinder-rs_amd/csrc/ob_linalg.hpp"
 #include "../../oaxaca-blinder-rs_amd/csrc/ob_shard_layout.h"
 
 static int failures = 0;
@@ -200,12 +202,83 @@ static void shard_layout() {
       }
 }
 
+// ob_linalg.hpp: the host solves of the logit, the AKM OLS and the Mahalanobis factor. Matrices are
+// column-major.
+static bool chol(std::vector<double> a, int k, std::vector<double>& b, ob::BackSub back,
+                 std::vector<double>* l = nullptr) {
+  const bool ok = ob::chol_factor_solve(a.data(), k, b.data(), back);
+  if (l) *l = a;
+  return ok;
+}
+
+static void linalg() {
+  const double nan = std::nan("");
+  const ob::BackSub orders[] = {ob::BackSub::Dot, ob::BackSub::Sequential};
+  for (ob::BackSub back : orders) {
+    // A = L L^T for L = [[2,0,0],[1,3,0],[-1,2,4]], b = A [1,2,3]: every operation is exact. The
+    // strict upper triangle holds a sentinel that must survive.
+    const std::vector<double> a3 = {4, 2, -2, 777, 10, 5, 777, 777, 21};
+    std::vector<double> b3 = {2, 37, 71}, l3;
+    CHECK(chol(a3, 3, b3, back, &l3));
+    CHECK((l3 == std::vector<double>{2, 1, -1, 777, 3, 2, 777, 777, 4}));
+    CHECK((b3 == std::vector<double>{1, 2, 3}));
+    std::vector<double> b1 = {8};
+    CHECK(chol({4}, 1, b1, back, &l3) && l3[0] == 2.0 && b1[0] == 2.0);
+    // k = 64, the logit's column limit: A = I + 1 1^T / 64 and x_i = i + 1, so b_i = x_i + 2080 / 64
+    const int k = 64;
+    std::vector<double> a((size_t)k * k, 1.0 / k), b(k);
+    for (int i = 0; i < k; ++i) {
+      a[i + (size_t)i * k] += 1.0;
+      b[i] = (i + 1) + 32.5;
+    }
+    CHECK(chol(a, k, b, back));
+    for (int i = 0; i < k; ++i) CHECK(std::fabs(b[i] - (i + 1)) <= 1e-12 * (i + 1));
+    // a zero, a negative and a NaN pivot, first and later
+    const std::vector<std::vector<double>> bad = {{0},          {-1},         {nan},          {1, 1, 1, 1},
+                                                  {1, 2, 2, 1}, {1, nan, nan, 1}, {4, 2, -2, 0, 10, nan, 0, 0, 21}};
+    for (const auto& m : bad) {
+      const int d = m.size() == 1 ? 1 : (m.size() == 4 ? 2 : 3);
+      std::vector<double> rhs(d, 1.0);
+      CHECK(!chol(m, d, rhs, back));
+    }
+  }
+
+  // LU: rows [0,1,2], [2,1,0], [1,3,1] need a swap at once; x = [1,2,3]
+  std::vector<double> m = {0, 2, 1, 1, 1, 3, 2, 0, 1}, b = {8, 4, 10};
+  CHECK(ob::host_lu_solve(m, 3, b));
+  for (int i = 0; i < 3; ++i) CHECK(std::fabs(b[i] - (i + 1)) <= 1e-12 * (i + 1));
+  m = {0, 0, 1, 2};  // a zero first column is skipped (no division by it), then U has a zero on its diagonal
+  b = {1, 4};
+  CHECK(!ob::host_lu_solve(m, 2, b) && b[1] == 2.0);
+  m = {1, 2, 2, 4};
+  b = {1, 1};
+  CHECK(!ob::host_lu_solve(m, 2, b));
+
+  // try_inverse: the adjugate up to 4, LU beyond
+  for (int d : {1, 2, 3, 4, 6}) {
+    std::vector<double> s((size_t)d * d), inv;
+    for (int r = 0; r < d; ++r)
+      for (int c = 0; c < d; ++c) s[r + (size_t)c * d] = (r == c ? d + 1.0 : 0.0) + 1.0 / (1 + r + 2 * c);
+    CHECK(ob::try_inverse(s, d, inv) && inv.size() == (size_t)d * d);
+    for (int r = 0; r < d; ++r)
+      for (int c = 0; c < d; ++c) {
+        double v = 0.0;
+        for (int j = 0; j < d; ++j) v += inv[r + (size_t)j * d] * s[j + (size_t)c * d];
+        CHECK(std::fabs(v - (r == c ? 1.0 : 0.0)) <= 1e-12);
+      }
+  }
+  std::vector<double> inv;
+  CHECK(!ob::try_inverse(std::vector<double>(4, 0.0), 2, inv));
+  CHECK(!ob::try_inverse(std::vector<double>(36, 0.0), 6, inv));
+}
+
 int main(int argc, char** argv) {
   const char* dir = argc > 1 ? argv[1] : "/tmp";
   csv_and_frames(dir);
   inference();
   no_gpu();
   shard_layout();
+  linalg();
   std::printf("host_asan: %s (%d failed checks)\n", failures ? "FAIL" : "ok", failures);
   return failures ? 1 : 0;
 }
