@@ -706,6 +706,49 @@ typedef struct {
 int ob_akm_results_info(const ob_akm_results* r, ob_akm_info* out);
 void ob_akm_results_free(ob_akm_results* r);
 
+/* ---- VIF collinearity diagnostic (math/diagnostics.rs:29-109 over math/ols.rs:44-144) -----------
+ * calculate_vif: for predictors x_0..x_{k-1}, in the order given, regress x_j on [the others in that
+ * order, then the intercept LAST] and score 1 / (1 - r2). The reference runs k fits of n rows; here
+ * all of them read one extended Gram G = Xe^T Xe, Xe = [x_0..x_{k-1}, 1], formed on the GPU, the k
+ * Cholesky solves run on the host in nalgebra's operation order, and one more GPU pass over the rows
+ * gives every fit's residual and total sums of squares from explicit residuals (never from
+ * G_jj - b^T beta, which cancels as r2 -> 1). Sums are f64 in a fixed order that depends on the shape
+ * only (no floating atomics), so a call repeated on the same input returns the same bytes.
+ *
+ * Errors, in this order and before any device work: k < 2 is OB_E_DIAG "VIF calculation requires at
+ * least two predictors."; k > OB_VIF_MAX_K is OB_E_UNSUPPORTED; n <= k is OB_E_INSUFFICIENT
+ * "Insufficient data for OLS calculation: n_obs (n) must be strictly greater than k (k)". A Cholesky
+ * failure of ANY fit is OB_E_LINALG "Failed to perform Cholesky decomposition. Matrix may be singular
+ * or not positive definite due to multicollinearity." and fails the whole call, as in the reference
+ * (whose INFINITY arm matches a message ols never produces). A NaN or infinite value ends there too.
+ *
+ * The one deliberate difference from the reference: a null in a named column of ob_vif_run is
+ * OB_E_INVALID naming the column. The reference reads a null regressand as 0.0 while the regressors
+ * keep it as missing. */
+#define OB_VIF_MAX_K 120
+/* x: column-major n x k, ldx >= n (entries past n of a column are never read). gram: (k + 1)^2
+   column-major, both triangles filled; row and column k are the intercept's (gram[k][k] = n). */
+int ob_vif_gram(ob_ctx* ctx, const double* x, int64_t ldx, int64_t n, int32_t k, double* gram);
+/* The k auxiliary fits from one Gram. Host only: takes no ctx and needs no GPU. coef: (k + 1) x k
+   column-major; column j holds fit j's coefficients at the positions of Xe (row k: the intercept),
+   with coef[j][j] = 0. */
+int ob_vif_solve(const double* gram, int64_t n, int32_t k, double* coef);
+/* ss_res[j] = sum_i (x_ij - xe_i . coef_j)^2 and ss_tot[j] = sum_i (x_ij - means[j])^2, j < k.
+   means[k]: ob_vif uses gram[j][k] / n. */
+int ob_vif_sums(ob_ctx* ctx, const double* x, int64_t ldx, int64_t n, int32_t k, const double* coef,
+                const double* means, double* ss_res, double* ss_tot);
+/* The three above over one upload of x. vif[k]: +inf where ss_tot == 0 or |1 - r2| < 1e-9 with
+   r2 = 1 - ss_res / ss_tot, else 1 / (1 - r2). */
+int ob_vif(ob_ctx* ctx, const double* x, int64_t ldx, int64_t n, int32_t k, double* vif);
+/* The calling thread's last ob_vif or ob_vif_run: HIP-event ms of the Gram pass and of the residual
+   pass (each with its reduce), host ms of the k solves. Any out pointer may be NULL. */
+int ob_vif_last_timing(double* gram_ms, double* solve_ms, double* sums_ms);
+/* calculate_vif over a column frame: vif[n_names] in the order of names. A missing column is
+   OB_E_COLUMN, an OB_COL_STR column OB_E_POLARS, OB_COL_I64 is cast to f64, a name given twice is
+   OB_E_INVALID (before any device work, with the shape errors above). */
+int ob_vif_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const char* const* names,
+               int32_t n_names, double* vif);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,10 +9,11 @@ from ._native import OaxacaError
 from .api import (AkmBuilder, AkmResult, BudgetAdjustment, ComponentResult, DecompositionDetail, DflResult,
                   MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder, OaxacaResults, PreparedRun,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
-                  ReferenceCoefficients, TwoFoldResults, estimate_akm, match_units, parse_formula, run_dfl,
-                  run_dfl_from_csv)
+                  ReferenceCoefficients, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
+                  parse_formula, run_dfl, run_dfl_from_csv)
 from .engine import (Panel, aggregate, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
-                     knn, logit, match_logistic, rif, row_layout, silverman_bandwidth)
+                     knn, logit, match_logistic, rif, row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing,
+                     vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
 __all__ = [
@@ -23,4 +24,5 @@ __all__ = [
     "DflResult", "run_dfl", "run_dfl_from_csv", "logit", "kde", "silverman_bandwidth",
     "MatchingEngine", "MatchResult", "match_units", "knn", "match_logistic",
     "AkmBuilder", "AkmResult", "estimate_akm", "akm_connected_set", "akm_demean", "akm_recover_fe",
+    "VifResult", "calculate_vif", "vif", "vif_gram", "vif_solve", "vif_sums", "vif_last_timing",
 ]

@@ -51,11 +51,13 @@ EXPORTED = (
     "ob_match_results_free",
     "ob_akm_connected_set", "ob_akm_set_get", "ob_akm_set_id", "ob_akm_set_free", "ob_akm_demean",
     "ob_akm_recover_fe", "ob_akm_run", "ob_akm_results_get", "ob_akm_results_info", "ob_akm_results_free",
+    "ob_vif_gram", "ob_vif_solve", "ob_vif_sums", "ob_vif", "ob_vif_run", "ob_vif_last_timing",
 )
 
 OB_E_CONVERGENCE = 12
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
 OB_AKM_MAX_CONTROLS = 64
+OB_VIF_MAX_K = 120
 OB_MATCH_MAX_DIM, OB_MATCH_MAX_K = 64, 16
 OB_MATCH_EUCLIDEAN, OB_MATCH_MAHALANOBIS, OB_MATCH_PSM = 0, 1, 2
 
@@ -292,6 +294,12 @@ _SIGS = {
                                      C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(_D), C.POINTER(C.c_double)]),
     "ob_akm_results_info": (C.c_int, [_P, C.POINTER(ob_akm_info)]),
     "ob_akm_results_free": (None, [_P]),
+    "ob_vif_gram": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, _D]),
+    "ob_vif_solve": (C.c_int, [_D, C.c_int64, C.c_int32, _D]),
+    "ob_vif_sums": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _D]),
+    "ob_vif": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, _D]),
+    "ob_vif_last_timing": (C.c_int, [_D, _D, _D]),
+    "ob_vif_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.c_int32, _D]),
 }
 
 _lib = None

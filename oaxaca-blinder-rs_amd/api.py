@@ -339,6 +339,17 @@ class OaxacaBuilder:
         finally:
             lib.ob_matrices_free(h)
 
+    def vif(self) -> list:
+        """The variance inflation factors of this builder's own design (``VifResult`` per column): the
+        predictors and the dummies of ``get_data_matrices()`` without the intercept, over the cleaned
+        frame with both groups stacked (A's rows, then B's). The check to make before ``run()``:
+        collinear columns make the detailed terms meaningless."""
+        from .engine import vif
+
+        xa, _, xb, _, names = self.get_data_matrices()
+        scores = vif(np.vstack([xa, xb])[:, 1:], device=self._device)
+        return [VifResult(nm, float(s)) for nm, s in zip(names[1:], scores)]
+
     def run(self) -> OaxacaResults:
         """builder.rs:787-951 on the MI355X engine."""
         lib = N.lib()
@@ -856,3 +867,30 @@ def estimate_akm(csv_path, outcome: str, worker_col: str, firm_col: str, control
 
     b = AkmBuilder(read_csv(csv_path), outcome, worker_col, firm_col, device=device)
     return b.controls(controls or []).tolerance(tolerance).max_iters(max_iters).run()
+
+
+@dataclass
+class VifResult:
+    """math/diagnostics.rs:12-18: a predictor's name and its variance inflation factor."""
+    variable_name: str
+    vif_score: float
+
+
+def calculate_vif(dataframe, predictor_names, device: int | None = None) -> list:
+    """math/diagnostics.rs:29-109 on the MI355X engine (``ob_vif_run``): one ``VifResult`` per name, in
+    the order given. ``dataframe`` is what ``OaxacaBuilder`` takes. Fewer than two names, a Cholesky
+    failure of any auxiliary fit (perfect multicollinearity) and too few rows raise as the reference
+    returns its errors; a null in a named column raises OB_E_INVALID (the reference would read it as
+    0.0 in the regressand and as missing in the regressors)."""
+    lib = N.lib()
+    frame = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
+    cols, ncol, nrow = frame.as_c()
+    names = [str(p) for p in predictor_names]
+    pp, pa = _strs(names)
+    out = np.empty(len(names))
+    try:
+        N.check(lib.ob_vif_run(N.context(device), cols, ncol, nrow, pp, len(names),
+                               out.ctypes.data_as(C.POINTER(C.c_double))))
+    finally:
+        del pa
+    return [VifResult(nm, float(s)) for nm, s in zip(names, out)]

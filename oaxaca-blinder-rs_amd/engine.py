@@ -416,3 +416,70 @@ def akm_recover_fe(r, worker_idx, firm_idx, n_workers: int, n_firms: int, tol: f
     N.check(N.lib().ob_akm_recover_fe(N.context(device), _dp(r), n, _i32(wi), _i32(fi), int(n_workers), int(n_firms),
                                       float(tol), int(max_iters), _dp(alpha), _dp(psi), C.byref(iters), C.byref(conv)))
     return alpha, psi, int(iters.value), bool(conv.value)
+
+
+def _vif_x(x):
+    """(n, K) predictors as the C ABI takes them: column-major, a Fortran-ordered view with a longer
+    leading dimension passed as it is. Returns (array, ldx, n, K)."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("x must be (n, K)")
+    n, k = x.shape
+    if not (x.strides[0] == 8 and x.strides[1] % 8 == 0 and x.strides[1] >= 8 * max(n, 1)):
+        x = np.asfortranarray(x)
+    ldx = x.strides[1] // 8 if k > 1 and n > 0 else max(n, 1)
+    return x, ldx, n, k
+
+
+def vif_gram(x, device: int | None = None):
+    """The extended Gram of the VIF fits on the GPU (``ob_vif_gram``): G = Xe'Xe for Xe = [x, 1],
+    (K + 1, K + 1) with both triangles filled; row and column K are the intercept's."""
+    x, ldx, n, k = _vif_x(x)
+    g = np.empty((k + 1, k + 1), order="F")
+    N.check(N.lib().ob_vif_gram(N.context(device), _dp(x), ldx, n, k, _dp(g)))
+    return g
+
+
+def vif_solve(gram, n: int):
+    """The K auxiliary fits of math/diagnostics.rs:43-66 from one Gram, on the host (``ob_vif_solve``,
+    no GPU needed): each x_j on [the others in order, the intercept last] by nalgebra's Cholesky.
+    Returns the (K + 1, K) coefficients at the positions of Xe, with B[j, j] = 0."""
+    g = np.asfortranarray(gram, dtype=np.float64)
+    if g.ndim != 2 or g.shape[0] != g.shape[1] or g.shape[0] < 1:
+        raise ValueError("gram must be (K + 1, K + 1)")
+    k = g.shape[0] - 1
+    b = np.empty((k + 1, max(k, 0)), order="F")
+    N.check(N.lib().ob_vif_solve(_dp(g), int(n), k, _dp(b)))
+    return b
+
+
+def vif_sums(x, coef, means, device: int | None = None):
+    """Every fit's sums of squares in one pass over the rows on the GPU (``ob_vif_sums``): ss_res[j] =
+    sum_i (x_ij - xe_i . coef[:, j])^2 from explicit residuals and ss_tot[j] = sum_i (x_ij -
+    means[j])^2. Returns (ss_res, ss_tot)."""
+    x, ldx, n, k = _vif_x(x)
+    b = np.asfortranarray(coef, dtype=np.float64)
+    m = np.ascontiguousarray(means, dtype=np.float64)
+    if b.shape != (k + 1, k) or m.shape != (k,):
+        raise ValueError("coef must be (K + 1, K) and means (K,)")
+    ss_res, ss_tot = np.empty(k), np.empty(k)
+    N.check(N.lib().ob_vif_sums(N.context(device), _dp(x), ldx, n, k, _dp(b), _dp(m), _dp(ss_res), _dp(ss_tot)))
+    return ss_res, ss_tot
+
+
+def vif(x, device: int | None = None):
+    """math/diagnostics.rs:29-109 on the GPU (``ob_vif``): the variance inflation factor of every
+    column of the (n, K) array ``x``, +inf where the reference gives it. A Cholesky failure of any
+    auxiliary fit raises OB_E_LINALG for the whole call, as in the reference."""
+    x, ldx, n, k = _vif_x(x)
+    out = np.empty(k)
+    N.check(N.lib().ob_vif(N.context(device), _dp(x), ldx, n, k, _dp(out)))
+    return out
+
+
+def vif_last_timing() -> dict:
+    """``ob_vif_last_timing``: this thread's last ``vif`` / ``calculate_vif`` call, in ms: the Gram pass
+    and the residual pass by HIP events, the K solves by the host clock."""
+    g, s, r = C.c_double(), C.c_double(), C.c_double()
+    N.check(N.lib().ob_vif_last_timing(C.byref(g), C.byref(s), C.byref(r)))
+    return {"gram_ms": g.value, "solve_ms": s.value, "sums_ms": r.value}
