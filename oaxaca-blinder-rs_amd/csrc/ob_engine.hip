@@ -77,7 +77,6 @@ struct GramArgs {
   int diag;  // OB_GRAM_DIAG bits: 2 no MFMAs, 4 no sub-tile DMA (tools/gram_ablate.py), 8 raw Heckman
              // statuses; count kernel timing ablations (wrong counts): 32 no LDS atomics, 64 no Philox
   int dbl;   // ob_gram_kernel: 1 = two staged sub-tile buffers (prefetch), 0 = one (k1 > kGramDblMaxK1)
-  uint32_t rb0;  // ob_count_kernel: the launch's first 64-replicate batch (a piece of the segment)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -591,10 +590,7 @@ __device__ __forceinline__ void level2_draws(const GramArgs& a, const Work& w, u
 // image (kImgRow) their atomics fall on distinct banks. The part calls (m % 16 draws, one per
 // replicate) form one extra window, one lane per replicate. Same (call, replicate) -> draws as
 // level2_draws, so the same counts.
-#ifndef OB_CNT_MAPCAP
-#define OB_CNT_MAPCAP 2048
-#endif
-constexpr uint32_t kCallMapCap = OB_CNT_MAPCAP;  // calls past the dense prefix a (tile, batch) map holds
+constexpr uint32_t kCallMapCap = 2048;  // calls past the dense prefix a (tile, batch) map holds
 
 __device__ __forceinline__ void level2_map_draws(const GramArgs& a, const Work& w, uint32_t tile, uint32_t* cnt,
                                                  const uint32_t* mc, const uint32_t* cmap, uint32_t C,
@@ -787,7 +783,7 @@ __global__ __launch_bounds__(kBlock) void ob_count_kernel(const GramArgs a) {
   __shared__ uint32_t cmap[OB_CNT_MAP ? kCallMapCap : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   Work w{};
-  w.rb = a.rb0 + blockIdx.y;
+  w.rb = blockIdx.y;
   w.rep0 = w.rb * 64;
   const uint32_t tt0 = blockIdx.x * kCntTilesPerBlock;
   const uint32_t tt1 = min(a.tiles_total, tt0 + kCntTilesPerBlock);
@@ -1861,9 +1857,7 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
   OB_TRY(ensure_buf(&p->d_counts, p->cap_counts, (size_t)tiles * pl.nb_rep * 4 * kCimgWords));
   OB_TRY(ensure_buf(&p->d_partial, p->cap_partial, need_partial * p->e_pad));
   OB_TRY(ensure_buf(&p->d_gram, p->cap_gram, (size_t)2 * pl.rep_pad * p->e_pad));
-  bool s_work = false;  // this call put work on s that its Gram reads (tail_stream: g_stream waits for it)
   if (!p->chunks_ready) {  // the chunk table depends on the panel only: uploaded once, never rewritten
-    s_work = true;
     p->chunks = pl.chunks;
     OB_TRY(ensure_buf(&p->d_chunks, p->cap_chunks, p->chunks.size()));
     OB_HIP(hipMemcpyAsync(p->d_chunks, p->chunks.data(), sizeof(uint32_t) * p->chunks.size(), hipMemcpyHostToDevice, s));
@@ -1884,7 +1878,6 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
     p->pending_gathers = 0;
   }
   if (use_i8) {
-    if (p->oz_state == 0) s_work = true;
     OB_TRY(ob::oz_prepare(p, s));
     use_i8 = p->oz_state == 1;
     if (!use_i8 && force == 2) return ob::fail(OB_E_UNSUPPORTED, "the i8 Gram's digit images do not fit in HBM");
@@ -1942,12 +1935,6 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
   // replicates/s), while a wide-tile block needs a whole CU's LDS, so resample blocks there delay
   // the Gram more than they hide (5,000 / 2,500 / 10k replicates: -9 / -11 / -4.5 %;
   // profiles/r06_ab_rs_double.txt)
-  const int rs_pieces = ob::opt_int(ob::Opt::RsPieces, 1);
-  if (overlap && rs_pieces > 1) {
-    if (!p->cnt_stream) OB_HIP(hipStreamCreateWithFlags(&p->cnt_stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : p->cnt_ev)
-      if (!e) OB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
   const int rs_opt = ob::opt_int(ob::Opt::RsDouble, -1);
   const bool dbl = overlap && (rs_opt == 1 || (rs_opt < 0 && use_i8 && !ob::oz_wide(p, nch, pl.nb_rep)));
   if (dbl) {
@@ -1958,56 +1945,23 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
       OB_HIP(hipEventRecord(p->scratch_ev2, s));
     }
   }
-  const bool tov = overlap && ob::opt_int(ob::Opt::TailStream, 0) == 1;
-  if (tov) {
-    if (!p->g_stream) OB_HIP(hipStreamCreateWithFlags(&p->g_stream, hipStreamNonBlocking));
-    if (!p->t_stream) OB_HIP(hipStreamCreateWithFlags(&p->t_stream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&p->g_ev, &p->t_ev, &p->user_ev, &p->prep_ev})
-      if (!*e) OB_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (hipEvent_t& e : p->red_ev)
-      if (!e) {
-        OB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        OB_HIP(hipEventRecord(e, s));
-      }
-    OB_TRY(ensure_buf(&p->d_partialb, p->cap_partialb, need_partial * p->e_pad));
-    OB_HIP(hipEventRecord(p->user_ev, s));
-    if (s_work) {
-      OB_HIP(hipEventRecord(p->prep_ev, s));
-      OB_HIP(hipStreamWaitEvent(p->g_stream, p->prep_ev, 0));
-    }
-  }
-  const hipStream_t sg = tov ? p->g_stream : s;  // the Gram
-  const hipStream_t st = tov ? p->t_stream : s;  // reduce, exceptions, solve
   for (uint64_t s0 = 0; s0 < n_reps; s0 += seg) {
     const uint32_t ns = (uint32_t)std::min<uint64_t>(seg, n_reps - s0);
     const Plan& plx = (ns == seg) ? pl : pl_tail;
     const int nchx = plx.n_chunks();
     const uint32_t frep = (uint32_t)(first_rep + s0);
     hipEvent_t* ev = p->seg_events.data() + kSegEvents * (size_t)p->pending_segments;
-    const bool timed = true;
     const int buf = dbl ? p->rs_parity : 0;
     uint32_t* const m1 = buf ? p->d_m1b : p->d_m1;
     uint32_t* const counts = buf ? p->d_countsb : p->d_counts;
     const hipEvent_t sev = buf ? p->scratch_ev2 : p->scratch_ev;  // the last read of this buffer
     if (dbl) p->rs_parity ^= 1;
-    const int pb = tov ? p->part_parity : 0;
-    if (tov) p->part_parity ^= 1;
-    double* const partial = pb ? p->d_partialb : p->d_partial;
     if (overlap) OB_HIP(hipStreamWaitEvent(sr, sev, 0));
-    if (timed) OB_HIP(hipEventRecord(ev[0], sr));
-    // pieces (option rs_pieces): level 1 over replicate batches [b0, b1) of piece k, then (below) the
-    // count kernel of each piece on cnt_stream once its level 1 is done, beside the next piece's
-    const int npc = overlap ? std::max(1, std::min({rs_pieces, 8, (int)plx.nb_rep})) : 1;
-    for (int k = 0; k < npc; ++k) {
-      const uint32_t r0 = std::min<uint32_t>(64u * (plx.nb_rep * k / npc), ns);
-      const uint32_t r1 = std::min<uint32_t>(64u * (plx.nb_rep * (k + 1) / npc), ns);
-      if (r1 > r0)
-        hipLaunchKernelGGL(l1k, dim3(r1 - r0, 2), dim3(kBlock), lds_l1, sr, p->n[0], p->n[1], p->ntiles[0],
-                           frep + r0, tiles, key0, key1, m1 + (size_t)r0 * tiles, ky);
-      OB_HIP(hipGetLastError());
-      if (npc > 1) OB_HIP(hipEventRecord(p->cnt_ev[k], sr));
-    }
-    if (timed) OB_HIP(hipEventRecord(ev[1], sr));
+    OB_HIP(hipEventRecord(ev[0], sr));
+    hipLaunchKernelGGL(l1k, dim3(ns, 2), dim3(kBlock), lds_l1, sr, p->n[0], p->n[1], p->ntiles[0], frep, tiles, key0,
+                       key1, m1, ky);
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipEventRecord(ev[1], sr));
     GramArgs ga = gram_args(p, plx);
     ga.chunks = p->d_chunks;
     ga.m1 = m1;
@@ -2015,54 +1969,39 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
     ga.first_rep = frep;
     ga.key0 = key0;
     ga.key1 = key1;
-    ga.partial = partial;
+    ga.partial = p->d_partial;
     ga.counts = counts;
     ga.tiles_total = tiles;
     ga.diag = diag_mode();
-    const hipStream_t sc = npc > 1 ? p->cnt_stream : sr;
-    for (int k = 0; k < npc; ++k) {
-      const uint32_t b0 = plx.nb_rep * k / npc, b1 = plx.nb_rep * (k + 1) / npc;
-      if (npc > 1) OB_HIP(hipStreamWaitEvent(sc, p->cnt_ev[k], 0));
-      if (b1 == b0) continue;
-      ga.rb0 = b0;
-      const dim3 cgrid((tiles + kCntTilesPerBlock - 1) / kCntTilesPerBlock, b1 - b0);
-      if (use_i8) hipLaunchKernelGGL(ob_count_kernel<true>, cgrid, dim3(kBlock), 0, sc, ga);
-      else hipLaunchKernelGGL(ob_count_kernel<false>, cgrid, dim3(kBlock), 0, sc, ga);
-      OB_HIP(hipGetLastError());
-    }
-    ga.rb0 = 0;
-    if (timed) OB_HIP(hipEventRecord(ev[2], sc));
+    const dim3 cgrid((tiles + kCntTilesPerBlock - 1) / kCntTilesPerBlock, plx.nb_rep);
+    if (use_i8) hipLaunchKernelGGL(ob_count_kernel<true>, cgrid, dim3(kBlock), 0, sr, ga);
+    else hipLaunchKernelGGL(ob_count_kernel<false>, cgrid, dim3(kBlock), 0, sr, ga);
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipEventRecord(ev[2], sr));
     if (overlap) {
-      OB_HIP(hipEventRecord(p->rs_ev, sc));
-      OB_HIP(hipStreamWaitEvent(sg, p->rs_ev, 0));
+      OB_HIP(hipEventRecord(p->rs_ev, sr));
+      OB_HIP(hipStreamWaitEvent(s, p->rs_ev, 0));
     }
-    if (tov) OB_HIP(hipStreamWaitEvent(sg, p->red_ev[pb], 0));  // the reduce two segments back read it
-    if (timed) OB_HIP(hipEventRecord(ev[3], sg));
+    OB_HIP(hipEventRecord(ev[3], s));
     if (use_i8) {
-      OB_TRY(ob::oz_gram(p, p->d_chunks, nchx, counts, plx.nb_rep, plx.rep_pad, ns, partial, sg));
+      OB_TRY(ob::oz_gram(p, p->d_chunks, nchx, counts, plx.nb_rep, plx.rep_pad, ns, p->d_partial, s));
     } else {
       const uint32_t blocks = plx.nb_rep * plx.n_cg * (uint32_t)nchx;
-      OB_HIP(launch_gram(p, plx.cb, false, ga, blocks, sg));
+      OB_HIP(launch_gram(p, plx.cb, false, ga, blocks, s));
     }
-    if (timed) OB_HIP(hipEventRecord(ev[4], sg));
+    OB_HIP(hipEventRecord(ev[4], s));
     const bool exc = use_i8 && ob::oz_exceptions_pending(p);
-    if (overlap && !exc) OB_HIP(hipEventRecord(sev, sg));  // the count images are free again
-    if (tov) {
-      OB_HIP(hipEventRecord(p->g_ev, sg));
-      OB_HIP(hipStreamWaitEvent(st, p->g_ev, 0));
-      OB_HIP(hipStreamWaitEvent(st, p->user_ev, 0));  // the caller's use of the rows buffers so far
-    }
+    if (overlap && !exc) OB_HIP(hipEventRecord(sev, s));  // the count images are free again
     const size_t nred = (size_t)ns * p->e_pad;
-    hipLaunchKernelGGL(ob_reduce_kernel, dim3((unsigned)((nred + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       (const double*)partial, (const uint32_t*)p->d_chunks, nchx, plx.rep_pad, p->e_pad, ns,
+    hipLaunchKernelGGL(ob_reduce_kernel, dim3((unsigned)((nred + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                       (const double*)p->d_partial, (const uint32_t*)p->d_chunks, nchx, plx.rep_pad, p->e_pad, ns,
                        p->d_gram);
     OB_HIP(hipGetLastError());
-    if (tov) OB_HIP(hipEventRecord(p->red_ev[pb], st));
     if (exc) {
-      OB_TRY(ob::oz_exceptions(p, counts, plx.nb_rep, ns, p->d_gram, st));
-      if (overlap) OB_HIP(hipEventRecord(sev, st));
+      OB_TRY(ob::oz_exceptions(p, counts, plx.nb_rep, ns, p->d_gram, s));
+      if (overlap) OB_HIP(hipEventRecord(sev, s));
     }
-    if (timed) OB_HIP(hipEventRecord(ev[5], st));
+    OB_HIP(hipEventRecord(ev[5], s));
     if (p->heckman) {  // probit iterations + IMR sums + two-step solve (synchronizes the stream)
       ob_heck_seg hs = heck_seg(p, plx, p->d_chunks, p->d_gram, ref_mode);
       hs.counts = counts;
@@ -2089,15 +2028,11 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
       sa.gram_out = nullptr;
       sa.raw_beta_b = nullptr;
       sa.raw_status = 0;
-      OB_HIP(launch_solve(p, sa, ns, st));
+      OB_HIP(launch_solve(p, sa, ns, s));
     }
-    if (timed) OB_HIP(hipEventRecord(ev[6], st));
+    OB_HIP(hipEventRecord(ev[6], s));
     p->timing.gram_launches += 1;
     p->pending_segments += 1;
-  }
-  if (tov) {  // the caller's stream sees the rows complete, as without the tail stream
-    OB_HIP(hipEventRecord(p->t_ev, st));
-    OB_HIP(hipStreamWaitEvent(s, p->t_ev, 0));
   }
   p->timing_pending = true;
   p->last_stream = s;
@@ -2344,6 +2279,7 @@ void ob_panel_destroy(ob_panel* p) {
   if (!p) return;
   (void)hipSetDevice(p->ctx->device);
   if (p->timing_pending) (void)hipStreamSynchronize(p->last_stream);
+  if (p->rs_stream) (void)hipStreamSynchronize(p->rs_stream);  // its kernels write d_m1 / d_counts
   for (int g = 0; g < 2; ++g) {
     (void)hipFree(p->d_cols[g]);
     (void)hipFree(p->d_gpanel[g]);
@@ -2365,27 +2301,13 @@ void ob_panel_destroy(ob_panel* p) {
   (void)hipFree(p->d_ok_tmp);
   (void)hipFree(p->d_pe);
   (void)hipFree(p->d_pe_ok);
-  if (p->rs_stream) (void)hipStreamSynchronize(p->rs_stream);
-  if (p->rs_ev) (void)hipEventDestroy(p->rs_ev);
-  if (p->scratch_ev) (void)hipEventDestroy(p->scratch_ev);
-  if (p->scratch_ev2) (void)hipEventDestroy(p->scratch_ev2);
-  for (hipStream_t x : {p->g_stream, p->t_stream})
-    if (x) (void)hipStreamSynchronize(x);
-  for (hipEvent_t e : {p->g_ev, p->t_ev, p->user_ev, p->prep_ev, p->red_ev[0], p->red_ev[1]})
-    if (e) (void)hipEventDestroy(e);
-  for (hipStream_t x : {p->g_stream, p->t_stream})
-    if (x) (void)hipStreamDestroy(x);
-  (void)hipFree(p->d_partialb);
-  if (p->cnt_stream) (void)hipStreamSynchronize(p->cnt_stream);
-  for (hipEvent_t e : p->cnt_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (p->cnt_stream) (void)hipStreamDestroy(p->cnt_stream);
-  if (p->rs_stream) (void)hipStreamDestroy(p->rs_stream);
+  (void)hipFree(p->d_mm_fail);
   ob::shard_free(p);
   ob::oz_free(p);
-  (void)hipFree(p->d_mm_fail);
+  for (hipEvent_t e : {p->rs_ev, p->scratch_ev, p->scratch_ev2, p->order_ev})
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : p->seg_events) (void)hipEventDestroy(e);
-  if (p->order_ev) (void)hipEventDestroy(p->order_ev);
+  if (p->rs_stream) (void)hipStreamDestroy(p->rs_stream);
   if (p->mm_ws_free) p->mm_ws_free(p->mm_ws);
   delete p;
 }

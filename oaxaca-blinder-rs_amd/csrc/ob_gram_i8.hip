@@ -475,15 +475,11 @@ struct OzArgs {
 };
 
 constexpr int kWaves = 8;                         // 2 per SIMD: (replicate batch, slice group)
-#ifndef OB_OZ_SUB2
-// 1: two 64-row sub-tiles per barrier (one barrier per 128 rows) over an 8-stage ring; 0: one
-// sub-tile per barrier over a 4-stage ring
-#define OB_OZ_SUB2 1
-#endif
-constexpr int kNbuf = OB_OZ_SUB2 ? 8 : 4;         // LDS ring stages (sub-tiles)
+// two 64-row sub-tiles per barrier (one barrier per 128 rows) over an 8-stage ring
+constexpr int kNbuf = 8;                          // LDS ring stages (sub-tiles)
 constexpr int kBDma = (kSubUnits + 64 * kWaves - 1) / (64 * kWaves);  // B DMA instructions per wave (<=)
 constexpr int kBDmaTotal = kSubUnits / 64;        // 14 per sub-tile, spread over the waves
-constexpr size_t kLdsB = kNbuf * (size_t)kSubUnits * 16;      // B ring (56 KB; 112 KB with OB_OZ_SUB2)
+constexpr size_t kLdsB = kNbuf * (size_t)kSubUnits * 16;      // B ring (112 KB)
 constexpr size_t kLdsX = 4 * 64 * (size_t)kPairsPerTile * 8;  // slice-group exchange (64 KB, over the ring)
 constexpr size_t kLdsBytes = kLdsB > kLdsX ? kLdsB : kLdsX;
 static_assert(kBDma == 2 && kBDmaTotal == 14, "B DMA split below assumes 14 instructions over 8 waves");
@@ -512,20 +508,15 @@ __device__ __forceinline__ void oz_dma16s(uint32_t voff, const void* sbase, uint
 
 __device__ __forceinline__ void oz_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-#ifndef OB_OZ_RASTER
-#define OB_OZ_RASTER 1
-#endif
 // Block -> (column tile, replicate tile, chunk). A "group" is the n_ct column tiles of one
 // (chunk, replicate tile); its blocks share that tile's count images, so they run on one XCD
 // (blocks b and b + 8 share an XCD under round-robin dispatch: speed only, never correctness).
-// OB_OZ_RASTER 1: groups are dealt to the 8 XCDs in turn (8 consecutive groups = one "super group"
-// of 8 n_ct blocks, group = bid mod 8 inside it), so all XCDs sweep the chunks together and the
-// chunk's digit block (47 MB at configs[1]) is re-read from the Infinity Cache by every replicate
-// tile. 0: each XCD sweeps a contiguous eighth of the groups (8 chunks in flight at once).
+// Groups are dealt to the 8 XCDs in turn (8 consecutive groups = one "super group" of 8 n_ct
+// blocks, group = bid mod 8 inside it), so all XCDs sweep the chunks together and the chunk's digit
+// block (47 MB at configs[1]) is re-read from the Infinity Cache by every replicate tile.
 __device__ __forceinline__ void oz_map(const OzArgs& a, uint32_t* ct, uint32_t* rt, uint32_t* chunk) {
   const uint32_t nwg = gridDim.x, bid = blockIdx.x, nct = (uint32_t)a.n_ct;
   uint32_t grp, c;
-#if OB_OZ_RASTER
   const uint32_t sgb = 8u * nct, sg = bid / sgb, r = bid - sg * sgb;
   const uint32_t left = nwg - sg * sgb;  // blocks from this super group on
   if (left >= sgb) {
@@ -536,12 +527,6 @@ __device__ __forceinline__ void oz_map(const OzArgs& a, uint32_t* ct, uint32_t* 
     grp = sg * 8u + r % ng;
     c = r / ng;
   }
-#else
-  const uint32_t xcd = bid & 7u, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7u;
-  const uint32_t wi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-  grp = wi / nct;
-  c = wi - grp * nct;
-#endif
   *ct = c;
   *rt = grp % a.n_rt;
   *chunk = grp / a.n_rt;
@@ -578,7 +563,6 @@ __device__ __forceinline__ void oz_mfmas(ob_v4i (&acc)[4][kSlo][2], int h, const
 // replicates 16 m + 4 (l >> 4) + i.
 template <int NQ, int SLO, int NB, bool LIVE, int DIAG>
 __device__ __forceinline__ void oz_gram_body(const OzArgs& a, unsigned char* smem, int wave) {
-  constexpr int PER = NB + (LIVE ? 4 : 0);  // this wave's vector-memory ops per sub-tile
   const ob_v4i* bs = reinterpret_cast<const ob_v4i*>(smem);  // [kNbuf][kSubUnits]
   const int lane = threadIdx.x & 63;
   const int wb = wave & 3, grp = wave >> 2;  // replicate batch in the tile, slice group
@@ -591,10 +575,9 @@ __device__ __forceinline__ void oz_gram_body(const OzArgs& a, unsigned char* sme
   const uint32_t g = a.chunks[3 * chunk];
   const uint32_t n = g ? a.n1 : a.n0, tg0 = g ? a.tiles0 : 0u;
   const uint32_t s0 = a.chunks[3 * chunk + 1] * 4u;
-  // OB_OZ_SUB2: an odd sub-tile count (a group's last chunk) runs one padding sub-tile more, whose
-  // count image and digits exist (tiles are 4 sub-tiles, s0 a multiple of 4) and hold zeros
-  const uint32_t s1 = OB_OZ_SUB2 ? (min(a.chunks[3 * chunk + 2] * 4u, (n + 63u) >> 6) + 1u) & ~1u
-                                 : min(a.chunks[3 * chunk + 2] * 4u, (n + 63u) >> 6);
+  // an odd sub-tile count (a group's last chunk) runs one padding sub-tile more, whose count image
+  // and digits exist (tiles are 4 sub-tiles, s0 a multiple of 4) and hold zeros
+  const uint32_t s1 = (min(a.chunks[3 * chunk + 2] * 4u, (n + 63u) >> 6) + 1u) & ~1u;
   const ob_v4i* Bg = g ? a.B1 : a.B0;
   const uint32_t batch = rt * 4u + (uint32_t)wb;
   auto dma = [&](int buf, uint32_t s) {
@@ -647,53 +630,18 @@ __device__ __forceinline__ void oz_gram_body(const OzArgs& a, unsigned char* sme
   ob_v4i fb0[kSlo], fb1[kSlo];
   if constexpr (LIVE) read(0, 0, fb0);
 
-  // Half-step (s, 0): read (s, 1); MFMAs on (s, 0). Barrier B_s: sub-tile s + 1 landed (own loads,
-  // then everyone's), every read of sub-tile s done. Refill stage s with B of s + 4. Half-step
-  // (s, 1): read (s + 1, 0) (after the last sub-tile: a stale stage, never used); MFMAs on (s, 1);
-  // then A of s + 3 into the register slot s frees. Issue order per sub-tile t: B(t + 4) after
-  // B_t, A(t + 3) at the end of step t, so at B_s the loads newer than those of s + 1 are
-  // B(s + 3), A(s + 2) (after step s - 1) and B(s + 2) is older than A(s + 1): the wait leaves
-  // PER in flight. Every step issues the same loads (past the end: the last sub-tile again, into a
-  // stage nobody reads, and a dead A slot), so every step waits the same count and the wait
-  // pattern is a property of the code, not of the chunk length (tools/isa_vmem_check.py checks it
-  // on the built ISA: no DMA older than two barriers at a barrier, no register of an un-waited load
-  // touched). Round 4 measured the alternatives to this schedule and kept none.
-  auto step = [&](uint32_t s, auto J) {
-    constexpr int j = decltype(J)::value;
-    const int buf = (int)((s - s0) & (kNbuf - 1));
-    if constexpr (LIVE) {
-      read(buf, 1, fb1);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (!(DIAG & 2)) oz_mfmas<NQ>(acc, 0, ar[j], fb0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (DIAG & 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-    if constexpr (DIAG & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // timing only: no barrier
-    else oz_barrier();
-    if constexpr (!(DIAG & 4)) dma(buf, min(s + kNbuf, s1 - 1));
-    if constexpr (LIVE) {
-      read((buf + 1) & (kNbuf - 1), 0, fb0);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (!(DIAG & 2)) oz_mfmas<NQ>(acc, 1, ar[j], fb1);
-      __builtin_amdgcn_sched_barrier(0);
-      // unconditional (past the end: a re-read of the last sub-tile, never used), so the compiler's
-      // count of outstanding A loads is exact at every MFMA
-      if constexpr (!(DIAG & 4)) aload(ar[j], min(s + 3, s1 - 1));
-    }
-  };
-  // groups of three steps, then the one or two left: every step, the tail's included, issues the
-  // same loads and waits, so each path through the loop presents the same queue at each barrier.
-  // (Ghost steps past the end with branch-guarded MFMAs, the round-4 first form, read 5 GB more
-  // per launch and ran 1.5 % slower: profiles/r04_ab_gram_tail.txt.)
-#if OB_OZ_SUB2
   // Two sub-tiles (s, s + 1) per barrier. Sub-tile u uses A slot (u - s0) % 3 and ring stage
   // (u - s0) % 8. Order: MFMAs (s, 0) | read (s, 1); MFMAs (s, 1) | read (s + 1, 0); A(s + 3) into
   // s's slot; MFMAs (s + 1, 0) | read (s + 1, 1); wait + barrier: stages s + 2, s + 3 landed (their
   // DMA was issued three barriers earlier), every read of s, s + 1 done; refill those two stages
   // with s + 8, s + 9; read (s + 2, 0); MFMAs (s + 1, 1); A(s + 4) into s + 1's slot. Newer than the
   // DMA of s + 2, s + 3 at the barrier: A(s - 2); A(s - 1), 2 NB DMA, A(s); A(s + 1), 2 NB DMA,
-  // A(s + 2); A(s + 3) = 24 + 4 NB (LIVE) or 4 NB loads.
+  // A(s + 2); A(s + 3) = 24 + 4 NB (LIVE) or 4 NB loads. Every step issues the same loads (past the
+  // end: the last sub-tile again, into a stage nobody reads, and a dead A slot), so every step waits
+  // the same count and the wait pattern is a property of the code, not of the chunk length
+  // (tools/isa_vmem_check.py checks it on the built ISA: no DMA older than two barriers at a
+  // barrier, no register of an un-waited load touched). Round 4 measured the alternatives to this
+  // schedule and kept none.
   constexpr int PER2 = 4 * NB + (LIVE ? 24 : 0);
   auto step2 = [&](uint32_t s, auto J0, auto J1) {
     constexpr int j0 = decltype(J0)::value, j1 = decltype(J1)::value;
@@ -728,6 +676,10 @@ __device__ __forceinline__ void oz_gram_body(const OzArgs& a, unsigned char* sme
       if constexpr (!(DIAG & 4)) aload(ar[j1], min(s + 4, s1 - 1));
     }
   };
+  // groups of three steps, then the one or two left: every step, the tail's included, issues the
+  // same loads and waits, so each path through the loop presents the same queue at each barrier.
+  // (Ghost steps past the end with branch-guarded MFMAs, the round-4 first form, read 5 GB more
+  // per launch and ran 1.5 % slower: profiles/r04_ab_gram_tail.txt.)
   uint32_t s = s0;  // s1 - s0 is even here
   for (; s + 6 <= s1; s += 6) {
     step2(s, IC<0>{}, IC<1>{});
@@ -736,16 +688,6 @@ __device__ __forceinline__ void oz_gram_body(const OzArgs& a, unsigned char* sme
   }
   if (s < s1) step2(s, IC<0>{}, IC<1>{});
   if (s + 2 < s1) step2(s + 2, IC<2>{}, IC<0>{});
-#else
-  uint32_t s = s0;
-  for (; s + 3 <= s1; s += 3) {
-    step(s, IC<0>{});
-    step(s + 1, IC<1>{});
-    step(s + 2, IC<2>{});
-  }
-  if (s < s1) step(s, IC<0>{});
-  if (s + 1 < s1) step(s + 1, IC<1>{});
-#endif
   // slices -> f64: this wave's digits meet exactly in int64, one ldexp each; group 1 goes through
   // LDS to its group-0 partner, which adds (one rounding) and stores.
   int E[2];
@@ -852,9 +794,6 @@ constexpr int kWAgprTiles = 64;  // accumulator tiles (4 registers each) pinned 
 // 4 stages of B (two six-slice tiles: 24 KB; one seven-slice tile: 14 KB) + A (16 KB)
 constexpr size_t kWLds = kWNbuf * (size_t)(2 * 6 * 2 * 64 + 4 * 4 * 64) * 16;
 
-#ifndef OB_OZ_W_AFIRST
-#define OB_OZ_W_AFIRST 0  // 1: after the barrier, read the next step's A 0..3 with its first B block
-#endif
 #ifndef OB_OZ_W_SPLIT
 #define OB_OZ_W_SPLIT 1  // the engine may split a wide launch's chunks over two blocks (oz_gram_mode)
 #endif
@@ -1016,16 +955,7 @@ __device__ __forceinline__ void oz_gram_w2_body(const OzArgs& a, unsigned char* 
         constexpr int pu = u - (U - POST);  // 0 .. POST - 1
         const int nbuf = (buf + 1) % kWNbuf;
         constexpr bool rb = !(DIAG & 128), ra = !(DIAG & 256);  // timing ablations: no B / A reads
-        if constexpr (POST == 2 && OB_OZ_W_AFIRST) {
-          // in the order the next step needs them: A 0..3 and its first B block in the first unit,
-          // A 4..7 (its second replicate half) in the second
-          if constexpr (pu == 0) {
-            if constexpr (ra && q < 4) ar[j ^ 1][q] = aread1(nbuf, q);
-            if constexpr (rb) fb[fnext][q] = bread1(nbuf, 0, q);
-          } else if constexpr (ra && q < 4) {
-            ar[j ^ 1][q + 4] = aread1(nbuf, q + 4);
-          }
-        } else if constexpr (POST == 2) {
+        if constexpr (POST == 2) {
           if constexpr (pu == 0) {
             if constexpr (rb) fb[fnext][q] = bread1(nbuf, 0, q);
           } else if constexpr (ra) {

@@ -37,10 +37,6 @@ enum class Opt : int {
                        // error path that a real count above 255 would take, p < 1e-500 per row)
   RsDouble,     // 1: two count-image / m1 buffers, so a boot's resample runs under the previous Gram;
                 // 0: one; unset: the engine's rule (engine_boot)
-  RsPieces,     // level 1 and counts of a segment in this many replicate pieces, counts of piece k
-                // beside level 1 of piece k + 1 (1: one launch each); unset: the engine's rule
-  TailStream,   // 1: a boot's reduce / solve on a stream of their own, so the next segment's Gram
-                // need not wait for them (two partial buffers); 0: on the caller's stream; unset: rule
   MatchChunks,  // the matching distance pass splits the controls into this many chunks (1: no split);
                 // unset: the rule of match_knn, a function of the input sizes (results do not depend on it)
   AkmPoll,      // the AKM loops read their done flags every this many iterations (results and iteration

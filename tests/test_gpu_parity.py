@@ -509,46 +509,21 @@ def test_double_buffered_resample_bitwise(ob, O):
         assert np.array_equal(r2, long_rows) and np.array_equal(o2, long_ok)
 
 
-def test_pieced_resample_bitwise(ob, O):
-    """Option rs_pieces: level 1 and the count kernel of a segment in replicate pieces, each piece's
-    counts beside the next piece's level 1 (ob_engine.hip engine_boot). Same kernels on the same
-    (replicate, tile) units, so the rows equal the one-launch run bitwise, with and without the
-    double-buffered resample, across a two-segment call and a partial last batch."""
-    panel, _, _ = make(O, ob, 7000, 5, True)
-    small, _, _ = make(O, ob, 600, 2, False)
-    with ob._native.option("rs_pieces", 1), ob._native.option("rs_double", 0):
-        want = panel.boot(SEED, 11, 777, 3)
-        want_long = small.boot(SEED, 0, 16500, 0)
-        cnt = panel.debug_counts(SEED, 11, 128, 0)
-    for pieces in (2, 3, 5, 8):
-        for dbl in (0, 1):
-            with ob._native.option("rs_pieces", pieces), ob._native.option("rs_double", dbl):
-                got = panel.boot(SEED, 11, 777, 3)
-                assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (pieces, dbl)
-                got2 = panel.boot(SEED, 11, 777, 3)  # back to back on the same buffers
-                assert np.array_equal(got2[0], want[0]), (pieces, dbl)
-    with ob._native.option("rs_pieces", 4):
-        r, o = small.boot(SEED, 0, 16500, 0)
-        assert np.array_equal(r, want_long[0]) and np.array_equal(o, want_long[1])
-        assert all(np.array_equal(x, y) for x, y in zip(panel.debug_counts(SEED, 11, 128, 0), cnt))
-
-
-def test_tail_stream_bitwise_and_ordered(ob, O):
-    """Option tail_stream: the Gram on an engine stream, reduce / exceptions / solve on another, the
-    caller's stream waiting for them at the end of the call, so the next segment's Gram runs under
-    this one's tail (two partial buffers). Rows bitwise as on one stream; a copy the caller enqueues
-    between two calls that reuse one rows buffer still sees the first call's rows (the tail waits
-    for the caller's stream); calls alternate between two torch streams; with and without rs_double."""
+def test_rows_buffer_reuse_keeps_stream_order(ob, O):
+    """A boot's level 1 and counts run on the panel's resample stream, its Gram, reduce and solve on
+    the caller's (ob_engine.hpp). A copy the caller enqueues on its stream right after boot_device
+    sees that call's rows, while three calls reuse one rows / ok buffer and alternate between two
+    torch streams; a two-segment call matches afterwards; with and without rs_double."""
     import torch
 
     panel, _, _ = make(O, ob, 6000, 5, True)
     small, _, _ = make(O, ob, 600, 2, False)
-    with ob._native.option("tail_stream", 0), ob._native.option("rs_double", 0):
+    with ob._native.option("rs_double", 0):
         want = [panel.boot(SEED, r0, 256, 2) for r0 in (0, 256, 512)]
         want_long = small.boot(SEED, 0, 16500, 0)
     dev = torch.device("cuda", 0)
     for dbl in (0, 1):
-        with ob._native.option("tail_stream", 1), ob._native.option("rs_double", dbl):
+        with ob._native.option("rs_double", dbl):
             got = [panel.boot(SEED, r0, 256, 2) for r0 in (0, 256, 512)]
             for (a, oa), (b, obb) in zip(want, got):
                 assert np.array_equal(a, b) and np.array_equal(oa, obb), dbl

@@ -73,8 +73,8 @@ WIDE = "_ZN12_GLOBAL__N_116oz_gram_w_kernelILi0EEEvNS_6OzArgsE"  # oz_gram_w_ker
 
 def test_shipped_wide_gram_kernel_waits_are_clean():
     """The wide-tile kernel uses the same untracked LDS-DMA ring with hand-counted waits (a 4-stage
-    ring, one barrier per sub-tile, PER = 2 NB + 12) and pins its accumulators to AGPRs through
-    inline-asm MFMAs: the walk must find no DMA older than two barriers at a barrier and no
+    ring, one barrier per sub-tile, PER = (kWNbuf - 2) (NB + 4) = 2 NB + 8) and pins its
+    accumulators to AGPRs through inline-asm MFMAs: the walk must find no DMA older than two barriers at a barrier and no
     register (VGPR or AGPR) touched under an un-waited load."""
     if not os.path.exists(SO) or not os.path.exists(os.path.join(C.LLVM, "llvm-objdump")):
         pytest.skip("engine library or llvm-objdump missing (run __graft_entry__.build())")
