@@ -154,14 +154,26 @@ __device__ __forceinline__ uint32_t ky_walk(ob_bitstream& s, const KyLds& L, int
   }
 }
 
-// Work item q of the split of a node holding c draws (ob_spec.h, OBRS-2): a popcount word below
-// OB_KY_MIN_C draws, else one stream (one Knuth-Yao sample or the low popcount). rl = (round << 5)
-// + level.
+// Words q0, q0 + dq, ... of the popcount stream of a node holding c < OB_KY_MIN_C draws, summed
+// (ob_spec.h: word q counts bits [128 q, min(c, 128 q + 128))). The c >> 7 full words are four
+// bare popcounts each; only the partial last word, when this sequence holds it, pays for the
+// per-word bit masks. One Philox chain per lane: two independent ones measured slower
+// (DESIGN.md §5.1 "Level 1, re-measured"). rl = (round << 5) + level.
+__device__ __forceinline__ uint32_t l1_split_words(uint32_t q0, uint32_t dq, uint32_t c, uint32_t rep, uint32_t c2,
+                                                   uint32_t rl, uint32_t k0, uint32_t k1) {
+  const uint32_t tag = OB_TAG_L1T + rl, nf = c >> 7;
+  uint32_t left = 0, q = q0;
+  for (; q < nf; q += dq) left += ob_l1_full_bits(q, rep, c2, tag, k0, k1);
+  if ((c & 127u) && q == nf) left += ob_l1_split_bits(nf, c, rep, c2, tag, k0, k1);
+  return left;
+}
+
+// Work item q of the split of a node holding c >= OB_KY_MIN_C draws (ob_spec.h, OBRS-2): one
+// stream (one Knuth-Yao sample or the low popcount). rl = (round << 5) + level.
 __device__ __forceinline__ uint32_t l1_split_item(uint32_t q, uint32_t c, uint32_t rep, uint32_t c2, uint32_t rl,
                                                   uint32_t k0, uint32_t k1, const KyLds& L,
                                                   const uint32_t* __restrict__ goff,
                                                   const uint16_t* __restrict__ glist) {
-  if (c < OB_KY_MIN_C) return ob_l1_split_bits(q, c, rep, c2, OB_TAG_L1T + rl, k0, k1);
   const uint32_t c4 = c >> 12;
   ob_bitstream s = {q << 12, rep, c2, OB_TAG_L1K + rl, k0, k1, 0u, 0u, 0u, 0u, 0u};
   if (q < c4) return ky_walk(s, L, OB_KY_TABLES - 1, goff, glist);
@@ -228,19 +240,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         const uint32_t sh = 8 - ll, k = tid >> sh, j = tid & ((1u << sh) - 1);
         if (j == 0 && k < nodes) nxt[2 * k] = 0;
         __syncthreads();
+        uint32_t c = 0;
         if (k < nodes) {
-          const uint32_t c = cur[k];
+          c = cur[k];
           uint32_t left = 0;
-          const uint32_t ns = c ? ob_l1_items(c) : 0u;
           if constexpr (DIAG & 1) left = j == 0 ? c >> 1 : 0u;
+          else if (c < OB_KY_MIN_C) left = l1_split_words(j, 1u << sh, c, rep, ((kb + k) << 1) | g, rl, key0, key1);
           else
-            for (uint32_t q = j; q < ns; q += 1u << sh)
+            for (uint32_t q = j, ns = ob_l1_items(c); q < ns; q += 1u << sh)
               left += l1_split_item(q, c, rep, ((kb + k) << 1) | g, rl, key0, key1, kyl, ky_g.off, ky_g.list);
           if (left) atomicAdd(&nxt[2 * k], left);
         }
         __syncthreads();
         if (j == 0 && k < nodes) {
-          const uint32_t c = cur[k], right = c - nxt[2 * k];
+          const uint32_t right = c - nxt[2 * k];
           if (2 * (kb + k) + 1 < nnext) nxt[2 * k + 1] = right;
           else rej += right;
         }
@@ -250,11 +263,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         for (uint32_t k = tid; k < nodes; k += kBlock) {
           const uint32_t c = cur[k], kg = kb + k;
           uint32_t left = 0;
-          const uint32_t ns = c ? ob_l1_items(c) : 0u;
           if constexpr (DIAG & 1) left = c >> 1;
           else if ((DIAG & 32) && c < 128u) left = c >> 1;
+          else if (c < OB_KY_MIN_C) left = l1_split_words(0, 1, c, rep, (kg << 1) | g, rl, key0, key1);
           else
-            for (uint32_t q = 0; q < ns; ++q)
+            for (uint32_t q = 0, ns = ob_l1_items(c); q < ns; ++q)
               left += l1_split_item(q, c, rep, (kg << 1) | g, rl, key0, key1, kyl, ky_g.off, ky_g.list);
           const uint32_t right = c - left;
           if (to_m1) {

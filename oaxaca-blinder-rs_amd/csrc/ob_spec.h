@@ -157,6 +157,12 @@ OB_HD uint32_t ob_l1_split_bits(uint32_t q, uint32_t c, uint32_t rep, uint32_t c
   }
   return s;
 }
+// The same count for a word q < c >> 7, whose 128 bits are all counted (no masks).
+OB_HD uint32_t ob_l1_full_bits(uint32_t q, uint32_t rep, uint32_t c2, uint32_t tag, uint32_t k0, uint32_t k1) {
+  const ob_u32x4 u = OB_L1_PHILOX(q, rep, c2, tag, k0, k1);
+  return (uint32_t)(__builtin_popcount(u.x) + __builtin_popcount(u.y) + __builtin_popcount(u.z) +
+                    __builtin_popcount(u.w));
+}
 
 // Work items of a node's split: popcount words below OB_KY_MIN_C, else its streams (c >> 12 of
 // B(4096), one per set bit 11 .. 7, one for the popcount of c & 127 when nonzero).
