@@ -533,6 +533,35 @@ __device__ __forceinline__ void add_draws_word(uint32_t* img, uint32_t rep_off, 
   add_draw_byte<3>(img, rep_off, hi, m, one);
 }
 
+// The first n (0..3) draws of a Philox word, each under its own predicate.
+__device__ __forceinline__ void add_draws_bytes(uint32_t* img, uint32_t rep_off, uint32_t w, uint32_t one, uint32_t n) {
+  const uint32_t m = (w << 3) & 0x18181818u;
+  if (OB_CNT_PERM) {
+    const uint32_t q = (w >> 2) & 0x3F3F3F3Fu;
+    if (n > 0) add_draw_perm<0>(img, rep_off, q, m, one);
+    if (n > 1) add_draw_perm<1>(img, rep_off, q, m, one);
+    if (n > 2) add_draw_perm<2>(img, rep_off, q, m, one);
+    return;
+  }
+  const uint32_t lo = (w << 6) & 0x3F003F00u, hi = (w >> 2) & 0x3F003F00u;
+  if (n > 0) add_draw_byte<0>(img, rep_off, lo, m, one);
+  if (n > 1) add_draw_byte<1>(img, rep_off, hi, m, one);
+  if (n > 2) add_draw_byte<2>(img, rep_off, lo, m, one);
+}
+
+// A full tile's part call of replicate r: the first nd = m % 16 bytes of Philox call m / 16. Its
+// nd / 4 complete words go through add_draws_word, only the nd % 4 bytes of the next word one by
+// one: three predicated word steps and three predicated bytes.
+__device__ __forceinline__ void part_call_draws(uint32_t* img, uint32_t r, uint32_t nd, const ob_u32x4& u,
+                                                uint32_t one) {
+  const uint32_t nw = nd >> 2;
+  if (nw > 0) add_draws_word(img, r * 4u, u.x, one);
+  if (nw > 1) add_draws_word(img, r * 4u, u.y, one);
+  if (nw > 2) add_draws_word(img, r * 4u, u.z, one);
+  const uint32_t wl = nw == 0 ? u.x : nw == 1 ? u.y : nw == 2 ? u.z : u.w;
+  add_draws_bytes(img, r * 4u, wl, one, nd & 3u);
+}
+
 __device__ __forceinline__ void level2_draws(const GramArgs& a, const Work& w, uint32_t tile, uint32_t* cnt,
                                              const uint32_t* mc, const uint32_t* cum, int k, int nparts, int wv,
                                              int nw, int lane) {
@@ -585,10 +614,7 @@ __device__ __forceinline__ void level2_draws(const GramArgs& a, const Work& w, u
     const uint32_t m = mc[r], nd = m & 15u;
     if (nd) {
       const ob_u32x4 u = ob_philox_x3(m >> 4, rep0 + r, c2, OB_TAG_L2, a.key0, a.key1);
-      const uint32_t wd[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (uint32_t d = 0; d < 15; ++d)
-        if (d < nd) add_draw(cnt, (uint32_t)r, (wd[d >> 2] >> (8 * (d & 3))) & 0xFFu);
+      part_call_draws(cnt, (uint32_t)r, nd, u, one);
     }
   }
 }
@@ -597,13 +623,15 @@ __device__ __forceinline__ void level2_draws(const GramArgs& a, const Work& w, u
 // that the block's waves walk in 64-call windows, window j on wave j mod 4, one lane per call. The
 // list is call-major: call index p of every replicate that has one, replicates ascending, then p + 1.
 // The first cmin = min_r(calls) indices hold all 64 replicates, so window p < cmin is call p of
-// replicate `lane` (no lookup); past them an LDS call map (word = p << 6 | r, written by wave 0
-// when it publishes the tile's counts) lists the rest. Either way the lanes of a window draw for
+// replicate `lane` (no lookup); past them an LDS call map (word = p << 6 | r, written with the
+// tile's counts, publish_counts) lists the rest. Either way the lanes of a window draw for
 // distinct replicates (up to the seam between two indices past cmin), and with the replicate-minor
 // image (kImgRow) their atomics fall on distinct banks. The part calls (m % 16 draws, one per
 // replicate) form one extra window, one lane per replicate. Same (call, replicate) -> draws as
 // level2_draws, so the same counts.
-constexpr uint32_t kCallMapCap = 2048;  // calls past the dense prefix a (tile, batch) map holds
+// Calls past the dense prefix that a (tile, batch) map holds. A full batch needs about 200; two
+// maps (the kernel double-buffers them) of 1,024 keep the block's LDS at six blocks per CU.
+constexpr uint32_t kCallMapCap = 1024;
 
 __device__ __forceinline__ void level2_map_draws(const GramArgs& a, const Work& w, uint32_t tile, uint32_t* cnt,
                                                  const uint32_t* mc, const uint32_t* cmap, uint32_t C,
@@ -639,10 +667,7 @@ __device__ __forceinline__ void level2_map_draws(const GramArgs& a, const Work& 
       const uint32_t m = mc[lane], nd = m & 15u;
       if (nd) {
         const ob_u32x4 u = ob_philox_x3(m >> 4, rep0 + (uint32_t)lane, c2, OB_TAG_L2, a.key0, a.key1);
-        const uint32_t wd[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (uint32_t d = 0; d < 15; ++d)
-          if (d < nd) add_draw(cnt, (uint32_t)lane, (wd[d >> 2] >> (8 * (d & 3))) & 0xFFu);
+        part_call_draws(cnt, (uint32_t)lane, nd, u, one);
       }
     }
   }
@@ -715,29 +740,41 @@ __device__ __forceinline__ uint32_t level1_count(const GramArgs& a, uint32_t rep
   return rep < a.n_reps ? a.m1[(size_t)rep * a.tiles_total + tt] : 0u;
 }
 
+// Wave-wide scan and reductions in the vector pipe (DPP row shifts, then the row broadcasts): lane
+// l of a row takes lane l - n of its row, `idle` where there is none; row_bcast:15 hands a row's last
+// lane to the next row (rows 1 and 3), row_bcast:31 lane 31 to rows 2 and 3. After the six steps
+// lane l holds op over lanes 0..l, so lane 63 the whole wave's.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp_take(uint32_t v, uint32_t idle) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)idle, (int)v, CTRL, ROWS, 0xF, false);
+}
+template <class Op>
+__device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t idle, Op op) {
+  v = op(v, dpp_take<0x111, 0xF>(v, idle));  // row_shr:1
+  v = op(v, dpp_take<0x112, 0xF>(v, idle));  // row_shr:2
+  v = op(v, dpp_take<0x114, 0xF>(v, idle));  // row_shr:4
+  v = op(v, dpp_take<0x118, 0xF>(v, idle));  // row_shr:8
+  v = op(v, dpp_take<0x142, 0xA>(v, idle));  // row_bcast:15
+  v = op(v, dpp_take<0x143, 0xC>(v, idle));  // row_bcast:31
+  return v;
+}
+
 __device__ __forceinline__ void publish_counts(const Work& w, uint32_t tile, uint32_t m, uint32_t* mc, uint32_t* cum,
                                                int lane, uint32_t* cmap, uint32_t* cminp) {
   mc[lane] = m;
   // calls in the whole-call list: full tile floor(m/16) (the part call goes apart), else ceil(m/2)
   const bool full = full_tile(w, tile);
   const uint32_t c = full ? m >> 4 : (m + 1) >> 1;
-  uint32_t v = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
+  const uint32_t v = wave_scan(c, 0u, [](uint32_t x, uint32_t y) { return x + y; });
   cum[lane + 1] = v;
   if (lane == 0) cum[0] = 0;
   // the call map of a full tile (level2_map_draws): call-major past the dense prefix of cmin
   // indices, when those calls fit it
   if (cmap && full) {
-    uint32_t cmin = c, cmax = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      cmin = min(cmin, (uint32_t)__shfl_xor(cmin, o));
-      cmax = max(cmax, (uint32_t)__shfl_xor(cmax, o));
-    }
+    const uint32_t cmin = (uint32_t)__builtin_amdgcn_readlane(
+        wave_scan(c, 0xFFFFFFFFu, [](uint32_t x, uint32_t y) { return min(x, y); }), 63);
+    const uint32_t cmax =
+        (uint32_t)__builtin_amdgcn_readlane(wave_scan(c, 0u, [](uint32_t x, uint32_t y) { return max(x, y); }), 63);
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane(v, 63);
     if (total - cmin * 64u <= kCallMapCap) {
       uint32_t base = 0;
@@ -789,52 +826,72 @@ constexpr int kCntTilesPerBlock = OB_CNT_TILES;
 // I8: the image is written in the A-fragment order of ob_gram_i8.hip instead (v_mfma_i32_16x16x64_i8):
 // per (tile, batch) [sub-tile][16-replicate block m][lane][16 B], lane l = replicate 16 m + (l & 15),
 // rows 16 (l >> 4) + j of the sub-tile -- 16 KB, one 16-byte store per thread and unit.
+//
+// Two barriers per tile: draws | check, store and clear | next tile's draws. Tile tt + 1's counts,
+// call prefix, cmin and call map are published while tile tt's draws run, by the wave that the
+// round-robin of tile tt's windows would serve next (so it has no more windows than any other), into
+// buffer (tt + 1) & 1 of mcb, cumb, cminb and cmap. Those buffers were last read by the draws of tile
+// tt - 1, before that tile's first barrier, and by check_sums of tile tt - 1, which the same wave
+// runs just before it publishes (one wave's LDS accesses stay in order). The draws of tile tt read
+// buffer tt & 1 only. check_sums of tile tt - 1 follows the barrier after that tile's
+// check_store_counts, so its sums are complete, and clears them two barriers before tile tt + 1's
+// check_store_counts adds to them again. The wave loads tile tt + 1's level-1 counts before its own
+// windows, so the draws cover the load.
 template <bool I8>
 __global__ __launch_bounds__(kBlock) void ob_count_kernel(const GramArgs a) {
   __shared__ uint32_t img[kImgWords];
   __shared__ uint32_t mcb[2][64], cumb[2][65], lsumb[2][64], cminb[2];
-  __shared__ uint32_t cmap[OB_CNT_MAP ? kCallMapCap : 1];
+  __shared__ uint32_t cmapb[2][kCallMapCap];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   Work w{};
   w.rb = blockIdx.y;
   w.rep0 = w.rb * 64;
   const uint32_t tt0 = blockIdx.x * kCntTilesPerBlock;
   const uint32_t tt1 = min(a.tiles_total, tt0 + kCntTilesPerBlock);
-  // wave 0 loads tile tt+1's level-1 counts while the block draws tile tt
-  uint32_t m_next = (wave == 0 && tt0 < tt1) ? level1_count(a, w.rep0, tt0, lane) : 0u;
+  if (tt0 >= tt1) return;
   // the image starts zeroed once; check_store_counts clears what it read
   for (int i = tid; i < kImgWords; i += kBlock) img[i] = 0u;
   if (tid < 128) lsumb[tid >> 6][tid & 63] = 0u;
-  // Two barriers per tile: the call prefix, counts and sums are double-buffered, so publishing
-  // tile tt + 1's (buffer (tt + 1) & 1) never races the checks of tile tt (buffer tt & 1), and the
-  // image clears of tile tt complete before the barrier that follows that publish.
+  if (wave == 0) {
+    w.g = tt0 >= a.tiles0 ? 1u : 0u;
+    w.n = w.g ? a.n1 : a.n0;
+    publish_counts(w, tt0 - (w.g ? a.tiles0 : 0u), level1_count(a, w.rep0, tt0, lane), mcb[tt0 & 1], cumb[tt0 & 1], lane,
+                   cmapb[tt0 & 1], &cminb[tt0 & 1]);
+  }
+  __syncthreads();
   for (uint32_t tt = tt0; tt < tt1; ++tt) {
-    uint32_t* mc = mcb[tt & 1];
-    uint32_t* cum = cumb[tt & 1];
+    const uint32_t* mc = mcb[tt & 1];
     w.g = tt >= a.tiles0 ? 1u : 0u;
     w.n = w.g ? a.n1 : a.n0;
     const uint32_t tile = tt - (w.g ? a.tiles0 : 0u);
-    if (wave == 0) {
-      publish_counts(w, tile, m_next, mc, cum, lane, OB_CNT_MAP ? cmap : nullptr, &cminb[tt & 1]);
-      if (tt + 1 < tt1) m_next = level1_count(a, w.rep0, tt + 1, lane);
-    }
-    __syncthreads();
-    if (wave == 0 && tt > tt0) check_sums(a, lsumb[(tt - 1) & 1], mcb[(tt - 1) & 1], lane);
-    const uint32_t C = cum[64];
+    const uint32_t C = cumb[tt & 1][64];
     const uint32_t cmin = cminb[tt & 1];
+    const bool mapped = OB_CNT_MAP && full_tile(w, tile) && C - cmin * 64u <= kCallMapCap;
+    // the wave after the one that takes the last window (whole-call windows, then the part-call one)
+    const bool pub = (uint32_t)wave == (mapped ? (((C + 63u) >> 6) + 1u) & 3u : 0u);
+    uint32_t m_next = 0u;
+    if (pub && tt + 1 < tt1) m_next = level1_count(a, w.rep0, tt + 1, lane);
     if (a.diag & 1024) {  // timing ablation (gram_diag 1024): no level-2 draws at all
-    } else if (OB_CNT_MAP && full_tile(w, tile) && C - cmin * 64u <= kCallMapCap)
-      level2_map_draws(a, w, tile, img, mc, cmap, C, cmin, wave, lane);
+    } else if (mapped)
+      level2_map_draws(a, w, tile, img, mc, cmapb[tt & 1], C, cmin, wave, lane);
     else
-      level2_draws(a, w, tile, img, mc, cum, 0, 1, wave, 4, lane);
+      level2_draws(a, w, tile, img, mc, cumb[tt & 1], 0, 1, wave, 4, lane);
+    if (pub) {
+      if (tt > tt0) check_sums(a, lsumb[(tt - 1) & 1], mcb[(tt - 1) & 1], lane);
+      if (tt + 1 < tt1) {
+        Work wn = w;
+        wn.g = tt + 1 >= a.tiles0 ? 1u : 0u;
+        wn.n = wn.g ? a.n1 : a.n0;
+        publish_counts(wn, tt + 1 - (wn.g ? a.tiles0 : 0u), m_next, mcb[(tt + 1) & 1], cumb[(tt + 1) & 1], lane,
+                       cmapb[(tt + 1) & 1], &cminb[(tt + 1) & 1]);
+      }
+    }
     __syncthreads();
     const uint32_t ns = (min(OB_TILE_ROWS, w.n - tile * OB_TILE_ROWS) + 63) >> 6;
     check_store_counts<I8>(a, img, lsumb[tt & 1], tid, tt, w.rb, ns);
-  }
-  if (tt0 < tt1) {
     __syncthreads();
-    if (wave == 0) check_sums(a, lsumb[(tt1 - 1) & 1], mcb[(tt1 - 1) & 1], lane);
   }
+  if (wave == 0) check_sums(a, lsumb[(tt1 - 1) & 1], mcb[(tt1 - 1) & 1], lane);
 }
 
 // ---------------------------------------------------------------------------------------------
