@@ -134,26 +134,6 @@ __device__ __forceinline__ void ky_stage(KyLds& L, const ob_ky_tables& g, uint32
   for (uint32_t i = tid; 2 * i < g.hot_entries; i += kBlock) reinterpret_cast<uint32_t*>(L.hlist)[i] = he[i];
 }
 
-// One B(2^(t + 7), 1/2) sample: the Knuth-Yao walk (ob_spec.h), one stream bit per column.
-__device__ __forceinline__ uint32_t ky_walk(ob_bitstream& s, const KyLds& L, int t, const uint32_t* __restrict__ goff,
-                                            const uint16_t* __restrict__ glist) {
-  const uint32_t i0 = L.i0[t];
-  uint32_t d = ob_bs_take_msb(s, i0 - 1u);  // columns 1 .. i0 - 1 hold no entries
-  for (uint32_t c = 0;; ++c) {
-    d = 2u * d + ob_bs_bit(s);
-    if (c < OB_KY_HOT) {
-      const uint32_t lo = L.hoff[t][c], cnt = L.hoff[t][c + 1] - lo;
-      if (d < cnt) return L.hlist[lo + d];
-      d -= cnt;
-    } else {
-      const uint32_t* off = goff + L.obase[t];
-      const uint32_t i = i0 + c, lo = off[i], cnt = off[i + 1] - lo;
-      if (d < cnt) return glist[L.lbase[t] + lo + d];
-      d -= cnt;
-    }
-  }
-}
-
 // Words q0, q0 + dq, ... of the popcount stream of a node holding c < OB_KY_MIN_C draws, summed
 // (ob_spec.h: word q counts bits [128 q, min(c, 128 q + 128))). The c >> 7 full words are four
 // bare popcounts each; only the partial last word, when this sequence holds it, pays for the
@@ -169,22 +149,32 @@ __device__ __forceinline__ uint32_t l1_split_words(uint32_t q0, uint32_t dq, uin
 }
 
 // Work item q of the split of a node holding c >= OB_KY_MIN_C draws (ob_spec.h, OBRS-2): one
-// stream (one Knuth-Yao sample or the low popcount). rl = (round << 5) + level.
+// stream, whose first Philox call every kind of item draws in the same place: a B(2^(t + 7), 1/2)
+// sample by the register-resident Knuth-Yao walk (ob_spec.h ob_ky_walk) over the LDS-staged hot
+// columns of table t, or the low popcount, the call's first c & 127 bits. rl = (round << 5) + level.
+// DIAG 64 (timing only): a walk item is its mean, without its call; 192: its mean, after the call.
+template <int DIAG>
 __device__ __forceinline__ uint32_t l1_split_item(uint32_t q, uint32_t c, uint32_t rep, uint32_t c2, uint32_t rl,
                                                   uint32_t k0, uint32_t k1, const KyLds& L,
                                                   const uint32_t* __restrict__ goff,
                                                   const uint16_t* __restrict__ glist) {
-  const uint32_t c4 = c >> 12;
-  ob_bitstream s = {q << 12, rep, c2, OB_TAG_L1K + rl, k0, k1, 0u, 0u, 0u, 0u, 0u};
-  if (q < c4) return ky_walk(s, L, OB_KY_TABLES - 1, goff, glist);
-  const uint32_t i = q - c4, nd = (uint32_t)__builtin_popcount((c >> 7) & 31u);
-  if (i < nd) return ky_walk(s, L, (int)ob_l1_digit_log(c, i) - OB_KY_MIN_LOG, goff, glist);
-  return ob_bs_popcount(s, c & 127u);
+  const uint32_t c4 = c >> 12, tag = OB_TAG_L1K + rl, ctr0 = q << 12;
+  const uint32_t nk = c4 + (uint32_t)__builtin_popcount((c >> 7) & 31u);  // the Knuth-Yao streams
+  const int t = q < c4 ? OB_KY_TABLES - 1 : q < nk ? (int)ob_l1_digit_log(c, q - c4) - OB_KY_MIN_LOG : 0;
+  if constexpr ((DIAG & 192) == 64)
+    if (q < nk) return 64u << t;
+  const ob_u32x4 u = OB_L1_PHILOX(ctr0, rep, c2, tag, k0, k1);
+  if (q >= nk) return ob_l1_head_bits(u, c & 127u);
+  if constexpr ((DIAG & 192) == 192) return (64u << t) + (u.x == 7u ? 1u : 0u);
+  uint32_t bits;
+  return ob_ky_walk(u, ctr0, rep, c2, tag, k0, k1, L.i0[t], L.hoff[t], L.hlist, goff + L.obase[t],
+                    glist + L.lbase[t], &bits);
 }
 
 // DIAG (OB_L1_DIAG, timing ablations only, wrong counts): 1 no random bits (left = c / 2),
 // 2 one round only, 4 no Knuth-Yao staging, 8 no m1 stores, 16 return after the staging barrier,
-// 32 no random bits for the one-thread-per-node levels' nodes below 128 draws.
+// 32 no random bits for the one-thread-per-node levels' nodes below 128 draws, 64 every Knuth-Yao
+// walk a constant, 192 the same with the walk's Philox call kept (l1_split_item).
 template <int DIAG>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void ob_level1_kernel(uint32_t n0, uint32_t n1, uint32_t tiles0,
                                                            uint32_t first_rep, uint32_t stride,
@@ -248,7 +238,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
           else if (c < OB_KY_MIN_C) left = l1_split_words(j, 1u << sh, c, rep, ((kb + k) << 1) | g, rl, key0, key1);
           else
             for (uint32_t q = j, ns = ob_l1_items(c); q < ns; q += 1u << sh)
-              left += l1_split_item(q, c, rep, ((kb + k) << 1) | g, rl, key0, key1, kyl, ky_g.off, ky_g.list);
+              left += l1_split_item<DIAG>(q, c, rep, ((kb + k) << 1) | g, rl, key0, key1, kyl, ky_g.off, ky_g.list);
           if (left) atomicAdd(&nxt[2 * k], left);
         }
         __syncthreads();
@@ -268,7 +258,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
           else if (c < OB_KY_MIN_C) left = l1_split_words(0, 1, c, rep, (kg << 1) | g, rl, key0, key1);
           else
             for (uint32_t q = 0, ns = ob_l1_items(c); q < ns; ++q)
-              left += l1_split_item(q, c, rep, (kg << 1) | g, rl, key0, key1, kyl, ky_g.off, ky_g.list);
+              left += l1_split_item<DIAG>(q, c, rep, (kg << 1) | g, rl, key0, key1, kyl, ky_g.off, ky_g.list);
           const uint32_t right = c - left;
           if (to_m1) {
             emit(2 * kg, left);
@@ -1472,6 +1462,8 @@ int ky_device(int device, ob_ky_tables* out) {
   if (it == cache.end()) {
     const KyHost& h = ky_host();
     if (h.hot_entries > OB_KY_HOT_CAP) return ob::fail(OB_E_INVALID, "internal: Knuth-Yao hot columns exceed the LDS stage");
+    for (int x = 0; x < OB_KY_TABLES; ++x)
+      if (!ob_ky_fast_ok(h.i0[x])) return ob::fail(OB_E_INVALID, "internal: Knuth-Yao hot columns exceed the stream's first word");
     ob_ky_tables t{};
     uint32_t *off = nullptr, *hot = nullptr;
     uint16_t* list = nullptr;
@@ -1961,11 +1953,13 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
   using L1Kernel = void (*)(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
                             const ob_ky_tables);
 #if OB_TUNING  // timing ablations of level 1 (l1_diag, tools/l1_ablate.sh)
-  const int l1_diag = ob::opt_int(ob::Opt::L1Diag, 0) & 63;
+  const int l1_diag = ob::opt_int(ob::Opt::L1Diag, 0) & 255;
   const L1Kernel l1k = l1_diag == 0    ? ob_level1_kernel<0>
                        : l1_diag == 1  ? ob_level1_kernel<1>
                        : l1_diag == 2  ? ob_level1_kernel<2>
                        : l1_diag == 32 ? ob_level1_kernel<32>
+                       : l1_diag == 64 ? ob_level1_kernel<64>
+                       : l1_diag == 192 ? ob_level1_kernel<192>
                        : l1_diag == 3  ? ob_level1_kernel<3>
                        : l1_diag == 11 ? ob_level1_kernel<11>
                        : l1_diag == 16 ? ob_level1_kernel<16>

@@ -1365,6 +1365,7 @@ int oz_gram(ob_panel* p, const uint32_t* d_chunks, int n_chunks, const uint32_t*
   const int mode = oz_gram_mode(p, n_chunks, nb_rep);
   const bool wide = mode != 0;
   p->timing.oz_wide = mode;
+  p->timing.blocks = (int32_t)(wide ? wblocks * (mode == 2 ? 2u : 1u) : blocks8);  // the launched grid
   if (wide) {  // oz_gram_w_kernel: 4 waves, 256 replicates x 64 pairs per block
     a.ksplit = mode == 2 ? 2 : 1;
     a.n_chunks = n_chunks;

@@ -145,10 +145,8 @@ struct ob_ky_tables {
 
 // Fair bits [128 q, min(c, 128 q + 128)) of a node's popcount stream, counted (nodes of c < 4096
 // draws): bit b is bit (b & 31) of word ((b >> 5) & 3) of Philox({b >> 7, rep, c2, tag}).
-OB_HD uint32_t ob_l1_split_bits(uint32_t q, uint32_t c, uint32_t rep, uint32_t c2, uint32_t tag, uint32_t k0,
-                                uint32_t k1) {
-  const ob_u32x4 u = OB_L1_PHILOX(q, rep, c2, tag, k0, k1);
-  const uint32_t r = c - 128u * q;
+// The first min(r, 128) bits of one Philox call's output, counted: four masked popcounts.
+OB_HD uint32_t ob_l1_head_bits(ob_u32x4 u, uint32_t r) {
   const uint32_t wd[4] = {u.x, u.y, u.z, u.w};
   uint32_t s = 0;
   for (uint32_t i = 0; i < 4; ++i) {
@@ -156,6 +154,10 @@ OB_HD uint32_t ob_l1_split_bits(uint32_t q, uint32_t c, uint32_t rep, uint32_t c
     s += (uint32_t)__builtin_popcount(nb >= 32u ? wd[i] : (wd[i] & ((1u << nb) - 1u)));
   }
   return s;
+}
+OB_HD uint32_t ob_l1_split_bits(uint32_t q, uint32_t c, uint32_t rep, uint32_t c2, uint32_t tag, uint32_t k0,
+                                uint32_t k1) {
+  return ob_l1_head_bits(OB_L1_PHILOX(q, rep, c2, tag, k0, k1), c - 128u * q);
 }
 // The same count for a word q < c >> 7, whose 128 bits are all counted (no masks).
 OB_HD uint32_t ob_l1_full_bits(uint32_t q, uint32_t rep, uint32_t c2, uint32_t tag, uint32_t k0, uint32_t k1) {
@@ -206,14 +208,27 @@ OB_HD uint32_t ob_bs_bit(ob_bitstream& s) {
   return b;
 }
 
+OB_HD uint32_t ob_bitrev32(uint32_t v) {
+#if defined(__clang__)
+  return __builtin_bitreverse32(v);
+#else
+  v = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
+  v = ((v >> 2) & 0x33333333u) | ((v & 0x33333333u) << 2);
+  v = ((v >> 4) & 0x0F0F0F0Fu) | ((v & 0x0F0F0F0Fu) << 4);
+  return __builtin_bswap32(v);
+#endif
+}
+
 // The next m <= 32 stream bits as an integer, the first bit most significant (d = 2 d + bit, m times).
+// This and ob_bs_popcount are the stream as defined, bit by bit: the device reads a stream's first
+// call directly (ob_ky_walk, ob_l1_head_bits) and tests/l1_walk_host.cpp holds the two against each other.
 OB_HD uint32_t ob_bs_take_msb(ob_bitstream& s, uint32_t m) {
   uint32_t v = 0;
   while (m) {
     const uint32_t sh = s.pos & 31u, take = m < 32u - sh ? m : 32u - sh;
     const uint32_t w = ob_bs_word(s) >> sh;
     const uint32_t chunk = take == 32u ? w : (w & ((1u << take) - 1u));
-    const uint32_t rev = __builtin_bitreverse32(chunk) >> (32u - take);
+    const uint32_t rev = ob_bitrev32(chunk) >> (32u - take);
     v = take == 32u ? rev : ((v << take) | rev);
     s.pos += take;
     m -= take;
@@ -233,8 +248,49 @@ OB_HD uint32_t ob_bs_popcount(ob_bitstream& s, uint32_t m) {
   }
   return left;
 }
-// The walk and the stream split (device, LDS-staged hot columns): ob_engine.hip ky_walk,
-// l1_split_stream; restated independently in oracle/ob_oracle.c orc_split_left.
+
+// One B(2^j, 1/2) sample from node stream {ctr0, rep, c2, tag}: the Knuth-Yao walk with its state
+// in registers. The i0 - 1 leading bits (columns without entries) and the OB_KY_HOT hot columns take
+// at most 32 bits (ob_ky_fast_ok), so they all come from word 0 of the stream's first Philox call:
+// bit-reversed once, the next stream bit is the register's top bit and d = 2 d + bit one funnel
+// shift. hoff[c], hoff[c + 1] bound hot column i0 + c's entries in hlist (ob_ky_tables hot). A walk
+// that leaves the hot columns (p < 0.01) goes on bit by bit on the generic ob_bitstream, entered at
+// its position with the four words already drawn: off / list are the table's own column offsets
+// and entries. u = the stream's first call, OB_L1_PHILOX(ctr0, rep, c2, tag, k0, k1); *bits = the
+// stream bits consumed.
+OB_HD bool ob_ky_fast_ok(uint32_t i0) { return i0 >= 2u && i0 - 1u + OB_KY_HOT <= 32u; }
+
+OB_HD uint32_t ob_ky_walk(ob_u32x4 u, uint32_t ctr0, uint32_t rep, uint32_t c2, uint32_t tag, uint32_t k0,
+                          uint32_t k1, uint32_t i0, const uint32_t* hoff, const uint16_t* hlist,
+                          const uint32_t* off, const uint16_t* list, uint32_t* bits) {
+  uint32_t r = ob_bitrev32(u.x);  // stream bit b at bit 31 - b
+  uint32_t d = r >> (33u - i0);              // the i0 - 1 leading bits, first bit most significant
+  r <<= i0 - 1u;
+  uint32_t lo = hoff[0];
+  for (uint32_t c = 0; c < OB_KY_HOT; ++c) {
+    d = (d << 1) | (r >> 31);
+    r <<= 1;
+    const uint32_t hi = hoff[c + 1], cnt = hi - lo;
+    if (d < cnt) {
+      *bits = i0 + c;
+      return hlist[lo + d];
+    }
+    d -= cnt;
+    lo = hi;
+  }
+  ob_bitstream s = {ctr0, rep, c2, tag, k0, k1, i0 - 1u + OB_KY_HOT, u.x, u.y, u.z, u.w};
+  for (uint32_t i = i0 + OB_KY_HOT;; ++i) {
+    d = 2u * d + ob_bs_bit(s);
+    const uint32_t l0 = off[i], cnt = off[i + 1] - l0;
+    if (d < cnt) {
+      *bits = s.pos;
+      return list[l0 + d];
+    }
+    d -= cnt;
+  }
+}
+// The stream split on the device (LDS-staged hot columns): ob_engine.hip l1_split_item; restated
+// independently in oracle/ob_oracle.c orc_split_left.
 
 // floor(u * s / 2^64), s < 2^32.
 OB_HD uint32_t ob_mulhi64(uint32_t lo, uint32_t hi, uint32_t s) {
