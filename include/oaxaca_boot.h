@@ -745,6 +745,115 @@ int ob_vif_last_timing(double* gram_ms, double* solve_ms, double* sums_ms);
 int ob_vif_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const char* const* names,
                int32_t n_names, double* vif);
 
+/* ---- Pay-equity remediation: fair-wage scoring and budget allocation (engine/src/analysis.rs:309-869,
+ * optimize_inner) over arrays. The engine's "A" is the reference group, "B" the target. The design is
+ * [1, features]: k columns, the intercept FIRST and implicit (x holds the k - 1 features), rows stacked
+ * with A's n_a rows first. The chain: the Gram of [features, y] (ob_vif_gram, over A's rows and, for the
+ * Pooled target, over all rows) -> ob_remedy_solve (host) -> ob_remedy_score (one GPU pass: fair wage,
+ * leverage, A's residual sum) -> ob_remedy_allocate (GPU: classify, stable descending sort, running
+ * budget in closed form, output ordered by original index).
+ *
+ * Deliberate differences from the reference: beta comes from the Cholesky solve of the normal
+ * equations in nalgebra's operation order, not from an SVD (the reference needs X'X invertible two
+ * lines later anyway); greedy pay is clamp(budget - P_c, 0, diff_c) with P_c the exclusive prefix sum of
+ * the eligible diffs before candidate c in sorted order, which agrees with the reference's sequential
+ * current_spend to rounding. P_c's order: an inclusive Kogge-Stone scan (offsets 1, 2, .. 128) within
+ * each tile of 256 sorted candidates, plus the totals of the tiles before it added one by one in tile
+ * order; it depends on the candidate count alone. Every sum is f64 in a fixed order (no floating
+ * atomics), so a repeated call returns the same bytes. */
+#define OB_REMEDY_MAX_K 120 /* design columns, the intercept included: at most 119 beside it */
+enum { OB_REMEDY_TARGET_REFERENCE = 0, OB_REMEDY_TARGET_POOLED = 1 };
+enum { OB_REMEDY_GREEDY = 0, OB_REMEDY_EQUITABLE = 1 };
+enum { OB_REMEDY_MIDPOINT = 0, OB_REMEDY_LOWER = 1, OB_REMEDY_UPPER = 2 };
+typedef struct {
+  double budget;              /* > 0, else the auto budget total_need * 1.00001 (analysis.rs:697-703) */
+  double min_gap_pct;         /* a row is eligible when diff / actual >= this */
+  double confidence_level;    /* clamped to [0.50, 0.999]; 0.95 when NaN */
+  int32_t strategy;           /* OB_REMEDY_GREEDY | OB_REMEDY_EQUITABLE */
+  int32_t range_target;       /* OB_REMEDY_MIDPOINT | _LOWER | _UPPER: group B's target wage */
+  int32_t forensic_mode;      /* also return the ineligible and non-positive rows, with pay 0 */
+  int32_t adjust_both_groups; /* group A's positive gaps are eligible too (always against the midpoint) */
+} ob_remedy_request;
+typedef struct ob_remedy_results ob_remedy_results;
+typedef struct {
+  int64_t n_a, n_b, n_adjustments;
+  double total_cost, required_budget, effective_budget, net_residual_sum_b;
+  double original_unexplained_gap, new_unexplained_gap; /* analysis.rs:847-857 */
+  double z_score, sigma_squared;
+  double classify_ms, order_ms, allocate_ms; /* HIP-event ms */
+  double original_gap, new_gap;              /* ob_remedy_run only (analysis.rs:836-845), else 0 */
+  double gram_ms, score_ms;                  /* ob_remedy_run only: HIP-event ms of the Gram and score passes */
+} ob_remedy_info;
+/* statrs Normal(0, 1)::inverse_cdf(p) = -sqrt(2) erfc_inv(2 p), term by term (its erf_inv_impl
+   rational approximations in its evaluation order). NaN outside [0, 1]. Host only. */
+double ob_normal_inverse_cdf(double p);
+/* beta[k] and cov[k * k] (column-major, (X_A'X_A)^-1 by nalgebra's try_inverse) in DESIGN order
+   (intercept first) from Grams in ob_vif_gram's layout over [features(k - 1), y]: (k + 1)^2, the
+   columns being the features, then y, then the ones. gram_fit: the fit rows' Gram, or NULL to fit on
+   A (OptimizationTarget::Reference). Host only. k < 2 or NULL is OB_E_INVALID, k > OB_REMEDY_MAX_K
+   OB_E_UNSUPPORTED, a singular matrix OB_E_LINALG "Covariance matrix is singular, likely due to perfect
+   multicollinearity." */
+int ob_remedy_solve(const double* gram_a, const double* gram_fit, int32_t k, double* beta, double* cov);
+/* One pass over n stacked rows: fair[i] = xe_i . beta, leverage[i] = xe_i' cov xe_i (T = Xe cov on the
+   f64 matrix units, then a row dot with xe_i), *rss = sum over the FIRST n_rss rows of (y_i - fair_i)^2
+   from explicit residuals, and on request contrib[i + j * n] = xe_ij beta_j. x: column-major
+   n x (k - 1), ldx >= n. y (n_rss entries read), rss and contrib may be NULL. */
+int ob_remedy_score(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int64_t n_rss,
+                    int32_t k, const double* beta, const double* cov, double* fair, double* leverage,
+                    double* rss, double* contrib);
+/* analysis.rs:516-834 over the stacked rows (A's n_a first, then B's n_b): intervals from sigma_squared
+   and the request's confidence, classification, allocation. index[n_a + n_b]: each row's original
+   index, or NULL for its stacked position. Returns one entry per adjustment, ordered by index. A
+   non-finite y, fair or leverage is OB_E_INVALID: the reference's partial_cmp(..).unwrap_or(Equal) gives
+   a NaN gap an order that depends on its sort's internals. */
+int ob_remedy_allocate(ob_ctx* ctx, const double* y, const double* fair, const double* leverage, int64_t n_a,
+                       int64_t n_b, const int64_t* index, double sigma_squared, const ob_remedy_request* request,
+                       ob_remedy_results** out);
+int ob_remedy_results_info(const ob_remedy_results* r, ob_remedy_info* out);
+/* Arrays of n_adjustments entries, owned by r; any out pointer may be NULL. group: 0 = A, 1 = B;
+   row: the stacked row. */
+int ob_remedy_results_get(const ob_remedy_results* r, const int64_t** index, const double** adjustment,
+                          const double** current_wage, const double** new_wage, const double** fair_wage,
+                          const double** lower, const double** upper, const int32_t** group, const int64_t** row);
+void ob_remedy_results_free(ob_remedy_results* r);
+/* optimize_inner over a column frame (ob_remedy_run only): the design's k column names (the intercept
+   first) with the fair-wage coefficients, and, when contributions were asked for, n_adjustments x k
+   row-major values xe_ij beta_j (else NULL). Owned by r. */
+int ob_remedy_results_model(const ob_remedy_results* r, int32_t* k, const char* const** names, const double** beta,
+                            const double** contributions);
+/* optimize_inner (analysis.rs:309-869) over a column frame and a builder configuration: the builder's
+   design (intercept and dummies included), Pooled reference coefficients and the existing point estimate
+   for original_gap, one upload of the stacked rows, then the Gram, the solve, the score pass and the
+   allocation above. target: OB_REMEDY_TARGET_REFERENCE | _POOLED (A's and B's Grams are formed separately
+   and added on the host). As in the reference, whose optimize_inner calls run() first, a group with no more
+   rows than design columns is OB_E_INSUFFICIENT from the point estimate; the dof <= 0 rule (sigma_squared
+   = 0) is therefore reachable only through the array pieces.
+   Errors, before any device work and in this order: a bad request or target is OB_E_INVALID; a named
+   column that is missing is OB_E_COLUMN "Column '<name>' not found in dataset."; a null in a named
+   column is OB_E_INVALID (deliberate: the reference indexes the uncleaned frame with rows of the cleaned
+   one); a non-finite outcome is OB_E_INVALID (a NaN gap has no place in the order); a group column that is
+   not a string column is OB_E_POLARS, as the reference's `.str()` fails; anything but exactly two group
+   values with the reference group among them is OB_E_UNSUPPORTED (deliberate: with more, the reference's
+   indices and matrices disagree); more than OB_REMEDY_MAX_K design columns is OB_E_UNSUPPORTED. */
+int ob_remedy_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                  const ob_remedy_request* request, int32_t target, int32_t contributions, ob_remedy_results** out);
+
+/* calculate_efficient_frontier_inner (analysis.rs:871-1153): ob_remedy_run with budget 0, Reference target,
+   Greedy and Midpoint gives the gaps; max_budget (NaN: 1.1 x total need; below 1e-9: 1000) is cut into `steps`
+   slices, and for each of the steps + 1 budgets b_s = s * max_budget / steps the wages y + pay_s, pay_s[i] =
+   clamp(b_s - P_i, 0, gap_i) (P_i: the gaps before i in descending order, ties by original index, added one by
+   one on the host), are regressed on the pooled design [1, group dummy (A = 0, B = 1), features]. Two GPU
+   passes serve all budgets at once: X_p'Y on the f64 matrix units with Y never stored, then rss_s from explicit
+   residuals; the steps + 1 solves use nalgebra's try_inverse of X_p'X_p on the host ("Singular matrix in Pooled
+   OLS" is OB_E_LINALG). Deliberate difference: beta_s = (X_p'X_p)^-1 (X_p'Y_s), not the reference's dense K x n
+   projector times Y_s. Per point: t = beta_group / sqrt(sigma2 (X_p'X_p)^-1[1][1]), p = 2 Phi(-|t|), significant
+   when p < 0.05; (0, 1, 0) when n - (k + 1) <= 0. The arrays hold steps + 1 entries. steps < 1 is OB_E_INVALID,
+   steps > OB_REMEDY_MAX_STEPS OB_E_UNSUPPORTED. ms (may be NULL): HIP-event ms of the two passes. */
+#define OB_REMEDY_MAX_STEPS 127
+int ob_remedy_frontier(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                       int32_t steps, double max_budget, double* budget, double* t_statistic, double* p_value,
+                       int32_t* is_significant, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,12 +52,20 @@ EXPORTED = (
     "ob_akm_connected_set", "ob_akm_set_get", "ob_akm_set_id", "ob_akm_set_free", "ob_akm_demean",
     "ob_akm_recover_fe", "ob_akm_run", "ob_akm_results_get", "ob_akm_results_info", "ob_akm_results_free",
     "ob_vif_gram", "ob_vif_solve", "ob_vif_sums", "ob_vif", "ob_vif_run", "ob_vif_last_timing",
+    "ob_normal_inverse_cdf", "ob_remedy_solve", "ob_remedy_score", "ob_remedy_allocate", "ob_remedy_results_info",
+    "ob_remedy_results_get", "ob_remedy_results_free", "ob_remedy_results_model", "ob_remedy_run",
+    "ob_remedy_frontier",
 )
 
 OB_E_CONVERGENCE = 12
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
 OB_AKM_MAX_CONTROLS = 64
 OB_VIF_MAX_K = 120
+OB_REMEDY_MAX_K = 120  # design columns, the intercept included
+OB_REMEDY_MAX_STEPS = 127
+OB_REMEDY_TARGETS = {"reference": 0, "pooled": 1}
+OB_REMEDY_STRATEGIES = {"greedy": 0, "equitable": 1}
+OB_REMEDY_RANGE_TARGETS = {"midpoint": 0, "lower": 1, "upper": 2}
 OB_MATCH_MAX_DIM, OB_MATCH_MAX_K = 64, 16
 OB_MATCH_EUCLIDEAN, OB_MATCH_MAHALANOBIS, OB_MATCH_PSM = 0, 1, 2
 
@@ -161,6 +169,22 @@ class ob_akm_info(C.Structure):
                 ("n_components", C.c_int64), ("demean_iterations", C.POINTER(C.c_int32)), ("n_demean", C.c_int32),
                 ("recover_iterations", C.c_int32), ("launches_per_iteration", C.c_int32),
                 ("demean_ms", C.c_double), ("ols_ms", C.c_double), ("recover_ms", C.c_double)]
+
+
+class ob_remedy_request(C.Structure):
+    _fields_ = [("budget", C.c_double), ("min_gap_pct", C.c_double), ("confidence_level", C.c_double),
+                ("strategy", C.c_int32), ("range_target", C.c_int32), ("forensic_mode", C.c_int32),
+                ("adjust_both_groups", C.c_int32)]
+
+
+class ob_remedy_info(C.Structure):
+    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("n_adjustments", C.c_int64),
+                ("total_cost", C.c_double), ("required_budget", C.c_double), ("effective_budget", C.c_double),
+                ("net_residual_sum_b", C.c_double), ("original_unexplained_gap", C.c_double),
+                ("new_unexplained_gap", C.c_double), ("z_score", C.c_double), ("sigma_squared", C.c_double),
+                ("classify_ms", C.c_double), ("order_ms", C.c_double), ("allocate_ms", C.c_double),
+                ("original_gap", C.c_double), ("new_gap", C.c_double), ("gram_ms", C.c_double),
+                ("score_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -300,6 +324,22 @@ _SIGS = {
     "ob_vif": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, _D]),
     "ob_vif_last_timing": (C.c_int, [_D, _D, _D]),
     "ob_vif_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.c_int32, _D]),
+    "ob_normal_inverse_cdf": (C.c_double, [C.c_double]),
+    "ob_remedy_solve": (C.c_int, [_D, _D, C.c_int32, _D, _D]),
+    "ob_remedy_score": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _D, _D, _D]),
+    "ob_remedy_allocate": (C.c_int, [_P, _D, _D, _D, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_double,
+                                     C.POINTER(ob_remedy_request), C.POINTER(_P)]),
+    "ob_remedy_results_info": (C.c_int, [_P, C.POINTER(ob_remedy_info)]),
+    "ob_remedy_results_get": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(_D), C.POINTER(_D),
+                                        C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D),
+                                        C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int64))]),
+    "ob_remedy_results_free": (None, [_P]),
+    "ob_remedy_results_model": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(_D),
+                                          C.POINTER(_D)]),
+    "ob_remedy_frontier": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
+                                     C.c_int32, C.c_double, _D, _D, _D, C.POINTER(C.c_int32), _D]),
+    "ob_remedy_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
+                                C.POINTER(ob_remedy_request), C.c_int32, C.c_int32, C.POINTER(_P)]),
 }
 
 _lib = None

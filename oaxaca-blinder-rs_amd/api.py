@@ -68,6 +68,50 @@ class BudgetAdjustment:
 
 
 @dataclass
+class Contribution:
+    """engine/src/types.rs:89-93"""
+    name: str
+    value: float
+
+
+@dataclass
+class Adjustment:
+    """engine/src/types.rs:95-107 (the defensibility fields belong to check_defensibility, not built)."""
+    index: int
+    adjustment: float
+    current_wage: float
+    new_wage: float
+    fair_wage: float
+    fair_wage_lower_bound: float | None = None
+    fair_wage_upper_bound: float | None = None
+    contributions: list = field(default_factory=list)
+    is_defensible: bool | None = None
+    defensibility_message: str | None = None
+
+
+@dataclass
+class OptimizationResult:
+    """engine/src/types.rs:109-119"""
+    adjustments: list
+    total_cost: float
+    original_gap: float
+    new_gap: float
+    original_unexplained_gap: float
+    new_unexplained_gap: float
+    required_budget: float
+    model_coefficients: list
+
+
+@dataclass
+class FrontierPoint:
+    """engine/src/types.rs:135-141"""
+    budget: float
+    t_statistic: float
+    p_value: float
+    is_significant: bool
+
+
+@dataclass
 class OaxacaResults:
     total_gap: float
     two_fold: TwoFoldResults
@@ -349,6 +393,82 @@ class OaxacaBuilder:
         xa, _, xb, _, names = self.get_data_matrices()
         scores = vif(np.vstack([xa, xb])[:, 1:], device=self._device)
         return [VifResult(nm, float(s)) for nm, s in zip(names[1:], scores)]
+
+    def optimize(self, budget: float = 0.0, target: str = "reference", strategy: str = "greedy",
+                 min_gap_pct: float = 0.0, forensic_mode: bool = False, adjust_both_groups: bool = False,
+                 confidence_level: float = 0.95, range_target: str = "midpoint",
+                 contributions: bool = False) -> OptimizationResult:
+        """engine/src/analysis.rs:309-869 (optimize_inner) on the MI355X engine (``ob_remedy_run``): the
+        fair-wage model of the reference group (``target="reference"``) or of both groups (``"pooled"``), a
+        prediction interval per employee, and the greedy or equitable allocation of ``budget`` (0: what
+        closes every eligible gap) over the target group's positive gaps. ``contributions`` fills each
+        adjustment's ``contributions`` (x_ij beta_j per design column). ``last_remedy_info`` keeps the
+        call's ``ob_remedy_info`` (counts, z, sigma squared, HIP-event times per pass)."""
+        if target not in N.OB_REMEDY_TARGETS or strategy not in N.OB_REMEDY_STRATEGIES \
+                or range_target not in N.OB_REMEDY_RANGE_TARGETS:
+            raise ValueError("target: reference|pooled, strategy: greedy|equitable, range_target: midpoint|lower|upper")
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        rq = N.ob_remedy_request(float(budget), float(min_gap_pct), float(confidence_level),
+                                 N.OB_REMEDY_STRATEGIES[strategy], N.OB_REMEDY_RANGE_TARGETS[range_target],
+                                 int(bool(forensic_mode)), int(bool(adjust_both_groups)))
+        h = C.c_void_p()
+
+        def call(ctx):
+            return lib.ob_remedy_run(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(rq), N.OB_REMEDY_TARGETS[target],
+                                     int(bool(contributions)), C.byref(h))
+
+        try:
+            ctx = N.context(self._device)
+        except (N.OaxacaError, ImportError):
+            rc = call(None)  # the argument errors come before the device, as in ob_vif_run
+            if not (rc == N.OB_E_INVALID and b"null pointer" in lib.ob_last_error()):
+                N.check(rc)
+            raise  # the arguments are good: the missing device is the error
+        N.check(call(ctx))
+        try:
+            info = N.ob_remedy_info()
+            N.check(lib.ob_remedy_results_info(h, C.byref(info)))
+            m = int(info.n_adjustments)
+            pi = C.POINTER(C.c_int64)()
+            pd = [C.POINTER(C.c_double)() for _ in range(6)]
+            N.check(lib.ob_remedy_results_get(h, C.byref(pi), *[C.byref(p) for p in pd], None, None))
+            k, pn = C.c_int32(), C.POINTER(C.c_char_p)()
+            pb, pc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+            N.check(lib.ob_remedy_results_model(h, C.byref(k), C.byref(pn), C.byref(pb), C.byref(pc)))
+            names = [pn[j].decode() for j in range(k.value)]
+            adjustments = []
+            for i in range(m):
+                con = [Contribution(names[j], pc[i * k.value + j]) for j in range(k.value)] if contributions and pc else []
+                adjustments.append(Adjustment(int(pi[i]), *[p[i] for p in pd], con))
+            self.last_remedy_info = {name: getattr(info, name) for name, _ in info._fields_}
+            return OptimizationResult(
+                adjustments=adjustments, total_cost=info.total_cost, original_gap=info.original_gap,
+                new_gap=info.new_gap, original_unexplained_gap=info.original_unexplained_gap,
+                new_unexplained_gap=info.new_unexplained_gap, required_budget=info.required_budget,
+                model_coefficients=[Contribution(names[j], pb[j]) for j in range(k.value)])
+        finally:
+            lib.ob_remedy_results_free(h)
+
+    def efficient_frontier(self, steps: int = 50, max_budget: float | None = None) -> list:
+        """engine/src/analysis.rs:871-1153 (calculate_efficient_frontier_inner) on the MI355X engine
+        (``ob_remedy_frontier``): ``steps + 1`` ``FrontierPoint``s, the first at budget 0, each the group
+        dummy's t statistic in the pooled regression after the greedy raises that budget pays for.
+        ``max_budget`` defaults to 1.1 times the total need. ``last_frontier_ms`` keeps the HIP-event ms of the
+        two passes (X'Y, rss)."""
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        s = max(int(steps), 0) + 1
+        b, t, p, ms = np.zeros(s), np.zeros(s), np.zeros(s), np.zeros(2)
+        sig = np.zeros(s, dtype=np.int32)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        N.check(lib.ob_remedy_frontier(N.context(self._device), cols, ncol, nrow, C.byref(cfg), int(steps),
+                                       float("nan") if max_budget is None else float(max_budget), dp(b), dp(t), dp(p),
+                                       sig.ctypes.data_as(C.POINTER(C.c_int32)), dp(ms)))
+        self.last_frontier_ms = {"xty_ms": float(ms[0]), "rss_ms": float(ms[1])}
+        return [FrontierPoint(float(b[i]), float(t[i]), float(p[i]), bool(sig[i])) for i in range(s)]
 
     def run(self) -> OaxacaResults:
         """builder.rs:787-951 on the MI355X engine."""

@@ -483,3 +483,100 @@ def vif_last_timing() -> dict:
     g, s, r = C.c_double(), C.c_double(), C.c_double()
     N.check(N.lib().ob_vif_last_timing(C.byref(g), C.byref(s), C.byref(r)))
     return {"gram_ms": g.value, "solve_ms": s.value, "sums_ms": r.value}
+
+
+def normal_inverse_cdf(p: float) -> float:
+    """statrs ``Normal::new(0, 1).inverse_cdf(p)`` term by term (``ob_normal_inverse_cdf``, host only): the
+    z of the remediation's prediction intervals. NaN outside [0, 1]."""
+    return float(N.lib().ob_normal_inverse_cdf(float(p)))
+
+
+def remedy_solve(gram_a, gram_fit=None):
+    """The fair-wage model of analysis.rs:434-500 from Grams, on the host (``ob_remedy_solve``, no GPU
+    needed). ``gram_a`` is ``vif_gram(np.column_stack([features, y]))`` over the reference group's rows,
+    ``gram_fit`` the same over the rows the model is fit on (None: the reference group; for the pooled
+    target, both groups stacked). Returns (beta, cov) in the design's order, the intercept first: beta by
+    nalgebra's Cholesky of the fit rows' normal equations, cov = (X_A'X_A)^-1 of the reference group."""
+    ga = np.asfortranarray(gram_a, dtype=np.float64)
+    if ga.ndim != 2 or ga.shape[0] != ga.shape[1] or ga.shape[0] < 2:
+        raise ValueError("gram_a must be (K + 1, K + 1)")
+    k = ga.shape[0] - 1
+    gf = None
+    if gram_fit is not None:
+        gf = np.asfortranarray(gram_fit, dtype=np.float64)
+        if gf.shape != ga.shape:
+            raise ValueError("gram_fit must have gram_a's shape")
+    beta, cov = np.empty(k), np.empty((k, k), order="F")
+    N.check(N.lib().ob_remedy_solve(_dp(ga), _dp(gf), k, _dp(beta), _dp(cov)))
+    return beta, cov
+
+
+def remedy_score(x, beta, cov, y=None, contributions: bool = False, device: int | None = None):
+    """One pass over the rows on the GPU (``ob_remedy_score``): for the (n, K - 1) features ``x`` and the
+    design xe = [1, x], fair = xe . beta, leverage = xe' cov xe, and rss = sum (y_i - fair_i)^2 over the
+    first len(y) rows from explicit residuals (0.0 without ``y``). Returns (fair, leverage, rss), and the
+    (n, K) contributions xe_ij beta_j as a fourth item when asked for."""
+    x, ldx, n, p = _vif_x(x)
+    k = p + 1
+    b = np.ascontiguousarray(beta, dtype=np.float64)
+    c = np.asfortranarray(cov, dtype=np.float64)
+    if b.shape != (k,) or c.shape != (k, k):
+        raise ValueError("beta must be (K,) and cov (K, K) for K - 1 feature columns")
+    yv = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    n_rss = 0 if yv is None else int(yv.shape[0])
+    if yv is not None and (yv.ndim != 1 or n_rss > n):
+        raise ValueError("y must be 1-D with at most n entries")
+    fair, lev, rss = np.empty(n), np.empty(n), C.c_double(0.0)
+    con = np.empty((n, k), order="F") if contributions else None
+    N.check(N.lib().ob_remedy_score(N.context(device), _dp(x), ldx, _dp(yv), n, n_rss, k, _dp(b), _dp(c), _dp(fair),
+                                    _dp(lev), C.byref(rss), _dp(con)))
+    return (fair, lev, rss.value, con) if contributions else (fair, lev, rss.value)
+
+
+def remedy_allocate(y, fair, leverage, n_a: int, sigma_squared: float, budget: float = 0.0, strategy: str = "greedy",
+                    min_gap_pct: float = 0.0, forensic_mode: bool = False, adjust_both_groups: bool = False,
+                    confidence_level: float = 0.95, range_target: str = "midpoint", index=None,
+                    device: int | None = None) -> dict:
+    """analysis.rs:516-857 on the GPU (``ob_remedy_allocate``) over stacked rows, the reference group's
+    ``n_a`` first and the target group's after them: prediction intervals, classification, the stable
+    descending order of the gaps and the greedy or equitable allocation. ``index`` gives each stacked
+    row's original index (default: its stacked position). Returns a dict of arrays with one entry per
+    adjustment, ordered by index (index, adjustment, current_wage, new_wage, fair_wage, lower, upper,
+    group with 0 = reference and 1 = target, row), and the scalars of ``ob_remedy_info``."""
+    yv, fv, hv = (np.ascontiguousarray(a, dtype=np.float64) for a in (y, fair, leverage))
+    n = yv.shape[0]
+    if yv.ndim != 1 or fv.shape != (n,) or hv.shape != (n,) or not 0 <= int(n_a) <= n:
+        raise ValueError("y, fair and leverage must be 1-D of one length, with 0 <= n_a <= n")
+    iv = None
+    if index is not None:
+        iv = np.ascontiguousarray(index, dtype=np.int64)
+        if iv.shape != (n,):
+            raise ValueError("index must have one entry per row")
+    rq = N.ob_remedy_request(float(budget), float(min_gap_pct), float(confidence_level),
+                             N.OB_REMEDY_STRATEGIES[strategy], N.OB_REMEDY_RANGE_TARGETS[range_target],
+                             int(bool(forensic_mode)), int(bool(adjust_both_groups)))
+    lib = N.lib()
+    h = C.c_void_p()
+    N.check(lib.ob_remedy_allocate(N.context(device), _dp(yv), _dp(fv), _dp(hv), int(n_a), n - int(n_a),
+                                   None if iv is None else iv.ctypes.data_as(C.POINTER(C.c_int64)),
+                                   float(sigma_squared), C.byref(rq), C.byref(h)))
+    try:
+        info = N.ob_remedy_info()
+        N.check(lib.ob_remedy_results_info(h, C.byref(info)))
+        m = int(info.n_adjustments)
+        pi, pr = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)()
+        pg = C.POINTER(C.c_int32)()
+        pd = [C.POINTER(C.c_double)() for _ in range(6)]
+        N.check(lib.ob_remedy_results_get(h, C.byref(pi), *[C.byref(p) for p in pd], C.byref(pg), C.byref(pr)))
+
+        def arr(p, dtype):
+            return np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, dtype=dtype)
+
+        out = {"index": arr(pi, np.int64), "group": arr(pg, np.int32), "row": arr(pr, np.int64)}
+        for name, p in zip(("adjustment", "current_wage", "new_wage", "fair_wage", "lower", "upper"), pd):
+            out[name] = arr(p, np.float64)
+        for name, _ in info._fields_:
+            out[name] = getattr(info, name)
+        return out
+    finally:
+        lib.ob_remedy_results_free(h)
