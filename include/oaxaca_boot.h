@@ -854,6 +854,92 @@ int ob_remedy_frontier(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64
                        int32_t steps, double max_budget, double* budget, double* t_statistic, double* p_value,
                        int32_t* is_significant, double* ms);
 
+/* ---- Defensibility and verification of edited raises (engine/src/defensibility.rs, check_defensibility_inner;
+ * analysis.rs:40-96, verify_inner). check_defensibility scores every proposed raise against the reference
+ * group's fair-wage interval and reports the gaps before and after; verify applies the raises to the wages and
+ * runs the decomposition again.
+ *
+ * The reference finds a row's adjustment by walking the whole result list and stopping at the first hit
+ * (defensibility.rs:292-301, :343-349): O(n m). Here first[row] = min { j : row_j = row } by a 32-bit integer
+ * atomicMin (order-free, so deterministic) and one streamed pass over the rows: the FIRST adjustment of a row in
+ * request order decides its new wage in every sum, while every adjustment, duplicates included, is returned.
+ * Sums are f64 in a fixed order that depends on the sizes only (wave butterfly, waves in order, the ordered sum
+ * of the block partials; no floating atomics), so a repeated call returns the same bytes. The reference adds
+ * group B's terms in HashMap iteration order, so there is no order of its own to copy. */
+typedef struct {
+  int64_t n_a, n_b, n_adjustments; /* n_adjustments: the kept ones, as returned */
+  int64_t n_skipped;               /* ob_remedy_defend: adjustments whose index is outside the frame */
+  double total_cost;               /* the values of the kept adjustments, request order (:279-282) */
+  double original_gap, new_gap;    /* mean_A - mean_B of the wages before and after (:316-330) */
+  double original_unexplained_gap, new_unexplained_gap; /* sum_B (fair - wage) / n_b (:332-365) */
+  double required_budget;          /* sum_B (fair - y) over fair > y (:266-276) */
+  double z_score, sigma_squared;
+  double gram_ms, score_ms;        /* ob_remedy_defend only: HIP-event ms of the Gram and score passes */
+  double defend_ms;                /* HIP-event ms of the three passes below together */
+  double scatter_ms, adjust_ms, rows_ms; /* the first-wins map, the per-adjustment pass, the row pass */
+  double sums[7]; /* sum_A y, sum_A new, sum_B y, sum_B new, sum_B (fair - y), sum_B (fair - new), required_budget */
+} ob_defend_info;
+/* defensibility.rs:199-365 over stacked arrays as ob_remedy_allocate takes them (A's n_a rows first). rows[m],
+   values[m]: the proposed adjustments as (stacked row, raise) in request order. Per adjustment: current =
+   y[row], new = current + value (one add), fair, lower / upper = fair -+ z sqrt(sigma_squared (1 + h)) with z
+   from confidence_level as in ob_remedy_request (the reference hard-wires 0.95), both equal to fair when
+   sigma_squared <= 1e-9, and is_defensible = new >= lower - 1.0. Results through ob_remedy_results_get (index =
+   row), ob_remedy_results_defensible and ob_remedy_results_defend_info.
+   Errors, before any device work and in this order: negative n_a, n_b or m is OB_E_INVALID; n_a + n_b >= 2^31 -
+   257 or m >= 2^31 - 1 is OB_E_UNSUPPORTED; a NULL array is OB_E_INVALID; a non-finite y, fair or leverage
+   (deliberate, as ob_remedy_allocate) or a NaN sigma_squared is OB_E_INVALID; then, adjustment by adjustment, a
+   row outside [0, n_a + n_b) or a non-finite value is OB_E_INVALID; a NULL ctx or out comes last. */
+int ob_remedy_defend_rows(ob_ctx* ctx, const double* y, const double* fair, const double* leverage, int64_t n_a,
+                          int64_t n_b, const int64_t* rows, const double* values, int64_t m, double sigma_squared,
+                          double confidence_level, ob_remedy_results** out);
+/* check_defensibility_inner over a column frame and a builder configuration. index[m], value[m]: the proposed
+   adjustments by ORIGINAL row index, request order. Predictor overrides are a flat list of n_overrides entries
+   (override_adjustment[i]: a position in the adjustments array; override_name[i]; override_value[i]), resolved
+   by ob_remedy_resolve_overrides and applied to copies of the touched columns before the design is built. An
+   override of a reference-group row therefore changes beta, cov and sigma_squared for everyone: that is the
+   reference's behaviour (defensibility.rs:32-73 runs before the model is fit). Then, as ob_remedy_run with the
+   Reference target: the builder's design, one upload of the stacked rows, the Gram over A, ob_remedy_solve, the
+   score pass, sigma_squared = rss_A / (n_A - K) (0 when n_A = K), and ob_remedy_defend_rows' passes. No point
+   estimate is run: original_gap is the difference of the group means, as in the reference.
+   An adjustment whose index is outside [0, n_rows) is skipped and counted in n_skipped, not an error (:200, the
+   map lookup fails); the handle holds one entry per kept adjustment in request order, with the model behind
+   ob_remedy_results_model (contributions on request).
+   Errors before any device work, in this order: NULL cfg or arrays and negative counts are OB_E_INVALID; m >=
+   2^31 - 1 OB_E_UNSUPPORTED; ob_remedy_run's frame checks in its order (missing column, null, non-finite outcome,
+   group dtype, two groups, column count); a non-finite value or override value, or an override position outside
+   [0, m), is OB_E_INVALID; a NULL ctx or out comes last. A null in a named column stays OB_E_INVALID even where
+   an override would fill it (the reference would take the override). */
+int ob_remedy_defend(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                     const int64_t* index, const double* value, int64_t m, const int64_t* override_adjustment,
+                     const char* const* override_name, const double* override_value, int64_t n_overrides,
+                     double confidence_level, int32_t contributions, ob_remedy_results** out);
+/* defensibility.rs:32-73 on the host (needs no GPU): per original index the LAST adjustment that carries any
+   override replaces every earlier set for that index as a whole (HashMap::insert of the row's map; within one
+   set a name given twice keeps its last value); then only names among predictors[n_predictors] and indices below
+   n_rows take effect. Writes the cells to change, predictor by predictor and by ascending row: out_row,
+   out_predictor (a position in predictors) and out_value hold up to n_overrides entries, *n_out of them filled. */
+int ob_remedy_resolve_overrides(const int64_t* index, int64_t m, const int64_t* override_adjustment,
+                                const char* const* override_name, const double* override_value, int64_t n_overrides,
+                                const char* const* predictors, int32_t n_predictors, int64_t n_rows, int64_t* out_row,
+                                int32_t* out_predictor, double* out_value, int64_t* n_out);
+/* is_defensible per returned adjustment (1 / 0), owned by r; NULL for a handle of ob_remedy_run or _allocate. */
+int ob_remedy_results_defensible(const ob_remedy_results* r, const int32_t** is_defensible);
+/* OB_E_INVALID for a handle that is not ob_remedy_defend's or ob_remedy_defend_rows'. */
+int ob_remedy_results_defend_info(const ob_remedy_results* r, ob_defend_info* out);
+/* analysis.rs:76-88 on the host (needs no GPU): out[n_rows] = wage with out[index[j]] += value[j] applied one by
+   one in request order, so two raises of one row give (w + a1) + a2. valid (may be NULL): 0 marks a null wage,
+   which no raise touches. An index outside [0, n_rows) is OB_E_INVALID "Adjustment index <i> is out of bounds
+   (dataset has <n> rows)", a non-finite value OB_E_INVALID, whichever comes first in request order. */
+int ob_remedy_apply_adjustments(const double* wage, const uint8_t* valid, int64_t n_rows, const int64_t* index,
+                                const double* value, int64_t m, double* out);
+/* verify_inner: ob_remedy_apply_adjustments on a copy of the outcome column (OB_COL_I64 is cast to f64, a string
+   column is OB_E_POLARS, a missing one OB_E_COLUMN "Column '<name>' not found in dataset."), then ob_builder_run
+   with the caller's configuration as it stands (reference coefficients, replicates, seed, weights,
+   normalisation) and its ordinary handle. The argument errors come before any device work; a NULL ctx or out is
+   OB_E_INVALID after them. The reference's `quantile` switch (Machado-Mata) is not built. */
+int ob_remedy_verify(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                     const int64_t* index, const double* value, int64_t m, ob_results** out);
+
 #ifdef __cplusplus
 }
 #endif

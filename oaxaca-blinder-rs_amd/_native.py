@@ -55,6 +55,8 @@ EXPORTED = (
     "ob_normal_inverse_cdf", "ob_remedy_solve", "ob_remedy_score", "ob_remedy_allocate", "ob_remedy_results_info",
     "ob_remedy_results_get", "ob_remedy_results_free", "ob_remedy_results_model", "ob_remedy_run",
     "ob_remedy_frontier",
+    "ob_remedy_defend_rows", "ob_remedy_defend", "ob_remedy_resolve_overrides", "ob_remedy_results_defensible",
+    "ob_remedy_results_defend_info", "ob_remedy_apply_adjustments", "ob_remedy_verify",
 )
 
 OB_E_CONVERGENCE = 12
@@ -185,6 +187,16 @@ class ob_remedy_info(C.Structure):
                 ("classify_ms", C.c_double), ("order_ms", C.c_double), ("allocate_ms", C.c_double),
                 ("original_gap", C.c_double), ("new_gap", C.c_double), ("gram_ms", C.c_double),
                 ("score_ms", C.c_double)]
+
+
+class ob_defend_info(C.Structure):
+    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("n_adjustments", C.c_int64), ("n_skipped", C.c_int64),
+                ("total_cost", C.c_double), ("original_gap", C.c_double), ("new_gap", C.c_double),
+                ("original_unexplained_gap", C.c_double), ("new_unexplained_gap", C.c_double),
+                ("required_budget", C.c_double), ("z_score", C.c_double), ("sigma_squared", C.c_double),
+                ("gram_ms", C.c_double), ("score_ms", C.c_double), ("defend_ms", C.c_double),
+                ("scatter_ms", C.c_double), ("adjust_ms", C.c_double), ("rows_ms", C.c_double),
+                ("sums", C.c_double * 7)]
 
 
 class ob_component(C.Structure):
@@ -340,6 +352,20 @@ _SIGS = {
                                      C.c_int32, C.c_double, _D, _D, _D, C.POINTER(C.c_int32), _D]),
     "ob_remedy_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
                                 C.POINTER(ob_remedy_request), C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ob_remedy_defend_rows": (C.c_int, [_P, _D, _D, _D, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _D, C.c_int64,
+                                        C.c_double, C.c_double, C.POINTER(_P)]),
+    "ob_remedy_defend": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
+                                   C.POINTER(C.c_int64), _D, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_char_p), _D,
+                                   C.c_int64, C.c_double, C.c_int32, C.POINTER(_P)]),
+    "ob_remedy_resolve_overrides": (C.c_int, [C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_char_p), _D, C.c_int64, C.POINTER(C.c_char_p), C.c_int32,
+                                              C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _D,
+                                              C.POINTER(C.c_int64)]),
+    "ob_remedy_results_defensible": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int32))]),
+    "ob_remedy_results_defend_info": (C.c_int, [_P, C.POINTER(ob_defend_info)]),
+    "ob_remedy_apply_adjustments": (C.c_int, [_D, _U8, C.c_int64, C.POINTER(C.c_int64), _D, C.c_int64, _D]),
+    "ob_remedy_verify": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
+                                   C.POINTER(C.c_int64), _D, C.c_int64, C.POINTER(_P)]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import enum
 import json
+import re
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -76,7 +77,9 @@ class Contribution:
 
 @dataclass
 class Adjustment:
-    """engine/src/types.rs:95-107 (the defensibility fields belong to check_defensibility, not built)."""
+    """engine/src/types.rs:95-107. ``optimize()`` leaves ``is_defensible`` and ``defensibility_message``
+    None; ``check_defensibility()`` fills both (``new_wage >= lower bound - 1.0`` and the reference's two
+    message strings)."""
     index: int
     adjustment: float
     current_wage: float
@@ -100,6 +103,75 @@ class OptimizationResult:
     new_unexplained_gap: float
     required_budget: float
     model_coefficients: list
+
+
+@dataclass
+class DataSummary:
+    """engine/src/types.rs:27-34: counts and group means of the (adjusted) outcome; group A is the
+    reference group, B every other row."""
+    total_count: int
+    group_a_count: int
+    group_b_count: int
+    group_a_mean: float
+    group_b_mean: float
+
+
+@dataclass
+class DecompositionResult:
+    """engine/src/types.rs:36-49. The detailed lists hold ``ComponentResult``s (the reference's
+    ``DetailedComponent`` fields and ``t_stat``); ``results`` is the full ``OaxacaResults``."""
+    total_gap: float
+    explained_gap: float
+    unexplained_gap: float
+    interaction_gap: float | None
+    explained_percentage: float
+    unexplained_percentage: float
+    interaction_percentage: float | None
+    detailed_explained: list
+    detailed_unexplained: list
+    data_summary: DataSummary | None
+    unexplained_standard_error: float | None
+    results: "OaxacaResults" = field(default=None, repr=False)
+
+
+_RUST_F64 = re.compile(r"[+-]?(?:(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?|(?i:inf|infinity|nan))")
+
+
+def parse_rust_f64(text):
+    """``str::parse::<f64>`` (defensibility.rs:40): the float, or None where Rust returns Err. No
+    surrounding whitespace and no underscores; ``inf``, ``infinity`` and ``nan`` in any case, a sign and
+    an exponent are taken."""
+    if not isinstance(text, str) or not _RUST_F64.fullmatch(text):
+        return None
+    return float(text)
+
+
+def defensibility_message(is_defensible: bool, new_wage: float, lower: float) -> str:
+    """defensibility.rs:227-235; ``:.2f`` rounds the exact binary value to even, as Rust's ``{:.2}``."""
+    if is_defensible:
+        return "Wage is within or above the calculated fair range."
+    return f"Wage is {lower - new_wage:.2f} below the defensible lower bound ({lower:.2f})."
+
+
+def _proposed(adjustments):
+    """(index, value, overrides) per proposed adjustment: an ``Adjustment`` (its ``.adjustment``), an
+    ``(index, value[, overrides])`` tuple or a dict with the reference's field names. Override values are
+    numbers or strings; a string Rust would not parse is dropped (defensibility.rs:40)."""
+    out = []
+    for a in adjustments:
+        if isinstance(a, Adjustment):
+            idx, val, ovr = a.index, a.adjustment, None
+        elif isinstance(a, dict):
+            idx, val, ovr = a["index"], a["value"], a.get("predictor_overrides")
+        else:
+            idx, val, ovr = (tuple(a) + (None,))[:3]
+        kept = {}
+        for name, v in (ovr or {}).items():
+            v = parse_rust_f64(v) if isinstance(v, str) else float(v)
+            if v is not None:
+                kept[str(name)] = v
+        out.append((int(idx), float(val), kept))
+    return out
 
 
 @dataclass
@@ -469,6 +541,140 @@ class OaxacaBuilder:
                                        sig.ctypes.data_as(C.POINTER(C.c_int32)), dp(ms)))
         self.last_frontier_ms = {"xty_ms": float(ms[0]), "rss_ms": float(ms[1])}
         return [FrontierPoint(float(b[i]), float(t[i]), float(p[i]), bool(sig[i])) for i in range(s)]
+
+    def check_defensibility(self, adjustments, confidence_level: float = 0.95,
+                            contributions: bool = True) -> OptimizationResult:
+        """engine/src/defensibility.rs (check_defensibility_inner) on the MI355X engine
+        (``ob_remedy_defend``): every proposed raise scored against the reference group's fair-wage
+        interval, and the gaps before and after. ``adjustments``: ``Adjustment``s (as ``optimize()``
+        returns them, perhaps edited), ``(index, value)`` or ``(index, value, overrides)`` tuples, or dicts
+        with ``index``, ``value`` and ``predictor_overrides``. An override replaces a numeric predictor of
+        that row before the model is fit ("what if this person were re-levelled"); per row the last
+        adjustment that carries overrides replaces every earlier set as a whole, and an override of a
+        reference-group row changes the model for everyone, as in the reference. Where several
+        adjustments name one row, all are returned and the first decides the row's new wage in the gaps.
+        An index outside the frame is skipped (``last_defend_info["n_skipped"]``). The reference
+        hard-wires ``confidence_level`` 0.95. ``last_defend_info`` keeps the call's ``ob_defend_info``."""
+        prop = _proposed(adjustments)
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        m = len(prop)
+        idx = np.array([p[0] for p in prop], dtype=np.int64)
+        val = np.array([p[1] for p in prop], dtype=np.float64)
+        flat = [(j, name, v) for j, p in enumerate(prop) for name, v in p[2].items()]
+        opos = np.array([f[0] for f in flat], dtype=np.int64)
+        oval = np.array([f[2] for f in flat], dtype=np.float64)
+        onames, keep_names = _strs([f[1] for f in flat])
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        h = C.c_void_p()
+
+        def call(ctx):
+            return lib.ob_remedy_defend(ctx, cols, ncol, nrow, C.byref(cfg), ip(idx), dp(val), m, ip(opos), onames,
+                                        dp(oval), len(flat), float(confidence_level), int(bool(contributions)),
+                                        C.byref(h))
+
+        try:
+            ctx = N.context(self._device)
+        except (N.OaxacaError, ImportError):
+            rc = call(None)  # the argument errors come before the device, as in optimize()
+            if not (rc == N.OB_E_INVALID and b"null pointer" in lib.ob_last_error()):
+                N.check(rc)
+            raise
+        N.check(call(ctx))
+        try:
+            info = N.ob_defend_info()
+            N.check(lib.ob_remedy_results_defend_info(h, C.byref(info)))
+            kept = int(info.n_adjustments)
+            pi, pf = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
+            pd = [C.POINTER(C.c_double)() for _ in range(6)]
+            N.check(lib.ob_remedy_results_get(h, C.byref(pi), *[C.byref(p) for p in pd], None, None))
+            N.check(lib.ob_remedy_results_defensible(h, C.byref(pf)))
+            k, pn = C.c_int32(), C.POINTER(C.c_char_p)()
+            pb, pc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+            N.check(lib.ob_remedy_results_model(h, C.byref(k), C.byref(pn), C.byref(pb), C.byref(pc)))
+            names = [pn[j].decode() for j in range(k.value)]
+            out = []
+            for i in range(kept):
+                con = [Contribution(names[j], pc[i * k.value + j]) for j in range(k.value)] if contributions and pc else []
+                ok = bool(pf[i])
+                out.append(Adjustment(int(pi[i]), *[p[i] for p in pd], con, ok,
+                                      defensibility_message(ok, pd[2][i], pd[4][i])))
+            self.last_defend_info = {name: (list(getattr(info, name)) if name == "sums" else getattr(info, name))
+                                     for name, _ in info._fields_}
+            return OptimizationResult(
+                adjustments=out, total_cost=info.total_cost, original_gap=info.original_gap, new_gap=info.new_gap,
+                original_unexplained_gap=info.original_unexplained_gap,
+                new_unexplained_gap=info.new_unexplained_gap, required_budget=info.required_budget,
+                model_coefficients=[Contribution(names[j], pb[j]) for j in range(k.value)])
+        finally:
+            lib.ob_remedy_results_free(h)
+
+    def verify_adjustments(self, adjustments, three_fold: bool = False) -> "DecompositionResult":
+        """engine/src/analysis.rs:40-96 (verify_inner) on the MI355X engine (``ob_remedy_verify``): the
+        raises are added to a copy of the outcome one by one in request order (two raises of one row give
+        ``(w + a1) + a2``) and the decomposition runs again with this builder's configuration as it stands
+        (reference coefficients, replicates, seed, weights, normalisation). The gaps come from the two-fold
+        table, or from the three-fold one with ``interaction_gap`` when ``three_fold`` is set (the detailed
+        lists and ``unexplained_standard_error`` are two-fold only). An index outside the frame raises
+        ``OB_E_INVALID``. The reference's ``quantile`` switch is not built."""
+        from .engine import remedy_apply_adjustments
+
+        prop = _proposed(adjustments)
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        idx = np.array([p[0] for p in prop], dtype=np.int64)
+        val = np.array([p[1] for p in prop], dtype=np.float64)
+        h = C.c_void_p()
+
+        def call(ctx):
+            return lib.ob_remedy_verify(ctx, cols, ncol, nrow, C.byref(cfg), idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        val.ctypes.data_as(C.POINTER(C.c_double)), len(prop), C.byref(h))
+
+        try:
+            ctx = N.context(self._device)
+        except (N.OaxacaError, ImportError):
+            rc = call(None)  # the argument errors come before the device
+            if not (rc == N.OB_E_INVALID and b"null pointer" in lib.ob_last_error()):
+                N.check(rc)
+            raise
+        N.check(call(ctx))
+        res = _results_from_c(h)
+        # run_decomposition_on_df's summary (analysis.rs:102-140) of the adjusted wages
+        kind, wage, valid = self._frame.columns[self.outcome]
+        adjusted = remedy_apply_adjustments(wage, idx, val, valid)
+        ok = np.ones(len(adjusted), dtype=bool) if valid is None else valid.astype(bool)
+        gkind, groups, _ = self._frame.columns[self.group]
+        ref = self.reference_group.encode()
+        in_a = np.array([g == ref for g in groups], dtype=bool) if gkind == N.OB_COL_STR else np.zeros(len(adjusted), bool)
+        mean = lambda mask: float(np.mean(adjusted[mask & ok])) if (mask & ok).any() else 0.0  # noqa: E731
+        summary = DataSummary(len(adjusted), int(in_a.sum()), int((~in_a).sum()), mean(in_a), mean(~in_a))
+        total = res.total_gap
+        comp = {c.name: c for c in (res.three_fold.aggregate if three_fold else res.two_fold.aggregate)}
+        exp_ = comp.get("endowments" if three_fold else "explained")
+        une = comp.get("coefficients" if three_fold else "unexplained")
+        inter = comp.get("interaction") if three_fold else None
+        e, u = (exp_.estimate if exp_ else 0.0), (une.estimate if une else 0.0)
+
+        def pct(x):  # analysis.rs:299-301; IEEE division, so a zero gap gives inf or NaN as there
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return float((np.float64(x) / np.float64(total)) * 100.0)
+
+        return DecompositionResult(
+            total_gap=total, explained_gap=e, unexplained_gap=u,
+            interaction_gap=inter.estimate if inter else None,
+            explained_percentage=pct(e), unexplained_percentage=pct(u),
+            interaction_percentage=pct(inter.estimate) if inter else None,
+            detailed_explained=[] if three_fold else list(res.two_fold.detailed_explained),
+            detailed_unexplained=[] if three_fold else list(res.two_fold.detailed_unexplained),
+            data_summary=summary,
+            unexplained_standard_error=None if three_fold or une is None else une.std_err, results=res)
+
+    def decompose(self, three_fold: bool = False) -> "DecompositionResult":
+        """engine/src/analysis.rs:8-38 (decompose_inner): ``verify_adjustments`` with no adjustments."""
+        return self.verify_adjustments([], three_fold)
 
     def run(self) -> OaxacaResults:
         """builder.rs:787-951 on the MI355X engine."""

@@ -10,11 +10,21 @@
 // Deliberate difference: beta is the Cholesky solve of the normal equations in nalgebra's operation
 // order (ob_linalg.hpp), not the reference's SVD solve. The reference inverts X_A'X_A two lines later and
 // fails when it is singular, so the two differ by rounding of order cond u only.
+//
+// Also here: check_defensibility_inner (engine/src/defensibility.rs) as ob_remedy_defend / ob_remedy_defend_rows
+// and verify_inner (analysis.rs:40-96) as ob_remedy_verify. Predictor overrides are resolved on the host
+// (resolve_overrides) and applied to copies of the touched columns BEFORE the design is built, so an override of
+// a reference-group row changes beta, cov and sigma squared for every row, as in the reference. Deliberate
+// differences: a null or non-finite value in a named column is OB_E_INVALID (ob_remedy_run's checks, shared);
+// the group sums are added in a fixed order (the reference's follow HashMap iteration); an adjustment whose
+// index is outside the frame is skipped by ob_remedy_defend, as there, but rejected by ob_remedy_defend_rows
+// and ob_remedy_verify.
 #include <algorithm>
 #include <cmath>
 #include <limits>
 #include <vector>
 
+#include <map>
 #include <set>
 #include <string>
 
@@ -250,14 +260,12 @@ static const Col* remedy_column(const Frame& f, const char* name, int* rc) {
   return &c;
 }
 
-static int remedy_run(ob_ctx* ctx, const ob_column* cols, int n_cols, int64_t n_rows, const ob_builder_config* cfg,
-                      const ob_remedy_request* rq, int target, int want_contrib, ob_remedy_results** out) {
-  if (out) *out = nullptr;
-  OB_TRY(remedy_check_request(rq));
-  if (target != OB_REMEDY_TARGET_REFERENCE && target != OB_REMEDY_TARGET_POOLED) return fail(OB_E_INVALID, "bad target");
+// The frame checks of ob_remedy_run, shared with ob_remedy_defend: all before any device work, in this order.
+// index: the reference group's original rows, then the target group's (analysis.rs:387-398). n_ref: A's rows.
+static int remedy_check_frame(const ob_column* cols, int n_cols, int64_t n_rows, const ob_builder_config* cfg, Frame& f,
+                              std::vector<int64_t>& index, int64_t* n_ref) {
   if (!cfg || !cfg->outcome || !cfg->group || !cfg->reference_group) return fail(OB_E_INVALID, "null pointer");
   if (cfg->n_predictors < 0 || cfg->n_categorical < 0) return fail(OB_E_INVALID, "bad name list");
-  Frame f;
   OB_TRY(load_frame(cols, n_cols, n_rows, f));
   int rc = OB_OK;
   const Col* yc = remedy_column(f, cfg->outcome, &rc);
@@ -285,11 +293,26 @@ static int remedy_run(ob_ctx* ctx, const ob_column* cols, int n_cols, int64_t n_
   if (width > kRemedyMaxK)
     return fail(OB_E_UNSUPPORTED, "remedy: %lld design columns beside the intercept, the kernels take at most %d",
                 (long long)(width - 1), kRemedyMaxK - 1);
-  std::vector<int64_t> index;  // the reference group's original rows, then the target group's (analysis.rs:387-398)
+  index.clear();
   index.reserve((size_t)f.nrows);
   for (int pass = 0; pass < 2; ++pass)
     for (int64_t r = 0; r < f.nrows; ++r)
       if ((gc->s[r] == cfg->reference_group) == (pass == 0)) index.push_back(r);
+  *n_ref = 0;
+  for (int64_t r = 0; r < f.nrows; ++r) *n_ref += gc->s[r] == cfg->reference_group;
+  return OB_OK;
+}
+
+static int remedy_run(ob_ctx* ctx, const ob_column* cols, int n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                      const ob_remedy_request* rq, int target, int want_contrib, ob_remedy_results** out) {
+  if (out) *out = nullptr;
+  OB_TRY(remedy_check_request(rq));
+  if (target != OB_REMEDY_TARGET_REFERENCE && target != OB_REMEDY_TARGET_POOLED) return fail(OB_E_INVALID, "bad target");
+  Frame f;
+  std::vector<int64_t> index;
+  int64_t n_ref = 0;
+  int rc = OB_OK;
+  OB_TRY(remedy_check_frame(cols, n_cols, n_rows, cfg, f, index, &n_ref));
   if (!ctx || !out) return fail(OB_E_INVALID, "null pointer");
 
   ob_builder_config c2 = *cfg;
@@ -310,8 +333,6 @@ static int remedy_run(ob_ctx* ctx, const ob_column* cols, int n_cols, int64_t n_
   const int64_t n = n_a + n_b;
   OB_TRY(remedy_check_shape(n, k));
   if (n != (int64_t)index.size()) return fail(OB_E_INVALID, "rows were dropped while cleaning the frame");
-  int64_t n_ref = 0;
-  for (int64_t r = 0; r < f.nrows; ++r) n_ref += gc->s[r] == cfg->reference_group;
   if (n_ref != n_a) return fail(OB_E_INVALID, "rows were dropped while cleaning the frame");
   ob_results* point = nullptr;
   OB_TRY(ob_builder_run(ctx, cols, n_cols, n_rows, &c2, &point));
@@ -497,6 +518,241 @@ static int remedy_frontier(ob_ctx* ctx, const ob_column* cols, int n_cols, int64
   return OB_OK;
 }
 
+// ---- check_defensibility_inner (engine/src/defensibility.rs) and verify_inner (analysis.rs:40-96) -----------
+
+// The checks of the array pass that need no device, in the order the header gives.
+static int defend_check_arrays(const double* y, const double* fair, const double* lev, int64_t n_a, int64_t n_b,
+                               const int64_t* rows, const double* values, int64_t m, double sigma2) {
+  if (n_a < 0 || n_b < 0 || m < 0) return fail(OB_E_INVALID, "bad remedy dimensions");
+  OB_TRY(remedy_check_shape(n_a + n_b, 2));
+  if (m >= (int64_t)0x7fffffff) return fail(OB_E_UNSUPPORTED, "defend: too many adjustments");
+  const int64_t n = n_a + n_b;
+  if ((n > 0 && (!y || !fair || !lev)) || (m > 0 && (!rows || !values))) return fail(OB_E_INVALID, "null pointer");
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(y[i]) || !std::isfinite(fair[i]) || !std::isfinite(lev[i]))
+      return fail(OB_E_INVALID, "non-finite wage, fair wage or leverage (row %lld)", (long long)i);
+  if (std::isnan(sigma2)) return fail(OB_E_INVALID, "NaN sigma_squared");
+  for (int64_t j = 0; j < m; ++j) {
+    if (rows[j] < 0 || rows[j] >= n)
+      return fail(OB_E_INVALID, "adjustment %lld names stacked row %lld outside [0, %lld)", (long long)j, (long long)rows[j], (long long)n);
+    if (!std::isfinite(values[j])) return fail(OB_E_INVALID, "non-finite adjustment value (adjustment %lld)", (long long)j);
+  }
+  return OB_OK;
+}
+
+struct OverrideCell {
+  int64_t row;
+  int pred;
+  double value;
+};
+
+// defensibility.rs:32-73. The flat list keeps every name, a predictor or not: a set of ignored names still
+// replaces the row's earlier set, as the reference's insert does.
+static int resolve_overrides(const int64_t* index, int64_t m, const int64_t* opos, const char* const* oname,
+                             const double* ovalue, int64_t n_ovr, const char* const* preds, int n_preds, int64_t n_rows,
+                             std::vector<OverrideCell>& cells) {
+  cells.clear();
+  if (m < 0 || n_ovr < 0 || n_preds < 0) return fail(OB_E_INVALID, "bad override list");
+  if ((m > 0 && !index) || (n_ovr > 0 && (!opos || !oname || !ovalue)) || (n_preds > 0 && !preds)) return fail(OB_E_INVALID, "null pointer");
+  for (int64_t i = 0; i < n_ovr; ++i) {
+    if (opos[i] < 0 || opos[i] >= m) return fail(OB_E_INVALID, "override %lld names adjustment %lld of %lld", (long long)i, (long long)opos[i], (long long)m);
+    if (!oname[i]) return fail(OB_E_INVALID, "null pointer");
+    if (!std::isfinite(ovalue[i])) return fail(OB_E_INVALID, "non-finite override value for `%s` (adjustment %lld)", oname[i], (long long)opos[i]);
+  }
+  // entries by adjustment position, stable: the sets in request order, a set's names in the order given
+  std::vector<int64_t> order((size_t)n_ovr);
+  for (int64_t i = 0; i < n_ovr; ++i) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return opos[a] < opos[b]; });
+  std::map<int64_t, std::map<std::string, double>> by_index;  // HashMap<usize, HashMap<String, f64>>
+  for (size_t a = 0; a < order.size();) {
+    size_t b = a;
+    std::map<std::string, double> set;
+    while (b < order.size() && opos[order[b]] == opos[order[a]]) {
+      set[oname[order[b]]] = ovalue[order[b]];
+      ++b;
+    }
+    by_index[index[opos[order[a]]]] = std::move(set);  // the last set for an index wins as a whole
+    a = b;
+  }
+  for (int p = 0; p < n_preds; ++p) {
+    if (!preds[p]) return fail(OB_E_INVALID, "null pointer");
+    for (const auto& kv : by_index) {
+      if (kv.first < 0 || kv.first >= n_rows) continue;  // :59
+      const auto it = kv.second.find(preds[p]);
+      if (it != kv.second.end()) cells.push_back({kv.first, p, it->second});
+    }
+  }
+  return OB_OK;
+}
+
+static int apply_adjustments(const double* wage, const uint8_t* valid, int64_t n_rows, const int64_t* index,
+                             const double* value, int64_t m, double* out) {
+  if (n_rows < 0 || m < 0) return fail(OB_E_INVALID, "bad remedy dimensions");
+  if ((n_rows > 0 && (!wage || !out)) || (m > 0 && (!index || !value))) return fail(OB_E_INVALID, "null pointer");
+  std::copy(wage, wage + n_rows, out);
+  for (int64_t j = 0; j < m; ++j) {
+    if (index[j] < 0 || index[j] >= n_rows)  // analysis.rs:81-87
+      return fail(OB_E_INVALID, "Adjustment index %lld is out of bounds (dataset has %lld rows)", (long long)index[j], (long long)n_rows);
+    if (!std::isfinite(value[j])) return fail(OB_E_INVALID, "non-finite adjustment value (adjustment %lld)", (long long)j);
+    if (!valid || valid[index[j]]) out[index[j]] = out[index[j]] + value[j];  // :78-80, one by one
+  }
+  return OB_OK;
+}
+
+static int remedy_defend(ob_ctx* ctx, const ob_column* cols, int n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                         const int64_t* index_in, const double* value, int64_t m, const int64_t* opos,
+                         const char* const* oname, const double* ovalue, int64_t n_ovr, double confidence_level,
+                         int want_contrib, ob_remedy_results** out) {
+  if (out) *out = nullptr;
+  if (m < 0 || n_ovr < 0) return fail(OB_E_INVALID, "bad adjustment list");
+  if ((m > 0 && (!index_in || !value)) || (n_ovr > 0 && (!opos || !oname || !ovalue))) return fail(OB_E_INVALID, "null pointer");
+  if (m >= (int64_t)0x7fffffff) return fail(OB_E_UNSUPPORTED, "defend: too many adjustments");
+  Frame f;
+  std::vector<int64_t> index;
+  int64_t n_ref = 0;
+  OB_TRY(remedy_check_frame(cols, n_cols, n_rows, cfg, f, index, &n_ref));
+  for (int64_t j = 0; j < m; ++j)
+    if (!std::isfinite(value[j])) return fail(OB_E_INVALID, "non-finite adjustment value (adjustment %lld)", (long long)j);
+  std::vector<OverrideCell> cells;
+  OB_TRY(resolve_overrides(index_in, m, opos, oname, ovalue, n_ovr, cfg->predictors, cfg->n_predictors, f.nrows, cells));
+  if (!ctx || !out) return fail(OB_E_INVALID, "null pointer");
+
+  // the touched predictor columns, copied as f64 and edited; every other column is the caller's
+  std::vector<ob_column> cols2(cols, cols + n_cols);
+  std::vector<std::vector<double>> edited;
+  edited.reserve(cells.size());
+  for (size_t c = 0; c < cells.size();) {
+    const int p = cells[c].pred;
+    const int ci = f.find(cfg->predictors[p]);
+    const Col& src = f.cols[ci];
+    size_t e = c;
+    while (e < cells.size() && cells[e].pred == p) ++e;
+    if (src.kind != OB_COL_STR) {  // `.f64()` of a string column fails and the reference goes on (:53)
+      edited.emplace_back((size_t)f.nrows);
+      std::vector<double>& v = edited.back();
+      for (int64_t r = 0; r < f.nrows; ++r) v[r] = src.kind == OB_COL_F64 ? src.f[r] : (double)src.i[r];
+      for (size_t q = c; q < e; ++q) v[cells[q].row] = cells[q].value;
+      for (int j = 0; j < n_cols; ++j)  // a predictor named twice edits one column
+        if (src.name == cols[j].name) {
+          cols2[j].kind = OB_COL_F64;
+          cols2[j].f64 = v.data();
+          cols2[j].i64 = nullptr;
+        }
+    }
+    c = e;
+  }
+
+  ob_builder_config c2 = *cfg;
+  c2.reference_coeffs = 2;  // ReferenceCoefficients::Pooled (defensibility.rs:95); the matrices do not depend on it
+  c2.bootstrap_reps = 0;
+  ob_matrices* mats = nullptr;
+  OB_TRY(ob_builder_data_matrices(cols2.data(), n_cols, n_rows, &c2, &mats));
+  struct Free {
+    ob_matrices* m;
+    ~Free() { ob_matrices_free(m); }
+  } free_mats{mats};
+  int64_t n_b = 0, n_a = 0;
+  int32_t k = 0;
+  const double *xt = nullptr, *yt = nullptr, *xr = nullptr, *yr = nullptr;
+  OB_TRY(ob_matrices_dims(mats, &n_b, &n_a, &k));
+  OB_TRY(ob_matrices_get(mats, &xt, &yt, &xr, &yr));
+  const int64_t n = n_a + n_b;
+  OB_TRY(remedy_check_shape(n, k));
+  if (n != (int64_t)index.size() || n_ref != n_a) return fail(OB_E_INVALID, "rows were dropped while cleaning the frame");
+  // original index -> stacked row; an index outside the frame is skipped (:200)
+  std::vector<int64_t> inverse((size_t)f.nrows, -1), rows, kept_index;
+  std::vector<double> kept_value;
+  for (int64_t s = 0; s < n; ++s) inverse[index[s]] = s;
+  int64_t n_skipped = 0;
+  for (int64_t j = 0; j < m; ++j) {
+    const int64_t s = index_in[j] >= 0 && index_in[j] < f.nrows ? inverse[index_in[j]] : -1;
+    if (s < 0) {
+      ++n_skipped;
+      continue;
+    }
+    rows.push_back(s);
+    kept_index.push_back(index_in[j]);
+    kept_value.push_back(value[j]);
+  }
+
+  std::vector<double> xy((size_t)n * k);  // one upload: [features, y] column-major, A's rows first
+  for (int c = 0; c < k; ++c) {
+    double* dst = xy.data() + (size_t)c * n;
+    const double* sa = c < k - 1 ? xr + (size_t)(c + 1) * n_a : yr;
+    const double* sb = c < k - 1 ? xt + (size_t)(c + 1) * n_b : yt;
+    std::copy(sa, sa + n_a, dst);
+    std::copy(sb, sb + n_b, dst + n_a);
+  }
+  OB_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf dxy, dfair, dlev, dcontrib;
+  OB_HIP(dxy.alloc(sizeof(double) * (size_t)n * k));
+  OB_HIP(dfair.alloc(sizeof(double) * (size_t)n));
+  OB_HIP(dlev.alloc(sizeof(double) * (size_t)n));
+  if (want_contrib) OB_HIP(dcontrib.alloc(sizeof(double) * (size_t)n * k));
+  OB_HIP(hipMemcpyAsync(dxy.p, xy.data(), sizeof(double) * (size_t)n * k, hipMemcpyHostToDevice, st));
+  const int k1 = k + 1;
+  std::vector<double> ga((size_t)k1 * k1), beta(k), cov((size_t)k * k);
+  double gram_ms = 0.0, score_ms = 0.0, rss = 0.0;
+  OB_TRY(vif_gram_device(ctx, dxy.d(), n, n_a, k, ga.data(), &gram_ms));
+  OB_TRY(remedy_solve(ga.data(), nullptr, k, beta.data(), cov.data()));
+  const double* dy = dxy.d() + (size_t)(k - 1) * n;
+  OB_TRY(remedy_score_device(ctx, dxy.d(), n, dy, n, n_a, k, beta.data(), cov.data(), dfair.d(), dlev.d(), &rss,
+                             want_contrib ? dcontrib.d() : nullptr, &score_ms));
+  const double dof = (double)n_a - (double)k;  // defensibility.rs:135-140
+  const double sigma2 = dof > 0.0 ? rss / dof : 0.0;
+  ob_remedy_results* r = new ob_remedy_results();
+  int rc = remedy_defend_device(ctx, dy, dfair.d(), dlev.d(), n_a, n_b, rows.data(), kept_value.data(), (int64_t)rows.size(),
+                                sigma2, confidence_level, *r);
+  if (rc == OB_OK && want_contrib && !r->row.empty()) {
+    std::vector<double> con((size_t)n * k);
+    const hipError_t e = hipMemcpy(con.data(), dcontrib.p, sizeof(double) * (size_t)n * k, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(OB_E_HIP, "HIP error %s", hipGetErrorString(e));
+    r->contrib.resize(r->row.size() * (size_t)k);
+    for (size_t i = 0; i < r->row.size() && rc == OB_OK; ++i)
+      for (int c = 0; c < k; ++c) r->contrib[i * k + c] = con[(size_t)c * n + r->row[i]];
+  }
+  if (rc != OB_OK) {
+    delete r;
+    return rc;
+  }
+  r->index = kept_index;
+  for (int c = 0; c < k; ++c) r->names.push_back(ob_matrices_name(mats, c));
+  for (const std::string& s : r->names) r->name_ptrs.push_back(s.c_str());
+  r->beta = beta;
+  r->dinfo.n_skipped = n_skipped;
+  r->dinfo.gram_ms = gram_ms;
+  r->dinfo.score_ms = score_ms;
+  r->info.gram_ms = gram_ms;
+  r->info.score_ms = score_ms;
+  *out = r;
+  return OB_OK;
+}
+
+static int remedy_verify(ob_ctx* ctx, const ob_column* cols, int n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                         const int64_t* index, const double* value, int64_t m, ob_results** out) {
+  if (out) *out = nullptr;
+  if (!cfg || !cfg->outcome) return fail(OB_E_INVALID, "null pointer");
+  Frame f;
+  OB_TRY(load_frame(cols, n_cols, n_rows, f));
+  const int ci = f.find(cfg->outcome);
+  if (ci < 0) return fail(OB_E_COLUMN, "Column '%s' not found in dataset.", cfg->outcome);  // analysis.rs:64
+  const Col& yc = f.cols[ci];
+  if (yc.kind == OB_COL_STR) return fail(OB_E_POLARS, "%sColumn '%s' contains non-numeric data.", error_prefix(OB_E_POLARS), cfg->outcome);
+  std::vector<double> wage((size_t)f.nrows), adjusted((size_t)f.nrows);
+  for (int64_t r = 0; r < f.nrows; ++r) wage[r] = yc.kind == OB_COL_F64 ? yc.f[r] : (double)yc.i[r];
+  OB_TRY(apply_adjustments(wage.data(), yc.valid.data(), f.nrows, index, value, m, adjusted.data()));
+  if (!ctx || !out) return fail(OB_E_INVALID, "null pointer");
+  std::vector<ob_column> cols2(cols, cols + n_cols);
+  for (int j = 0; j < n_cols; ++j)
+    if (yc.name == cols[j].name) {
+      cols2[j].kind = OB_COL_F64;
+      cols2[j].f64 = adjusted.data();
+      cols2[j].i64 = nullptr;
+    }
+  return ob_builder_run(ctx, cols2.data(), n_cols, n_rows, cfg, out);
+}
+
 }  // namespace ob
 
 extern "C" {
@@ -621,5 +877,82 @@ int ob_remedy_results_get(const ob_remedy_results* r, const int64_t** index, con
 }
 
 void ob_remedy_results_free(ob_remedy_results* r) { delete r; }
+
+int ob_remedy_defend_rows(ob_ctx* ctx, const double* y, const double* fair, const double* leverage, int64_t n_a,
+                          int64_t n_b, const int64_t* rows, const double* values, int64_t m, double sigma_squared,
+                          double confidence_level, ob_remedy_results** out) {
+  using namespace ob;
+  if (out) *out = nullptr;
+  OB_TRY(defend_check_arrays(y, fair, leverage, n_a, n_b, rows, values, m, sigma_squared));
+  if (!ctx || !out) return fail(OB_E_INVALID, "null pointer");
+  const int64_t n = n_a + n_b;
+  OB_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf d;  // y, fair and leverage side by side
+  OB_HIP(d.alloc(sizeof(double) * 3 * (size_t)n));
+  const double* src[3] = {y, fair, leverage};
+  for (int i = 0; i < 3 && n > 0; ++i)
+    OB_HIP(hipMemcpyAsync(d.d() + (size_t)i * n, src[i], sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  ob_remedy_results* r = new ob_remedy_results();
+  const int rc = remedy_defend_device(ctx, d.d(), d.d() + n, d.d() + 2 * (size_t)n, n_a, n_b, rows, values, m, sigma_squared,
+                                      confidence_level, *r);
+  (void)hipStreamSynchronize(st);
+  if (rc != OB_OK) {
+    delete r;
+    return rc;
+  }
+  *out = r;
+  return OB_OK;
+}
+
+int ob_remedy_defend(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                     const int64_t* index, const double* value, int64_t m, const int64_t* override_adjustment,
+                     const char* const* override_name, const double* override_value, int64_t n_overrides,
+                     double confidence_level, int32_t contributions, ob_remedy_results** out) {
+  return ob::remedy_defend(ctx, cols, n_cols, n_rows, cfg, index, value, m, override_adjustment, override_name,
+                           override_value, n_overrides, confidence_level, contributions, out);
+}
+
+int ob_remedy_resolve_overrides(const int64_t* index, int64_t m, const int64_t* override_adjustment,
+                                const char* const* override_name, const double* override_value, int64_t n_overrides,
+                                const char* const* predictors, int32_t n_predictors, int64_t n_rows, int64_t* out_row,
+                                int32_t* out_predictor, double* out_value, int64_t* n_out) {
+  using namespace ob;
+  if (!n_out || (n_overrides > 0 && (!out_row || !out_predictor || !out_value))) return fail(OB_E_INVALID, "null pointer");
+  *n_out = 0;
+  std::vector<OverrideCell> cells;
+  OB_TRY(resolve_overrides(index, m, override_adjustment, override_name, override_value, n_overrides, predictors,
+                           n_predictors, n_rows, cells));
+  for (size_t i = 0; i < cells.size(); ++i) {
+    out_row[i] = cells[i].row;
+    out_predictor[i] = cells[i].pred;
+    out_value[i] = cells[i].value;
+  }
+  *n_out = (int64_t)cells.size();
+  return OB_OK;
+}
+
+int ob_remedy_results_defensible(const ob_remedy_results* r, const int32_t** is_defensible) {
+  if (!r || !is_defensible) return ob::fail(OB_E_INVALID, "null pointer");
+  *is_defensible = r->defend ? r->defensible.data() : nullptr;
+  return OB_OK;
+}
+
+int ob_remedy_results_defend_info(const ob_remedy_results* r, ob_defend_info* out) {
+  if (!r || !out) return ob::fail(OB_E_INVALID, "null pointer");
+  if (!r->defend) return ob::fail(OB_E_INVALID, "not a defensibility handle");
+  *out = r->dinfo;
+  return OB_OK;
+}
+
+int ob_remedy_apply_adjustments(const double* wage, const uint8_t* valid, int64_t n_rows, const int64_t* index,
+                                const double* value, int64_t m, double* out) {
+  return ob::apply_adjustments(wage, valid, n_rows, index, value, m, out);
+}
+
+int ob_remedy_verify(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                     const int64_t* index, const double* value, int64_t m, ob_results** out) {
+  return ob::remedy_verify(ctx, cols, n_cols, n_rows, cfg, index, value, m, out);
+}
 
 }  // extern "C"

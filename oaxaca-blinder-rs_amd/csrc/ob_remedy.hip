@@ -23,6 +23,13 @@
 //   (the same sort by original index, ascending: :834)
 //   ob_remedy_gather_kernel    the result arrays in that order
 //
+// check_defensibility_inner (engine/src/defensibility.rs:199-365) over the same stacked rows:
+//   ob_defend_first_kernel     first[row] = the first request position that names the row (32-bit atomicMin)
+//   ob_defend_adjust_kernel    per proposed adjustment, in request order: current and new wage, the fair-wage
+//                              interval, is_defensible; block partials of the values (total_cost)
+//   ob_defend_rows_kernel      per stacked row: the wage after its first adjustment, and block partials of the
+//                              seven group sums behind the gaps and required_budget
+//
 // The score kernel follows ob_vif_resid_kernel: B' (at most 120 x 144 f64) stays in LDS for the whole
 // block, X streams through registers in the A-operand shape of v_mfma_f64_16x16x4_f64, a wave owns a
 // 16-row block and feeds up to 8 column-block accumulators. The epilogue reads the same 16 x K tile of x
@@ -578,6 +585,117 @@ __global__ __launch_bounds__(kScBlock) void ob_remedy_front_rss_kernel(const Fro
   }
 }
 
+// ---- defensibility (engine/src/defensibility.rs:199-365) ---------------------------------------------------
+// The reference looks every row's adjustment up by walking the whole result list (:292-301, :343-349) and stops at
+// the first hit. Here first[row] = the smallest request position that names the row, by an integer atomicMin
+// (order-free, so deterministic), and one pass over the rows reads its adjustment through that map.
+// A row nobody names keeps 0xffffffff, above every position (m < 2^31 - 1).
+constexpr int kDfSums = 7;  // the row sums; total_cost is the per-adjustment kernel's
+
+__global__ __launch_bounds__(kAlBlock) void ob_defend_first_kernel(const uint32_t* row, uint32_t m, uint32_t* first) {
+  const uint32_t j = blockIdx.x * kAlBlock + threadIdx.x;
+  if (j < m) atomicMin(&first[row[j]], j);
+}
+
+// defensibility.rs:156-165, apart from ob_remedy_classify_kernel's copy on purpose: that one's bytes are pinned by
+// the optimize tests.
+__device__ __forceinline__ void defend_interval(double fair, double lev, double sigma2, double z, double& lo, double& up) {
+  lo = fair;
+  up = fair;
+  if (!(sigma2 <= 1e-9)) {
+    const double margin = z * sqrt(sigma2 * (1.0 + lev));
+    lo = fair - margin;
+    up = fair + margin;
+  }
+}
+
+struct DefendAdjArgs {
+  const double *y, *fair, *lev;  // device, stacked rows
+  const uint32_t* row;           // [m] stacked row of each adjustment, request order
+  const double* value;           // [m]
+  uint32_t m;
+  double sigma2, z;
+  double *current, *new_wage, *fair_out, *lower, *upper;  // [m]
+  int32_t* flag;                                           // [m] is_defensible
+  double* partial;                                         // [blocks]: the values (total_cost)
+};
+
+__global__ __launch_bounds__(kAlBlock) void ob_defend_adjust_kernel(const DefendAdjArgs a) {
+  __shared__ double red[kAlWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t j = blockIdx.x * kAlBlock + tid;
+  double v = 0.0;
+  if (j < a.m) {
+    const uint32_t row = a.row[j];
+    v = a.value[j];
+    const double cur = a.y[row], fair = a.fair[row];
+    const double nw = cur + v;  // :222
+    double lo, up;
+    defend_interval(fair, a.lev[row], a.sigma2, a.z, lo, up);
+    a.current[j] = cur;
+    a.new_wage[j] = nw;
+    a.fair_out[j] = fair;
+    a.lower[j] = lo;
+    a.upper[j] = up;
+    a.flag[j] = nw >= lo - 1.0 ? 1 : 0;  // :225
+  }
+  v = wave_sum(v);
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  if (tid == 0) {
+    double t = red[0];
+    for (int w = 1; w < kAlWaves; ++w) t += red[w];
+    a.partial[blockIdx.x] = t;
+  }
+}
+
+struct DefendRowArgs {
+  const double *y, *fair;  // device, stacked: A's n_a rows, then B's
+  const uint32_t* first;   // [n]
+  const double* value;     // [m]
+  uint32_t m;
+  int64_t n_a, n;
+  double* partial;  // [kDfSums][blocks]: sum_A y, sum_A new, sum_B y, sum_B new, sum_B (fair - y), sum_B (fair - new),
+                    // sum_B max(fair - y, 0)
+  uint32_t blocks;
+};
+
+__global__ __launch_bounds__(kAlBlock) void ob_defend_rows_kernel(const DefendRowArgs a) {
+  __shared__ double red[kDfSums][kAlWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t i = (int64_t)blockIdx.x * kAlBlock + tid;
+  double s[kDfSums];
+#pragma unroll
+  for (int q = 0; q < kDfSums; ++q) s[q] = 0.0;
+  if (i < a.n) {
+    const double y = a.y[i];
+    const uint32_t f = a.first[i];
+    const double nw = f < a.m ? y + a.value[f] : y;  // the first adjustment of the row decides (:296-301)
+    if (i < a.n_a) {
+      s[0] = y;
+      s[1] = nw;
+    } else {
+      const double fair = a.fair[i];
+      s[2] = y;
+      s[3] = nw;
+      s[4] = fair - y;
+      s[5] = fair - nw;
+      if (fair > y) s[6] = fair - y;  // :272
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kDfSums; ++q) {
+    const double t = wave_sum(s[q]);
+    if (lane == 0) red[q][wave] = t;
+  }
+  __syncthreads();
+  if (tid < kDfSums) {
+    double t = red[tid][0];
+    for (int w = 1; w < kAlWaves; ++w) t += red[tid][w];
+    a.partial[(size_t)tid * a.blocks + blockIdx.x] = t;
+  }
+}
+
 }  // namespace
 
 namespace ob {
@@ -950,6 +1068,142 @@ int remedy_allocate_device(ob_ctx* ctx, const double* dy, const double* dfair, c
   const double nt = (double)n_b;
   info.original_unexplained_gap = nt > 0.0 ? -net / nt : 0.0;
   info.new_unexplained_gap = nt > 0.0 ? -(net - cost) / nt : info.original_unexplained_gap;
+  return OB_OK;
+}
+
+int remedy_defend_device(ob_ctx* ctx, const double* dy, const double* dfair, const double* dlev, int64_t n_a,
+                         int64_t n_b, const int64_t* rows, const double* values, int64_t m64, double sigma2,
+                         double confidence_level, ob_remedy_results& out) {
+  const int64_t n = n_a + n_b;
+  if (!ctx || (n > 0 && (!dy || !dfair || !dlev)) || (m64 > 0 && (!rows || !values))) return fail(OB_E_INVALID, "null pointer");
+  if (m64 < 0 || m64 >= (int64_t)0x7fffffff || n >= (int64_t)0x7fffffff - 256) return fail(OB_E_UNSUPPORTED, "defend: too many rows or adjustments");
+  const uint32_t m = (uint32_t)m64;
+  out.defend = true;
+  ob_defend_info& info = out.dinfo;
+  info = ob_defend_info();
+  info.n_a = n_a;
+  info.n_b = n_b;
+  info.n_adjustments = m;
+  info.sigma_squared = sigma2;
+  info.z_score = remedy_z_score(confidence_level);
+  std::vector<uint32_t> row32(m);
+  for (uint32_t j = 0; j < m; ++j) {
+    if (rows[j] < 0 || rows[j] >= n) return fail(OB_E_INVALID, "adjustment %u names stacked row %lld outside [0, %lld)", j, (long long)rows[j], (long long)n);
+    row32[j] = (uint32_t)rows[j];
+  }
+  OB_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Events<4> ev;
+  OB_HIP(ev.create());
+  const uint32_t rblocks = (uint32_t)((n + kAlBlock - 1) / kAlBlock), ablocks = (m + kAlBlock - 1) / kAlBlock;
+  DevBuf dfirst, drow, dval, dpart, dsum, dapart, ocur, onew, ofair, olower, oupper, oflag;
+  OB_HIP(dfirst.alloc(sizeof(uint32_t) * (size_t)n));
+  OB_HIP(drow.alloc(sizeof(uint32_t) * (size_t)m));
+  OB_HIP(dval.alloc(sizeof(double) * (size_t)m));
+  OB_HIP(dpart.alloc(sizeof(double) * (size_t)kDfSums * rblocks));
+  OB_HIP(dapart.alloc(sizeof(double) * (size_t)ablocks));
+  OB_HIP(dsum.alloc(sizeof(double) * (kDfSums + 1)));
+  for (DevBuf* b : {&ocur, &onew, &ofair, &olower, &oupper}) OB_HIP(b->alloc(sizeof(double) * (size_t)m));
+  OB_HIP(oflag.alloc(sizeof(int32_t) * (size_t)m));
+  OB_HIP(hipMemsetAsync(dsum.p, 0, sizeof(double) * (kDfSums + 1), st));
+  if (m > 0) {
+    OB_HIP(hipMemcpyAsync(drow.p, row32.data(), sizeof(uint32_t) * (size_t)m, hipMemcpyHostToDevice, st));
+    OB_HIP(hipMemcpyAsync(dval.p, values, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, st));
+  }
+  OB_HIP(hipEventRecord(ev.e[0], st));
+  if (n > 0) OB_HIP(hipMemsetAsync(dfirst.p, 0xff, sizeof(uint32_t) * (size_t)n, st));  // no position
+  if (m > 0) {
+    hipLaunchKernelGGL(ob_defend_first_kernel, dim3(ablocks), dim3(kAlBlock), 0, st, drow.as<uint32_t>(), m, dfirst.as<uint32_t>());
+    OB_HIP(hipGetLastError());
+  }
+  OB_HIP(hipEventRecord(ev.e[1], st));
+  if (m > 0) {
+    DefendAdjArgs a = {};
+    a.y = dy;
+    a.fair = dfair;
+    a.lev = dlev;
+    a.row = drow.as<uint32_t>();
+    a.value = dval.d();
+    a.m = m;
+    a.sigma2 = sigma2;
+    a.z = info.z_score;
+    a.current = ocur.d();
+    a.new_wage = onew.d();
+    a.fair_out = ofair.d();
+    a.lower = olower.d();
+    a.upper = oupper.d();
+    a.flag = oflag.as<int32_t>();
+    a.partial = dapart.d();
+    hipLaunchKernelGGL(ob_defend_adjust_kernel, dim3(ablocks), dim3(kAlBlock), 0, st, a);
+    OB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ob_ordered_sum_kernel<>, dim3(1), dim3(kSumBlock), 0, st, dapart.d(), ablocks, dsum.d() + kDfSums);
+    OB_HIP(hipGetLastError());
+  }
+  OB_HIP(hipEventRecord(ev.e[2], st));
+  if (n > 0) {
+    DefendRowArgs r = {};
+    r.y = dy;
+    r.fair = dfair;
+    r.first = dfirst.as<uint32_t>();
+    r.value = dval.d();
+    r.m = m;
+    r.n_a = n_a;
+    r.n = n;
+    r.partial = dpart.d();
+    r.blocks = rblocks;
+    hipLaunchKernelGGL(ob_defend_rows_kernel, dim3(rblocks), dim3(kAlBlock), 0, st, r);
+    OB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ob_ordered_sum_kernel<>, dim3(kDfSums), dim3(kSumBlock), 0, st, dpart.d(), rblocks, dsum.d());
+    OB_HIP(hipGetLastError());
+  }
+  OB_HIP(hipEventRecord(ev.e[3], st));
+  double s[kDfSums + 1] = {};
+  OB_HIP(hipMemcpyAsync(s, dsum.p, sizeof(s), hipMemcpyDeviceToHost, st));
+  std::vector<double>* hv[5] = {&out.current_wage, &out.new_wage, &out.fair_wage, &out.lower, &out.upper};
+  DevBuf* dv[5] = {&ocur, &onew, &ofair, &olower, &oupper};
+  for (int i = 0; i < 5; ++i) {
+    hv[i]->resize(m);
+    if (m > 0) OB_HIP(hipMemcpyAsync(hv[i]->data(), dv[i]->p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+  }
+  out.defensible.resize(m);
+  if (m > 0) OB_HIP(hipMemcpyAsync(out.defensible.data(), oflag.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, st));
+  OB_HIP(hipStreamSynchronize(st));  // row32 and values are read by the copies above until here
+  out.row.assign(rows, rows + m);
+  out.index = out.row;
+  out.adjustment.assign(values, values + m);
+  out.group.resize(m);
+  for (uint32_t j = 0; j < m; ++j) out.group[j] = rows[j] >= n_a ? 1 : 0;
+  float ms = 0.f;
+  OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  info.scatter_ms = ms;
+  OB_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+  info.adjust_ms = ms;
+  OB_HIP(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+  info.rows_ms = ms;
+  OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[3]));
+  info.defend_ms = ms;
+  // defensibility.rs:316-365: a count of zero gives 0.0
+  const double ca = (double)n_a, cb = (double)n_b;
+  info.original_gap = (ca > 0.0 ? s[0] / ca : 0.0) - (cb > 0.0 ? s[2] / cb : 0.0);
+  info.new_gap = (ca > 0.0 ? s[1] / ca : 0.0) - (cb > 0.0 ? s[3] / cb : 0.0);
+  info.original_unexplained_gap = cb > 0.0 ? s[4] / cb : 0.0;
+  info.new_unexplained_gap = cb > 0.0 ? s[5] / cb : 0.0;
+  info.required_budget = s[6];
+  info.total_cost = s[kDfSums];
+  for (int q = 0; q < kDfSums; ++q) info.sums[q] = s[q];
+  // what ob_remedy_results_info reports of a defensibility handle
+  out.info = ob_remedy_info();
+  out.info.n_a = n_a;
+  out.info.n_b = n_b;
+  out.info.n_adjustments = m;
+  out.info.total_cost = info.total_cost;
+  out.info.required_budget = info.required_budget;
+  out.info.original_unexplained_gap = info.original_unexplained_gap;
+  out.info.new_unexplained_gap = info.new_unexplained_gap;
+  out.info.original_gap = info.original_gap;
+  out.info.new_gap = info.new_gap;
+  out.info.z_score = info.z_score;
+  out.info.sigma_squared = sigma2;
   return OB_OK;
 }
 

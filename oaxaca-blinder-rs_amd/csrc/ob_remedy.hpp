@@ -1,5 +1,6 @@
-// ob_remedy.hpp -- pay-equity remediation (engine/src/analysis.rs:309-869): the device passes of
-// ob_remedy.hip and the host pieces of ob_remedy.cpp. The device routines take DEVICE pointers to the
+// ob_remedy.hpp -- pay-equity remediation (engine/src/analysis.rs:309-869) and the defensibility check of
+// edited raises (engine/src/defensibility.rs): the device passes of ob_remedy.hip and the host pieces of
+// ob_remedy.cpp. The device routines take DEVICE pointers to the
 // stacked rows (group A's first), so that a caller uploads them once; everything else is a host pointer.
 #pragma once
 #include <cstdint>
@@ -8,7 +9,8 @@
 
 #include "ob_engine.hpp"
 
-// What ob_remedy_results_get hands out: one entry per returned adjustment, ordered by original index.
+// What ob_remedy_results_get hands out: one entry per returned adjustment, ordered by original index
+// (ob_remedy_run, ob_remedy_allocate) or in request order (ob_remedy_defend, ob_remedy_defend_rows).
 struct ob_remedy_results {
   std::vector<int64_t> index, row;
   std::vector<double> adjustment, current_wage, new_wage, fair_wage, lower, upper;
@@ -17,6 +19,10 @@ struct ob_remedy_results {
   std::vector<const char*> name_ptrs;
   std::vector<double> beta, contrib;    // contrib: n_adjustments x k row-major, or empty
   ob_remedy_info info = {};
+  // ob_remedy_defend and ob_remedy_defend_rows only: one entry per kept adjustment in REQUEST order
+  std::vector<int32_t> defensible;
+  ob_defend_info dinfo = {};
+  bool defend = false;
 };
 
 namespace ob {
@@ -41,6 +47,13 @@ int remedy_score_device(ob_ctx* ctx, const double* dx, int64_t ldx, const double
 int remedy_allocate_device(ob_ctx* ctx, const double* dy, const double* dfair, const double* dlev, int64_t n_a,
                            int64_t n_b, const int64_t* index, double sigma2, const ob_remedy_request& rq,
                            ob_remedy_results& out);
+
+// defensibility.rs:199-365 over the stacked rows. dy, dfair, dlev: device, n_a + n_b entries. rows (each in
+// [0, n_a + n_b), checked again here before anything is launched) and values: host, m entries in request order.
+// Fills out's arrays in request order (index = row; the frame entry rewrites it), defensible, dinfo and info.
+int remedy_defend_device(ob_ctx* ctx, const double* dy, const double* dfair, const double* dlev, int64_t n_a,
+                         int64_t n_b, const int64_t* rows, const double* values, int64_t m, double sigma2,
+                         double confidence_level, ob_remedy_results& out);
 
 // Frontier passes (analysis.rs:871-1153) over the stacked rows: dgap and dpre hold, per row, the gap to pay (0
 // for a non-candidate) and the exclusive prefix P_i of the gaps before it in descending order. xty: host,

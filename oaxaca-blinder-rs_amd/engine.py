@@ -580,3 +580,87 @@ def remedy_allocate(y, fair, leverage, n_a: int, sigma_squared: float, budget: f
         return out
     finally:
         lib.ob_remedy_results_free(h)
+
+
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def remedy_defend_rows(y, fair, leverage, n_a: int, sigma_squared: float, rows, values, confidence_level: float = 0.95,
+                       device: int | None = None) -> dict:
+    """engine/src/defensibility.rs:199-365 on the GPU (``ob_remedy_defend_rows``) over stacked rows, the
+    reference group's ``n_a`` first: ``rows`` and ``values`` are the proposed adjustments as (stacked row,
+    raise) in request order. Returns, per adjustment and in that order, row, adjustment, current_wage,
+    new_wage (one add), fair_wage, lower, upper and is_defensible (``new_wage >= lower - 1.0``), and the
+    scalars of ``ob_defend_info``; ``sums`` holds the seven group sums behind the gaps. Where several
+    adjustments name one row, the first decides that row's new wage in the sums."""
+    yv, fv, hv = (np.ascontiguousarray(a, dtype=np.float64) for a in (y, fair, leverage))
+    n = yv.shape[0]
+    if yv.ndim != 1 or fv.shape != (n,) or hv.shape != (n,) or not 0 <= int(n_a) <= n:
+        raise ValueError("y, fair and leverage must be 1-D of one length, with 0 <= n_a <= n")
+    rv = np.ascontiguousarray(rows, dtype=np.int64)
+    vv = np.ascontiguousarray(values, dtype=np.float64)
+    if rv.ndim != 1 or vv.shape != rv.shape:
+        raise ValueError("rows and values must be 1-D of one length")
+    m = int(rv.shape[0])
+    lib = N.lib()
+    h = C.c_void_p()
+    N.check(lib.ob_remedy_defend_rows(N.context(device), _dp(yv), _dp(fv), _dp(hv), int(n_a), n - int(n_a), _i64p(rv),
+                                      _dp(vv), m, float(sigma_squared), float(confidence_level), C.byref(h)))
+    try:
+        info = N.ob_defend_info()
+        N.check(lib.ob_remedy_results_defend_info(h, C.byref(info)))
+        pr, pf = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
+        pd = [C.POINTER(C.c_double)() for _ in range(6)]
+        N.check(lib.ob_remedy_results_get(h, None, *[C.byref(p) for p in pd], None, C.byref(pr)))
+        N.check(lib.ob_remedy_results_defensible(h, C.byref(pf)))
+
+        def arr(p, dtype):
+            return np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, dtype=dtype)
+
+        out = {"row": arr(pr, np.int64), "is_defensible": arr(pf, np.int32).astype(bool)}
+        for name, p in zip(("adjustment", "current_wage", "new_wage", "fair_wage", "lower", "upper"), pd):
+            out[name] = arr(p, np.float64)
+        for name, _ in info._fields_:
+            out[name] = np.array(info.sums) if name == "sums" else getattr(info, name)
+        return out
+    finally:
+        lib.ob_remedy_results_free(h)
+
+
+def remedy_resolve_overrides(index, overrides, predictors, n_rows: int) -> list:
+    """engine/src/defensibility.rs:32-73 on the host (``ob_remedy_resolve_overrides``, no GPU needed).
+    ``index``: each adjustment's original row index; ``overrides``: ``(adjustment position, column name,
+    value)`` triples. Per index the last adjustment that carries overrides replaces every earlier set as a
+    whole; names outside ``predictors`` and indices past ``n_rows`` have no effect. Returns the cells to
+    change as ``(row, predictor name, value)``, predictor by predictor and by ascending row."""
+    iv = np.ascontiguousarray(index, dtype=np.int64)
+    ov = list(overrides)
+    pos = np.array([o[0] for o in ov], dtype=np.int64)
+    val = np.array([o[2] for o in ov], dtype=np.float64)
+    names = (C.c_char_p * max(len(ov), 1))(*[str(o[1]).encode() for o in ov])
+    preds = [str(p) for p in predictors]
+    pn = (C.c_char_p * max(len(preds), 1))(*[p.encode() for p in preds])
+    cap = max(len(ov), 1)
+    orow, opred, oval, n_out = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap), C.c_int64(0)
+    N.check(N.lib().ob_remedy_resolve_overrides(_i64p(iv), int(iv.shape[0]), _i64p(pos), C.cast(names, C.POINTER(C.c_char_p)),
+                                                _dp(val), len(ov), C.cast(pn, C.POINTER(C.c_char_p)), len(preds),
+                                                int(n_rows), _i64p(orow), _ip(opred), _dp(oval), C.byref(n_out)))
+    return [(int(orow[i]), preds[opred[i]], float(oval[i])) for i in range(n_out.value)]
+
+
+def remedy_apply_adjustments(wage, index, value, valid=None):
+    """engine/src/analysis.rs:76-88 on the host (``ob_remedy_apply_adjustments``, no GPU needed): a copy
+    of ``wage`` with ``wage[index[j]] += value[j]`` applied one by one in request order. ``valid`` marks
+    the non-null wages; no raise touches a null. An index outside the frame raises ``OB_E_INVALID`` with
+    the reference's text."""
+    wv = np.ascontiguousarray(wage, dtype=np.float64)
+    iv = np.ascontiguousarray(index, dtype=np.int64)
+    vv = np.ascontiguousarray(value, dtype=np.float64)
+    if wv.ndim != 1 or iv.ndim != 1 or vv.shape != iv.shape:
+        raise ValueError("wage must be 1-D, index and value 1-D of one length")
+    ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+    out = np.empty_like(wv)
+    N.check(N.lib().ob_remedy_apply_adjustments(_dp(wv), None if ok is None else ok.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                int(wv.shape[0]), _i64p(iv), _dp(vv), int(iv.shape[0]), _dp(out)))
+    return out
