@@ -105,7 +105,9 @@ typedef struct {
   /* Heckman two-step (builder .heckman_selection; estimation.rs:114-260, heckman.rs:38-108):
      heckman = 1 runs a probit of s on [1, z] (math/probit.rs:25-170) and the outcome OLS on the
      rows with s = 1 augmented by the inverse Mills ratio. z: n x n_zsel column-major with
-     leading dimension ldx (intercept implicit, n_zsel <= 7); s: the 0/1 selection outcome.
+     leading dimension ldx (intercept implicit, n_zsel <= OB_HECKMAN_MAX_ZSEL = 31, else
+     OB_E_UNSUPPORTED; up to 7 run register-resident kernels, more the f64 MFMA kernels of
+     csrc/ob_heckman.hip); s: the 0/1 selection outcome.
      With heckman = 1 the group w (if weighted) only feeds the total gap and the Cotton weights
      (the Heckman OLS is unweighted), n_norm must be 0, n_y 1, and rows carry K' = K + 1
      coefficients (IMR last) then 1 + n_zsel selection components (OB_ROW_* with K'). */
@@ -276,6 +278,9 @@ int ob_debug_mm_betas(ob_panel* panel, uint64_t seed, int32_t simulations, uint6
                    0: one buffer (default: the engine's rule)
      "akm_poll"    n >= 1: the AKM loops read their device-side done flags every n iterations (default 8;
                    results and iteration counts bitwise unchanged)
+     "hk_batch"    n >= 1: Heckman panels with more than 7 selection predictors run each boot segment in
+                   batches of at most n 64-replicate blocks (default: as many as keep the chunk partials
+                   within 1 GiB; rows bitwise unchanged)
    Unknown names are OB_E_INVALID. ob_get_option reads back what ob_set_option stored (NaN: unset). ob_tuning_build() is 1 in a -DOB_TUNING=1 build (`make tuning`),
    which also reads OB_<NAME> from the environment for options nobody set. */
 int ob_set_option(const char* name, double value);
@@ -335,7 +340,7 @@ typedef struct {
   int32_t reference_coeffs;      /* builder default OB_REF_GROUP_A (builder.rs:123) */
   int32_t has_seed;              /* 0: fresh entropy per run, like the unseeded reference */
   uint64_t seed;
-  const char* const* selection_predictors; /* Heckman: z (intercept implicit), at most 7 */
+  const char* const* selection_predictors; /* Heckman: z (intercept implicit), at most OB_HECKMAN_MAX_ZSEL */
   int32_t n_selection_predictors;
 } ob_builder_config;
 
@@ -482,6 +487,18 @@ void ob_qd_results_free(ob_qd_results* r);
 #define OB_LOGIT_MAX_K 64
 int ob_logit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int32_t k, int32_t max_iter,
              double tol, double* beta, double* probs, int32_t* converged, int32_t* iterations);
+/* probit(): math/probit.rs::probit, Fisher scoring from beta = 0 on unresampled rows. x: column-major
+   n x k, ldx >= n, with the caller's intercept as column 0 (all ones: the device kernels take z_0 = 1
+   as given, anything else is OB_E_UNSUPPORTED); y: the 0/1 outcome. Phi is clamped to [1e-10,
+   1 - 1e-10]; each step solves (sum w z z' + 1e-9 I) step = sum lambda z by Cholesky, LU with partial
+   pivoting if that fails, and a step neither can solve is OB_E_LINALG "Failed to solve Hessian system
+   in Probit". converged: ||step||_2 < tol within max_iter iterations (running out is not an error);
+   *iterations: the steps taken. It runs the Heckman kernels as a one-replicate segment (register-
+   resident for k <= 8, f64 MFMA above). k <= 32 (1 + OB_HECKMAN_MAX_ZSEL), else OB_E_UNSUPPORTED before
+   any device work, as are the argument checks (OB_E_INVALID: null pointers, n <= 0, k < 1, ldx < n). */
+#define OB_HECKMAN_MAX_ZSEL 31
+int ob_probit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int32_t k, int32_t max_iter,
+              double tol, double* beta, int32_t* converged, int32_t* iterations);
 /* kde(): density[g] = sum_i w_i phi((grid[g] - data[i]) / bandwidth) / bandwidth with phi the
    standard normal pdf and w the weights over their sum (weights NULL: 1 / n). A grid point whose
    every term underflows gets exactly 0. */

@@ -13,7 +13,7 @@ from .api import (Adjustment, AkmBuilder, AkmResult, BudgetAdjustment, Component
                   ReferenceCoefficients, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
                   parse_formula, run_dfl, run_dfl_from_csv)
 from .engine import (Panel, aggregate, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
-                     knn, logit, match_logistic, normal_inverse_cdf, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
+                     knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
                      remedy_resolve_overrides, remedy_score, remedy_solve, rif,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
@@ -23,7 +23,7 @@ __all__ = [
     "ComponentResult", "BudgetAdjustment", "ReferenceCoefficients", "OaxacaError", "PreparedRun",
     "Panel", "boot_multi", "Frame", "read_csv", "aggregate", "bootstrap_stats", "rif", "row_layout", "parse_formula",
     "QuantileDecompositionBuilder", "QuantileDecompositionDetail", "QuantileDecompositionResults",
-    "DflResult", "run_dfl", "run_dfl_from_csv", "logit", "kde", "silverman_bandwidth",
+    "DflResult", "run_dfl", "run_dfl_from_csv", "logit", "probit", "kde", "silverman_bandwidth",
     "MatchingEngine", "MatchResult", "match_units", "knn", "match_logistic",
     "AkmBuilder", "AkmResult", "estimate_akm", "akm_connected_set", "akm_demean", "akm_recover_fe",
     "VifResult", "calculate_vif", "vif", "vif_gram", "vif_solve", "vif_sums", "vif_last_timing",

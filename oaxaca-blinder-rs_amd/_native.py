@@ -45,7 +45,7 @@ EXPORTED = (
     "ob_debug_gram_exceptions", "ob_panel_set_gather_columns", "ob_debug_shard_sim", "ob_debug_mm_fail",
     "ob_debug_chunks", "ob_debug_mm_betas", "ob_set_option", "ob_get_option", "ob_tuning_build",
     "ob_debug_normal",
-    "ob_logit", "ob_kde", "ob_silverman_bandwidth", "ob_dfl_run", "ob_dfl_results_get", "ob_dfl_results_info",
+    "ob_logit", "ob_probit", "ob_kde", "ob_silverman_bandwidth", "ob_dfl_run", "ob_dfl_results_get", "ob_dfl_results_info",
     "ob_dfl_results_free",
     "ob_knn", "ob_match_logistic", "ob_match_run", "ob_match_results_get", "ob_match_results_info",
     "ob_match_results_free",
@@ -61,6 +61,7 @@ EXPORTED = (
 
 OB_E_CONVERGENCE = 12
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
+OB_HECKMAN_MAX_ZSEL = 31
 OB_AKM_MAX_CONTROLS = 64
 OB_VIF_MAX_K = 120
 OB_REMEDY_MAX_K = 120  # design columns, the intercept included
@@ -291,6 +292,8 @@ _SIGS = {
     "ob_debug_normal": (C.c_int, [C.c_int, _D, C.c_int64, _D, _D]),
     "ob_logit": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int32, C.c_int32, C.c_double, _D, _D,
                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ob_probit": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int32, C.c_int32, C.c_double, _D,
+                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ob_kde": (C.c_int, [_P, _D, _D, C.c_int64, _D, C.c_int64, C.c_double, _D]),
     "ob_silverman_bandwidth": (C.c_int, [_D, C.c_int64, _D]),
     "ob_dfl_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_dfl_config),

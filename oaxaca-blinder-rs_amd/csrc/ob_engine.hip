@@ -1672,11 +1672,25 @@ GramArgs gram_args(const ob_panel* p, const Plan& pl) {
   return ga;
 }
 
+// Replicates of a segment that one Heckman pass takes. The narrow path (ks <= 8) takes the segment
+// whole. The wide path writes up to 560 values per (chunk, replicate), so it runs a segment in
+// batches of 64-replicate blocks whose partials stay within kHeckPartialBudget; the chunk table never
+// changes, and a replicate's sums do not depend on its batch (ob_heckman.hip), so rows do not either.
+constexpr size_t kHeckPartialBudget = (size_t)1 << 30;  // bytes
+uint32_t heck_batch(const ob_panel* p, const Plan& pl) {
+  if (p->ks <= ob::kHeckMaxKs) return pl.rep_pad;
+  const size_t per64 = (size_t)pl.n_chunks() * 64 * ob::heck_partial_len(p->k, p->ks) * sizeof(double);
+  size_t blocks = std::max<size_t>(1, kHeckPartialBudget / std::max<size_t>(per64, 1));
+  const int forced = ob::opt_int(ob::Opt::HkBatch, 0);  // tests: a batch size the budget would not pick
+  if (forced > 0) blocks = std::min<size_t>(blocks, (size_t)forced);
+  return (uint32_t)std::min<size_t>(pl.rep_pad, blocks * 64);
+}
+
 int ensure_heck(ob_panel* p, const Plan& pl) {
-  const int vals = std::max(ob::heck_probit_len(p->ks), ob::heck_sums_len(p->k));
+  const size_t vals = ob::heck_partial_len(p->k, p->ks);
   OB_TRY(ensure_buf(&p->d_hgamma, p->cap_hgamma, (size_t)2 * pl.rep_pad * p->ks));
   OB_TRY(ensure_buf(&p->d_hflags, p->cap_hflags, (size_t)2 * pl.rep_pad));
-  OB_TRY(ensure_buf(&p->d_hpartial, p->cap_hpartial, (size_t)pl.n_chunks() * pl.rep_pad * vals));
+  OB_TRY(ensure_buf(&p->d_hpartial, p->cap_hpartial, (size_t)pl.n_chunks() * heck_batch(p, pl) * vals));
   if (!p->d_hactive) OB_HIP(hipMalloc(&p->d_hactive, sizeof(uint32_t)));
   return OB_OK;
 }
@@ -1692,11 +1706,13 @@ ob_heck_seg heck_seg(const ob_panel* p, const Plan& pl, const uint32_t* d_chunks
   h.tiles0 = p->ntiles[0];
   h.p = p->p;
   h.ks = p->ks;
+  h.sz_col = p->p + 2;
   h.weighted = p->h_weighted;
   h.nb_rep = pl.nb_rep;
   h.chunks = d_chunks;
   h.n_chunks = pl.n_chunks();
   h.rep_pad = pl.rep_pad;
+  h.part_pad = pl.rep_pad;
   h.gram = d_gram;
   h.e_pad = p->e_pad;
   h.k1 = p->k1;
@@ -1707,6 +1723,7 @@ ob_heck_seg heck_seg(const ob_panel* p, const Plan& pl, const uint32_t* d_chunks
   h.ref_mode = ref_mode;
   h.row_len = p->row_len;
   h.max_iter = 100;  // heckman.rs:46
+  h.tol = 1e-6;
   return h;
 }
 
@@ -2076,7 +2093,22 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
       hs.raw_status = (diag_mode() & 8) ? 1 : 0;  // OB_GRAM_DIAG bit 8: ok[] = ob_heck_status codes
       int it = 0;
       ob::ob_heck_times ht;
-      OB_TRY(ob::heckman_segment(hs, s, &it, &ht));
+      const uint32_t hb = heck_batch(p, plx);  // == rep_pad unless the wide path's partials need batches
+      for (uint32_t b0 = 0; b0 < ns; b0 += hb) {  // replicates b0 .. b0 + hb of the segment: the same
+        ob_heck_seg hb_seg = hs;                  // images and strides, every per-replicate base moved
+        const uint32_t blk = b0 / 64;
+        hb_seg.n_reps = std::min(hb, ns - b0);
+        hb_seg.part_pad = hb;
+        hb_seg.counts = hs.counts + (size_t)blk * (use_i8 ? 4096 : 4 * kCimgWords);
+        hb_seg.gram = hs.gram + (size_t)b0 * 2 * p->e_pad;
+        hb_seg.gamma = hs.gamma + (size_t)b0 * p->ks;
+        hb_seg.hflags = hs.hflags + b0;
+        hb_seg.rows = hs.rows + (size_t)b0 * p->row_len;
+        hb_seg.ok = hs.ok + b0;
+        int itb = 0;
+        OB_TRY(ob::heckman_segment(hb_seg, s, &itb, &ht));
+        it = std::max(it, itb);
+      }
       p->timing.probit_iterations = std::max(p->timing.probit_iterations, it);
       p->timing.probit_ms += ht.probit_ms;
       p->timing.probit_launches += ht.probit_launches;
@@ -2205,9 +2237,10 @@ int ob_panel_create(ob_ctx* ctx, const ob_panel_desc* d, ob_panel** out) {
   const ob_group_desc* gd[2] = {&d->a, &d->b};
   const bool heck = d->heckman != 0;
   if (heck) {
-    if (d->n_zsel < 0 || d->n_zsel > ob::kHeckMaxKs - 1)
-      return ob::fail(OB_E_UNSUPPORTED, "Heckman selection predictors must be in [0, %d], got %d", ob::kHeckMaxKs - 1,
-                      d->n_zsel);
+    static_assert(OB_HECKMAN_MAX_ZSEL == ob::kHeckWideMaxKs - 1, "the header's limit is the wide kernels'");
+    if (d->n_zsel < 0 || d->n_zsel > OB_HECKMAN_MAX_ZSEL)
+      return ob::fail(OB_E_UNSUPPORTED, "Heckman selection predictors must be in [0, %d] (OB_HECKMAN_MAX_ZSEL), got %d",
+                      OB_HECKMAN_MAX_ZSEL, d->n_zsel);
     if (d->p > ob::kHeckMaxP)
       return ob::fail(OB_E_UNSUPPORTED, "Heckman panels take at most %d predictor columns, got %d", ob::kHeckMaxP, d->p);
     if (d->n_y > 1 || d->n_norm > 0)

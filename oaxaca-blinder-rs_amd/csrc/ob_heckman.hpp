@@ -13,6 +13,7 @@ struct ob_heck_seg {
   uint32_t n[2];
   uint32_t tiles0;
   int p, ks, weighted;  // ks = 1 + selection predictors; weighted: the w column is present
+  int sz_col;           // panel column of s (z_1.. follow it): p + 2 in the layout above
   // resampling: level-2 count images (NULL = every row once: the point estimate) and chunks
   const uint32_t* counts;
   int counts_i8;  // 1: the i8 Gram's A-fragment images (ob_count_kernel<true>), 0: the f64 Gram's
@@ -26,7 +27,8 @@ struct ob_heck_seg {
   // workspace
   double* gamma;     // [2][rep_pad][ks]
   uint32_t* hflags;  // [2][rep_pad]
-  double* partial;   // [chunk][rep_pad][max(probit, sums) values]
+  double* partial;   // [chunk][rep_pad][max(probit, sums) values]; the wide path (ks > 8): [chunk][part_pad][..]
+  uint32_t part_pad; // wide path: replicates per chunk of `partial` (>= n_reps)
   uint32_t* active;  // one word
   // output rows (ob_heck_row_len) and status
   int ref_mode;
@@ -35,6 +37,7 @@ struct ob_heck_seg {
   int row_len;
   int raw_status;  // 1: ok[] receives the status code (ob_heck_status)
   int max_iter;    // probit iterations (probit.rs: 100)
+  double tol;      // a replicate stops once ||step|| < tol (probit.rs: 1e-6)
 };
 
 enum ob_heck_status {
@@ -47,12 +50,17 @@ enum ob_heck_status {
 };
 
 namespace ob {
+// ks up to kHeckMaxKs runs the register-resident kernels (lane = replicate); wider selection
+// equations, up to kHeckWideMaxKs columns, run the MFMA kernels (ob_heck_wide_kernel).
 constexpr int kHeckMaxKs = 8;
+constexpr int kHeckWideMaxKs = 32;
+// Slots of the selection means in the sums layout: 8 on the narrow path whatever ks, else ks.
+__host__ __device__ inline int heck_sel_slots(int ks) { return ks <= kHeckMaxKs ? kHeckMaxKs : ks; }
 // Values per (chunk, replicate) of the sums kernel for K = p + 1 outcome columns.
-__host__ __device__ inline int heck_sums_len(int k) { return 13 + k; }
+__host__ __device__ inline int heck_sums_len(int k, int ks) { return 5 + heck_sel_slots(ks) + k; }
 __host__ __device__ inline int heck_probit_len(int ks) { return ks * (ks + 1) / 2 + ks; }
 __host__ __device__ inline int heck_row_len(int k, int ks) { return 6 + 7 * (k + 1) + ks; }
-// Largest p the register-resident sums kernel takes (13 + K <= 64).
+// Largest p the register-resident sums kernel takes (13 + K <= 64); the wide path keeps it.
 constexpr int kHeckMaxP = 50;
 // Kernel timings of one segment (HIP events on the segment's stream).
 struct ob_heck_times {
@@ -64,4 +72,9 @@ struct ob_heck_times {
 // (after a stream sync) rows/ok are final. iters: the probit iterations run; tm (optional): the
 // kernel timings, added to.
 int heckman_segment(const ob_heck_seg& h, hipStream_t s, int* iters, ob_heck_times* tm = nullptr);
+// Values of `partial` per (chunk, replicate) that a segment of this shape needs.
+inline size_t heck_partial_len(int k, int ks) {
+  const int a = heck_probit_len(ks), b = heck_sums_len(k, ks);
+  return (size_t)(a > b ? a : b);
+}
 }  // namespace ob

@@ -26,7 +26,7 @@ constexpr Entry kNames[] = {
     {"gram_diag", ob::Opt::GramDiag},         {"l1_diag", ob::Opt::L1Diag},
     {"gram_tile", ob::Opt::GramTile},         {"debug_count_overflow", ob::Opt::DebugCountOverflow},
     {"rs_double", ob::Opt::RsDouble},         {"match_chunks", ob::Opt::MatchChunks},
-    {"akm_poll", ob::Opt::AkmPoll},
+    {"akm_poll", ob::Opt::AkmPoll},           {"hk_batch", ob::Opt::HkBatch},
 };
 static_assert(sizeof(kNames) / sizeof(kNames[0]) == (size_t)ob::Opt::Count, "one name per option");
 

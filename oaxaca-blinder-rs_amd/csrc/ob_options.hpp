@@ -41,6 +41,8 @@ enum class Opt : int {
                 // unset: the rule of match_knn, a function of the input sizes (results do not depend on it)
   AkmPoll,      // the AKM loops read their done flags every this many iterations (results and iteration
                 // counts do not depend on it); unset: kAkmPollDefault
+  HkBatch,      // the wide Heckman path (more than 7 selection predictors) runs a segment in batches of this
+                // many 64-replicate blocks (rows do not depend on it); unset: the rule of heck_batch
   Count
 };
 

@@ -285,6 +285,24 @@ def logit(y, x, max_iter: int = 100, tol: float = 1e-6, device: int | None = Non
     return beta, probs, bool(conv.value), int(iters.value)
 
 
+def probit(x, y, max_iter: int = 100, tol: float = 1e-6, device: int | None = None):
+    """math/probit.rs::probit with the Fisher-scoring passes on the GPU (``ob_probit``). ``x``: (n, k)
+    with the intercept (all ones) as column 0, ``k <= 32``; ``y``: the 0/1 outcome. Returns
+    (coefficients, converged, iterations); running out of iterations is not an error."""
+    xf = np.asfortranarray(x, dtype=np.float64)
+    if xf.ndim != 2:
+        raise ValueError("x must be (n, k)")
+    n, k = xf.shape
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.shape != (n,):
+        raise ValueError("y must have one entry per row of x")
+    beta = np.empty(k)
+    conv, iters = C.c_int32(0), C.c_int32(0)
+    N.check(N.lib().ob_probit(N.context(device), _dp(xf), max(n, 1), _dp(y), n, k, int(max_iter), float(tol),
+                              _dp(beta), C.byref(conv), C.byref(iters)))
+    return beta, bool(conv.value), int(iters.value)
+
+
 def knn(queries, controls, k: int, device: int | None = None):
     """The min(k, n_c) nearest controls of each query (``ob_knn``): squared Euclidean distance summed
     in covariate order without FMA, ties by control position. ``queries``: (n_q, d), ``controls``:
