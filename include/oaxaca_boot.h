@@ -957,6 +957,75 @@ int ob_remedy_apply_adjustments(const double* wage, const uint8_t* valid, int64_
 int ob_remedy_verify(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
                      const int64_t* index, const double* value, int64_t m, ob_results** out);
 
+/* ---- Jackknife influence pass and BCa bootstrap intervals (no reference counterpart: inference.rs:21-31 has
+ * floor-index percentile intervals only) ----------------------------------------------------------------
+ * The bias-corrected and accelerated interval needs the leave-one-out value theta_(i) of every component for
+ * every row. In closed form (Sherman-Morrison on the group's Gram) that is one streaming pass over the panel in
+ * HBM: per row of group g, t = G_g^-1 x on the f64 matrix units, h = w x't, e = y - x'beta_g, beta_g(i) =
+ * beta_g - t w e / (1 - h), the means (S_g - w x) / (W_g - w) (w = 1, W_g = n_g without weights), for Pooled /
+ * Neumark the same update of the pooled fit on [x, 1[g = A]] and for Weighted / Cotton the weights from W_g - w;
+ * the other group stays at its point estimate. The C = 6 + 2 K components are the first C columns of a
+ * replicate row (OB_ROW_EXPLAINED .. OB_ROW_TOTAL_GAP, detailed explained, detailed unexplained).
+ * A row is DROPPED, and counted per group, when the fit without it has no solution: 1 - h <= 2^-40 (for Pooled
+ * also 1 - h^P <= 2^-40) or W_g - w <= 0; this mirrors the reference dropping a replicate whose Cholesky fails.
+ * Sums are f64 in a fixed order (per-wave slots, ob_ordered_sum; no floating atomics), so a repeated call
+ * returns the same bytes.
+ * Limits, each OB_E_UNSUPPORTED before any device work: Heckman panels, n_norm > 0, n_y > 1, K >
+ * OB_JACK_MAX_K, the rows output above 2^24 rows. A group with n_g <= K + 1 is OB_E_INSUFFICIENT; a Cholesky
+ * failure of the point fit OB_E_LINALG. */
+#define OB_JACK_MAX_K 119 /* design columns, the intercept included: the pooled design's 120 fits the LDS shape */
+/* The limits above on their own (host only, needs no GPU): k design columns with the intercept; want_rows: the
+   rows output is asked for. Every jackknife entry point makes exactly these checks first. */
+int ob_jackknife_check_shape(int32_t k, int64_t n_a, int64_t n_b, int32_t n_norm, int32_t n_y, int32_t heckman,
+                             int32_t want_rows);
+typedef struct {
+  int32_t capacity;     /* in: components the caller's arrays hold; at least 6 + 2 ob_panel_k(panel) */
+  int32_t n_components; /* out: C */
+  int64_t n_used[2];    /* out: kept rows of A and of B */
+  int64_t n_dropped[2];
+  double* point;        /* caller's, [C]: the point estimate's components */
+  double* sums;         /* caller's, [2][C][3]: sum d, sum d^2, sum d^3 of d = theta_(i) - theta_hat per group */
+  double* stats;        /* caller's, [C][3]: accel, jack_se, jack_bias (ob_jackknife_finish) */
+} ob_jackknife_out;
+/* The production path: the power sums and the statistics; nothing of size n x C is stored. */
+int ob_jackknife(ob_panel* panel, int ref_mode, ob_jackknife_out* out);
+/* For tests and small panels: theta[(n_a + n_b) x C] row-major, A's rows first, and kept[n_a + n_b] (a dropped
+   row's theta is NaN). n_dropped[2] may be NULL. */
+int ob_jackknife_rows(ob_panel* panel, int ref_mode, double* theta, uint8_t* kept, int64_t* n_dropped);
+/* The calling thread's last ob_jackknife / ob_jackknife_rows (or a builder entry that ran one): HIP-event ms of
+   the pass with its reduce. */
+int ob_jackknife_last_timing(double* pass_ms);
+/* Host only. With m_g the kept rows of group g, dbar_g = sum d / m_g, U2_g = sum d^2 - m_g dbar_g^2 and U3_g =
+   -(sum d^3 - 3 dbar_g sum d^2 + 2 m_g dbar_g^3) (the power sums of u_gi = thetabar_g - theta_g(i)):
+   stats[c] = {accel = sum_g U3_g / (6 (sum_g U2_g)^1.5) or 0 where the denominator is 0,
+               jack_se = sqrt(sum_g (m_g - 1) / m_g U2_g), jack_bias = sum_g (m_g - 1) dbar_g}.
+   sums: [2][n_components][3]; a group with m_g = 0 adds nothing. */
+int ob_jackknife_finish(const double* sums, const int64_t* n_used, int32_t n_components, double* stats);
+/* The BCa interval of n replicate values. p0 = (#{v < point} + #{v = point} / 2) / n, z0 =
+   ob_normal_inverse_cdf(p0); for alpha in {(1 - level) / 2, 1 - (1 - level) / 2}: q = z0 +
+   ob_normal_inverse_cdf(alpha), alpha' = Phi(z0 + q / (1 - accel q)) with Phi(z) = erfc(-z / sqrt 2) / 2, endpoint
+   sorted[min(floor(alpha' n), n - 1)] (the index convention of inference.rs:25-31). out = {ci_lower, ci_upper,
+   z0, alpha'_lo, alpha'_hi, flag}; flag != 0 with NaN endpoints when n = 0 (1), p0 is 0 or 1 (2), accel is not
+   finite (3) or 1 - accel q <= 0 (4). level outside (0, 1) is OB_E_INVALID. Host only. */
+int ob_bca_stats(const double* estimates, int64_t n, double point_estimate, double accel, double level, double out[6]);
+/* ob_aggregate with one point estimate and one accel per column: out is n_cols x the six values above. */
+int ob_aggregate_bca(const double* rows, const uint8_t* ok, uint64_t n_reps, int32_t row_len, const int32_t* cols,
+                     int32_t n_cols, const double* point, const double* accel, double level, double* out);
+/* ob_jackknife on the prepared panel with its reference coefficients; the result is kept in the handle. */
+int ob_prepared_jackknife(ob_prepared* prep, ob_jackknife_out* out);
+/* ob_prepared_finish with ci_lower / ci_upper of every component replaced by the BCa endpoints at `level`
+   (estimate, std_err, t_stat and p_value are untouched). Runs ob_prepared_jackknife if the handle has none yet.
+   It reads only the aggregated columns, so rows of any boot serve, sharded ones included. A component that
+   pools several row columns (a repeated name) takes the accel of its own column. */
+int ob_prepared_finish_bca(ob_prepared* prep, const double* rows, const uint8_t* ok, uint64_t n_reps, double level,
+                           ob_results** out);
+/* ob_builder_run with BCa intervals: prepare + every replicate + the jackknife pass + ob_prepared_finish_bca. */
+int ob_builder_run_bca(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                       const ob_builder_config* cfg, double level, ob_results** out);
+/* out[5] = {accel, jack_se, jack_bias, z0, flag} of component i of a table of such a result. OB_E_INVALID on a
+   result without a jackknife (ob_prepared_finish, ob_builder_run) or for OB_TABLE_DETAILED_SELECTION. */
+int ob_results_jackknife(const ob_results* r, int32_t table, int32_t i, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,12 +7,13 @@ hyphen). See DESIGN.md for the kernels and INTEGRATION.md for the Rust/C binding
 from . import _native
 from ._native import OaxacaError
 from .api import (Adjustment, AkmBuilder, AkmResult, BudgetAdjustment, ComponentResult, Contribution, DataSummary,
-                  DecompositionDetail, DecompositionResult, DflResult, defensibility_message, parse_rust_f64, FrontierPoint, MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder,
+                  DecompositionDetail, DecompositionResult, DflResult, JackknifeResult, defensibility_message, parse_rust_f64, FrontierPoint, MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder,
                   OaxacaResults, OptimizationResult, PreparedRun,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
                   ReferenceCoefficients, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
                   parse_formula, run_dfl, run_dfl_from_csv)
-from .engine import (Panel, aggregate, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
+from .engine import (Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
+                     jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
                      knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
                      remedy_resolve_overrides, remedy_score, remedy_solve, rif,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
@@ -30,4 +31,6 @@ __all__ = [
     "OptimizationResult", "Adjustment", "Contribution", "FrontierPoint", "normal_inverse_cdf", "remedy_solve", "remedy_score",
     "remedy_allocate", "remedy_defend_rows", "remedy_resolve_overrides", "remedy_apply_adjustments",
     "DecompositionResult", "DataSummary", "defensibility_message", "parse_rust_f64",
+    "JackknifeResult", "jackknife_rows", "jackknife_finish", "jackknife_check_shape", "jackknife_last_timing", "bca_stats",
+    "aggregate_bca",
 ]

@@ -57,6 +57,9 @@ EXPORTED = (
     "ob_remedy_frontier",
     "ob_remedy_defend_rows", "ob_remedy_defend", "ob_remedy_resolve_overrides", "ob_remedy_results_defensible",
     "ob_remedy_results_defend_info", "ob_remedy_apply_adjustments", "ob_remedy_verify",
+    "ob_jackknife_check_shape", "ob_jackknife", "ob_jackknife_rows", "ob_jackknife_last_timing", "ob_jackknife_finish",
+    "ob_bca_stats", "ob_aggregate_bca", "ob_prepared_jackknife", "ob_prepared_finish_bca", "ob_builder_run_bca",
+    "ob_results_jackknife",
 )
 
 OB_E_CONVERGENCE = 12
@@ -66,6 +69,7 @@ OB_AKM_MAX_CONTROLS = 64
 OB_VIF_MAX_K = 120
 OB_REMEDY_MAX_K = 120  # design columns, the intercept included
 OB_REMEDY_MAX_STEPS = 127
+OB_JACK_MAX_K = 119  # design columns, the intercept included
 OB_REMEDY_TARGETS = {"reference": 0, "pooled": 1}
 OB_REMEDY_STRATEGIES = {"greedy": 0, "equitable": 1}
 OB_REMEDY_RANGE_TARGETS = {"midpoint": 0, "lower": 1, "upper": 2}
@@ -198,6 +202,12 @@ class ob_defend_info(C.Structure):
                 ("gram_ms", C.c_double), ("score_ms", C.c_double), ("defend_ms", C.c_double),
                 ("scatter_ms", C.c_double), ("adjust_ms", C.c_double), ("rows_ms", C.c_double),
                 ("sums", C.c_double * 7)]
+
+
+class ob_jackknife_out(C.Structure):
+    _fields_ = [("capacity", C.c_int32), ("n_components", C.c_int32), ("n_used", C.c_int64 * 2),
+                ("n_dropped", C.c_int64 * 2), ("point", C.POINTER(C.c_double)), ("sums", C.POINTER(C.c_double)),
+                ("stats", C.POINTER(C.c_double))]
 
 
 class ob_component(C.Structure):
@@ -369,6 +379,19 @@ _SIGS = {
     "ob_remedy_apply_adjustments": (C.c_int, [_D, _U8, C.c_int64, C.POINTER(C.c_int64), _D, C.c_int64, _D]),
     "ob_remedy_verify": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
                                    C.POINTER(C.c_int64), _D, C.c_int64, C.POINTER(_P)]),
+    "ob_jackknife_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ob_jackknife": (C.c_int, [_P, C.c_int, C.POINTER(ob_jackknife_out)]),
+    "ob_jackknife_rows": (C.c_int, [_P, C.c_int, _D, _U8, C.POINTER(C.c_int64)]),
+    "ob_jackknife_last_timing": (C.c_int, [_D]),
+    "ob_jackknife_finish": (C.c_int, [_D, C.POINTER(C.c_int64), C.c_int32, _D]),
+    "ob_bca_stats": (C.c_int, [_D, C.c_int64, C.c_double, C.c_double, C.c_double, _D]),
+    "ob_aggregate_bca": (C.c_int, [_D, _U8, C.c_uint64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _D, _D, C.c_double,
+                                   _D]),
+    "ob_prepared_jackknife": (C.c_int, [_P, C.POINTER(ob_jackknife_out)]),
+    "ob_prepared_finish_bca": (C.c_int, [_P, _D, _U8, C.c_uint64, C.c_double, C.POINTER(_P)]),
+    "ob_builder_run_bca": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
+                                     C.c_double, C.POINTER(_P)]),
+    "ob_results_jackknife": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
 }
 
 _lib = None

@@ -48,6 +48,21 @@ class ComponentResult:
 
 
 @dataclass
+class JackknifeResult:
+    """The leave-one-out pass over the panel: one entry per component, in the order of a
+    replicate row's first 6 + 2K columns. ``names``: explained, unexplained, endowments, coefficients,
+    interaction, total_gap, then ``explained:<column>`` and ``unexplained:<column>`` per design column."""
+    names: list
+    estimate: np.ndarray
+    accel: np.ndarray
+    std_err: np.ndarray
+    bias: np.ndarray
+    n_used: tuple
+    n_dropped: tuple
+    sums: np.ndarray = field(repr=False, default=None)
+
+
+@dataclass
 class TwoFoldResults:
     aggregate: list
     detailed_explained: list
@@ -195,6 +210,7 @@ class OaxacaResults:
     xb_mean: np.ndarray = field(repr=False)
     beta_star: np.ndarray = field(repr=False)
     n_failed: int = 0
+    jackknife: dict = None  # run_bca / finish_bca: (table, name) -> {accel, std_err, bias, z0, flag}
 
     def explained(self):
         return next((c for c in self.two_fold.aggregate if c.name == "explained"), None)
@@ -280,8 +296,45 @@ class OaxacaResults:
                 f"endowments (observables), while {u / t * 100:.1f}% is unexplained (coefficients/discrimination).")
 
 
-def _results_from_c(handle) -> OaxacaResults:
+def _jackknife_out(k: int):
+    c = 6 + 2 * k
+    bufs = (np.zeros(c), np.zeros((2, c, 3)), np.zeros((c, 3)))
+    o = N.ob_jackknife_out()
+    o.capacity = c
+    o.point, o.sums, o.stats = (b.ctypes.data_as(C.POINTER(C.c_double)) for b in bufs)
+    return o, bufs
+
+
+def _jackknife_result(o, bufs, names) -> JackknifeResult:
+    k = (o.n_components - 6) // 2
+    names = list(names) if names else [f"x{j}" for j in range(k)]
+    full = (["explained", "unexplained", "endowments", "coefficients", "interaction", "total_gap"]
+            + [f"explained:{n}" for n in names] + [f"unexplained:{n}" for n in names])
+    point, sums, stats = bufs
+    return JackknifeResult(full, point.copy(), stats[:, 0].copy(), stats[:, 1].copy(), stats[:, 2].copy(),
+                           (int(o.n_used[0]), int(o.n_used[1])), (int(o.n_dropped[0]), int(o.n_dropped[1])),
+                           sums.copy())
+
+
+_JACK_TABLES = {"two_fold": N.OB_TABLE_TWO_FOLD, "three_fold": N.OB_TABLE_THREE_FOLD,
+                "detailed_explained": N.OB_TABLE_DETAILED_EXPLAINED,
+                "detailed_unexplained": N.OB_TABLE_DETAILED_UNEXPLAINED}
+
+
+def _results_from_c(handle, jackknife: bool = False) -> OaxacaResults:
     lib = N.lib()
+
+    def jack():
+        out = {}
+        for tname, t in _JACK_TABLES.items():
+            for i in range(lib.ob_results_count(handle, t)):
+                c = N.ob_component()
+                N.check(lib.ob_results_component(handle, t, i, C.byref(c)))
+                v = (C.c_double * 5)()
+                N.check(lib.ob_results_jackknife(handle, t, i, v))
+                out[(tname, c.name.decode())] = {"accel": v[0], "std_err": v[1], "bias": v[2], "z0": v[3],
+                                                 "flag": int(v[4])}
+        return out
 
     def table(t):
         out = []
@@ -306,7 +359,8 @@ def _results_from_c(handle) -> OaxacaResults:
             three_fold=DecompositionDetail(table(N.OB_TABLE_THREE_FOLD), []),
             n_a=int(lib.ob_results_n_a(handle)), n_b=int(lib.ob_results_n_b(handle)),
             residuals=vec(N.OB_VEC_RESIDUALS), xa_mean=vec(N.OB_VEC_XA_MEAN), xb_mean=vec(N.OB_VEC_XB_MEAN),
-            beta_star=vec(N.OB_VEC_BETA_STAR), n_failed=int(lib.ob_results_n_failed(handle)))
+            beta_star=vec(N.OB_VEC_BETA_STAR), n_failed=int(lib.ob_results_n_failed(handle)),
+            jackknife=jack() if jackknife else None)
     finally:
         lib.ob_results_free(handle)
 
@@ -685,6 +739,27 @@ class OaxacaBuilder:
         N.check(lib.ob_builder_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
         return _results_from_c(h)
 
+    def run_bca(self, confidence_level: float = 0.95) -> OaxacaResults:
+        """``run()`` with every component's interval replaced by the bias-corrected and accelerated (BCa)
+        one: z0 from the replicates, the acceleration from one leave-one-out pass over the panel. Estimates,
+        standard errors and p-values are those of ``run()`` with the same seed; ``.jackknife`` holds, per
+        (table, name), the acceleration, the jackknife standard error and bias, z0 and the BCa flag."""
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        h = C.c_void_p()
+        N.check(lib.ob_builder_run_bca(N.context(self._device), cols, ncol, nrow, C.byref(cfg),
+                                       float(confidence_level), C.byref(h)))
+        return _results_from_c(h, jackknife=True)
+
+    def jackknife(self) -> "JackknifeResult":
+        """The leave-one-out pass alone: acceleration, jackknife standard error and bias of every component."""
+        pr = self.prepare()
+        try:
+            return pr.jackknife()
+        finally:
+            pr.close()
+
     def decompose_quantile(self, quantile: float) -> OaxacaResults:
         """builder.rs:711-757: RIF-regression decomposition at ``quantile``."""
         lib = N.lib()
@@ -773,6 +848,23 @@ class PreparedRun:
         N.check(N.lib().ob_prepared_finish(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
                                            ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
         return _results_from_c(h)
+
+    def jackknife(self) -> "JackknifeResult":
+        """ob_prepared_jackknife: the leave-one-out pass over the resident panel (kept in the handle)."""
+        panel = N.lib().ob_prepared_panel(self._h)
+        o, bufs = _jackknife_out(N.lib().ob_panel_k(panel))
+        N.check(N.lib().ob_prepared_jackknife(self._h, C.byref(o)))
+        return _jackknife_result(o, bufs, None)
+
+    def finish_bca(self, rows: np.ndarray, ok: np.ndarray, confidence_level: float = 0.95) -> OaxacaResults:
+        """``finish`` with BCa intervals (ob_prepared_finish_bca); rows of ``boot`` or ``boot_sharded``."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        h = C.c_void_p()
+        N.check(N.lib().ob_prepared_finish_bca(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                               ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok),
+                                               float(confidence_level), C.byref(h)))
+        return _results_from_c(h, jackknife=True)
 
     def close(self):
         if self._h:

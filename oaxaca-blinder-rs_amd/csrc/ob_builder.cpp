@@ -25,25 +25,12 @@
 #include "ob_engine.hpp"
 #include "ob_frame.hpp"
 #include "ob_host.hpp"
+#include "ob_builder.hpp"
 #include "ob_mm.hpp"
 #include "ob_spec.h"
 
 namespace ob {
 
-struct Config {
-  std::string outcome, group, reference_group;
-  std::vector<std::string> outcomes;  // RIF multi-tau: y columns of one panel (empty: {outcome})
-  std::vector<std::string> predictors, categorical, normalize;
-  bool has_weights = false;
-  std::string weights;
-  bool has_selection = false;
-  std::string selection;
-  std::vector<std::string> selection_predictors;
-  uint64_t reps = 20;
-  int ref = OB_REF_GROUP_A;
-  bool has_seed = false;
-  uint64_t seed = 0;
-};
 
 const char* dtype_name(int kind) {
   switch (kind) {
@@ -119,7 +106,7 @@ static Frame take(const Frame& f, const std::vector<int64_t>& rows) {
   return o;
 }
 
-static int config_from(const ob_builder_config* c, Config& out) {
+int config_from(const ob_builder_config* c, Config& out) {
   if (!c || !c->outcome || !c->group || !c->reference_group) return fail(OB_E_INVALID, "incomplete builder config");
   out.outcome = c->outcome;
   out.group = c->group;
@@ -343,32 +330,7 @@ static bool starts_with(const std::string& s, const std::string& pre) {
 // ---------------------------------------------------------------------------------------------
 // prepared run: panel in HBM + point estimate; boot ranges; aggregation
 // ---------------------------------------------------------------------------------------------
-struct ob_results {
-  double total_gap = 0.0;
-  int64_t n_a = 0, n_b = 0, n_failed = 0;
-  struct Comp {
-    std::string name;
-    double estimate, std_err, t_stat, p_value, ci_lower, ci_upper;
-  };
-  std::vector<Comp> tables[5];
-  std::vector<double> residuals, xa_mean, xb_mean, beta_star;
-};
 
-struct ob_prepared {
-  ob_ctx* ctx = nullptr;
-  ob_panel* panel = nullptr;
-  ob::Config cfg;
-  int ref = OB_REF_GROUP_A;
-  uint64_t seed = 0;
-  int k = 0, n_base = 0, row_len = 0;
-  std::vector<std::string> names;         // K final predictor names
-  std::vector<std::string> detail_names;  // K + n_base (base categories appended)
-  std::vector<double> point_row, resid_b;  // n_y x row_len, n_y x n_b
-  int64_t n_a = 0, n_b = 0;
-  int n_y = 1;
-  int64_t n_resid = 0;                     // residuals per outcome: n_b, or B's selected rows (Heckman)
-  std::vector<std::string> selection_names;  // Heckman: intercept + selection predictors
-};
 
 struct ob_matrices {
   int64_t n_a = 0, n_b = 0;
@@ -384,7 +346,7 @@ static uint64_t fresh_seed() {
   return ((uint64_t)rd() << 32) ^ (uint64_t)rd();
 }
 
-static int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out) {
+int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out) {
   const bool heck = c.has_selection;
   if (heck && (c.ref == OB_REF_POOLED || c.ref == OB_REF_NEUMARK))
     return fail(OB_E_UNSUPPORTED,
@@ -522,8 +484,7 @@ static int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared
 }
 
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block).
-static int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps,
-                  ob_results** out) {
+int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
   const int k = pr->k, kd = k + pr->n_base, rl = pr->row_len;
   const double* point_row = pr->point_row.data() + (size_t)t_out * rl;
   uint64_t ng = 0;

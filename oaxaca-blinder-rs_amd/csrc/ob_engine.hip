@@ -1761,6 +1761,7 @@ int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_
   const size_t o_gout = o_row + n_row, n_gout = (size_t)2 * p->e_pad;
   const size_t o_beta = o_gout + n_gout, n_beta = (size_t)p->k * p->n_y;
   const size_t o_res = o_beta + n_beta, n_res = std::max<uint32_t>(p->n[1], 1);
+  p->pe_gram_ready = false;
   OB_TRY(ensure_buf(&p->d_pe, p->cap_pe, o_res + (resid_b ? n_res : 0)));
   OB_TRY(ensure_buf(&p->d_pe_ok, p->cap_pe_ok, (size_t)std::max(p->n_y, 1)));
   double* d_gram = p->d_pe + o_gram;
@@ -1850,6 +1851,8 @@ int engine_point_estimate(ob_panel* p, int ref_mode, double* row, double* resid_
                     "%sFailed to perform Cholesky decomposition. Matrix may be singular or not positive "
                     "definite due to multicollinearity.",
                     error_prefix(OB_E_LINALG));
+  p->pe_gram_off = o_gout;
+  p->pe_gram_ready = true;
   return OB_OK;
 }
 

@@ -66,6 +66,8 @@ struct ob_panel {
   double* d_pe = nullptr;        // point estimate scratch (unit-Gram partials, Gram, rows, beta, residuals)
   uint8_t* d_pe_ok = nullptr;
   size_t cap_pe = 0, cap_pe_ok = 0;
+  size_t pe_gram_off = 0;        // where the last point estimate left its two extended Grams in d_pe
+  bool pe_gram_ready = false;    // (2 x e_pad doubles, the first outcome's; ob_jackknife.hip reads them)
 
   double* d_hgamma = nullptr;     // Heckman: [2][rep_pad][ks] probit coefficients
   uint32_t* d_hflags = nullptr;   // Heckman: [2][rep_pad] done / failed

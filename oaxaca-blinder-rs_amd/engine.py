@@ -95,6 +95,23 @@ class Panel:
             res = None if res is None else res[0]
         return (row, res) if residuals else row
 
+    def jackknife(self, ref=ReferenceCoefficients.GroupA):
+        """ob_jackknife: the leave-one-out pass's power sums and statistics (api.JackknifeResult)."""
+        from .api import _jackknife_out, _jackknife_result
+
+        o, bufs = _jackknife_out(self.k)
+        N.check(N.lib().ob_jackknife(self._h, int(ref), C.byref(o)))
+        return _jackknife_result(o, bufs, None)
+
+    def jackknife_rows(self, ref=ReferenceCoefficients.GroupA):
+        """ob_jackknife_rows -> (theta (n_a + n_b, 6 + 2K), kept, n_dropped (A, B))."""
+        c = 6 + 2 * self.k
+        theta = np.empty((self.n_a + self.n_b, c))
+        kept = np.zeros(self.n_a + self.n_b, dtype=np.uint8)
+        nd = (C.c_int64 * 2)()
+        N.check(N.lib().ob_jackknife_rows(self._h, int(ref), _dp(theta), kept.ctypes.data_as(C.POINTER(C.c_uint8)), nd))
+        return theta, kept, (int(nd[0]), int(nd[1]))
+
     def boot(self, seed: int, first_rep: int, n_reps: int, ref=ReferenceCoefficients.GroupA):
         rows = np.empty((self.n_y, n_reps, self.row_len))
         ok = np.zeros((self.n_y, n_reps), dtype=np.uint8)
@@ -255,6 +272,60 @@ def aggregate(rows, ok, cols):
     out = np.empty((len(cols), 4))
     N.check(N.lib().ob_aggregate(_dp(rows), ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), rows.shape[1],
                                  _ip(cols), len(cols), _dp(out)))
+    return out
+
+
+def jackknife_rows(xa, ya, wa, xb, yb, wb, ref_mode=ReferenceCoefficients.GroupA, n_num=None, device=None):
+    """theta_(i) of every row (A's first) for predictor-only designs xa, xb -> (theta, kept, n_dropped)."""
+    panel = Panel(xa, ya, xb, yb, wa, wb, n_num=n_num, device=device)
+    try:
+        return panel.jackknife_rows(ref_mode)
+    finally:
+        panel.close()
+
+
+def jackknife_last_timing() -> float:
+    ms = C.c_double()
+    N.check(N.lib().ob_jackknife_last_timing(C.byref(ms)))
+    return ms.value
+
+
+def jackknife_check_shape(k: int, n_a: int, n_b: int, n_norm: int = 0, n_y: int = 1, heckman: bool = False,
+                          want_rows: bool = False) -> None:
+    """ob_jackknife_check_shape: raises OaxacaError where the jackknife entry points would (host only)."""
+    N.check(N.lib().ob_jackknife_check_shape(k, n_a, n_b, n_norm, n_y, int(heckman), int(want_rows)))
+
+
+def jackknife_finish(sums, n_used):
+    """ob_jackknife_finish: sums (2, C, 3), n_used (2,) -> (C, 3) = accel, jack_se, jack_bias."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    if sums.ndim != 3 or sums.shape[0] != 2 or sums.shape[2] != 3:
+        raise ValueError("sums must be (2, C, 3)")
+    m = (C.c_int64 * 2)(int(n_used[0]), int(n_used[1]))
+    out = np.zeros((sums.shape[1], 3))
+    N.check(N.lib().ob_jackknife_finish(_dp(sums), m, sums.shape[1], _dp(out)))
+    return out
+
+
+def bca_stats(estimates, point: float, accel: float, level: float = 0.95) -> dict:
+    """ob_bca_stats -> dict(ci_lower, ci_upper, z0, alpha_lo, alpha_hi, flag)."""
+    v = np.ascontiguousarray(estimates, dtype=np.float64)
+    out = np.zeros(6)
+    N.check(N.lib().ob_bca_stats(_dp(v), len(v), float(point), float(accel), float(level), _dp(out)))
+    return {"ci_lower": out[0], "ci_upper": out[1], "z0": out[2], "alpha_lo": out[3], "alpha_hi": out[4],
+            "flag": int(out[5])}
+
+
+def aggregate_bca(rows, ok, cols, point, accel, level: float = 0.95):
+    """ob_aggregate_bca -> (len(cols), 6)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    point = np.ascontiguousarray(point, dtype=np.float64)
+    accel = np.ascontiguousarray(accel, dtype=np.float64)
+    out = np.zeros((len(cols), 6))
+    N.check(N.lib().ob_aggregate_bca(_dp(rows), ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), rows.shape[1],
+                                     _ip(cols), len(cols), _dp(point), _dp(accel), float(level), _dp(out)))
     return out
 
 
