@@ -1026,6 +1026,80 @@ int ob_builder_run_bca(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64
    result without a jackknife (ob_prepared_finish, ob_builder_run) or for OB_TABLE_DETAILED_SELECTION. */
 int ob_results_jackknife(const ob_results* r, int32_t table, int32_t i, double* out);
 
+/* ---- Cluster bootstrap (no reference counterpart: builder.rs:822-827 resamples rows) -------------------
+ * The row bootstrap assumes independent rows within a group. For panels whose rows are nested in clusters
+ * (workers with repeated observations, employees in firms) a replicate resamples whole clusters instead, the
+ * counterpart of Stata's `bootstrap, cluster()`. The extended Gram is linear in the cluster counts,
+ *     G_r[g] = sum_c k[r][c] Q[c][g],   Q[c][g] = sum over the rows i of cluster c in group g of v_i v_i',
+ * with v_i the engine's row vector (sqrt(w) [1, x, y] weighted, [1, x, y] otherwise). One pass forms Q
+ * (ob_cluster_gram), an exact multinomial draws k (ob_cluster_counts, the OBRC-1 stream of ob_spec.h) and an
+ * f64 GEMM forms counts x Q (ob_cluster_apply) in the [rep][2][e_pad] layout the solve reads, together with
+ * each replicate's row count per group; beta, beta*, normalization, the row layout, ob_prepared_finish and
+ * ob_aggregate are the row bootstrap's. The point estimate does not change. A replicate in which a group
+ * has rows <= K is dropped (ok = 0, the reference's InsufficientData).
+ * Cluster ids: after clean_dataframe (a null in the cluster column drops the row) and the group split, the
+ * column's values over the rows of groups A and B become dense ids 0 .. C-1 in order of first appearance.
+ * The column is a string or an integer column; a float column is OB_E_INVALID.
+ * Modes: joint (stratified = 0): one multinomial of C draws over all C clusters, shared by both groups.
+ * stratified: C_A draws over A's clusters and C_B over B's, independently; every cluster must lie in exactly
+ * one group (OB_E_INVALID naming the first that does not) and A's clusters are renumbered to [0, C_A).
+ * Every sum is f64 in a fixed order that depends on the cluster sizes and on C alone: a replicate's row has
+ * the same bytes alone, in any batch and at any first_rep.
+ * Limits, each before any device work: C < 2 OB_E_INSUFFICIENT; C >= 2^24, or Q above 8 GiB
+ * (C * 2 * (e_pad + 1) doubles): OB_E_UNSUPPORTED; Heckman selection, ob_prepared_boot_sharded,
+ * ob_prepared_jackknife, ob_prepared_finish_bca on a clustered handle: OB_E_UNSUPPORTED (delete-one-row is
+ * the wrong jackknife under clustering). Machado-Mata has no clustered entry point. */
+typedef struct {
+  const char* column; /* the cluster id column */
+  int32_t stratified; /* 0: joint, 1: stratified */
+} ob_cluster_config;
+typedef struct {
+  int64_t n_clusters, n_clusters_a, n_clusters_b; /* C; clusters with rows in A / in B */
+  int64_t max_cluster_rows;                       /* rows of the largest cluster (both groups together) */
+  int32_t stratified;
+} ob_cluster_info;
+typedef struct {
+  double gram_ms, counts_ms, apply_ms, solve_ms;
+} ob_cluster_timing;
+/* The size limits above on their own (host only): C clusters, k1 = P + 1 + n_y columns of v. */
+int ob_cluster_check_shape(int64_t n_clusters, int32_t k1);
+/* Host only. ids: one column over n_rows frame rows; group[r] = 0 (A), 1 (B), anything else: the row is in
+   neither. A null id drops the row. dense[n_rows]: the row's cluster id or -1. perm_a / perm_b (as long as the
+   groups' kept rows; n_rows each is always enough): the group's kept rows, as positions among them in frame
+   order, sorted stably by cluster id. off_a / off_b [C + 1] (n_rows + 1 each is always enough): cluster c's
+   rows of the group are perm[off[c] .. off[c + 1]). Any output may be NULL. */
+int ob_cluster_index(const ob_column* ids, const int32_t* group, int64_t n_rows, int32_t stratified, int32_t* dense,
+                     int64_t* perm_a, int64_t* perm_b, int64_t* off_a, int64_t* off_b, ob_cluster_info* info);
+/* Q of one group: x (n x p, column-major, ldx), y[n], w[n] or NULL; perm[n] / off[C + 1] as above. q: [C][e_pad]
+   with e_pad = 16 ceil(E / 16), E = (p + 2)(p + 3) / 2 pairs in ob_spec.h's order; rows[C]: the clusters' row
+   counts. Rows go in permuted order in pieces of 256, the pieces are added in order. */
+int ob_cluster_gram(ob_ctx* ctx, const double* x, int64_t n, int64_t ldx, int32_t p, const double* y, const double* w,
+                    const int64_t* perm, const int64_t* off, int64_t n_clusters, double* q, uint32_t* rows);
+/* counts[n_reps][C] (C = n_clusters_a + n_clusters_b) of replicates first_rep .. first_rep + n_reps - 1 from
+   OBRC-1. Joint: C draws over [0, C). Stratified: n_clusters_a draws over [0, C_A), n_clusters_b over the rest. */
+int ob_cluster_counts(ob_ctx* ctx, uint64_t seed, uint64_t first_rep, uint32_t n_reps, int64_t n_clusters_a,
+                      int64_t n_clusters_b, int32_t stratified, uint32_t* counts);
+/* out[n_reps][width] = counts[n_reps][C] (exact in f64) x q[C][width] on the f64 matrix units; width a multiple
+   of 16. C is walked in cluster order in runs of 8192 whose partial sums are added in order. */
+int ob_cluster_apply(ob_ctx* ctx, const uint32_t* counts, uint32_t n_reps, int64_t n_clusters, const double* q,
+                     int32_t width, double* out);
+/* The calling thread's last clustered boot (ob_prepared_boot, ob_builder_run_clustered): HIP-event ms. gram_ms is
+   the one pass that forms Q, charged to the call that ran it. */
+int ob_cluster_last_timing(ob_cluster_timing* out);
+/* ob_builder_prepare / ob_builder_run / ob_builder_decompose_quantiles with the cluster bootstrap. A handle
+   prepared this way routes ob_prepared_boot, ob_prepared_boot_device and ob_prepared_finish through it. */
+int ob_builder_prepare_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                 const ob_builder_config* cfg, const ob_cluster_config* ccfg, ob_prepared** out);
+int ob_builder_run_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                             const ob_builder_config* cfg, const ob_cluster_config* ccfg, ob_results** out);
+int ob_builder_decompose_quantiles_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                             const ob_builder_config* cfg, const ob_cluster_config* ccfg,
+                                             const double* taus, int32_t n_taus, ob_results** out);
+/* C of the clustered run behind a result, -1 for a row bootstrap's. */
+int64_t ob_results_n_clusters(const ob_results* r);
+/* OB_E_INVALID on a handle that is not clustered. */
+int ob_prepared_cluster_info(const ob_prepared* prep, ob_cluster_info* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ from .api import (Adjustment, AkmBuilder, AkmResult, BudgetAdjustment, Component
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
                   ReferenceCoefficients, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
                   parse_formula, run_dfl, run_dfl_from_csv)
-from .engine import (Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
+from .engine import (cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
+                     cluster_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
                      knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
                      remedy_resolve_overrides, remedy_score, remedy_solve, rif,
@@ -33,4 +34,5 @@ __all__ = [
     "DecompositionResult", "DataSummary", "defensibility_message", "parse_rust_f64",
     "JackknifeResult", "jackknife_rows", "jackknife_finish", "jackknife_check_shape", "jackknife_last_timing", "bca_stats",
     "aggregate_bca",
+    "cluster_index", "cluster_gram", "cluster_counts", "cluster_apply", "cluster_check_shape", "cluster_last_timing",
 ]

@@ -60,6 +60,9 @@ EXPORTED = (
     "ob_jackknife_check_shape", "ob_jackknife", "ob_jackknife_rows", "ob_jackknife_last_timing", "ob_jackknife_finish",
     "ob_bca_stats", "ob_aggregate_bca", "ob_prepared_jackknife", "ob_prepared_finish_bca", "ob_builder_run_bca",
     "ob_results_jackknife",
+    "ob_cluster_check_shape", "ob_cluster_index", "ob_cluster_gram", "ob_cluster_counts", "ob_cluster_apply",
+    "ob_cluster_last_timing", "ob_builder_prepare_clustered", "ob_builder_run_clustered",
+    "ob_builder_decompose_quantiles_clustered", "ob_prepared_cluster_info", "ob_results_n_clusters",
 )
 
 OB_E_CONVERGENCE = 12
@@ -208,6 +211,20 @@ class ob_jackknife_out(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("n_components", C.c_int32), ("n_used", C.c_int64 * 2),
                 ("n_dropped", C.c_int64 * 2), ("point", C.POINTER(C.c_double)), ("sums", C.POINTER(C.c_double)),
                 ("stats", C.POINTER(C.c_double))]
+
+
+class ob_cluster_config(C.Structure):
+    _fields_ = [("column", C.c_char_p), ("stratified", C.c_int32)]
+
+
+class ob_cluster_info(C.Structure):
+    _fields_ = [("n_clusters", C.c_int64), ("n_clusters_a", C.c_int64), ("n_clusters_b", C.c_int64),
+                ("max_cluster_rows", C.c_int64), ("stratified", C.c_int32)]
+
+
+class ob_cluster_timing(C.Structure):
+    _fields_ = [("gram_ms", C.c_double), ("counts_ms", C.c_double), ("apply_ms", C.c_double),
+                ("solve_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -392,6 +409,26 @@ _SIGS = {
     "ob_builder_run_bca": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
                                      C.c_double, C.POINTER(_P)]),
     "ob_results_jackknife": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
+    "ob_cluster_check_shape": (C.c_int, [C.c_int64, C.c_int32]),
+    "ob_cluster_index": (C.c_int, [C.POINTER(ob_column), C.POINTER(C.c_int32), C.c_int64, C.c_int32,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(ob_cluster_info)]),
+    "ob_cluster_gram": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, _D, _D, C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64), C.c_int64, _D, C.POINTER(C.c_uint32)]),
+    "ob_cluster_counts": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int64, C.c_int64, C.c_int32,
+                                    C.POINTER(C.c_uint32)]),
+    "ob_cluster_apply": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_uint32, C.c_int64, _D, C.c_int32, _D]),
+    "ob_cluster_last_timing": (C.c_int, [C.POINTER(ob_cluster_timing)]),
+    "ob_builder_prepare_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                               C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config),
+                                               C.POINTER(_P)]),
+    "ob_builder_run_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                           C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config), C.POINTER(_P)]),
+    "ob_builder_decompose_quantiles_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                           C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config),
+                                                           _D, C.c_int32, C.POINTER(_P)]),
+    "ob_prepared_cluster_info": (C.c_int, [_P, C.POINTER(ob_cluster_info)]),
+    "ob_results_n_clusters": (C.c_int64, [_P]),
 }
 
 _lib = None

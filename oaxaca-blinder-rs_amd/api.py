@@ -211,6 +211,7 @@ class OaxacaResults:
     beta_star: np.ndarray = field(repr=False)
     n_failed: int = 0
     jackknife: dict = None  # run_bca / finish_bca: (table, name) -> {accel, std_err, bias, z0, flag}
+    n_clusters: int = None  # a cluster bootstrap's C (OaxacaBuilder.cluster), else None
 
     def explained(self):
         return next((c for c in self.two_fold.aggregate if c.name == "explained"), None)
@@ -263,6 +264,8 @@ class OaxacaResults:
             "n_b": self.n_b,
             "residuals": [fix(float(v)) for v in self.residuals],
         }
+        if self.n_clusters is not None:  # absent without clustering: the JSON of a row bootstrap is unchanged
+            d["n_clusters"] = self.n_clusters
         return json.dumps(d)
 
     def summary(self) -> str:
@@ -352,7 +355,9 @@ def _results_from_c(handle, jackknife: bool = False) -> OaxacaResults:
         return np.ctypeslib.as_array(ptr, shape=(n.value,)).copy() if n.value else np.zeros(0)
 
     try:
+        nc = int(lib.ob_results_n_clusters(handle))
         return OaxacaResults(
+            n_clusters=None if nc < 0 else nc,
             total_gap=lib.ob_results_total_gap(handle),
             two_fold=TwoFoldResults(table(N.OB_TABLE_TWO_FOLD), table(N.OB_TABLE_DETAILED_EXPLAINED),
                                     table(N.OB_TABLE_DETAILED_UNEXPLAINED), table(N.OB_TABLE_DETAILED_SELECTION)),
@@ -412,6 +417,8 @@ class OaxacaBuilder:
         self._seed: int | None = None
         self._device: int | None = None
         self._ctx = None  # an explicit ob_ctx (distributed.fit_sharded's rank context)
+        self._cluster: str | None = None
+        self._cluster_stratified = False
 
     @classmethod
     def from_formula(cls, dataframe, formula: str, group: str, reference_group: str):
@@ -443,6 +450,26 @@ class OaxacaBuilder:
     def weights(self, name: str):
         self._weights = name
         return self
+
+    def cluster(self, column: str | None, stratified: bool = False):
+        """Extension: resample whole clusters (the values of ``column``, strings or integers) instead of rows
+        in ``run()``, ``prepare()``, ``decompose_quantile(s)``: Stata's ``bootstrap, cluster()``. Joint mode
+        draws C clusters from all C, both groups sharing the counts; ``stratified=True`` draws C_A from group
+        A's clusters and C_B from B's (every cluster must lie in one group). Point estimates do not change."""
+        self._cluster = None if column is None else str(column)
+        self._cluster_stratified = bool(stratified)
+        return self
+
+    def _cluster_config(self):
+        cc = N.ob_cluster_config()
+        cc.column = self._cluster.encode()
+        cc.stratified = 1 if self._cluster_stratified else 0
+        return cc
+
+    def _refuse_clustered(self, what: str):
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, f"cluster bootstrap: {what} is outside its scope "
+                                                    "(delete-one-row is the wrong jackknife under clustering)")
 
     def heckman_selection(self, outcome: str, predictors):
         self._selection = outcome
@@ -736,6 +763,11 @@ class OaxacaBuilder:
         cols, ncol, nrow = self._frame.as_c()
         cfg, keep = self._config()
         h = C.c_void_p()
+        if self._cluster is not None:
+            cc = self._cluster_config()
+            N.check(lib.ob_builder_run_clustered(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(cc),
+                                                 C.byref(h)))
+            return _results_from_c(h)
         N.check(lib.ob_builder_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
         return _results_from_c(h)
 
@@ -744,6 +776,7 @@ class OaxacaBuilder:
         one: z0 from the replicates, the acceleration from one leave-one-out pass over the panel. Estimates,
         standard errors and p-values are those of ``run()`` with the same seed; ``.jackknife`` holds, per
         (table, name), the acceleration, the jackknife standard error and bias, z0 and the BCa flag."""
+        self._refuse_clustered("run_bca")
         lib = N.lib()
         cols, ncol, nrow = self._frame.as_c()
         cfg, keep = self._config()
@@ -754,6 +787,7 @@ class OaxacaBuilder:
 
     def jackknife(self) -> "JackknifeResult":
         """The leave-one-out pass alone: acceleration, jackknife standard error and bias of every component."""
+        self._refuse_clustered("jackknife")
         pr = self.prepare()
         try:
             return pr.jackknife()
@@ -766,6 +800,8 @@ class OaxacaBuilder:
         cols, ncol, nrow = self._frame.as_c()
         cfg, keep = self._config()
         h = C.c_void_p()
+        if self._cluster is not None:
+            return self.decompose_quantiles([float(quantile)])[0]
         N.check(lib.ob_builder_decompose_quantile(N.context(self._device), cols, ncol, nrow, C.byref(cfg),
                                                   float(quantile), C.byref(h)))
         return _results_from_c(h)
@@ -781,6 +817,12 @@ class OaxacaBuilder:
         cols, ncol, nrow = self._frame.as_c()
         cfg, keep = self._config()
         hs = (C.c_void_p * taus.size)()
+        if self._cluster is not None:
+            cc = self._cluster_config()
+            N.check(lib.ob_builder_decompose_quantiles_clustered(
+                N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(cc),
+                taus.ctypes.data_as(C.POINTER(C.c_double)), int(taus.size), C.cast(hs, C.POINTER(C.c_void_p))))
+            return [_results_from_c(C.c_void_p(h)) for h in hs]
         N.check(lib.ob_builder_decompose_quantiles(N.context(self._device), cols, ncol, nrow, C.byref(cfg),
                                                    taus.ctypes.data_as(C.POINTER(C.c_double)), int(taus.size),
                                                    C.cast(hs, C.POINTER(C.c_void_p))))
@@ -794,7 +836,11 @@ class OaxacaBuilder:
         cfg, keep = self._config()
         h = C.c_void_p()
         ctx = self._ctx if self._ctx is not None else N.context(self._device)
-        N.check(lib.ob_builder_prepare(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+        if self._cluster is not None:
+            cc = self._cluster_config()
+            N.check(lib.ob_builder_prepare_clustered(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(cc), C.byref(h)))
+        else:
+            N.check(lib.ob_builder_prepare(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h)))
         return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
 
 
@@ -807,6 +853,10 @@ class PreparedRun:
         self.device = device  # the GPU holding the panel
         self.row_len = N.lib().ob_prepared_row_len(handle)
         self.seed = int(N.lib().ob_prepared_seed(handle))
+        info = N.ob_cluster_info()
+        self.cluster_info = None  # a clustered run: n_clusters, n_clusters_a, n_clusters_b, max_cluster_rows, stratified
+        if N.lib().ob_prepared_cluster_info(handle, C.byref(info)) == N.OB_OK:
+            self.cluster_info = {f: int(getattr(info, f)) for f, _ in N.ob_cluster_info._fields_}
 
     def boot(self, first_rep: int, n_reps: int):
         rows = np.empty((n_reps, self.row_len), dtype=np.float64)
@@ -883,7 +933,7 @@ class OaxacaBlinder:
 
     def __init__(self, dataframe, outcome, group, reference_group, predictors, categorical_predictors=(),
                  bootstrap_reps=100, weights=None, selection_outcome=None, selection_predictors=None, *,
-                 seed=None, device=None):
+                 seed=None, device=None, cluster=None):
         self.dataframe = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
         self.outcome, self.group, self.reference_group = outcome, group, reference_group
         self.predictors = list(predictors)
@@ -894,6 +944,7 @@ class OaxacaBlinder:
         self.selection_predictors = list(selection_predictors or [])
         self.seed = seed
         self.device = device
+        self.cluster = cluster
 
     def _create_builder(self) -> OaxacaBuilder:
         b = OaxacaBuilder(self.dataframe, self.outcome, self.group, self.reference_group)
@@ -903,6 +954,8 @@ class OaxacaBlinder:
             b.weights(self.weights)
         if self.selection_outcome:
             b.heckman_selection(self.selection_outcome, self.selection_predictors)
+        if self.cluster:
+            b.cluster(self.cluster)
         return b
 
     def fit(self) -> OaxacaResults:
@@ -1000,8 +1053,16 @@ class QuantileDecompositionBuilder:
         self._device = device
         return self
 
+    def cluster(self, column: str | None, stratified: bool = False):
+        """Accepted for symmetry with ``OaxacaBuilder.cluster``; ``run()`` then refuses: the Machado-Mata
+        passes draw rows (MM-1), and a cluster bootstrap of them is not built."""
+        self._cluster = None if column is None else str(column)
+        return self
+
     def run(self) -> QuantileDecompositionResults:
         """quantile_decomposition.rs:281-445 on the MI355X engine."""
+        if getattr(self, "_cluster", None) is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, "cluster bootstrap: Machado-Mata is outside its scope")
         lib = N.lib()
         cols, ncol, nrow = self._frame.as_c()
         cfg = N.ob_qd_config()

@@ -26,11 +26,16 @@
 #include "ob_frame.hpp"
 #include "ob_host.hpp"
 #include "ob_builder.hpp"
+#include "ob_cluster.hpp"
 #include "ob_mm.hpp"
 #include "ob_spec.h"
 
 namespace ob {
 
+ClusterHooks& cluster_hooks() {
+  static ClusterHooks h;
+  return h;
+}
 
 const char* dtype_name(int kind) {
   switch (kind) {
@@ -145,6 +150,7 @@ static int clean_dataframe(const Frame& f, const Config& c, Frame& out) {
   if (c.has_weights) cols.push_back(c.weights);
   if (c.has_selection) cols.push_back(c.selection);
   cols.insert(cols.end(), c.selection_predictors.begin(), c.selection_predictors.end());
+  if (c.has_cluster) cols.push_back(c.cluster);  // a null cluster id drops the row like any named column
   std::vector<int> idx;
   for (const auto& name : cols) {
     const int i = f.find(name);
@@ -348,6 +354,8 @@ static uint64_t fresh_seed() {
 
 int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out) {
   const bool heck = c.has_selection;
+  if (heck && c.has_cluster)
+    return fail(OB_E_UNSUPPORTED, "cluster bootstrap: Heckman selection panels are outside its scope");
   if (heck && (c.ref == OB_REF_POOLED || c.ref == OB_REF_NEUMARK))
     return fail(OB_E_UNSUPPORTED,
                 "Heckman selection with pooled reference coefficients: the reference's pooled beta* has no IMR "
@@ -375,6 +383,17 @@ int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out)
       return fail(OB_E_INSUFFICIENT,
                   "%sInsufficient data for OLS calculation: n_obs (%lld) must be strictly greater than k (%d)",
                   error_prefix(OB_E_INSUFFICIENT), (long long)d->n, k);
+  }
+  // the cluster index and its limits, before any device work (ob_cluster.cpp)
+  ClusterIndex cidx;
+  if (c.has_cluster) {
+    if (!cluster_hooks().index) return fail(OB_E_UNSUPPORTED, "this build carries no cluster bootstrap");
+    const int ci = st.df.find(c.cluster);
+    std::vector<int32_t> grp((size_t)st.df.nrows, -1);
+    for (int64_t r : st.split.a) grp[r] = 0;
+    for (int64_t r : st.split.b) grp[r] = 1;
+    OB_TRY(cluster_hooks().index(st.df.cols[ci], grp.data(), st.df.nrows, c.cluster_stratified,
+                                 k + (int)std::max<size_t>(c.outcomes.size(), 1), cidx));
   }
   // names: [intercept, predictors, dummies] and the pooled list with the indicator
   std::vector<std::string> names = {"__ob_intercept__"};
@@ -474,7 +493,9 @@ int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out)
   pr->point_row.assign((size_t)pr->row_len * pr->n_y, 0.0);
   pr->resid_b.assign((size_t)pr->n_resid * pr->n_y, 0.0);  // Heckman: zeros (estimation.rs:152-153)
   rc = ob_point_estimate(pr->panel, pr->ref, pr->point_row.data(), heck ? nullptr : pr->resid_b.data());
+  if (rc == OB_OK && c.has_cluster) rc = cluster_hooks().attach(pr, cidx);
   if (rc != OB_OK) {
+    if (pr->cluster) cluster_hooks().free_state(pr->cluster);
     ob_panel_destroy(pr->panel);
     delete pr;
     return rc;
@@ -499,6 +520,11 @@ int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* 
   res->n_a = pr->n_a;
   res->n_b = pr->n_b;
   res->n_failed = (int64_t)(n_reps - ng);
+  if (pr->cluster) {
+    ob_cluster_info ci;
+    cluster_hooks().info(pr->cluster, &ci);
+    res->n_clusters = ci.n_clusters;
+  }
   res->residuals.assign(pr->resid_b.begin() + (size_t)t_out * pr->n_resid,
                         pr->resid_b.begin() + (size_t)(t_out + 1) * pr->n_resid);
   const double* tail = point_row + 6 + 2 * kd;
@@ -555,7 +581,7 @@ static int run_all(ob_ctx* ctx, const Frame& f, const Config& c, ob_results** ou
   std::vector<double> rows((size_t)c.reps * pr->row_len * ny);
   std::vector<uint8_t> ok(c.reps * ny, 0);
   int rc = OB_OK;
-  if (c.reps > 0) rc = ob_boot_run(pr->panel, pr->seed, 0, c.reps, pr->ref, rows.data(), ok.data());
+  if (c.reps > 0) rc = ob_prepared_boot(pr, 0, c.reps, rows.data(), ok.data());
   for (size_t t = 0; t < ny && rc == OB_OK; ++t) {
     rc = finish(pr, (int)t, rows.data() + t * c.reps * pr->row_len, ok.data() + t * c.reps, c.reps, &out[t]);
     if (rc != OB_OK)
@@ -564,9 +590,17 @@ static int run_all(ob_ctx* ctx, const Frame& f, const Config& c, ob_results** ou
         out[u] = nullptr;
       }
   }
-  ob_panel_destroy(pr->panel);
-  delete pr;
+  ob_prepared_destroy(pr);
   return rc;
+}
+
+// The cluster settings of the *_clustered entry points, beside the builder config (which has no size field).
+static int cluster_config_from(const ob_cluster_config* cc, Config& c) {
+  if (!cc || !cc->column) return fail(OB_E_INVALID, "incomplete cluster config");
+  c.has_cluster = true;
+  c.cluster = cc->column;
+  c.cluster_stratified = cc->stratified != 0;
+  return OB_OK;
 }
 
 }  // namespace ob
@@ -800,11 +834,13 @@ ob_panel* ob_prepared_panel(ob_prepared* p) { return p ? p->panel : nullptr; }
 
 int ob_prepared_boot(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
+  if (p->cluster) return ob::cluster_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   return ob_boot_run(p->panel, p->seed, first_rep, n_reps, p->ref, rows, ok);
 }
 
 int ob_prepared_boot_sharded(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
+  if (p->cluster) return ob::fail(OB_E_UNSUPPORTED, "cluster bootstrap: sharded runs are outside its scope");
   // the RCCL all-gather moves only the columns finish() aggregates: two-fold, three-fold, total
   // gap, detailed [0, 6 + 2 Kd) and a Heckman row's selection terms after its 5K' tail
   const int kd = p->k + p->n_base, sel0 = 6 + 2 * kd + 5 * p->k;
@@ -823,6 +859,9 @@ int ob_prepared_boot_sharded(ob_prepared* p, uint64_t first_rep, uint64_t n_reps
 int ob_prepared_boot_device(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
                             void* hip_stream) {
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
+  if (p->cluster)
+    return ob::cluster_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok,
+                                           reinterpret_cast<hipStream_t>(hip_stream));
   return ob_boot_run_device(p->panel, p->seed, first_rep, n_reps, p->ref, d_rows, d_ok, hip_stream);
 }
 
@@ -834,8 +873,33 @@ int ob_prepared_finish(ob_prepared* p, const double* rows, const uint8_t* ok, ui
 
 void ob_prepared_destroy(ob_prepared* p) {
   if (!p) return;
+  if (p->cluster) ob::cluster_hooks().free_state(p->cluster);
   ob_panel_destroy(p->panel);
   delete p;
+}
+
+int ob_builder_prepare_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                 const ob_builder_config* cfg, const ob_cluster_config* ccfg, ob_prepared** out) {
+  if (!ctx || !out) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  ob::Frame f;
+  ob::Config c;
+  OB_TRY(ob::config_from(cfg, c));
+  OB_TRY(ob::cluster_config_from(ccfg, c));
+  OB_TRY(ob::load_frame(cols, n_cols, n_rows, f));
+  return ob::prepare(ctx, f, c, out);
+}
+
+int ob_builder_run_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                             const ob_builder_config* cfg, const ob_cluster_config* ccfg, ob_results** out) {
+  if (!ctx || !out) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  ob::Frame f;
+  ob::Config c;
+  OB_TRY(ob::config_from(cfg, c));
+  OB_TRY(ob::cluster_config_from(ccfg, c));
+  OB_TRY(ob::load_frame(cols, n_cols, n_rows, f));
+  return ob::run_all(ctx, f, c, out);
 }
 
 int ob_builder_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
@@ -853,12 +917,14 @@ int ob_builder_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n
 // Several quantiles share one panel: the RIF columns are the panel's outcomes (n_y = n_taus), so
 // one Gram pass serves every tau; out[t] is bitwise the single-tau run.
 static int decompose_quantiles(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
-                               const ob_builder_config* cfg, const double* taus, int32_t n_taus, ob_results** out) {
+                               const ob_builder_config* cfg, const double* taus, int32_t n_taus, ob_results** out,
+                               const ob_cluster_config* ccfg = nullptr) {
   if (!ctx || !out || !taus || n_taus < 1) return ob::fail(OB_E_INVALID, "null pointer or no quantiles");
   for (int32_t t = 0; t < n_taus; ++t) out[t] = nullptr;
   ob::Frame f, df;
   ob::Config c;
   OB_TRY(ob::config_from(cfg, c));
+  if (ccfg) OB_TRY(ob::cluster_config_from(ccfg, c));  // the fresh builder carries the cluster setting over
   OB_TRY(ob::load_frame(cols, n_cols, n_rows, f));
   OB_TRY(ob::clean_dataframe(f, c, df));
   ob::Split sp;
@@ -906,6 +972,13 @@ int ob_builder_decompose_quantiles(ob_ctx* ctx, const ob_column* cols, int32_t n
   return decompose_quantiles(ctx, cols, n_cols, n_rows, cfg, taus, n_taus, out);
 }
 
+int ob_builder_decompose_quantiles_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                             const ob_builder_config* cfg, const ob_cluster_config* ccfg,
+                                             const double* taus, int32_t n_taus, ob_results** out) {
+  if (!ccfg) return ob::fail(OB_E_INVALID, "incomplete cluster config");
+  return decompose_quantiles(ctx, cols, n_cols, n_rows, cfg, taus, n_taus, out, ccfg);
+}
+
 int ob_builder_data_matrices(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
                              ob_matrices** out) {
   if (!out) return ob::fail(OB_E_INVALID, "null pointer");
@@ -942,6 +1015,7 @@ double ob_results_total_gap(const ob_results* r) { return r ? r->total_gap : NAN
 int64_t ob_results_n_a(const ob_results* r) { return r ? r->n_a : 0; }
 int64_t ob_results_n_b(const ob_results* r) { return r ? r->n_b : 0; }
 int64_t ob_results_n_failed(const ob_results* r) { return r ? r->n_failed : 0; }
+int64_t ob_results_n_clusters(const ob_results* r) { return r ? r->n_clusters : -1; }
 
 int ob_results_count(const ob_results* r, int32_t table) {
   if (!r || table < 0 || table > 4) return -1;

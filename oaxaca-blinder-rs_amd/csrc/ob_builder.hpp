@@ -25,13 +25,20 @@ struct Config {
   int ref = OB_REF_GROUP_A;
   bool has_seed = false;
   uint64_t seed = 0;
+  // cluster bootstrap (ob_cluster.hpp): the id column and the sampling mode
+  bool has_cluster = false;
+  std::string cluster;
+  bool cluster_stratified = false;
 };
+
+struct ClusterState;
 
 }  // namespace ob
 
 struct ob_results {
   double total_gap = 0.0;
   int64_t n_a = 0, n_b = 0, n_failed = 0;
+  int64_t n_clusters = -1;  // a clustered run's C (ob_results_n_clusters), else -1
   struct Comp {
     std::string name;
     double estimate, std_err, t_stat, p_value, ci_lower, ci_upper;
@@ -60,6 +67,8 @@ struct ob_prepared {
   ob::JackResult jack;
   std::vector<double> jack_stats;
   bool has_jack = false;
+  // ob_builder_prepare_clustered: the cluster index and Q on the device; boots run through ob_cluster.hip
+  ob::ClusterState* cluster = nullptr;
 };
 
 namespace ob {

@@ -1057,6 +1057,7 @@ struct SolveArgs {
   double* gram_out;    // optional copy of the replicate-0 extended Grams (point estimate)
   double* raw_beta_b;  // optional: replicate-0 beta_B before normalization (ols.rs residuals)
   int raw_status;      // 1: ok[] receives the status code (1 ok, 0 Cholesky, 2 zero weight)
+  const uint32_t* rep_rows;  // optional [rep][2]: the replicate's own rows per group (cluster bootstrap)
 };
 
 // normalization.rs:5-51
@@ -1160,8 +1161,8 @@ __global__ __launch_bounds__(128) void ob_solve_kernel(const SolveArgs a) {
       if (lane == 0)
         for (int v = 0; v < a.n_norm; ++v) base_s[v] = a.ref_mode == OB_REF_GROUP_A ? base_a[v] : base_b[v];
     } else if (a.ref_mode == OB_REF_WEIGHTED || a.ref_mode == OB_REF_COTTON) {
-      const double sa = a.weighted ? GA[0] : a.rows_a;
-      const double sb = a.weighted ? GB[0] : a.rows_b;
+      const double sa = a.weighted ? GA[0] : (a.rep_rows ? (double)a.rep_rows[2 * rep] : a.rows_a);
+      const double sb = a.weighted ? GB[0] : (a.rep_rows ? (double)a.rep_rows[2 * rep + 1] : a.rows_b);
       const double tot = sa + sb;
       if (tot == 0.0) {
         status = 2;
@@ -2136,6 +2137,23 @@ int engine_boot(ob_panel* p, uint64_t seed, uint64_t first_rep, uint64_t n_reps,
   p->timing_pending = true;
   p->last_stream = s;
   return engine_mark(p, s, !overlap);
+}
+
+// The solve stage of engine_boot on reduced Grams another pass formed (ob_cluster.hip): every outcome's
+// rows, outcome-major, for replicates s0 .. s0 + ns of a call of n_reps.
+int engine_solve_grams(ob_panel* p, const double* d_gram, const uint32_t* d_rep_rows, uint32_t ns, uint64_t n_reps,
+                       uint64_t s0, int ref_mode, double* d_rows, uint8_t* d_ok, hipStream_t s) {
+  for (int t = 0; t < p->n_y; ++t) {
+    SolveArgs sa = solve_args(p, ref_mode);
+    sa.yc = p->p + 1 + t;
+    sa.gram = d_gram;
+    sa.rows = d_rows + ((size_t)t * n_reps + s0) * p->row_len;
+    sa.ok = d_ok + (size_t)t * n_reps + s0;
+    sa.n_reps = ns;
+    sa.rep_rows = d_rep_rows;
+    OB_HIP(launch_solve(p, sa, ns, s));
+  }
+  return OB_OK;
 }
 
 // Synchronize the last boot run, sum its per-segment kernel timings and check the

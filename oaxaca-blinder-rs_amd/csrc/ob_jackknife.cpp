@@ -240,6 +240,8 @@ static int finish_bca(const ob_prepared* pr, const double* rows, const uint8_t* 
 // The checks of ob_prepared_jackknife and ob_prepared_finish_bca, before any device work.
 static int prepared_jack_check(const ob_prepared* p) {
   if (!p) return fail(OB_E_INVALID, "null pointer");
+  if (p->cluster)  // delete-one-row is the wrong jackknife under clustering
+    return fail(OB_E_UNSUPPORTED, "jackknife: a clustered run needs a delete-one-cluster pass, which is not built");
   const bool heck = !p->selection_names.empty();
   return jackknife_check_shape(heck ? p->k - 1 : p->k, p->n_a, p->n_b, p->n_base > 0 || !p->cfg.normalize.empty(),
                                p->n_y, heck, 0);

@@ -299,6 +299,34 @@ OB_HD uint32_t ob_mulhi64(uint32_t lo, uint32_t hi, uint32_t s) {
   return (uint32_t)((h + l) >> 32);
 }
 
+// ---- OBRC-1: the cluster bootstrap's draws ---------------------------------
+// A cluster bootstrap resamples whole clusters: stratum s draws m_s clusters uniformly with
+// replacement from its m_s clusters. `joint` mode has one stratum, s = 0, m_0 = C (every cluster,
+// both groups share the counts); `stratified` mode has s = 0 over group A's C_A clusters [0, C_A)
+// and s = 1 over group B's C_B clusters [C_A, C_A + C_B).
+// For replicate rep, stratum s, draw j in [0, m_s), attempt t = 0, 1, ...:
+//   u = word (j & 3) of Philox4x32-10 with counter {j >> 2, rep, 2 t + s, "OBC1"} and key
+//       {seed_lo, seed_hi};  p = (u64)u * m_s;
+//   reject when (uint32)p < ((2^32 - m_s) mod m_s) and go to attempt t + 1,
+//   otherwise the cluster is p >> 32 (+ C_A for s = 1).
+// Lemire's multiply-and-reject, the rule of OBRS-3's direct draws: exactly uniform, a function of
+// (seed, rep) only. m_s < 2^24, so an attempt is rejected with probability below 2^-8.
+#define OB_TAG_OBC 0x4F424331u /* "OBC1" */
+
+// Draw j of stratum s (m clusters), given the attempt-0 call u0 = Philox({j >> 2, rep, s, OBC1}).
+OB_HD uint32_t ob_cluster_draw(ob_u32x4 u0, uint32_t j, uint32_t rep, uint32_t s, uint32_t m, uint32_t k0,
+                               uint32_t k1) {
+  const uint32_t thresh = (0u - m) % m;
+  ob_u32x4 u = u0;
+  for (uint32_t t = 0;; ++t) {
+    if (t) u = ob_philox(j >> 2, rep, 2u * t + s, OB_TAG_OBC, k0, k1);
+    const uint32_t h = j & 3u;
+    const uint32_t wd = h == 0 ? u.x : h == 1 ? u.y : h == 2 ? u.z : u.w;
+    const uint64_t p = (uint64_t)wd * m;
+    if ((uint32_t)p >= thresh) return (uint32_t)(p >> 32);
+  }
+}
+
 // ---- per-replicate result row (also include/oaxaca_boot.h OB_ROW_*) ------------------------
 // [0] explained [1] unexplained [2] endowments [3] coefficients [4] interaction [5] total_gap
 // [6, 6+Kd) detailed explained  [6+Kd, 6+2Kd) detailed unexplained   (Kd = K + n_base)

@@ -753,3 +753,93 @@ def remedy_apply_adjustments(wage, index, value, valid=None):
     N.check(N.lib().ob_remedy_apply_adjustments(_dp(wv), None if ok is None else ok.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                 int(wv.shape[0]), _i64p(iv), _dp(vv), int(iv.shape[0]), _dp(out)))
     return out
+
+
+# ---- cluster bootstrap ------------------------------------------------------
+def cluster_check_shape(n_clusters: int, k1: int) -> None:
+    """ob_cluster_check_shape: raises OaxacaError where a clustered prepare would (host only)."""
+    N.check(N.lib().ob_cluster_check_shape(int(n_clusters), int(k1)))
+
+
+def cluster_index(ids, group, stratified: bool = False) -> dict:
+    """ob_cluster_index (host only). ``ids``: one column (strings or integers, ``None`` = null);
+    ``group``: per row 0 (A), 1 (B) or anything else for a row in neither group. Returns dense ids in
+    order of first appearance (-1: dropped), each group's stable permutation by cluster id with its
+    CSR offsets, and n_clusters / n_clusters_a / n_clusters_b / max_cluster_rows / stratified."""
+    from .frame import Frame
+
+    fr = Frame({"ids": ids})
+    cols, _, n = fr.as_c()
+    grp = np.ascontiguousarray(group, dtype=np.int32)
+    if grp.shape != (n,):
+        raise ValueError("group must have one entry per row")
+    dense = np.full(n, -1, dtype=np.int32)
+    perm = [np.zeros(max(n, 1), dtype=np.int64) for _ in range(2)]
+    off = [np.zeros(n + 1, dtype=np.int64) for _ in range(2)]
+    info = N.ob_cluster_info()
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    N.check(N.lib().ob_cluster_index(cols, _ip(grp), n, int(bool(stratified)), _ip(dense), lp(perm[0]), lp(perm[1]),
+                                     lp(off[0]), lp(off[1]), C.byref(info)))
+    nc = int(info.n_clusters)
+    kept = [int(((grp == g) & (dense >= 0)).sum()) for g in (0, 1)]
+    return {"dense": dense, "perm_a": perm[0][:kept[0]].copy(), "perm_b": perm[1][:kept[1]].copy(),
+            "off_a": off[0][:nc + 1].copy(), "off_b": off[1][:nc + 1].copy(), "n_clusters": nc,
+            "n_clusters_a": int(info.n_clusters_a), "n_clusters_b": int(info.n_clusters_b),
+            "max_cluster_rows": int(info.max_cluster_rows), "stratified": bool(info.stratified)}
+
+
+def cluster_gram(x, y, w, perm, off, device=None):
+    """ob_cluster_gram for one group: x (n, p) predictors without the intercept, y (n,), w (n,) or None,
+    perm / off from ``cluster_index`` -> (Q (C, E) in ob_spec.h's pair order, rows (C,))."""
+    x = np.asfortranarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+    perm = np.ascontiguousarray(perm, dtype=np.int64)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    n, p = x.shape
+    if y.shape != (n,) or perm.shape != (n,) or (w is not None and w.shape != (n,)) or off.ndim != 1 or off.size < 2:
+        raise ValueError("cluster_gram: mismatched shapes")
+    nc = off.size - 1
+    e = (p + 2) * (p + 3) // 2
+    e_pad = (e + 15) // 16 * 16
+    q = np.zeros((nc, e_pad))
+    rows = np.zeros(nc, dtype=np.uint32)
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    N.check(N.lib().ob_cluster_gram(N.context(device), _dp(x), n, max(n, 1), p, _dp(y), None if w is None else _dp(w),
+                                    lp(perm), lp(off), nc, _dp(q), rows.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return q[:, :e].copy(), rows
+
+
+def cluster_counts(seed: int, first_rep: int, n_reps: int, n_clusters_a: int, n_clusters_b: int = 0,
+                   stratified: bool = False, device=None):
+    """ob_cluster_counts -> (n_reps, C) uint32 counts of the OBRC-1 stream (C = n_clusters_a + n_clusters_b)."""
+    nc = int(n_clusters_a) + int(n_clusters_b)
+    out = np.zeros((n_reps, max(nc, 0)), dtype=np.uint32)
+    N.check(N.lib().ob_cluster_counts(N.context(device), int(seed) & (2 ** 64 - 1), int(first_rep), int(n_reps),
+                                      int(n_clusters_a), int(n_clusters_b), int(bool(stratified)),
+                                      out.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out
+
+
+def cluster_apply(counts, q, device=None):
+    """ob_cluster_apply: counts (R, C) uint32 x q (C, W) -> (R, W) on the f64 matrix units (W is padded to a
+    multiple of 16 on the way in)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if counts.ndim != 2 or q.ndim != 2 or counts.shape[1] != q.shape[0]:
+        raise ValueError("cluster_apply: counts (R, C) and q (C, W)")
+    w = q.shape[1]
+    w_pad = max((w + 15) // 16 * 16, 16)
+    qp = np.zeros((q.shape[0], w_pad))
+    qp[:, :w] = q
+    out = np.zeros((counts.shape[0], w_pad))
+    N.check(N.lib().ob_cluster_apply(N.context(device), counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.shape[0],
+                                     counts.shape[1], _dp(qp), w_pad, _dp(out)))
+    return out[:, :w].copy()
+
+
+def cluster_last_timing() -> dict:
+    """ob_cluster_last_timing: gram / counts / apply / solve ms of this thread's last clustered host boot."""
+    t = N.ob_cluster_timing()
+    N.check(N.lib().ob_cluster_last_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in N.ob_cluster_timing._fields_}
