@@ -1100,6 +1100,51 @@ int64_t ob_results_n_clusters(const ob_results* r);
 /* OB_E_INVALID on a handle that is not clustered. */
 int ob_prepared_cluster_info(const ob_prepared* prep, ob_cluster_info* out);
 
+/* ---- RIF decompositions of the variance, the Gini and quantile ranges -------------------
+ * The recentred influence function of a distributional statistic as the outcome of the mean decomposition
+ * (Firpo, Fortin, Lemieux 2009, 2018). For a group's outcome y of n rows, unweighted: mu = sum y / n,
+ * r(i) = #{j : y_j <= y_i} (tied rows share the last rank of their run), p_i = r(i) / n.
+ *   OB_RIF_VARIANCE  RIF_i = (y_i - mu)^2, statistic sum (y - mu)^2 / n.
+ *   OB_RIF_GINI      GL_i = (1/n) sum_{y_j <= y_i} y_j, R = (1/n) sum GL_i, statistic G = 1 - 2R/mu,
+ *                    RIF_i = 1 + (2R/mu^2) y_i - (2/mu) [y_i (1 - p_i) + GL_i]. y >= 0 and mu > 0.
+ *   OB_RIF_IQR       p0 = tau_hi, p1 = tau_lo, 0 < tau_lo < tau_hi < 1: RIF_{tau_hi} - RIF_{tau_lo}, each ob_rif's
+ *                    (type-7 quantile, its Silverman bandwidth and fallbacks, Gaussian density, floor 1e-8,
+ *                    indicator y <= q); one sort and one bandwidth serve both. Statistic q_hi - q_lo.
+ * Device pass: a stable radix sort of (y, row), tie runs and ranks, block scans of ob_rif_scan_block() sorted
+ * values with the block totals scanned in block order, sums in pieces of that size added in order, the two
+ * densities over chunks of the sorted values, a scatter to row order. Every sum is f64 in an order that depends
+ * on n alone: a repeated call, or the same values in another row order, gives the same bytes per row.
+ * Errors, each before any device work (a NULL ctx with good arguments is OB_E_INVALID "null pointer"): an unknown
+ * statistic or bad tau OB_E_INVALID; n < 2 OB_E_INSUFFICIENT; n > 2^28 OB_E_UNSUPPORTED; a non-finite y
+ * OB_E_INVALID; for the Gini a negative y or no positive one OB_E_INVALID. */
+#define OB_RIF_VARIANCE 0
+#define OB_RIF_GINI 1
+#define OB_RIF_IQR 2
+typedef struct {
+  int32_t stat;  /* OB_RIF_* */
+  double p0, p1; /* OB_RIF_IQR: tau_hi, tau_lo; otherwise unused */
+} ob_rif_spec;
+typedef struct {
+  double sort_ms, scan_ms, kde_ms, scatter_ms; /* kde_ms: the quantile pieces and densities of OB_RIF_IQR */
+} ob_rif_timing;
+/* rif_out[n] in y's row order, *statistic_out the statistic itself. */
+int ob_rif_stat(ob_ctx* ctx, const double* y, int64_t n, const ob_rif_spec* spec, double* rif_out,
+                double* statistic_out);
+/* Sorted values per scan block and per piece of the ordered sums (a constant of the kernels). */
+int32_t ob_rif_scan_block(void);
+/* HIP-event ms of the calling thread's last ob_rif_stat / ob_builder_decompose_statistics (groups and statistics
+   added up). */
+int ob_rif_last_timing(ob_rif_timing* out);
+/* One panel whose outcomes are the n_specs RIF columns of each group's outcome, built exactly as
+   ob_builder_decompose_quantiles builds its panel: one resample and one Gram per replicate serve all of them, the
+   same cap on outcomes applies, and out[t] is bitwise the single-statistic call. */
+int ob_builder_decompose_statistics(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                    const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
+                                    ob_results** out);
+int ob_builder_decompose_statistics_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                              const ob_builder_config* cfg, const ob_cluster_config* ccfg,
+                                              const ob_rif_spec* specs, int32_t n_specs, ob_results** out);
+
 #ifdef __cplusplus
 }
 #endif

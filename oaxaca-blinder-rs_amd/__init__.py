@@ -16,7 +16,8 @@ from .engine import (cluster_apply, cluster_check_shape, cluster_counts, cluster
                      cluster_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
                      knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
-                     remedy_resolve_overrides, remedy_score, remedy_solve, rif,
+                     remedy_resolve_overrides, remedy_score, remedy_solve, rif, parse_rif_statistic, rif_last_timing,
+                     rif_scan_block, rif_statistic,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
@@ -35,4 +36,5 @@ __all__ = [
     "JackknifeResult", "jackknife_rows", "jackknife_finish", "jackknife_check_shape", "jackknife_last_timing", "bca_stats",
     "aggregate_bca",
     "cluster_index", "cluster_gram", "cluster_counts", "cluster_apply", "cluster_check_shape", "cluster_last_timing",
+    "rif_statistic", "rif_last_timing", "rif_scan_block", "parse_rif_statistic",
 ]

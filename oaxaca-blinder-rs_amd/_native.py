@@ -63,6 +63,8 @@ EXPORTED = (
     "ob_cluster_check_shape", "ob_cluster_index", "ob_cluster_gram", "ob_cluster_counts", "ob_cluster_apply",
     "ob_cluster_last_timing", "ob_builder_prepare_clustered", "ob_builder_run_clustered",
     "ob_builder_decompose_quantiles_clustered", "ob_prepared_cluster_info", "ob_results_n_clusters",
+    "ob_rif_stat", "ob_rif_scan_block", "ob_rif_last_timing", "ob_builder_decompose_statistics",
+    "ob_builder_decompose_statistics_clustered",
 )
 
 OB_E_CONVERGENCE = 12
@@ -78,6 +80,8 @@ OB_REMEDY_STRATEGIES = {"greedy": 0, "equitable": 1}
 OB_REMEDY_RANGE_TARGETS = {"midpoint": 0, "lower": 1, "upper": 2}
 OB_MATCH_MAX_DIM, OB_MATCH_MAX_K = 64, 16
 OB_MATCH_EUCLIDEAN, OB_MATCH_MAHALANOBIS, OB_MATCH_PSM = 0, 1, 2
+OB_RIF_VARIANCE, OB_RIF_GINI, OB_RIF_IQR = 0, 1, 2
+OB_RIF_STATS = {"variance": OB_RIF_VARIANCE, "gini": OB_RIF_GINI, "iqr": OB_RIF_IQR}
 
 
 class OaxacaError(RuntimeError):
@@ -225,6 +229,15 @@ class ob_cluster_info(C.Structure):
 class ob_cluster_timing(C.Structure):
     _fields_ = [("gram_ms", C.c_double), ("counts_ms", C.c_double), ("apply_ms", C.c_double),
                 ("solve_ms", C.c_double)]
+
+
+class ob_rif_spec(C.Structure):
+    _fields_ = [("stat", C.c_int32), ("p0", C.c_double), ("p1", C.c_double)]
+
+
+class ob_rif_timing(C.Structure):
+    _fields_ = [("sort_ms", C.c_double), ("scan_ms", C.c_double), ("kde_ms", C.c_double),
+                ("scatter_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -429,6 +442,16 @@ _SIGS = {
                                                            _D, C.c_int32, C.POINTER(_P)]),
     "ob_prepared_cluster_info": (C.c_int, [_P, C.POINTER(ob_cluster_info)]),
     "ob_results_n_clusters": (C.c_int64, [_P]),
+    "ob_rif_stat": (C.c_int, [_P, _D, C.c_int64, C.POINTER(ob_rif_spec), _D, _D]),
+    "ob_rif_scan_block": (C.c_int32, []),
+    "ob_rif_last_timing": (C.c_int, [C.POINTER(ob_rif_timing)]),
+    "ob_builder_decompose_statistics": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                  C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec), C.c_int32,
+                                                  C.POINTER(_P)]),
+    "ob_builder_decompose_statistics_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                            C.POINTER(ob_builder_config),
+                                                            C.POINTER(ob_cluster_config), C.POINTER(ob_rif_spec),
+                                                            C.c_int32, C.POINTER(_P)]),
 }
 
 _lib = None

@@ -828,6 +828,87 @@ class OaxacaBuilder:
                                                    C.cast(hs, C.POINTER(C.c_void_p))))
         return [_results_from_c(C.c_void_p(h)) for h in hs]
 
+    def decompose_statistic(self, stat, **params) -> OaxacaResults:
+        """RIF-regression decomposition of the gap in a distributional statistic (Firpo, Fortin, Lemieux):
+        ``"variance"``, ``"gini"`` or ``"iqr"`` (``upper=0.9, lower=0.1``). The statistic's recentred influence
+        function of each group's outcome, computed on the GPU (``ob_rif_stat``), is the outcome of ``run()``:
+        ``total_gap`` is the gap in mean RIF, the statistic's gap up to the identities of DESIGN.md §5.12."""
+        from .engine import parse_rif_statistic
+
+        return self.decompose_statistics([parse_rif_statistic(stat, **params)])[0]
+
+    def decompose_statistics(self, stats) -> list:
+        """Several statistics in one run: one panel whose outcomes are the RIF columns, so every replicate's
+        resample and Gram pass serve all of them. ``stats``: names, ``(name, params)`` pairs or dicts with a
+        ``stat`` key. Element t equals ``decompose_statistic`` of element t bitwise (same seed). Honours
+        ``.cluster(...)`` the way ``decompose_quantiles`` does."""
+        from .engine import parse_rif_statistic, with_context
+
+        stats = list(stats)
+        parsed = [s if isinstance(s, tuple) and len(s) == 3 else parse_rif_statistic(s) for s in stats]
+        if not parsed:
+            raise ValueError("statistics must be a non-empty sequence")
+        specs = (N.ob_rif_spec * len(parsed))(*[N.ob_rif_spec(*p) for p in parsed])
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        hs = (C.c_void_p * len(parsed))()
+        out = C.cast(hs, C.POINTER(C.c_void_p))
+        if self._cluster is not None:
+            cc = self._cluster_config()
+            with_context(lambda ctx: lib.ob_builder_decompose_statistics_clustered(
+                ctx, cols, ncol, nrow, C.byref(cfg), C.byref(cc), specs, len(parsed), out), self._device)
+        else:
+            with_context(lambda ctx: lib.ob_builder_decompose_statistics(
+                ctx, cols, ncol, nrow, C.byref(cfg), specs, len(parsed), out), self._device)
+        return [_results_from_c(C.c_void_p(h)) for h in hs]
+
+    def statistic_builder(self, stat, **params) -> "OaxacaBuilder":
+        """A fresh builder over this frame with the outcome replaced by the statistic's RIF of each group's
+        outcome (the rows ``run()`` would keep, group by group, as ``decompose_statistic`` forms it), so that
+        ``run_bca()``, ``jackknife()`` and ``prepare()`` serve the statistic. Every setting is carried over
+        except the Heckman selection, as in ``decompose_quantile``."""
+        from .engine import parse_rif_statistic, rif_statistic
+
+        code, p0, p1 = parse_rif_statistic(stat, **params)
+        name = {v: k for k, v in N.OB_RIF_STATS.items()}[code]
+        kw = {"upper": p0, "lower": p1} if code == N.OB_RIF_IQR else {}
+        used = [self.outcome, self.group, *self._predictors, *self._categorical, *self._selection_predictors]
+        used += [c for c in (self._weights, self._selection, self._cluster) if c]
+        fcols = self._frame.columns
+        keep = np.ones(self._frame.nrows, dtype=bool)
+        for c in used:  # clean_dataframe (builder.rs:760-784)
+            if c not in fcols:
+                raise N.OaxacaError(N.OB_E_COLUMN, f"Column not found: {c}")
+            kind, values, valid = fcols[c]
+            if kind == N.OB_COL_STR:
+                keep &= np.array([v is not None for v in values], dtype=bool)
+            elif valid is not None:
+                keep &= valid.astype(bool)
+        gkind, groups, _ = fcols[self.group]
+        ykind, y, _ = fcols[self.outcome]
+        if gkind != N.OB_COL_STR or ykind != N.OB_COL_F64:
+            raise N.OaxacaError(N.OB_E_POLARS, "Polars error: invalid series dtype: the group column must be "
+                                               "String and the outcome Float64")
+        levels = sorted({g for g, k in zip(groups, keep) if k})  # split_groups (builder.rs:61-102)
+        if len(levels) < 2:
+            raise N.OaxacaError(N.OB_E_GROUP, "Invalid group variable: Not enough groups for comparison")
+        ref = self.reference_group.encode()
+        name_a = levels[1] if levels[0] == ref else levels[0]
+        garr = np.array(groups, dtype=object)
+        new_y = y.copy()
+        for level in (name_a, ref):
+            rows = np.flatnonzero(keep & (garr == level))
+            new_y[rows] = rif_statistic(y[rows], name, device=self._device, **kw)[0]
+        b = OaxacaBuilder(self._frame.with_f64_column(self.outcome, new_y), self.outcome, self.group,
+                          self.reference_group)
+        for attr in ("_predictors", "_categorical", "_normalize"):
+            setattr(b, attr, list(getattr(self, attr)))
+        for attr in ("_bootstrap_reps", "_ref", "_weights", "_seed", "_device", "_ctx", "_cluster",
+                     "_cluster_stratified"):
+            setattr(b, attr, getattr(self, attr))
+        return b
+
     def prepare(self) -> "PreparedRun":
         """clean/dummies/split/upload/point estimate once; replicate ranges run separately
         (the multi-GPU path in ``distributed.py``)."""
@@ -967,6 +1048,14 @@ class OaxacaBlinder:
     def fit_quantiles(self, quantiles) -> list:
         """Several RIF quantiles sharing one bootstrap (``OaxacaBuilder.decompose_quantiles``)."""
         return self._create_builder().decompose_quantiles(quantiles)
+
+    def fit_statistic(self, stat, **params) -> OaxacaResults:
+        """The RIF decomposition of a distributional statistic (``OaxacaBuilder.decompose_statistic``)."""
+        return self._create_builder().decompose_statistic(stat, **params)
+
+    def fit_statistics(self, stats) -> list:
+        """Several statistics sharing one bootstrap (``OaxacaBuilder.decompose_statistics``)."""
+        return self._create_builder().decompose_statistics(stats)
 
     def optimize_budget(self, budget: float, target_gap: float):
         b = self._create_builder()

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <random>
 #include <string>
 #include <thread>
@@ -28,12 +29,18 @@
 #include "ob_builder.hpp"
 #include "ob_cluster.hpp"
 #include "ob_mm.hpp"
+#include "ob_rif.hpp"
 #include "ob_spec.h"
 
 namespace ob {
 
 ClusterHooks& cluster_hooks() {
   static ClusterHooks h;
+  return h;
+}
+
+RifHooks& rif_hooks() {
+  static RifHooks h;
   return h;
 }
 
@@ -916,10 +923,13 @@ int ob_builder_run(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n
 // builder.rs:711-757: RIF of each group's outcome on the cleaned data, then run() on vstack(A, B).
 // Several quantiles share one panel: the RIF columns are the panel's outcomes (n_y = n_taus), so
 // one Gram pass serves every tau; out[t] is bitwise the single-tau run.
-static int decompose_quantiles(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
-                               const ob_builder_config* cfg, const double* taus, int32_t n_taus, ob_results** out,
-                               const ob_cluster_config* ccfg = nullptr) {
-  if (!ctx || !out || !taus || n_taus < 1) return ob::fail(OB_E_INVALID, "null pointer or no quantiles");
+// fill(ya, yb, ra, rb) gives the RIF columns of each group's outcome: ra = [n_taus][n_a], rb = [n_taus][n_b]. The
+// quantile RIF is the host's ob::rif; the statistics of ob_builder_decompose_statistics come from the device pass.
+using RifFill = std::function<int(const std::vector<double>&, const std::vector<double>&, std::vector<double>&,
+                                 std::vector<double>&)>;
+static int decompose_rif(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                         const ob_builder_config* cfg, int32_t n_taus, ob_results** out, const ob_cluster_config* ccfg,
+                         const RifFill& fill) {
   for (int32_t t = 0; t < n_taus; ++t) out[t] = nullptr;
   ob::Frame f, df;
   ob::Config c;
@@ -938,16 +948,15 @@ static int decompose_quantiles(ob_ctx* ctx, const ob_column* cols, int32_t n_col
   ob::Frame mod = ob::take(df, order);
   const int mi = mod.find(c.outcome);
   const size_t na = sp.a.size(), nb = sp.b.size();
-  std::vector<double> ya(na), yb(nb), ra(na), rb(nb);
+  std::vector<double> ya(na), yb(nb), ra(na * (size_t)n_taus), rb(nb * (size_t)n_taus);
   for (size_t i = 0; i < na; ++i) ya[i] = mod.cols[mi].f[i];
   for (size_t i = 0; i < nb; ++i) yb[i] = mod.cols[mi].f[na + i];
+  OB_TRY(fill(ya, yb, ra, rb));
   for (int32_t t = 0; t < n_taus; ++t) {
-    ob::rif(ya.data(), (int64_t)na, taus[t], ra.data());
-    ob::rif(yb.data(), (int64_t)nb, taus[t], rb.data());
     ob::Col rc = mod.cols[mi];
     rc.name = "__ob_rif_" + std::to_string(t) + "__";
-    for (size_t i = 0; i < na; ++i) rc.f[i] = ra[i];
-    for (size_t i = 0; i < nb; ++i) rc.f[na + i] = rb[i];
+    for (size_t i = 0; i < na; ++i) rc.f[i] = ra[(size_t)t * na + i];
+    for (size_t i = 0; i < nb; ++i) rc.f[na + i] = rb[(size_t)t * nb + i];
     if (n_taus == 1) {
       mod.cols[mi] = std::move(rc);  // the reference's own layout: the outcome column replaced
       mod.cols[mi].name = c.outcome;
@@ -959,6 +968,57 @@ static int decompose_quantiles(ob_ctx* ctx, const ob_column* cols, int32_t n_col
   c.has_selection = false;  // the new builder carries no Heckman settings (builder.rs:743-754)
   c.selection_predictors.clear();
   return ob::run_all(ctx, mod, c, out);
+}
+
+static int decompose_quantiles(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                               const ob_builder_config* cfg, const double* taus, int32_t n_taus, ob_results** out,
+                               const ob_cluster_config* ccfg = nullptr) {
+  if (!ctx || !out || !taus || n_taus < 1) return ob::fail(OB_E_INVALID, "null pointer or no quantiles");
+  return decompose_rif(ctx, cols, n_cols, n_rows, cfg, n_taus, out, ccfg,
+                       [&](const std::vector<double>& ya, const std::vector<double>& yb, std::vector<double>& ra,
+                           std::vector<double>& rb) {
+                         for (int32_t t = 0; t < n_taus; ++t) {
+                           ob::rif(ya.data(), (int64_t)ya.size(), taus[t], ra.data() + (size_t)t * ya.size());
+                           ob::rif(yb.data(), (int64_t)yb.size(), taus[t], rb.data() + (size_t)t * yb.size());
+                         }
+                         return OB_OK;
+                       });
+}
+
+// The RIF columns of the statistics (ob_rif.hpp): every argument check, for both groups, comes before the
+// context is looked at, so a bad call fails the same way with or without a GPU.
+static int decompose_statistics(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
+                                ob_results** out, const ob_cluster_config* ccfg = nullptr) {
+  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+  OB_TRY(ob::rif_spec_check(specs, n_specs));
+  return decompose_rif(ctx, cols, n_cols, n_rows, cfg, n_specs, out, ccfg,
+                       [&](const std::vector<double>& ya, const std::vector<double>& yb, std::vector<double>& ra,
+                           std::vector<double>& rb) {
+                         OB_TRY(ob::rif_input_check(ya.data(), (int64_t)ya.size(), specs, n_specs));
+                         OB_TRY(ob::rif_input_check(yb.data(), (int64_t)yb.size(), specs, n_specs));
+                         if (!ctx) return ob::fail(OB_E_INVALID, "null pointer");
+                         if (!ob::rif_hooks().device)
+                           return ob::fail(OB_E_UNSUPPORTED, "this build carries no RIF statistics pass");
+                         std::vector<double> stats(2 * (size_t)n_specs);
+                         OB_TRY(ob::rif_hooks().device(ctx, ya.data(), (int64_t)ya.size(), specs, n_specs, ra.data(),
+                                                       stats.data(), true));
+                         return ob::rif_hooks().device(ctx, yb.data(), (int64_t)yb.size(), specs, n_specs, rb.data(),
+                                                       stats.data() + n_specs, false);
+                       });
+}
+
+int ob_builder_decompose_statistics(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                    const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
+                                    ob_results** out) {
+  return decompose_statistics(ctx, cols, n_cols, n_rows, cfg, specs, n_specs, out);
+}
+
+int ob_builder_decompose_statistics_clustered(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                              const ob_builder_config* cfg, const ob_cluster_config* ccfg,
+                                              const ob_rif_spec* specs, int32_t n_specs, ob_results** out) {
+  if (!ccfg) return ob::fail(OB_E_INVALID, "incomplete cluster config");
+  return decompose_statistics(ctx, cols, n_cols, n_rows, cfg, specs, n_specs, out, ccfg);
 }
 
 int ob_builder_decompose_quantile(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,

@@ -9,6 +9,7 @@
 
 #include "ob_common.hpp"
 #include "ob_host.hpp"
+#include "ob_rif.hpp"
 
 namespace ob {
 
@@ -92,6 +93,37 @@ void rif(const double* y, int64_t n, double tau, double* out) {
   dens /= (nf * bw);
   if (dens < 1e-8) dens = 1e-8;
   for (int64_t i = 0; i < n; ++i) out[i] = q + (tau - (y[i] <= q ? 1.0 : 0.0)) / dens;
+}
+
+int rif_spec_check(const ob_rif_spec* specs, int n_specs) {
+  if (!specs || n_specs < 1) return fail(OB_E_INVALID, "no statistic given");
+  for (int s = 0; s < n_specs; ++s) {
+    const ob_rif_spec& sp = specs[s];
+    if (sp.stat != OB_RIF_VARIANCE && sp.stat != OB_RIF_GINI && sp.stat != OB_RIF_IQR)
+      return fail(OB_E_INVALID, "unknown RIF statistic %d", sp.stat);
+    if (sp.stat == OB_RIF_IQR && !(0.0 < sp.p1 && sp.p1 < sp.p0 && sp.p0 < 1.0))  // also refuses NaN
+      return fail(OB_E_INVALID, "quantile range needs 0 < lower < upper < 1, got upper %g, lower %g", sp.p0, sp.p1);
+  }
+  return OB_OK;
+}
+
+int rif_input_check(const double* y, int64_t n, const ob_rif_spec* specs, int n_specs) {
+  OB_TRY(rif_spec_check(specs, n_specs));
+  if (n < 2)
+    return fail(OB_E_INSUFFICIENT, "%sa RIF statistic needs at least 2 rows in a group, got %lld",
+                error_prefix(OB_E_INSUFFICIENT), (long long)n);
+  if (n > kRifMaxRows) return fail(OB_E_UNSUPPORTED, "RIF statistics take at most 2^28 rows per group");
+  if (!y) return fail(OB_E_INVALID, "null pointer");
+  bool gini = false;
+  for (int s = 0; s < n_specs; ++s) gini = gini || specs[s].stat == OB_RIF_GINI;
+  bool positive = false;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!std::isfinite(y[i])) return fail(OB_E_INVALID, "outcome row %lld is not finite", (long long)i);
+    if (gini && y[i] < 0.0) return fail(OB_E_INVALID, "gini: outcome row %lld is negative", (long long)i);
+    positive = positive || y[i] > 0.0;
+  }
+  if (gini && !positive) return fail(OB_E_INVALID, "gini: the mean outcome must be positive");
+  return OB_OK;
 }
 
 void aggregate(const double* rows, const uint8_t* ok, uint64_t n_reps, int row_len,

@@ -337,6 +337,75 @@ def rif(y, quantile: float):
     return out
 
 
+def parse_rif_statistic(stat, **params) -> tuple:
+    """The Python surface of ``ob_rif_spec`` -> (code, p0, p1). ``stat``: "variance", "gini" or "iqr" (with
+    ``upper`` = 0.9 and ``lower`` = 0.1 by default); also a ``(stat, params)`` pair or a dict with a ``stat`` key,
+    as ``decompose_statistics`` lists them. An unknown statistic is ``OB_E_INVALID``; the quantiles' range is
+    checked by the library."""
+    if isinstance(stat, dict):
+        params = {**{k: v for k, v in stat.items() if k != "stat"}, **params}
+        stat = stat.get("stat")
+    elif isinstance(stat, (tuple, list)):
+        if len(stat) != 2 or not isinstance(stat[1], dict):
+            raise ValueError("a statistic is a name, a (name, params) pair or a dict with a 'stat' key")
+        stat, params = stat[0], {**stat[1], **params}
+    if not isinstance(stat, str) or stat not in N.OB_RIF_STATS:
+        raise N.OaxacaError(N.OB_E_INVALID, f"unknown RIF statistic {stat!r} (variance, gini, iqr)")
+    allowed = ("upper", "lower") if stat == "iqr" else ()
+    extra = sorted(set(params) - set(allowed))
+    if extra:
+        raise ValueError(f"{stat}: unexpected parameter(s) {', '.join(extra)}")
+    if stat == "iqr":
+        return N.OB_RIF_IQR, float(params.get("upper", 0.9)), float(params.get("lower", 0.1))
+    return N.OB_RIF_STATS[stat], 0.0, 0.0
+
+
+def rif_specs(stats):
+    """A ctypes array of ``ob_rif_spec`` for a list of statistics (``parse_rif_statistic`` each)."""
+    parsed = [parse_rif_statistic(s) for s in stats]
+    if not parsed:
+        raise ValueError("statistics must be a non-empty sequence")
+    return (N.ob_rif_spec * len(parsed))(*[N.ob_rif_spec(*p) for p in parsed])
+
+
+def with_context(call, device: int | None = None):
+    """``call(ctx)`` -> rc on the device's context. Without a GPU the call still runs once with a NULL context, so
+    that its argument errors surface as they do on a GPU machine; good arguments leave the missing device as the
+    error."""
+    try:
+        ctx = N.context(device)
+    except (N.OaxacaError, ImportError):
+        rc = call(None)
+        if not (rc == N.OB_E_INVALID and b"null pointer" in N.lib().ob_last_error()):
+            N.check(rc)
+        raise
+    N.check(call(ctx))
+
+
+def rif_statistic(y, stat, device: int | None = None, **params):
+    """``ob_rif_stat``: the recentred influence function of ``stat`` ("variance", "gini", "iqr" with ``upper`` /
+    ``lower``) over ``y`` on the GPU -> (rif in y's order, the statistic). Unweighted; n >= 2."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 1:
+        raise ValueError("y must be one-dimensional")
+    spec = N.ob_rif_spec(*parse_rif_statistic(stat, **params))
+    out, value = np.empty_like(y), C.c_double()
+    with_context(lambda ctx: N.lib().ob_rif_stat(ctx, _dp(y), len(y), C.byref(spec), _dp(out), C.byref(value)), device)
+    return out, value.value
+
+
+def rif_scan_block() -> int:
+    """ob_rif_scan_block: sorted values per scan block of the RIF statistics pass."""
+    return int(N.lib().ob_rif_scan_block())
+
+
+def rif_last_timing() -> dict:
+    """ob_rif_last_timing: sort / scan / kde / scatter ms of this thread's last RIF statistics call."""
+    t = N.ob_rif_timing()
+    N.check(N.lib().ob_rif_last_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in N.ob_rif_timing._fields_}
+
+
 def logit(y, x, max_iter: int = 100, tol: float = 1e-6, device: int | None = None):
     """math/logit.rs:31-118 with the Newton passes on the GPU (``ob_logit``). ``x``: (n, k) with the
     intercept column included, ``k <= OB_LOGIT_MAX_K``. Returns (coefficients, predicted_probs,

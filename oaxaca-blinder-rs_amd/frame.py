@@ -39,6 +39,18 @@ class Frame:
     def names(self):
         return list(self.columns)
 
+    def with_f64_column(self, name: str, values) -> "Frame":
+        """A new frame that shares every column with this one except ``name``, replaced by ``values`` (Float64,
+        the nulls of the old column kept)."""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        if len(values) != self.nrows:
+            raise ValueError(f"column '{name}' has {len(values)} rows, expected {self.nrows}")
+        out = Frame({})
+        out.nrows = self.nrows
+        out.columns = dict(self.columns)
+        out.columns[name] = (N.OB_COL_F64, values, self.columns[name][2] if name in self.columns else None)
+        return out
+
     def as_c(self):
         if self._c is None:
             arr = (N.ob_column * max(len(self.columns), 1))()
