@@ -1145,6 +1145,65 @@ int ob_builder_decompose_statistics_clustered(ob_ctx* ctx, const ob_column* cols
                                               const ob_builder_config* cfg, const ob_cluster_config* ccfg,
                                               const ob_rif_spec* specs, int32_t n_specs, ob_results** out);
 
+/* ---- Decomposition of a gap in a 0/1 outcome: bootstrapped probit Oaxaca-Blinder -------------
+ * The nonlinear decomposition of Fairlie (1999), Yun (2004) and Bauer-Sinning (2008). No counterpart in the
+ * reference crate. X = [1, x_1..x_p], K = p + 1 <= OB_BINARY_MAX_K columns; Phi the standard normal cdf; c the
+ * replicate's OBRS-3 counts (every row once in the point pass); n_g = sum c;
+ *     Pbar(g, beta) = (1 / n_g) sum_{i in g} c_i Phi(x_i' beta).
+ * beta_A, beta_B: the probit of y on X per group, by ob_probit's iteration (Fisher scoring from 0, the 1e-9
+ * ridge, Phi clamped to [1e-10, 1 - 1e-10], 100 iterations, tol 1e-6). beta*: the group's own for
+ * OB_REF_GROUP_A / OB_REF_GROUP_B, the row-share average wA beta_A + (1 - wA) beta_B, wA = n_A / (n_A + n_B),
+ * for OB_REF_WEIGHTED / OB_REF_COTTON; OB_REF_POOLED / OB_REF_NEUMARK are OB_E_UNSUPPORTED.
+ *     total_gap    = Pbar(A, beta_A) - Pbar(B, beta_B)
+ *     explained    E = Pbar(A, beta*) - Pbar(B, beta*),  unexplained U = total_gap - E = U_A + U_B,
+ *                  U_A = Pbar(A, beta_A) - Pbar(A, beta*), U_B = Pbar(B, beta*) - Pbar(B, beta_B)
+ *     endowments   = Pbar(A, beta_B) - Pbar(B, beta_B),  coefficients = Pbar(B, beta_A) - Pbar(B, beta_B),
+ *     interaction  = total_gap - endowments - coefficients
+ *     explained_k   = E (xbar_A^k - xbar_B^k) beta*^k / sum_j (xbar_A^j - xbar_B^j) beta*^j      (Yun's weights)
+ *     unexplained_k = U_A xbar_A^k (beta_A^k - beta*^k) / sum_j xbar_A^j (beta_A^j - beta*^j)
+ *                   + U_B xbar_B^k (beta*^k - beta_B^k) / sum_j xbar_B^j (beta*^j - beta_B^j)
+ * with xbar_g the replicate's count-weighted column means; a part whose denominator is exactly 0 contributes 0.0.
+ * Row of a replicate, ob_binary_row_len(K) = 6 + 7K + 8 doubles:
+ *     [0, 6)  explained, unexplained, endowments, coefficients, interaction, total_gap
+ *     K explained_k | K unexplained_k | beta_A, beta_B, xbar_A, xbar_B, beta* (K each)
+ *     Pbar(A,beta_A), Pbar(A,beta_B), Pbar(A,beta*), Pbar(B,beta_A), Pbar(B,beta_B), Pbar(B,beta*) | ybar_A, ybar_B
+ * A replicate whose probit cannot solve its Hessian in either group has ok = 0 and is dropped and counted by
+ * ob_prepared_finish; a point pass that fails so is OB_E_LINALG. Every sum is f64 in chunk order without atomics:
+ * a replicate's row has the same bytes alone, in any batch and at any first_rep.
+ * Errors of the frame entry points, all before any device work and before the context is read: model
+ * OB_BINARY_LOGIT, weights, normalize, Heckman settings, Pooled / Neumark: OB_E_UNSUPPORTED; a null in a named
+ * column: OB_E_INVALID; K > OB_BINARY_MAX_K: OB_E_UNSUPPORTED; an outcome value other than exactly 0.0 or 1.0, or a
+ * group whose outcome is constant: OB_E_INVALID; a group with rows <= K: OB_E_INSUFFICIENT. On a handle prepared
+ * here ob_prepared_boot, ob_prepared_boot_device (which synchronizes its stream) and ob_prepared_finish work;
+ * ob_prepared_boot_sharded, ob_prepared_jackknife and ob_prepared_finish_bca are OB_E_UNSUPPORTED. */
+#define OB_BINARY_MAX_K 32
+#define OB_BINARY_PROBIT 0
+#define OB_BINARY_LOGIT 1 /* OB_E_UNSUPPORTED: the per-replicate fit kernels are probit's */
+typedef struct {
+  double probit_ms;          /* the probit passes, summed over iterations and batches */
+  int32_t probit_launches;
+  int32_t probit_iterations; /* the longest batch's */
+  double means_ms;           /* the mean-probability pass */
+  double epilogue_ms;        /* the per-replicate rows */
+} ob_binary_timing;
+int ob_binary_row_len(int32_t k);
+/* The shape limits above on their own (host only). */
+int ob_binary_check_shape(int32_t k, int64_t n_a, int64_t n_b);
+/* The mean-probability pass alone over one group: x (n x k, column-major, ldx >= n, column 0 all ones), y, counts
+   (n bytes, or NULL for every row once), betas [3][k]. out[5 + k]: Pbar(beta_0), Pbar(beta_1), Pbar(beta_2), ybar,
+   sum c, xbar_0 .. xbar_{k-1}. */
+int ob_binary_means(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, int64_t n, int32_t k,
+                    const uint8_t* counts, const double* betas, double* out);
+/* HIP-event ms of the calling thread's last binary boot (or prepare: the point pass). */
+int ob_binary_last_timing(ob_binary_timing* out);
+int ob_builder_prepare_binary(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                              const ob_builder_config* cfg, int32_t model, ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish. The tables are ob_builder_run's; total_gap is the predicted gap. */
+int ob_builder_run_binary(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                          const ob_builder_config* cfg, int32_t model, ob_results** out);
+/* The point-estimate row of a prepared run (any kind), owned by the handle. */
+int ob_prepared_point_row(const ob_prepared* prep, const double** data, int64_t* len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,13 +6,13 @@ hyphen). See DESIGN.md for the kernels and INTEGRATION.md for the Rust/C binding
 """
 from . import _native
 from ._native import OaxacaError
-from .api import (Adjustment, AkmBuilder, AkmResult, BudgetAdjustment, ComponentResult, Contribution, DataSummary,
+from .api import (Adjustment, AkmBuilder, AkmResult, BinaryDecompositionResults, BudgetAdjustment, ComponentResult, Contribution, DataSummary,
                   DecompositionDetail, DecompositionResult, DflResult, JackknifeResult, defensibility_message, parse_rust_f64, FrontierPoint, MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder,
                   OaxacaResults, OptimizationResult, PreparedRun,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
                   ReferenceCoefficients, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
                   parse_formula, run_dfl, run_dfl_from_csv)
-from .engine import (cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
+from .engine import (binary_check_shape, binary_last_timing, binary_means, binary_row_len, cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
                      cluster_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
                      knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
@@ -37,4 +37,5 @@ __all__ = [
     "aggregate_bca",
     "cluster_index", "cluster_gram", "cluster_counts", "cluster_apply", "cluster_check_shape", "cluster_last_timing",
     "rif_statistic", "rif_last_timing", "rif_scan_block", "parse_rif_statistic",
+    "BinaryDecompositionResults", "binary_means", "binary_check_shape", "binary_row_len", "binary_last_timing",
 ]

@@ -65,6 +65,8 @@ EXPORTED = (
     "ob_builder_decompose_quantiles_clustered", "ob_prepared_cluster_info", "ob_results_n_clusters",
     "ob_rif_stat", "ob_rif_scan_block", "ob_rif_last_timing", "ob_builder_decompose_statistics",
     "ob_builder_decompose_statistics_clustered",
+    "ob_binary_row_len", "ob_binary_check_shape", "ob_binary_means", "ob_binary_last_timing",
+    "ob_builder_prepare_binary", "ob_builder_run_binary", "ob_prepared_point_row",
 )
 
 OB_E_CONVERGENCE = 12
@@ -82,6 +84,9 @@ OB_MATCH_MAX_DIM, OB_MATCH_MAX_K = 64, 16
 OB_MATCH_EUCLIDEAN, OB_MATCH_MAHALANOBIS, OB_MATCH_PSM = 0, 1, 2
 OB_RIF_VARIANCE, OB_RIF_GINI, OB_RIF_IQR = 0, 1, 2
 OB_RIF_STATS = {"variance": OB_RIF_VARIANCE, "gini": OB_RIF_GINI, "iqr": OB_RIF_IQR}
+OB_BINARY_MAX_K = 32  # design columns, the intercept included
+OB_BINARY_PROBIT, OB_BINARY_LOGIT = 0, 1
+OB_BINARY_MODELS = {"probit": OB_BINARY_PROBIT, "logit": OB_BINARY_LOGIT}
 
 
 class OaxacaError(RuntimeError):
@@ -238,6 +243,11 @@ class ob_rif_spec(C.Structure):
 class ob_rif_timing(C.Structure):
     _fields_ = [("sort_ms", C.c_double), ("scan_ms", C.c_double), ("kde_ms", C.c_double),
                 ("scatter_ms", C.c_double)]
+
+
+class ob_binary_timing(C.Structure):
+    _fields_ = [("probit_ms", C.c_double), ("probit_launches", C.c_int32), ("probit_iterations", C.c_int32),
+                ("means_ms", C.c_double), ("epilogue_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -452,6 +462,15 @@ _SIGS = {
                                                             C.POINTER(ob_builder_config),
                                                             C.POINTER(ob_cluster_config), C.POINTER(ob_rif_spec),
                                                             C.c_int32, C.POINTER(_P)]),
+    "ob_binary_row_len": (C.c_int, [C.c_int32]),
+    "ob_binary_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64]),
+    "ob_binary_means": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int32, _U8, _D, _D]),
+    "ob_binary_last_timing": (C.c_int, [C.POINTER(ob_binary_timing)]),
+    "ob_builder_prepare_binary": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                            C.POINTER(ob_builder_config), C.c_int32, C.POINTER(_P)]),
+    "ob_builder_run_binary": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                        C.POINTER(ob_builder_config), C.c_int32, C.POINTER(_P)]),
+    "ob_prepared_point_row": (C.c_int, [_P, C.POINTER(_D), C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -299,6 +299,49 @@ class OaxacaResults:
                 f"endowments (observables), while {u / t * 100:.1f}% is unexplained (coefficients/discrimination).")
 
 
+@dataclass
+class BinaryDecompositionResults:
+    """``OaxacaBuilder.decompose_binary``: the probit Oaxaca-Blinder decomposition of a 0/1 outcome. The
+    component objects are ``OaxacaResults``' (estimate, standard error, percentile interval, p-value over the
+    bootstrap); ``total_gap`` is the predicted gap Pbar(A, beta_A) - Pbar(B, beta_B), ``raw_gap`` the gap in the
+    groups' observed rates; ``probabilities`` maps (group, coefficients) to the six mean probabilities."""
+    model: str
+    total_gap: float
+    raw_gap: float
+    two_fold: list
+    three_fold: list
+    detailed_explained: list
+    detailed_unexplained: list
+    probabilities: dict
+    beta_a: np.ndarray = field(repr=False)
+    beta_b: np.ndarray = field(repr=False)
+    beta_star: np.ndarray = field(repr=False)
+    xa_mean: np.ndarray = field(repr=False)
+    xb_mean: np.ndarray = field(repr=False)
+    names: list = field(repr=False)
+    n_a: int = 0
+    n_b: int = 0
+    n_failed: int = 0
+
+    def to_json(self) -> str:
+        def fix(v):  # serde_json writes non-finite floats as null
+            return v if isinstance(v, str) or np.isfinite(v) else None
+
+        def comps(cs):
+            return [{k: fix(v) for k, v in c.__dict__.items()} for c in cs]
+
+        return json.dumps({
+            "model": self.model, "total_gap": fix(self.total_gap), "raw_gap": fix(self.raw_gap),
+            "two_fold": comps(self.two_fold), "three_fold": comps(self.three_fold),
+            "detailed_explained": comps(self.detailed_explained),
+            "detailed_unexplained": comps(self.detailed_unexplained),
+            "probabilities": {f"{g}|{b}": fix(v) for (g, b), v in self.probabilities.items()},
+            "names": list(self.names),
+            "beta_a": [fix(float(v)) for v in self.beta_a], "beta_b": [fix(float(v)) for v in self.beta_b],
+            "beta_star": [fix(float(v)) for v in self.beta_star],
+            "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed})
+
+
 def _jackknife_out(k: int):
     c = 6 + 2 * k
     bufs = (np.zeros(c), np.zeros((2, c, 3)), np.zeros((c, 3)))
@@ -863,6 +906,53 @@ class OaxacaBuilder:
                 ctx, cols, ncol, nrow, C.byref(cfg), specs, len(parsed), out), self._device)
         return [_results_from_c(C.c_void_p(h)) for h in hs]
 
+    def prepare_binary(self, model: str = "probit") -> "PreparedRun":
+        from .engine import with_context
+
+        if model not in N.OB_BINARY_MODELS:
+            raise ValueError(f"unknown binary model {model!r}: 'probit' (or 'logit', which is refused)")
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, "binary decomposition: the cluster bootstrap is outside its scope")
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        h = C.c_void_p()
+        code = N.OB_BINARY_MODELS[model]
+        if self._ctx is not None:
+            N.check(lib.ob_builder_prepare_binary(self._ctx, cols, ncol, nrow, C.byref(cfg), code, C.byref(h)))
+        else:
+            with_context(lambda ctx: lib.ob_builder_prepare_binary(ctx, cols, ncol, nrow, C.byref(cfg), code,
+                                                                   C.byref(h)), self._device)
+        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+
+    def decompose_binary(self, model: str = "probit") -> "BinaryDecompositionResults":
+        """Extension (no counterpart in the reference crate): the nonlinear decomposition of a gap in a 0/1
+        outcome (Fairlie 1999, Yun 2004, Bauer-Sinning 2008): a probit per group and replicate on the GPU, the
+        counterfactual mean probabilities Pbar(X_g, beta), two-fold and three-fold terms from them and Yun's
+        detailed terms, bootstrapped like ``run()``. Reference coefficients GroupA, GroupB, Weighted or Cotton.
+        Refused (``OB_E_UNSUPPORTED``): ``model="logit"``, weights, ``normalize``, ``cluster``, Heckman settings,
+        Pooled / Neumark, more than 32 design columns."""
+        pr = self.prepare_binary(model)
+        try:
+            rows, ok = pr.boot(0, self._bootstrap_reps)
+            res = pr.finish(rows, ok)
+            point = pr.point_row()
+        finally:
+            pr.close()
+        k = (len(point) - 14) // 7
+        tail = point[6 + 2 * k:]
+        names = [c.name for c in res.two_fold.detailed_explained]
+        keys = [(g, b) for g in ("A", "B") for b in ("beta_a", "beta_b", "beta_star")]
+        return BinaryDecompositionResults(
+            model=model, total_gap=float(point[5]), raw_gap=float(tail[5 * k + 6] - tail[5 * k + 7]),
+            two_fold=res.two_fold.aggregate, three_fold=res.three_fold.aggregate,
+            detailed_explained=res.two_fold.detailed_explained,
+            detailed_unexplained=res.two_fold.detailed_unexplained,
+            probabilities={key: float(v) for key, v in zip(keys, tail[5 * k:5 * k + 6])},
+            beta_a=tail[:k].copy(), beta_b=tail[k:2 * k].copy(), beta_star=tail[4 * k:5 * k].copy(),
+            xa_mean=tail[2 * k:3 * k].copy(), xb_mean=tail[3 * k:4 * k].copy(), names=names,
+            n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed)
+
     def statistic_builder(self, stat, **params) -> "OaxacaBuilder":
         """A fresh builder over this frame with the outcome replaced by the statistic's RIF of each group's
         outcome (the rows ``run()`` would keep, group by group, as ``decompose_statistic`` forms it), so that
@@ -963,6 +1053,13 @@ class PreparedRun:
         """Enqueue replicates into device buffers (e.g. torch tensors' data_ptr()) on ``stream``."""
         N.check(N.lib().ob_prepared_boot_device(self._h, first_rep, n_reps, C.c_void_p(rows_ptr),
                                                 C.c_void_p(ok_ptr), C.c_void_p(stream or 0)))
+
+    def point_row(self) -> np.ndarray:
+        """ob_prepared_point_row: the point-estimate row (a copy)."""
+        ptr = C.POINTER(C.c_double)()
+        n = C.c_int64()
+        N.check(N.lib().ob_prepared_point_row(self._h, C.byref(ptr), C.byref(n)))
+        return np.ctypeslib.as_array(ptr, shape=(n.value,)).copy() if n.value else np.zeros(0)
 
     def sync(self):
         N.check(N.lib().ob_panel_sync(N.lib().ob_prepared_panel(self._h)))

@@ -27,6 +27,7 @@
 #include "ob_frame.hpp"
 #include "ob_host.hpp"
 #include "ob_builder.hpp"
+#include "ob_binary.hpp"
 #include "ob_cluster.hpp"
 #include "ob_mm.hpp"
 #include "ob_rif.hpp"
@@ -36,6 +37,11 @@ namespace ob {
 
 ClusterHooks& cluster_hooks() {
   static ClusterHooks h;
+  return h;
+}
+
+BinaryHooks& binary_hooks() {
+  static BinaryHooks h;
   return h;
 }
 
@@ -842,12 +848,14 @@ ob_panel* ob_prepared_panel(ob_prepared* p) { return p ? p->panel : nullptr; }
 int ob_prepared_boot(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
   if (p->cluster) return ob::cluster_hooks().boot_host(p, first_rep, n_reps, rows, ok);
+  if (p->binary) return ob::binary_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   return ob_boot_run(p->panel, p->seed, first_rep, n_reps, p->ref, rows, ok);
 }
 
 int ob_prepared_boot_sharded(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
   if (p->cluster) return ob::fail(OB_E_UNSUPPORTED, "cluster bootstrap: sharded runs are outside its scope");
+  if (p->binary) return ob::fail(OB_E_UNSUPPORTED, "binary decomposition: sharded runs are outside its scope");
   // the RCCL all-gather moves only the columns finish() aggregates: two-fold, three-fold, total
   // gap, detailed [0, 6 + 2 Kd) and a Heckman row's selection terms after its 5K' tail
   const int kd = p->k + p->n_base, sel0 = 6 + 2 * kd + 5 * p->k;
@@ -869,6 +877,8 @@ int ob_prepared_boot_device(ob_prepared* p, uint64_t first_rep, uint64_t n_reps,
   if (p->cluster)
     return ob::cluster_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok,
                                            reinterpret_cast<hipStream_t>(hip_stream));
+  if (p->binary)
+    return ob::binary_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
   return ob_boot_run_device(p->panel, p->seed, first_rep, n_reps, p->ref, d_rows, d_ok, hip_stream);
 }
 
@@ -881,6 +891,7 @@ int ob_prepared_finish(ob_prepared* p, const double* rows, const uint8_t* ok, ui
 void ob_prepared_destroy(ob_prepared* p) {
   if (!p) return;
   if (p->cluster) ob::cluster_hooks().free_state(p->cluster);
+  if (p->binary) ob::binary_hooks().free_state(p->binary);
   ob_panel_destroy(p->panel);
   delete p;
 }

@@ -32,6 +32,7 @@ struct Config {
 };
 
 struct ClusterState;
+struct BinaryState;
 
 }  // namespace ob
 
@@ -69,6 +70,8 @@ struct ob_prepared {
   bool has_jack = false;
   // ob_builder_prepare_clustered: the cluster index and Q on the device; boots run through ob_cluster.hip
   ob::ClusterState* cluster = nullptr;
+  // ob_builder_prepare_binary: the probit panel and workspace on the device; boots run through ob_binary.hip
+  ob::BinaryState* binary = nullptr;
 };
 
 namespace ob {

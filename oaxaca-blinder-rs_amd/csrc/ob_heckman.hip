@@ -31,6 +31,7 @@
 #include "ob_device.hpp"
 #include "ob_engine.hpp"
 #include "ob_hip.hpp"
+#include "ob_normal.hpp"
 #include "ob_heckman.hpp"
 #include "ob_options.hpp"
 #include "ob_spec.h"
@@ -38,74 +39,7 @@
 namespace {
 
 constexpr int kHB = 256;
-constexpr uint32_t kDone = 1u, kFailed = 2u;
-
-// statrs Normal(0, 1): pdf = exp(-z^2 / 2) / sqrt(2 pi), cdf = erfc(-z / sqrt 2) / 2.
-// (The constant divisions are multiplications by the reciprocals: a last-bit difference.)
-__device__ __forceinline__ double npdf(double z) { return exp(-0.5 * z * z) * 0.3989422804014327; }
-__device__ __forceinline__ double ncdf(double z) { return 0.5 * erfc(-z * 0.7071067811865476); }
-
-// pdf and cdf together from one exp(-z^2 / 2) (OB_HK_ERFC=1): erfc(x), x = -z / sqrt 2, by W. J.
-// Cody's rational Chebyshev approximations (Math. Comp. 23 (1969), the CALERF regions |x| < 0.46875,
-// <= 4, > 4), whose two outer regions are exp(-x^2) times a rational function -- exp(-x^2) is the
-// pdf's exp(-z^2 / 2). Checked against scipy's erfc on z in [-12, 12]: at most 3e-14 relative (the
-// rounding of z^2 inside the shared exp, amplified at large |z|; about 1e-15 where the clamped
-// probabilities are used).
-__device__ __forceinline__ double nd_rcp(double v) {  // 1/v within ~1 ulp (as hk_rcp below)
-  double r = __builtin_amdgcn_rcp(v);
-  r = fma(fma(-v, r, 1.0), r, r);
-  return fma(fma(-v, r, 1.0), r, r);
-}
-__device__ __forceinline__ void npdf_ncdf(double z, double& pdf, double& cdf) {
-  const double x = -z * 0.7071067811865476, y = fabs(x);
-  const double e = exp(-0.5 * z * z);
-  pdf = e * 0.3989422804014327;
-  double r;
-  if (y <= 0.46875) {
-    const double ysq = y * y;
-    double xn = 1.85777706184603153e-1 * ysq, xd = ysq;
-    xn = (xn + 3.16112374387056560e00) * ysq;
-    xd = (xd + 2.36012909523441209e01) * ysq;
-    xn = (xn + 1.13864154151050156e02) * ysq;
-    xd = (xd + 2.44024637934444173e02) * ysq;
-    xn = (xn + 3.77485237685302021e02) * ysq;
-    xd = (xd + 1.28261652607737228e03) * ysq;
-    cdf = 0.5 * (1.0 - x * (xn + 3.20937758913846947e03) * nd_rcp(xd + 2.84423683343917062e03));
-    return;
-  }
-  if (y <= 4.0) {
-    double xn = 2.15311535474403846e-8 * y, xd = y;
-    xn = (xn + 5.64188496988670089e-1) * y;
-    xd = (xd + 1.57449261107098347e01) * y;
-    xn = (xn + 8.88314979438837594e00) * y;
-    xd = (xd + 1.17693950891312499e02) * y;
-    xn = (xn + 6.61191906371416295e01) * y;
-    xd = (xd + 5.37181101862009858e02) * y;
-    xn = (xn + 2.98635138197400131e02) * y;
-    xd = (xd + 1.62138957456669019e03) * y;
-    xn = (xn + 8.81952221241769090e02) * y;
-    xd = (xd + 3.29079923573345963e03) * y;
-    xn = (xn + 1.71204761263407058e03) * y;
-    xd = (xd + 4.36261909014324716e03) * y;
-    xn = (xn + 2.05107837782607147e03) * y;
-    xd = (xd + 3.43936767414372164e03) * y;
-    r = (xn + 1.23033935479799725e03) * nd_rcp(xd + 1.23033935480374942e03) * e;
-  } else {
-    const double iy = nd_rcp(y), ysq = iy * iy;
-    double xn = 1.63153871373020978e-2 * ysq, xd = ysq;
-    xn = (xn + 3.05326634961232344e-1) * ysq;
-    xd = (xd + 2.56852019228982242e00) * ysq;
-    xn = (xn + 3.60344899949804439e-1) * ysq;
-    xd = (xd + 1.87295284992346725e00) * ysq;
-    xn = (xn + 1.25781726111229246e-1) * ysq;
-    xd = (xd + 5.27905102951428412e-1) * ysq;
-    xn = (xn + 1.60837851487422766e-2) * ysq;
-    xd = (xd + 6.05183413124413191e-2) * ysq;
-    r = ysq * (xn + 6.58749161529837803e-4) * nd_rcp(xd + 2.33520497626869185e-3);
-    r = (5.6418958354775628695e-1 - r) * iy * e;
-  }
-  cdf = 0.5 * (x >= 0.0 ? r : 2.0 - r);
-}
+constexpr uint32_t kDone = ob::kProbitDone, kFailed = ob::kProbitFailed;
 
 // The probit and sums kernels take pdf and cdf from npdf_ncdf (one exp per row; probit launch 11.8
 // -> 9.0 ms at configs[1] + selection, profiles/r04_ab_heckman_erfc.txt) unless option hk_erfc = 0
@@ -1017,8 +951,16 @@ hipError_t probit_iter(const ob_heck_seg& a, hipStream_t s, hipEvent_t* ev) {
 namespace ob {
 
 // The Fisher-scoring loop of a segment from gamma = 0 (probit.rs:48-147), each replicate stopping on
-// its own; ev: [0, 1] around each probit pass when tm is given.
-static int probit_loop(const ob_heck_seg& a, hipStream_t s, int* iters, ob_heck_times* tm, hipEvent_t* ev) {
+// its own. On return (after a stream sync) gamma and hflags are final; the outcome fields of the
+// segment (p, gram, rows, ok) are not read. The probit stage of heckman_segment, of ob_probit and of
+// the binary decomposition (ob_binary.hip).
+int probit_stage(const ob_heck_seg& a, hipStream_t s, int* iters, ob_heck_times* tm) {
+  if (a.ks < 1 || a.ks > kHeckWideMaxKs || a.rep_pad % 64 != 0 || a.part_pad < a.n_reps ||
+      (a.ks <= kHeckMaxKs && a.part_pad != a.rep_pad))
+    return ob::fail(OB_E_INVALID, "probit stage: bad shape");
+  Events<2> evs;  // around each probit pass when tm is given
+  if (tm) OB_HIP(evs.create());
+  hipEvent_t* const ev = evs.e;
   if (a.part_pad == a.rep_pad) {
     OB_HIP(hipMemsetAsync(a.gamma, 0, sizeof(double) * 2 * a.rep_pad * a.ks, s));
     OB_HIP(hipMemsetAsync(a.hflags, 0, sizeof(uint32_t) * 2 * a.rep_pad, s));
@@ -1054,28 +996,21 @@ int heckman_segment(const ob_heck_seg& a, hipStream_t s, int* iters, ob_heck_tim
   if (a.ks < 1 || a.ks > kHeckWideMaxKs || a.p > kHeckMaxP || a.rep_pad % 64 != 0 || a.part_pad < a.n_reps ||
       (!wide && a.part_pad != a.rep_pad))
     return ob::fail(OB_E_INVALID, "heckman segment: bad shape");
-  struct Events {  // [0, 1] around each probit pass, [2, 3] around the sums pass
-    hipEvent_t e[4] = {};
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  if (tm)
-    for (hipEvent_t& x : ev.e) OB_HIP(hipEventCreate(&x));
-  OB_TRY(probit_loop(a, s, iters, tm, ev.e));
+  Events<2> ev;  // around the sums pass
+  if (tm) OB_HIP(ev.create());
+  OB_TRY(probit_stage(a, s, iters, tm));
   if (wide) {  // the IMR sums on the MFMA kernel, then the same solve
-    if (tm) OB_HIP(hipEventRecord(ev.e[2], s));
+    if (tm) OB_HIP(hipEventRecord(ev.e[0], s));
     OB_HIP(launch_wide(a, true, s));
-    if (tm) OB_HIP(hipEventRecord(ev.e[3], s));
+    if (tm) OB_HIP(hipEventRecord(ev.e[1], s));
     const size_t lds = heck_solve_lds(a);
     OB_HIP(hipFuncSetAttribute((const void*)ob_heck_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(ob_heck_solve_kernel, dim3(a.n_reps), dim3(64), lds, s, a);
     OB_HIP(hipGetLastError());
     if (tm) {
       float ms = 0.f;
-      OB_HIP(hipEventSynchronize(ev.e[3]));
-      OB_HIP(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+      OB_HIP(hipEventSynchronize(ev.e[1]));
+      OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
       tm->sums_ms += ms;
     }
     return OB_OK;
@@ -1097,19 +1032,19 @@ int heckman_segment(const ob_heck_seg& a, hipStream_t s, int* iters, ob_heck_tim
                    : nb == 40 ? (cody ? sums(std::integral_constant<int, 40>{}, T{}) : sums(std::integral_constant<int, 40>{}, F{}))
                               : (cody ? sums(std::integral_constant<int, 64>{}, T{}) : sums(std::integral_constant<int, 64>{}, F{}));
   OB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sums));
-  if (tm) OB_HIP(hipEventRecord(ev.e[2], s));
+  if (tm) OB_HIP(hipEventRecord(ev.e[0], s));
   void* args[] = {const_cast<ob_heck_seg*>(&a)};
   OB_HIP(hipLaunchKernel(fn, grid, dim3(kHB), args, lds_sums, s));
   OB_HIP(hipGetLastError());
-  if (tm) OB_HIP(hipEventRecord(ev.e[3], s));
+  if (tm) OB_HIP(hipEventRecord(ev.e[1], s));
   const size_t lds = heck_solve_lds(a);
   OB_HIP(hipFuncSetAttribute((const void*)ob_heck_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(ob_heck_solve_kernel, dim3(a.n_reps), dim3(64), lds, s, a);
   OB_HIP(hipGetLastError());
   if (tm) {  // the events die with this call: read the sums pass now
     float ms = 0.f;
-    OB_HIP(hipEventSynchronize(ev.e[3]));
-    OB_HIP(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+    OB_HIP(hipEventSynchronize(ev.e[1]));
+    OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
     tm->sums_ms += ms;
   }
   return OB_OK;
@@ -1170,7 +1105,7 @@ extern "C" int ob_probit(ob_ctx* ctx, const double* x, int64_t ldx, const double
   h.max_iter = max_iter;
   h.tol = tol;
   int it = 0;
-  OB_TRY(ob::probit_loop(h, s, &it, nullptr, nullptr));
+  OB_TRY(ob::probit_stage(h, s, &it, nullptr));
   uint32_t fl = 0;
   OB_HIP(hipMemcpyAsync(beta, h.gamma, sizeof(double) * k, hipMemcpyDeviceToHost, s));
   OB_HIP(hipMemcpyAsync(&fl, h.hflags, sizeof(uint32_t), hipMemcpyDeviceToHost, s));

@@ -72,6 +72,12 @@ struct ob_heck_times {
 // (after a stream sync) rows/ok are final. iters: the probit iterations run; tm (optional): the
 // kernel timings, added to.
 int heckman_segment(const ob_heck_seg& h, hipStream_t s, int* iters, ob_heck_times* tm = nullptr);
+// The probit stage alone: Fisher scoring from gamma = 0 on the panel columns s (sz_col), z_1.. that
+// follow it, over the segment's counts and chunks. On return (after a stream sync) gamma and hflags
+// (bit 0 done, bit 1 failed: the Hessian could not be solved) are final. Reads none of p, weighted,
+// gram, rows, ok, ref_mode. heckman_segment and the binary decomposition (ob_binary.hip) call it.
+int probit_stage(const ob_heck_seg& h, hipStream_t s, int* iters, ob_heck_times* tm = nullptr);
+constexpr uint32_t kProbitDone = 1u, kProbitFailed = 2u;  // hflags bits
 // Values of `partial` per (chunk, replicate) that a segment of this shape needs.
 inline size_t heck_partial_len(int k, int ks) {
   const int a = heck_probit_len(ks), b = heck_sums_len(k, ks);

@@ -443,6 +443,48 @@ def probit(x, y, max_iter: int = 100, tol: float = 1e-6, device: int | None = No
     return beta, bool(conv.value), int(iters.value)
 
 
+def binary_means(x, y, betas, counts=None, device: int | None = None) -> dict:
+    """The mean-probability pass of the binary decomposition alone (``ob_binary_means``) over one group.
+    ``x``: (n, k) with the intercept (all ones) as column 0, ``k <= 32``; ``y``: the outcome; ``betas``: (3, k);
+    ``counts``: n resample counts below 256 (``None``: every row once). Returns ``probabilities`` (the three
+    count-weighted means of Phi(x'beta)), ``y_mean``, ``n`` (the counts' sum) and ``x_mean`` (k)."""
+    xf = np.asfortranarray(x, dtype=np.float64)
+    if xf.ndim != 2:
+        raise ValueError("x must be (n, k)")
+    n, k = xf.shape
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    b = np.ascontiguousarray(betas, dtype=np.float64)
+    if y.shape != (n,) or b.shape != (3, k):
+        raise ValueError("y must have one entry per row of x and betas must be (3, k)")
+    cp = None
+    if counts is not None:
+        c = np.ascontiguousarray(counts)
+        if c.shape != (n,) or (c < 0).any() or (c > 255).any():
+            raise ValueError("counts must be n integers in [0, 255]")
+        c8 = c.astype(np.uint8)
+        cp = c8.ctypes.data_as(C.POINTER(C.c_uint8))
+    out = np.empty(5 + k)
+    with_context(lambda ctx: N.lib().ob_binary_means(ctx, _dp(xf), max(n, 1), _dp(y), n, k, cp, _dp(b), _dp(out)), device)
+    return {"probabilities": out[:3].copy(), "y_mean": float(out[3]), "n": float(out[4]), "x_mean": out[5:].copy()}
+
+
+def binary_check_shape(k: int, n_a: int, n_b: int) -> None:
+    """ob_binary_check_shape: raises OaxacaError where a binary decomposition would (host only)."""
+    N.check(N.lib().ob_binary_check_shape(int(k), int(n_a), int(n_b)))
+
+
+def binary_row_len(k: int) -> int:
+    """ob_binary_row_len: 6 + 7k + 8 doubles per replicate of a binary decomposition."""
+    return int(N.lib().ob_binary_row_len(int(k)))
+
+
+def binary_last_timing() -> dict:
+    """ob_binary_last_timing: HIP-event ms of this thread's last binary boot (probit, means pass, rows)."""
+    t = N.ob_binary_timing()
+    N.check(N.lib().ob_binary_last_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in N.ob_binary_timing._fields_}
+
+
 def knn(queries, controls, k: int, device: int | None = None):
     """The min(k, n_c) nearest controls of each query (``ob_knn``): squared Euclidean distance summed
     in covariate order without FMA, ties by control position. ``queries``: (n_q, d), ``controls``:
