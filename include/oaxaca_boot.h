@@ -1204,6 +1204,90 @@ int ob_builder_run_binary(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, in
 /* The point-estimate row of a prepared run (any kind), owned by the handle. */
 int ob_prepared_point_row(const ob_prepared* prep, const double** data, int64_t* len);
 
+/* ---- Reweighted Oaxaca-Blinder decomposition with a bootstrapped propensity logit -------------
+ * Fortin, Lemieux and Firpo (2011), section 5; Stata's `oaxaca_rif ..., rwlogit()`. No counterpart in the reference
+ * crate (dfl.rs stops at densities). A is the non-reference group, B cfg->reference_group; x the design row with the
+ * intercept (K <= OB_REWEIGHT_MAX_K columns, the builder's dummies included); w the sample weight (1 without
+ * cfg->weights); c the replicate's OBRS-3 count of the row (1 in the point pass).
+ *   Propensity: the logit of D = 1[A] on x over the stacked rows of A and B, each row's log-likelihood term times
+ *   c w, by the Newton iteration of math/logit.rs:31-118: gamma from 0, p clamped to [1e-10, 1 - 1e-10], the
+ *   information matrix sum c w p (1 - p) x x' solved by Cholesky, stop when ||step||_2 < 1e-6, at most 100 passes.
+ *   Weights: psi = p / (1 - p) with the clamped p. The factor P(B) / P(A) of dfl.rs:116 is left out: every quantity
+ *   below is a ratio of psi-weighted sums, in which it cancels.
+ *   Fits, each the Cholesky solve of the weighted extended Gram: (beta_A, xbar_A, ybar_A) on A's rows with weights
+ *   c w; (beta_B, xbar_B, ybar_B) on B's rows with c w; (beta_C, xbar_C, ybar_C) on B's rows with c w psi -- the
+ *   counterfactual sample C. cfg->reference_coeffs is ignored: the decomposition defines its own three fits.
+ *     total_gap           = ybar_A - ybar_B
+ *     composition         = xbar_C . beta_C - xbar_B . beta_B      structure         = xbar_A . beta_A - xbar_C . beta_C
+ *     pure_explained      = (xbar_C - xbar_B) . beta_B             pure_unexplained  = xbar_A . (beta_A - beta_C)
+ *     specification_error = xbar_C . (beta_C - beta_B)             reweighting_error = (xbar_A - xbar_C) . beta_C
+ * Row of a replicate, ob_reweight_row_len(K) = 7 + 11 K + 5 doubles:
+ *     [0, 7)  total_gap, composition, structure, pure_explained, specification_error, pure_unexplained,
+ *             reweighting_error (OB_RW_ROW_*)
+ *     K pure_explained_k | K specification_error_k | K pure_unexplained_k | K reweighting_error_k (the summands)
+ *     beta_A, beta_B, beta_C, xbar_A, xbar_B, xbar_C, gamma (K each)
+ *     ybar_A, ybar_B, ybar_C | the effective sample size of psi on B, (sum c w psi)^2 / sum c (w psi)^2 | the
+ *     logit's pass count
+ * A replicate whose logit does not converge within 100 passes, whose information matrix has no Cholesky factor
+ * (separation is the usual cause) or one of whose three fits fails has ok = 0 and a NaN row; ob_prepared_finish drops
+ * and counts it. A point pass that fails so is OB_E_LINALG "Failed to solve Information Matrix in Logit. Perfect
+ * separation?", ob_dfl_run's error. Every sum is f64 in chunk order without atomics: a replicate's row has the same
+ * bytes alone, in any batch and at any first_rep. Option "hk_batch" caps a batch at n 64-replicate blocks (default:
+ * as many as keep the chunk partials within 1 GiB).
+ * Errors of the frame entry points, all before any device work and before the context is read: normalize, Heckman
+ * settings: OB_E_UNSUPPORTED; a null or a non-finite value in a named column: OB_E_INVALID; K > OB_REWEIGHT_MAX_K:
+ * OB_E_UNSUPPORTED; a group with rows <= K: OB_E_INSUFFICIENT. One outcome; the cluster bootstrap is not served (the
+ * clustered entry points have no reweighted form). On a handle prepared here ob_prepared_boot,
+ * ob_prepared_boot_device (which synchronizes its stream), ob_prepared_finish and ob_prepared_point_row work;
+ * ob_prepared_boot_sharded, ob_prepared_jackknife and ob_prepared_finish_bca are OB_E_UNSUPPORTED.
+ * Results of ob_prepared_finish / ob_builder_run_reweighted: the tables OB_RW_TABLE_* (estimate, standard error,
+ * percentile interval and p over the replicates kept), ob_results_total_gap; OB_VEC_XA_MEAN, OB_VEC_XB_MEAN and
+ * OB_VEC_BETA_STAR hold xbar_A, xbar_B and beta_C; the rest of the point row is ob_prepared_point_row's. */
+#define OB_REWEIGHT_MAX_K 32
+#define OB_RW_ROW_TOTAL_GAP 0
+#define OB_RW_ROW_COMPOSITION 1
+#define OB_RW_ROW_STRUCTURE 2
+#define OB_RW_ROW_PURE_EXPLAINED 3
+#define OB_RW_ROW_SPECIFICATION_ERROR 4
+#define OB_RW_ROW_PURE_UNEXPLAINED 5
+#define OB_RW_ROW_REWEIGHTING_ERROR 6
+#define OB_RW_ROW_DETAILED 7
+#define OB_RW_TABLE_AGGREGATE 0 /* the seven aggregates, in row order */
+#define OB_RW_TABLE_PURE_EXPLAINED 1
+#define OB_RW_TABLE_SPECIFICATION_ERROR 2
+#define OB_RW_TABLE_PURE_UNEXPLAINED 3
+#define OB_RW_TABLE_REWEIGHTING_ERROR 4
+typedef struct {
+  int32_t logit_passes;   /* the longest batch's */
+  int32_t logit_launches; /* pass kernels over all batches */
+  double logit_ms;        /* the logit pass kernels (the Newton steps not included) */
+  double gram_ms;         /* the three Grams' kernels */
+  double row_ms;          /* the solves and rows */
+} ob_reweight_timing;
+int ob_reweight_row_len(int32_t k);
+/* The shape limits above on their own (host only). */
+int ob_reweight_check_shape(int32_t k, int64_t n_a, int64_t n_b);
+/* HIP-event ms of the calling thread's last reweighted boot (or prepare: the point pass). */
+int ob_reweight_last_timing(ob_reweight_timing* out);
+/* One logit pass alone: x (n x k, column-major, ldx >= n, column 0 all ones), d (n values, each 0.0 or 1.0), w (n
+   weights or NULL for 1), counts (n bytes or NULL for every row once), gammas [n_gammas][k] with n_gammas <= 64 (each
+   is one replicate's coefficient vector over the same counts). info [n_gammas][k x k] (symmetric, both triangles):
+   sum c w p (1 - p) x x'; grad [n_gammas][k]: sum c w (d - p) x. */
+int ob_reweight_logit_pass(ob_ctx* ctx, const double* x, int64_t ldx, const double* d, const double* w,
+                           const uint8_t* counts, int64_t n, int32_t k, const double* gammas, int32_t n_gammas,
+                           double* info, double* grad);
+/* The psi-weighted extended Gram alone over one group: v = [x_0 .. x_{k-1}, y], gram [n_gammas][(k + 1) x (k + 1)]
+   (symmetric, both triangles) = sum c w psi v v' with psi = p / (1 - p) of the clamped p at gammas[g];
+   ess_den [n_gammas] = sum c (w psi)^2. Arguments as ob_reweight_logit_pass. */
+int ob_reweight_gram(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, const double* w,
+                     const uint8_t* counts, int64_t n, int32_t k, const double* gammas, int32_t n_gammas, double* gram,
+                     double* ess_den);
+int ob_builder_prepare_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                  const ob_builder_config* cfg, ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish. */
+int ob_builder_run_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                              const ob_builder_config* cfg, ob_results** out);
+
 #ifdef __cplusplus
 }
 #endif

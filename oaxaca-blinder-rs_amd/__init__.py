@@ -10,14 +10,15 @@ from .api import (Adjustment, AkmBuilder, AkmResult, BinaryDecompositionResults,
                   DecompositionDetail, DecompositionResult, DflResult, JackknifeResult, defensibility_message, parse_rust_f64, FrontierPoint, MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder,
                   OaxacaResults, OptimizationResult, PreparedRun,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
-                  ReferenceCoefficients, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
+                  ReferenceCoefficients, ReweightedDecompositionResults, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
                   parse_formula, run_dfl, run_dfl_from_csv)
 from .engine import (binary_check_shape, binary_last_timing, binary_means, binary_row_len, cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
                      cluster_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
                      knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
                      remedy_resolve_overrides, remedy_score, remedy_solve, rif, parse_rif_statistic, rif_last_timing,
-                     rif_scan_block, rif_statistic,
+                     rif_scan_block, rif_statistic, reweight_check_shape, reweight_gram, reweight_last_timing,
+                     reweight_logit_pass, reweight_row_len,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
@@ -38,4 +39,6 @@ __all__ = [
     "cluster_index", "cluster_gram", "cluster_counts", "cluster_apply", "cluster_check_shape", "cluster_last_timing",
     "rif_statistic", "rif_last_timing", "rif_scan_block", "parse_rif_statistic",
     "BinaryDecompositionResults", "binary_means", "binary_check_shape", "binary_row_len", "binary_last_timing",
+    "ReweightedDecompositionResults", "reweight_logit_pass", "reweight_gram", "reweight_check_shape",
+    "reweight_row_len", "reweight_last_timing",
 ]

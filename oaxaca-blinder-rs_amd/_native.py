@@ -67,6 +67,8 @@ EXPORTED = (
     "ob_builder_decompose_statistics_clustered",
     "ob_binary_row_len", "ob_binary_check_shape", "ob_binary_means", "ob_binary_last_timing",
     "ob_builder_prepare_binary", "ob_builder_run_binary", "ob_prepared_point_row",
+    "ob_reweight_row_len", "ob_reweight_check_shape", "ob_reweight_last_timing", "ob_reweight_logit_pass",
+    "ob_reweight_gram", "ob_builder_prepare_reweighted", "ob_builder_run_reweighted",
 )
 
 OB_E_CONVERGENCE = 12
@@ -87,6 +89,9 @@ OB_RIF_STATS = {"variance": OB_RIF_VARIANCE, "gini": OB_RIF_GINI, "iqr": OB_RIF_
 OB_BINARY_MAX_K = 32  # design columns, the intercept included
 OB_BINARY_PROBIT, OB_BINARY_LOGIT = 0, 1
 OB_BINARY_MODELS = {"probit": OB_BINARY_PROBIT, "logit": OB_BINARY_LOGIT}
+OB_REWEIGHT_MAX_K = 32  # design columns, the intercept included
+OB_RW_TABLE_AGGREGATE, OB_RW_TABLE_PURE_EXPLAINED, OB_RW_TABLE_SPECIFICATION_ERROR = 0, 1, 2
+OB_RW_TABLE_PURE_UNEXPLAINED, OB_RW_TABLE_REWEIGHTING_ERROR = 3, 4
 
 
 class OaxacaError(RuntimeError):
@@ -248,6 +253,11 @@ class ob_rif_timing(C.Structure):
 class ob_binary_timing(C.Structure):
     _fields_ = [("probit_ms", C.c_double), ("probit_launches", C.c_int32), ("probit_iterations", C.c_int32),
                 ("means_ms", C.c_double), ("epilogue_ms", C.c_double)]
+
+
+class ob_reweight_timing(C.Structure):
+    _fields_ = [("logit_passes", C.c_int32), ("logit_launches", C.c_int32), ("logit_ms", C.c_double),
+                ("gram_ms", C.c_double), ("row_ms", C.c_double)]
 
 
 class ob_component(C.Structure):
@@ -471,6 +481,15 @@ _SIGS = {
     "ob_builder_run_binary": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
                                         C.POINTER(ob_builder_config), C.c_int32, C.POINTER(_P)]),
     "ob_prepared_point_row": (C.c_int, [_P, C.POINTER(_D), C.POINTER(C.c_int64)]),
+    "ob_reweight_row_len": (C.c_int, [C.c_int32]),
+    "ob_reweight_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64]),
+    "ob_reweight_last_timing": (C.c_int, [C.POINTER(ob_reweight_timing)]),
+    "ob_reweight_logit_pass": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D]),
+    "ob_reweight_gram": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D]),
+    "ob_builder_prepare_reweighted": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                C.POINTER(ob_builder_config), C.POINTER(_P)]),
+    "ob_builder_run_reweighted": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                            C.POINTER(ob_builder_config), C.POINTER(_P)]),
 }
 
 _lib = None

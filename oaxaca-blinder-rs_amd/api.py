@@ -342,6 +342,60 @@ class BinaryDecompositionResults:
             "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed})
 
 
+@dataclass
+class ReweightedDecompositionResults:
+    """``OaxacaBuilder.decompose_reweighted``: the reweighted Oaxaca-Blinder decomposition (Fortin, Lemieux and
+    Firpo 2011, section 5). ``aggregate`` holds total_gap, composition, structure, pure_explained,
+    specification_error, pure_unexplained and reweighting_error; the four detailed tables their summands per
+    design column. The component objects are ``OaxacaResults``' (estimate, standard error, percentile interval,
+    p-value over the bootstrap, in which the propensity logit is refitted per replicate)."""
+    total_gap: float
+    aggregate: list
+    detailed_pure_explained: list
+    detailed_specification_error: list
+    detailed_pure_unexplained: list
+    detailed_reweighting_error: list
+    beta_a: np.ndarray = field(repr=False)
+    beta_b: np.ndarray = field(repr=False)
+    beta_c: np.ndarray = field(repr=False)
+    gamma: np.ndarray = field(repr=False)
+    xa_mean: np.ndarray = field(repr=False)
+    xb_mean: np.ndarray = field(repr=False)
+    xc_mean: np.ndarray = field(repr=False)
+    y_means: tuple = (0.0, 0.0, 0.0)
+    effective_sample_size: float = 0.0
+    logit_passes: int = 0
+    names: list = field(default_factory=list, repr=False)
+    n_a: int = 0
+    n_b: int = 0
+    n_failed: int = 0
+
+    def component(self, name: str):
+        return next(c for c in self.aggregate if c.name == name)
+
+    def to_json(self) -> str:
+        def fix(v):  # serde_json writes non-finite floats as null
+            return v if isinstance(v, str) or np.isfinite(v) else None
+
+        def comps(cs):
+            return [{k: fix(v) for k, v in c.__dict__.items()} for c in cs]
+
+        def vec(a):
+            return [fix(float(v)) for v in a]
+
+        return json.dumps({
+            "total_gap": fix(self.total_gap), "aggregate": comps(self.aggregate),
+            "detailed_pure_explained": comps(self.detailed_pure_explained),
+            "detailed_specification_error": comps(self.detailed_specification_error),
+            "detailed_pure_unexplained": comps(self.detailed_pure_unexplained),
+            "detailed_reweighting_error": comps(self.detailed_reweighting_error),
+            "names": list(self.names), "beta_a": vec(self.beta_a), "beta_b": vec(self.beta_b),
+            "beta_c": vec(self.beta_c), "gamma": vec(self.gamma), "xa_mean": vec(self.xa_mean),
+            "xb_mean": vec(self.xb_mean), "xc_mean": vec(self.xc_mean), "y_means": vec(self.y_means),
+            "effective_sample_size": fix(self.effective_sample_size), "logit_passes": self.logit_passes,
+            "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed})
+
+
 def _jackknife_out(k: int):
     c = 6 + 2 * k
     bufs = (np.zeros(c), np.zeros((2, c, 3)), np.zeros((c, 3)))
@@ -951,6 +1005,56 @@ class OaxacaBuilder:
             probabilities={key: float(v) for key, v in zip(keys, tail[5 * k:5 * k + 6])},
             beta_a=tail[:k].copy(), beta_b=tail[k:2 * k].copy(), beta_star=tail[4 * k:5 * k].copy(),
             xa_mean=tail[2 * k:3 * k].copy(), xb_mean=tail[3 * k:4 * k].copy(), names=names,
+            n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed)
+
+    def prepare_reweighted(self) -> "PreparedRun":
+        from .engine import with_context
+
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED,
+                                "reweighted decomposition: the cluster bootstrap is outside its scope")
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        h = C.c_void_p()
+        if self._ctx is not None:
+            N.check(lib.ob_builder_prepare_reweighted(self._ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+        else:
+            with_context(lambda ctx: lib.ob_builder_prepare_reweighted(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h)),
+                         self._device)
+        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+
+    def decompose_reweighted(self) -> "ReweightedDecompositionResults":
+        """Extension (no counterpart in the reference crate): the reweighted decomposition of Fortin, Lemieux and
+        Firpo (2011, section 5), Stata's ``oaxaca_rif ..., rwlogit()``. A propensity logit of the non-reference
+        group on the design reweights the reference group B to A's covariates (the counterfactual sample C); a
+        third regression on C splits the composition effect into a pure explained part and a specification
+        error, and the structure effect into a pure unexplained part and a reweighting error. Every bootstrap
+        replicate refits the logit on the GPU. Sample weights are served; ``reference_coefficients`` is ignored.
+        Refused (``OB_E_UNSUPPORTED``): ``normalize``, ``cluster``, Heckman settings, more than 32 design
+        columns."""
+        pr = self.prepare_reweighted()
+        try:
+            rows, ok = pr.boot(0, self._bootstrap_reps)
+            res = pr.finish(rows, ok)
+            point = pr.point_row()
+        finally:
+            pr.close()
+        k = (len(point) - 12) // 11
+        tail = point[7 + 4 * k:]
+        sc = tail[7 * k:]
+        # the reweighted handle's five tables travel in the slots of run()'s (OB_RW_TABLE_*)
+        return ReweightedDecompositionResults(
+            total_gap=float(point[0]), aggregate=res.two_fold.aggregate,
+            detailed_pure_explained=res.two_fold.detailed_explained,
+            detailed_specification_error=res.two_fold.detailed_unexplained,
+            detailed_pure_unexplained=res.two_fold.detailed_selection,
+            detailed_reweighting_error=res.three_fold.aggregate,
+            beta_a=tail[:k].copy(), beta_b=tail[k:2 * k].copy(), beta_c=tail[2 * k:3 * k].copy(),
+            xa_mean=tail[3 * k:4 * k].copy(), xb_mean=tail[4 * k:5 * k].copy(), xc_mean=tail[5 * k:6 * k].copy(),
+            gamma=tail[6 * k:7 * k].copy(), y_means=(float(sc[0]), float(sc[1]), float(sc[2])),
+            effective_sample_size=float(sc[3]), logit_passes=int(sc[4]),
+            names=[c.name for c in res.two_fold.detailed_explained],
             n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed)
 
     def statistic_builder(self, stat, **params) -> "OaxacaBuilder":

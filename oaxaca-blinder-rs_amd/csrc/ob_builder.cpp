@@ -28,6 +28,7 @@
 #include "ob_host.hpp"
 #include "ob_builder.hpp"
 #include "ob_binary.hpp"
+#include "ob_reweight.hpp"
 #include "ob_cluster.hpp"
 #include "ob_mm.hpp"
 #include "ob_rif.hpp"
@@ -42,6 +43,11 @@ ClusterHooks& cluster_hooks() {
 
 BinaryHooks& binary_hooks() {
   static BinaryHooks h;
+  return h;
+}
+
+ReweightHooks& reweight_hooks() {
+  static ReweightHooks h;
   return h;
 }
 
@@ -355,6 +361,7 @@ struct ob_matrices {
   int64_t n_a = 0, n_b = 0;
   int32_t k = 0;
   std::vector<double> xa, ya, xb, yb;
+  std::vector<double> wa, wb;  // ob::data_matrices with want_w and a weights column, else empty
   std::vector<std::string> names;
 };
 
@@ -517,8 +524,59 @@ int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out)
   return OB_OK;
 }
 
+// finish() for a reweighted handle (ob_reweight.hpp's row): the seven aggregates, then the four detailed tables,
+// each component through the same aggregate() as an OLS row's.
+static int reweight_finish(const ob_prepared* pr, const double* rows, const uint8_t* ok, uint64_t n_reps,
+                           ob_results** out) {
+  const int k = pr->k, rl = pr->row_len;
+  const double* point = pr->point_row.data();
+  uint64_t ng = 0;
+  for (uint64_t r = 0; r < n_reps; ++r) ng += ok[r] ? 1 : 0;
+  if (ng < n_reps)
+    fprintf(stderr,
+            "Warning: %llu out of %llu bootstrap replications failed and were discarded. The analysis is based on "
+            "%llu successful replications.\n",
+            (unsigned long long)(n_reps - ng), (unsigned long long)n_reps, (unsigned long long)ng);
+  ob_results* res = new ob_results();
+  res->total_gap = point[OB_RW_ROW_TOTAL_GAP];
+  res->n_a = pr->n_a;
+  res->n_b = pr->n_b;
+  res->n_failed = (int64_t)(n_reps - ng);
+  const double* tail = point + 7 + 4 * k;  // beta_A, beta_B, beta_C, xbar_A, xbar_B, xbar_C, gamma
+  res->xa_mean.assign(tail + 3 * k, tail + 4 * k);
+  res->xb_mean.assign(tail + 4 * k, tail + 5 * k);
+  res->beta_star.assign(tail + 2 * k, tail + 3 * k);
+  static const char* agg[7] = {"total_gap", "composition", "structure", "pure_explained", "specification_error",
+                               "pure_unexplained", "reweighting_error"};
+  std::vector<int> table;
+  std::vector<std::string> names;
+  std::vector<std::vector<int>> groups;
+  for (int i = 0; i < 7; ++i) {
+    table.push_back(OB_RW_TABLE_AGGREGATE);
+    names.push_back(agg[i]);
+    groups.push_back({i});
+  }
+  for (int t = 0; t < 4; ++t)
+    for (int j = 0; j < k; ++j) {
+      table.push_back(OB_RW_TABLE_PURE_EXPLAINED + t);
+      names.push_back(pr->names[j]);
+      groups.push_back({7 + t * k + j});
+    }
+  std::vector<double> st(4 * groups.size());
+  aggregate(rows, ok, n_reps, rl, groups, st.data());
+  for (size_t ji = 0; ji < groups.size(); ++ji) {
+    const double* s4 = st.data() + 4 * ji;
+    const double pt = point[groups[ji][0]];
+    const double t = std::fabs(s4[0]) > 1e-9 ? pt / s4[0] : 0.0;  // as finish()
+    res->tables[table[ji]].push_back({names[ji], pt, s4[0], t, s4[1], s4[2], s4[3]});
+  }
+  *out = res;
+  return OB_OK;
+}
+
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block).
 int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
+  if (pr->reweight) return reweight_finish(pr, rows, ok, n_reps, out);
   const int k = pr->k, kd = k + pr->n_base, rl = pr->row_len;
   const double* point_row = pr->point_row.data() + (size_t)t_out * rl;
   uint64_t ng = 0;
@@ -849,6 +907,7 @@ int ob_prepared_boot(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
   if (p->cluster) return ob::cluster_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   if (p->binary) return ob::binary_hooks().boot_host(p, first_rep, n_reps, rows, ok);
+  if (p->reweight) return ob::reweight_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   return ob_boot_run(p->panel, p->seed, first_rep, n_reps, p->ref, rows, ok);
 }
 
@@ -856,6 +915,7 @@ int ob_prepared_boot_sharded(ob_prepared* p, uint64_t first_rep, uint64_t n_reps
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
   if (p->cluster) return ob::fail(OB_E_UNSUPPORTED, "cluster bootstrap: sharded runs are outside its scope");
   if (p->binary) return ob::fail(OB_E_UNSUPPORTED, "binary decomposition: sharded runs are outside its scope");
+  if (p->reweight) return ob::fail(OB_E_UNSUPPORTED, "reweighted decomposition: sharded runs are outside its scope");
   // the RCCL all-gather moves only the columns finish() aggregates: two-fold, three-fold, total
   // gap, detailed [0, 6 + 2 Kd) and a Heckman row's selection terms after its 5K' tail
   const int kd = p->k + p->n_base, sel0 = 6 + 2 * kd + 5 * p->k;
@@ -879,6 +939,8 @@ int ob_prepared_boot_device(ob_prepared* p, uint64_t first_rep, uint64_t n_reps,
                                            reinterpret_cast<hipStream_t>(hip_stream));
   if (p->binary)
     return ob::binary_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
+  if (p->reweight)
+    return ob::reweight_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
   return ob_boot_run_device(p->panel, p->seed, first_rep, n_reps, p->ref, d_rows, d_ok, hip_stream);
 }
 
@@ -892,6 +954,7 @@ void ob_prepared_destroy(ob_prepared* p) {
   if (!p) return;
   if (p->cluster) ob::cluster_hooks().free_state(p->cluster);
   if (p->binary) ob::binary_hooks().free_state(p->binary);
+  if (p->reweight) ob::reweight_hooks().free_state(p->reweight);
   ob_panel_destroy(p->panel);
   delete p;
 }
@@ -1050,24 +1113,32 @@ int ob_builder_decompose_quantiles_clustered(ob_ctx* ctx, const ob_column* cols,
   return decompose_quantiles(ctx, cols, n_cols, n_rows, cfg, taus, n_taus, out, ccfg);
 }
 
-int ob_builder_data_matrices(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
-                             ob_matrices** out) {
-  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+}  // extern "C"
+
+namespace ob {
+
+int data_matrices(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, bool want_w,
+                  ob_matrices** out) {
+  if (!out) return fail(OB_E_INVALID, "null pointer");
   *out = nullptr;
-  ob::Frame f;
-  ob::Config c;
-  OB_TRY(ob::config_from(cfg, c));
-  OB_TRY(ob::load_frame(cols, n_cols, n_rows, f));
-  ob::Staged st;
-  OB_TRY(ob::stage(f, c, st));
-  ob::Design da, db;
-  OB_TRY(ob::prepare_data(st.df, st.split.a, c, st.dummy_names, false, da));
-  OB_TRY(ob::prepare_data(st.df, st.split.b, c, st.dummy_names, false, db));
+  Frame f;
+  Config c;
+  OB_TRY(config_from(cfg, c));
+  OB_TRY(load_frame(cols, n_cols, n_rows, f));
+  Staged st;
+  OB_TRY(stage(f, c, st));
+  Design da, db;
+  OB_TRY(prepare_data(st.df, st.split.a, c, st.dummy_names, want_w, da));
+  OB_TRY(prepare_data(st.df, st.split.b, c, st.dummy_names, want_w, db));
+  if (want_w && c.has_weights)
+    for (const Design* d : {&da, &db})
+      for (double w : d->w)
+        if (w < 0.0) return fail(OB_E_GROUP, "%sWeights cannot be negative", error_prefix(OB_E_GROUP));
   ob_matrices* m = new ob_matrices();
   m->k = (int32_t)(c.predictors.size() + st.dummy_names.size() + 1);
   m->n_a = da.n;
   m->n_b = db.n;
-  auto with_intercept = [&](const ob::Design& d, std::vector<double>& x) {
+  auto with_intercept = [&](const Design& d, std::vector<double>& x) {
     x.assign((size_t)d.n * m->k, 1.0);
     std::copy(d.x.begin(), d.x.end(), x.begin() + d.n);
   };
@@ -1075,11 +1146,27 @@ int ob_builder_data_matrices(const ob_column* cols, int32_t n_cols, int64_t n_ro
   with_intercept(db, m->xb);
   m->ya = da.y;
   m->yb = db.y;
+  m->wa = da.w;
+  m->wb = db.w;
   m->names = {"__ob_intercept__"};
   m->names.insert(m->names.end(), c.predictors.begin(), c.predictors.end());
   m->names.insert(m->names.end(), st.dummy_names.begin(), st.dummy_names.end());
   *out = m;
   return OB_OK;
+}
+
+const double* matrices_weights(const ob_matrices* m, int g) {
+  const std::vector<double>& w = g ? m->wb : m->wa;
+  return w.empty() ? nullptr : w.data();
+}
+
+}  // namespace ob
+
+extern "C" {
+
+int ob_builder_data_matrices(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                             ob_matrices** out) {
+  return ob::data_matrices(cols, n_cols, n_rows, cfg, false, out);
 }
 
 double ob_results_total_gap(const ob_results* r) { return r ? r->total_gap : NAN; }

@@ -33,6 +33,7 @@ struct Config {
 
 struct ClusterState;
 struct BinaryState;
+struct ReweightState;
 
 }  // namespace ob
 
@@ -72,6 +73,8 @@ struct ob_prepared {
   ob::ClusterState* cluster = nullptr;
   // ob_builder_prepare_binary: the probit panel and workspace on the device; boots run through ob_binary.hip
   ob::BinaryState* binary = nullptr;
+  // ob_builder_prepare_reweighted: the three-fit panel and workspace on the device; boots run through ob_reweight.hip
+  ob::ReweightState* reweight = nullptr;
 };
 
 namespace ob {
@@ -81,5 +84,10 @@ int config_from(const ob_builder_config* c, Config& out);
 int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out);
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block)
 int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out);
+// ob_builder_data_matrices, with the groups' sample weights kept where want_w (matrices_weights: NULL without
+// a weights column; the weight column's dtype and sign are checked as prepare() checks them)
+int data_matrices(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, bool want_w,
+                  ob_matrices** out);
+const double* matrices_weights(const ob_matrices* m, int g);
 
 }  // namespace ob

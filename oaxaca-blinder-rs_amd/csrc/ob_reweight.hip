@@ -1,0 +1,986 @@
+// ob_reweight.hip -- the reweighted Oaxaca-Blinder decomposition with a bootstrapped propensity logit (Fortin,
+// Lemieux and Firpo 2011, section 5). No counterpart in the reference crate (dfl.rs stops at
+// densities).
+//
+// Per batch of replicates (the resample enters through the engine's level-2 count images, as in ob_binary.hip):
+//   ob_rw_kernel        block per (row chunk, 16 replicates), one kernel with a weight mode:
+//                         logit   sum c w p (1 - p) x x' and sum c w (D - p) x of one Newton pass,
+//                         Gram    the extended Grams of A and B with weights c w,
+//                         GramPsi the extended Gram of B with weights c w psi, psi = p / (1 - p),
+//                       all as (weight row) x (pair products) on v_mfma_f64_16x16x4_f64; the index x'gamma and
+//                       the weight are formed inside the tile, never stored in HBM;
+//   ob_rw_step_kernel   wave per replicate: chunk partials in chunk order, Cholesky, step, stopping rule, the
+//                       replicate's done flag and pass count;
+//   ob_rw_row_kernel    wave per replicate: the three Grams in chunk order, three Cholesky solves, the means, the
+//                       terms of include/oaxaca_boot.h's row.
+// The point pass is the same code with every row counted once (counts == NULL).
+//
+// The factor P(B) / P(A) of dfl.rs:116 is left out of psi: every quantity of the row is a ratio of psi-weighted
+// sums, in which it cancels.
+//
+// Panel of a reweighted run, per group [col][ld]: y | x_1 .. x_{K-1} | w (ones without sample weights).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "ob_builder.hpp"
+#include "ob_device.hpp"
+#include "ob_engine.hpp"
+#include "ob_hip.hpp"
+#include "ob_options.hpp"
+#include "ob_reweight.hpp"
+#include "ob_spec.h"
+
+namespace {
+
+using d4 = __attribute__((ext_vector_type(4))) double;
+constexpr int kRB = 256;     // threads of a pass block
+constexpr int kRS = 65;      // doubles per staged column: a tile's 16 column reads spread over the banks
+constexpr int kRReps = 16;   // replicates per block
+constexpr int kRMaxU = 9;    // column tiles per wave: 36 tiles at K = 32 (561 pairs of the extended Gram)
+constexpr int kRMaxK = ob::kReweightMaxK;
+constexpr uint32_t kRwDone = 1u, kRwFailed = 2u;
+constexpr int kModeLogit = 0, kModeGram = 1, kModeGramPsi = 2;
+
+struct RwArgs {
+  const double* cols[2];  // [y | x_1 .. x_{k-1} | w] x ld, zero past n
+  int64_t ld[2];
+  uint32_t n[2];
+  uint32_t tiles0;         // tiles of group A (the count images hold A's tiles first)
+  int k;
+  const uint32_t* counts;  // level-2 count images of the batch's first replicate block (NULL: every row once)
+  uint32_t nb_rep;         // 64-replicate blocks of the images
+  const uint32_t* chunks;  // [chunk][3] = (g, t0, t1)
+  int n_chunks;
+  uint32_t n_reps, part_pad;
+  double* gamma;           // [replicate][k]
+  uint32_t* flags;         // [replicate] kRwDone | kRwFailed
+  uint32_t* passes;        // [replicate] Newton passes taken
+  uint32_t* active;        // replicates still iterating after a step
+  double* partial;         // [chunk][part_pad][rw_nv(k, mode)] of the logit pass / the c w Grams
+  double* partial_c;       // [chunk][part_pad][rw_nv(k, kModeGramPsi)] (B's chunks only)
+  double* rows;
+  uint8_t* ok;
+  int row_len;
+  int mode;
+  double tol;
+};
+
+// Values per (chunk, replicate): the packed lower triangle (entry j (j + 1) / 2 + i, i <= j) of the k x k
+// information matrix then the k gradient entries; or that of the (k + 1) x (k + 1) extended Gram of
+// v = [x_0 .. x_{k-1}, y], followed under GramPsi by sum c (w psi)^2.
+__host__ __device__ inline int rw_nv(int k, int mode) {
+  if (mode == kModeLogit) return k * (k + 1) / 2 + k;
+  return (k + 1) * (k + 2) / 2 + (mode == kModeGramPsi ? 1 : 0);
+}
+
+// Row j of the packed lower triangle that holds entry e = j (j + 1) / 2 + i, i <= j.
+__device__ __forceinline__ int rw_tri_row(int e) {
+  int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+  while ((j + 1) * (j + 2) / 2 <= e) ++j;
+  while (j * (j + 1) / 2 > e) --j;
+  return j;
+}
+
+inline size_t rw_lds(int k) {
+  return sizeof(double) * ((size_t)(k + 2) * kRS + 2 * 64 * kRReps + (size_t)kRReps * (k | 1) + 16 * kRReps);
+}
+
+// Block = (row chunk, 16 replicates), 4 waves; the layout of ob_heck_wide_kernel. Per 64-row sub-tile:
+//   stage  the k + 1 columns of the sub-tile -> LDS [col][65] (+ a column of ones for x_0), one coalesced load
+//          per column, shared by the block;
+//   A      thread = (replicate t & 15, rows 4 (t >> 4) .. + 3: one count word): x'gamma from the staged columns
+//          and the replicate's gamma (LDS [16][k | 1]), p, the clamp, the mode's weight -> LDS [operand][row][16];
+//   B      wave w owns the column tiles w, w + 4, ..: at most 9 accumulators of 16 replicates x 16 columns. Per
+//          4-row step a lane reads its A values once and forms each tile's B value as the product of two staged
+//          columns (never stored in HBM).
+// A wave owns its tiles over the whole chunk, so there is no block sum: every partial is one accumulator
+// element, summed over the chunk's rows in row order. An output element of the MFMA depends on its own A row
+// and B column only, so a replicate's partials do not depend on its slot in the block, on its neighbours, on
+// the batch or on first_rep. No atomics.
+__global__ __launch_bounds__(kRB) void ob_rw_kernel(const RwArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double rsm[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t chunk = blockIdx.x, g = a.chunks[3 * chunk], t0 = a.chunks[3 * chunk + 1], t1 = a.chunks[3 * chunk + 2];
+  const int mode = a.mode;
+  if (mode == kModeGramPsi && g == 0) return;  // the counterfactual sample is B's rows
+  const int k = a.k, gs = k | 1, ncol = k + 1;
+  const int ones = ncol * kRS, wcol = k * kRS;
+  double* stg = rsm;                    // [ncol + 1][kRS]: y, x_1 .. x_{k-1}, w, ones
+  double* wl = stg + (ncol + 1) * kRS;  // [2][64 rows][16 replicates]
+  double* gm = wl + 2 * 64 * kRReps;    // [16][gs] gamma
+  double* red = gm + kRReps * gs;       // GramPsi: [16 row groups][16 replicates]
+  const int r16 = tid & 15, q = tid >> 4;
+  const uint32_t rep0 = blockIdx.y * kRReps, rep = rep0 + r16;
+  bool act = rep < a.n_reps;
+  if (mode == kModeLogit && act) act = !(a.flags[rep] & kRwDone);
+  if (!__syncthreads_or(act)) return;
+  if (mode != kModeGram)
+    for (int i = tid; i < kRReps * k; i += kRB) {
+      const int rr = i / k, j = i - rr * k;
+      gm[rr * gs + j] = rep0 + rr < a.n_reps ? a.gamma[(size_t)(rep0 + rr) * k + j] : 0.0;
+    }
+  if (tid < 64) stg[ones + tid] = 1.0;
+  // this lane's column of each of the wave's tiles: the two staged columns whose product is the B value, and
+  // the slot of the partial it lands in (-1: padding). v_j: x_0 = ones, x_j = column j, y = column 0.
+  const int dim = mode == kModeLogit ? k : k + 1;
+  const int NP = dim * (dim + 1) / 2;
+  const int nt0 = (NP + 15) / 16;                           // tiles of operand 0: the pair products
+  const int nt1 = mode == kModeLogit ? (k + 15) / 16 : 0;  // tiles of operand 1: the gradient's columns
+  const int NT = nt0 + nt1;
+  int oa[kRMaxU], ob2[kRMaxU], dst[kRMaxU];
+#pragma unroll
+  for (int u = 0; u < kRMaxU; ++u) {
+    const int c = wave + 4 * u, e16 = lane & 15;
+    oa[u] = ones;
+    ob2[u] = ones;
+    dst[u] = -1;
+    if (c < nt0) {
+      const int idx = 16 * c + e16;
+      if (idx < NP) {
+        const int j = rw_tri_row(idx), i = idx - j * (j + 1) / 2;
+        oa[u] = j == 0 ? ones : (j < k ? j * kRS : 0);
+        ob2[u] = i == 0 ? ones : (i < k ? i * kRS : 0);
+        dst[u] = idx;
+      }
+    } else if (c < NT) {
+      const int idx = 16 * (c - nt0) + e16;
+      if (idx < k) {
+        oa[u] = idx ? idx * kRS : ones;
+        dst[u] = NP + idx;
+      }
+    }
+  }
+  d4 acc[kRMaxU];
+#pragma unroll
+  for (int u = 0; u < kRMaxU; ++u) acc[u] = d4{0.0, 0.0, 0.0, 0.0};
+  double s1 = 0.0;  // GramPsi: c (w psi)^2 of this thread's rows
+  const double* X = a.cols[g];
+  const int64_t ld = a.ld[g];
+  const uint32_t n = a.n[g];
+  const uint32_t rb = rep >> 6, R = rep & 63;
+  const double dA = g == 0 ? 1.0 : 0.0;  // D = 1[A]
+  for (uint32_t tile = t0; tile < t1; ++tile) {
+    for (uint32_t sw = 0; sw < 4; ++sw) {
+      const uint32_t r0 = tile * OB_TILE_ROWS + sw * 64;
+      if (r0 >= n) break;
+      const uint32_t nr = min(64u, n - r0);
+      __syncthreads();  // the previous sub-tile's operand reads (and the gamma loads)
+      for (int i = tid; i < ncol * 64; i += kRB) {
+        const int c = i >> 6, r = i & 63;
+        stg[c * kRS + r] = (uint32_t)r < nr ? X[(size_t)c * ld + r0 + r] : 0.0;
+      }
+      __syncthreads();
+      uint32_t word = 0;  // counts of rows 4 q .. 4 q + 3 (the f64 Gram's count-image layout, ob_engine.hpp)
+      if (act) {
+        const size_t tt = (g ? a.tiles0 : 0u) + tile;
+        word = a.counts ? a.counts[((tt * a.nb_rep + rb) * 4 + sw) * kCimgWords + R * kCimgStride + q] : 0x01010101u;
+      }
+      double zg[4] = {0.0, 0.0, 0.0, 0.0};
+      if (word && mode != kModeGram) {
+        const double g0 = gm[r16 * gs];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) zg[i] = g0;
+        for (int j = 1; j < k; ++j) {
+          const double gj = gm[r16 * gs + j];
+          const double* xj = stg + j * kRS + 4 * q;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) zg[i] += xj[i] * gj;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t row = 4 * q + i;
+        const uint32_t cu = row < nr ? (word >> (8 * i)) & 255u : 0u;
+        double w0 = 0.0, w1 = 0.0;
+        if (cu) {
+          const double c = (double)cu, w = stg[wcol + row], cw = c * w;
+          if (mode == kModeGram) {
+            w0 = cw;
+          } else {
+            double p = 1.0 / (1.0 + exp(-zg[i]));  // logit.rs:15-17, :45 (a NaN stays a NaN)
+            p = p < 1e-10 ? 1e-10 : (p > 1.0 - 1e-10 ? 1.0 - 1e-10 : p);
+            if (mode == kModeLogit) {
+              w0 = cw * (p * (1.0 - p));
+              w1 = cw * (dA - p);
+            } else {
+              const double wp = w * (p / (1.0 - p));
+              w0 = c * wp;
+              s1 += c * (wp * wp);
+            }
+          }
+        }
+        wl[row * kRReps + r16] = w0;
+        wl[64 * kRReps + row * kRReps + r16] = w1;
+      }
+      __syncthreads();
+      const int rl = lane >> 4;
+#pragma unroll 2
+      for (int i = 0; i < 16; ++i) {
+        const double a0 = wl[i * 64 + lane], a1 = wl[64 * kRReps + i * 64 + lane];
+        const int row = 4 * i + rl;
+#pragma unroll
+        for (int u = 0; u < kRMaxU; ++u)
+          if (wave + 4 * u < NT)
+            acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(wave + 4 * u < nt0 ? a0 : a1, stg[oa[u] + row] * stg[ob2[u] + row],
+                                                          acc[u], 0, 0, 0);
+      }
+    }
+  }
+  // lane (rl, e16), element r of acc[u]: replicate rep0 + rl + 4 r, the tile's column e16
+  const int nv = rw_nv(k, mode);
+  double* out = (mode == kModeGramPsi ? a.partial_c : a.partial) + (size_t)chunk * a.part_pad * nv;
+#pragma unroll
+  for (int u = 0; u < kRMaxU; ++u)
+    if (wave + 4 * u < NT && dst[u] >= 0)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t rp = rep0 + (lane >> 4) + 4 * r;
+        if (rp < a.n_reps) out[(size_t)rp * nv + dst[u]] = acc[u][r];
+      }
+  if (mode == kModeGramPsi) {  // the sum that is not linear in psi: row groups in order
+    red[q * kRReps + r16] = s1;
+    __syncthreads();
+    if (tid < 16) {
+      double v = 0.0;
+      for (int qq = 0; qq < 16; ++qq) v += red[qq * kRReps + r16];
+      if (rep < a.n_reps) out[(size_t)rep * nv + NP] = v;
+    }
+  }
+}
+
+// One wave per replicate, after a logit pass: the chunk partials of both groups in chunk order, the Cholesky
+// factor of the information matrix, the step, the stopping rule (logit.rs:88-105). A replicate that has
+// converged keeps its gamma and its pass count while the batch runs on.
+__global__ __launch_bounds__(64) void ob_rw_step_kernel(const RwArgs a) {
+  __shared__ double m[kRMaxK * kRMaxK], step[kRMaxK];
+  const int lane = threadIdx.x, k = a.k, NH = k * (k + 1) / 2, NP = NH + k;
+  const uint32_t rep = blockIdx.x;
+  if (a.flags[rep] & kRwDone) return;
+  for (int e = lane; e < NP; e += 64) {
+    double v = 0.0;
+    for (int c = 0; c < a.n_chunks; ++c) v += a.partial[((size_t)c * a.part_pad + rep) * NP + e];
+    if (e < NH) {
+      const int j = rw_tri_row(e), i = e - j * (j + 1) / 2;
+      m[j + i * k] = v;
+      m[i + j * k] = v;
+    } else {
+      step[e - NH] = v;
+    }
+  }
+  __syncthreads();
+  const bool chol = wave_cholesky(m, k, lane);
+  __syncthreads();
+  if (!chol) {
+    if (lane == 0) {
+      a.flags[rep] = kRwDone | kRwFailed;
+      a.passes[rep] += 1;
+    }
+    return;
+  }
+  wave_chol_solve(m, k, step, lane);
+  __syncthreads();
+  if (lane == 0) {
+    double nrm = 0.0;
+    for (int i = 0; i < k; ++i) {
+      a.gamma[(size_t)rep * k + i] += step[i];
+      nrm += step[i] * step[i];
+    }
+    a.passes[rep] += 1;
+    if (sqrt(nrm) < a.tol)
+      a.flags[rep] = kRwDone;
+    else
+      atomicAdd(a.active, 1u);
+  }
+}
+
+// One wave per replicate: the three extended Grams from their chunk partials in chunk order, the three (W)LS
+// fits by Cholesky (ob::chol_factor's operation order, wave_cholesky), the means, the terms, the row. A
+// replicate whose logit failed or did not converge, or one of whose fits has no Cholesky factor, gets ok = 0
+// and a NaN row.
+__global__ __launch_bounds__(64) void ob_rw_row_kernel(const RwArgs a) {
+  constexpr int M1 = kRMaxK + 1;
+  __shared__ double G[3][M1 * (M1 + 1) / 2];
+  __shared__ double m[kRMaxK * kRMaxK];
+  __shared__ double beta[3][kRMaxK], xbar[3][kRMaxK];
+  __shared__ double ess_den;
+  const int lane = threadIdx.x, k = a.k, E = (k + 1) * (k + 2) / 2;
+  const uint32_t rep = blockIdx.x;
+  if (rep >= a.n_reps) return;
+  double* row = a.rows + (size_t)rep * a.row_len;
+  const uint32_t fl = a.flags[rep];
+  bool failed = !(fl & kRwDone) || (fl & kRwFailed);
+  if (!failed) {
+    for (int i = lane; i < 3 * E + 1; i += 64) {
+      const int f = i / E, e = i - f * E;  // f: A, B, C; i == 3 E: sum c (w psi)^2
+      const uint32_t g = f == 0 ? 0u : 1u;
+      const int nv = rw_nv(k, f == 2 || f == 3 ? kModeGramPsi : kModeGram);
+      const double* part = f >= 2 ? a.partial_c : a.partial;
+      const int slot = f == 3 ? E : e;
+      double v = 0.0;
+      for (int c = 0; c < a.n_chunks; ++c)
+        if (a.chunks[3 * c] == g) v += part[((size_t)c * a.part_pad + rep) * nv + slot];
+      if (f == 3)
+        ess_den = v;
+      else
+        G[f][e] = v;
+    }
+    __syncthreads();
+    for (int f = 0; f < 3 && !failed; ++f) {
+      const double* Gf = G[f];
+      for (int e = lane; e < k * (k + 1) / 2; e += 64) {
+        const int j = rw_tri_row(e), i = e - j * (j + 1) / 2;
+        m[j + i * k] = Gf[e];
+        m[i + j * k] = Gf[e];
+      }
+      const int yrow = k * (k + 1) / 2;  // entries (i, k): x_i y
+      const double s0 = Gf[0];
+      for (int j = lane; j < k; j += 64) {
+        beta[f][j] = Gf[yrow + j];
+        xbar[f][j] = Gf[j * (j + 1) / 2] / s0;
+      }
+      __syncthreads();
+      const bool chol = wave_cholesky(m, k, lane);
+      __syncthreads();
+      if (!chol || !(s0 > 0.0)) {
+        failed = true;
+        break;
+      }
+      wave_chol_solve(m, k, beta[f], lane);
+      __syncthreads();
+    }
+  }
+  if (failed) {
+    for (int i = lane; i < a.row_len; i += 64) row[i] = __builtin_nan("");
+    if (lane == 0) a.ok[rep] = 0;
+    return;
+  }
+  const double *ba = beta[0], *bb = beta[1], *bc = beta[2], *xa = xbar[0], *xb = xbar[1], *xc = xbar[2];
+  double* det = row + 7;
+  double* tail = det + 4 * k;
+  for (int j = lane; j < k; j += 64) {
+    det[j] = (xc[j] - xb[j]) * bb[j];
+    det[k + j] = xc[j] * (bc[j] - bb[j]);
+    det[2 * k + j] = xa[j] * (ba[j] - bc[j]);
+    det[3 * k + j] = (xa[j] - xc[j]) * bc[j];
+    tail[j] = ba[j];
+    tail[k + j] = bb[j];
+    tail[2 * k + j] = bc[j];
+    tail[3 * k + j] = xa[j];
+    tail[4 * k + j] = xb[j];
+    tail[5 * k + j] = xc[j];
+    tail[6 * k + j] = a.gamma[(size_t)rep * k + j];
+  }
+  if (lane == 0) {  // the aggregates, in column order
+    const int yrow = k * (k + 1) / 2;
+    double faa = 0.0, fbb = 0.0, fcc = 0.0, pe = 0.0, se = 0.0, pu = 0.0, re = 0.0;
+    for (int j = 0; j < k; ++j) {
+      faa += xa[j] * ba[j];
+      fbb += xb[j] * bb[j];
+      fcc += xc[j] * bc[j];
+      pe += (xc[j] - xb[j]) * bb[j];
+      se += xc[j] * (bc[j] - bb[j]);
+      pu += xa[j] * (ba[j] - bc[j]);
+      re += (xa[j] - xc[j]) * bc[j];
+    }
+    const double ya = G[0][yrow] / G[0][0], yb = G[1][yrow] / G[1][0], yc = G[2][yrow] / G[2][0];
+    row[OB_RW_ROW_TOTAL_GAP] = ya - yb;
+    row[OB_RW_ROW_COMPOSITION] = fcc - fbb;
+    row[OB_RW_ROW_STRUCTURE] = faa - fcc;
+    row[OB_RW_ROW_PURE_EXPLAINED] = pe;
+    row[OB_RW_ROW_SPECIFICATION_ERROR] = se;
+    row[OB_RW_ROW_PURE_UNEXPLAINED] = pu;
+    row[OB_RW_ROW_REWEIGHTING_ERROR] = re;
+    double* sc = tail + 7 * k;
+    sc[0] = ya;
+    sc[1] = yb;
+    sc[2] = yc;
+    sc[3] = G[2][0] * G[2][0] / ess_den;
+    sc[4] = (double)a.passes[rep];
+    a.ok[rep] = 1;
+  }
+}
+
+hipError_t launch_pass(const RwArgs& a, int mode, hipStream_t s) {
+  const size_t lds = rw_lds(a.k);
+  hipError_t e = hipFuncSetAttribute((const void*)ob_rw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  RwArgs arg = a;
+  arg.mode = mode;
+  hipLaunchKernelGGL(ob_rw_kernel, dim3(a.n_chunks, (a.n_reps + kRReps - 1) / kRReps), dim3(kRB), lds, s, arg);
+  return hipGetLastError();
+}
+
+thread_local ob_reweight_timing g_timing = {};
+constexpr int kRwMaxPasses = 100;
+
+// The stages over one batch (or the point pass): the Newton loop, each replicate stopping on its own, the
+// Grams, the rows.
+int rw_batch(const RwArgs& a, hipStream_t s) {
+  if (a.k < 1 || a.k > kRMaxK || a.n_reps < 1 || a.part_pad < a.n_reps) return ob::fail(OB_E_INVALID, "reweight batch: bad shape");
+  Events<5> ev;
+  OB_HIP(ev.create());
+  OB_HIP(hipMemsetAsync(a.gamma, 0, sizeof(double) * (size_t)a.n_reps * a.k, s));
+  OB_HIP(hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * a.n_reps, s));
+  OB_HIP(hipMemsetAsync(a.passes, 0, sizeof(uint32_t) * a.n_reps, s));
+  int it = 0;
+  while (it < kRwMaxPasses) {
+    OB_HIP(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
+    OB_HIP(hipEventRecord(ev.e[0], s));
+    OB_HIP(launch_pass(a, kModeLogit, s));
+    OB_HIP(hipEventRecord(ev.e[1], s));
+    hipLaunchKernelGGL(ob_rw_step_kernel, dim3(a.n_reps), dim3(64), 0, s, a);
+    OB_HIP(hipGetLastError());
+    ++it;
+    uint32_t active = 0;
+    OB_HIP(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    OB_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    g_timing.logit_ms += ms;
+    g_timing.logit_launches += 1;
+    if (active == 0) break;
+  }
+  g_timing.logit_passes = std::max(g_timing.logit_passes, (int32_t)it);
+  OB_HIP(hipEventRecord(ev.e[2], s));
+  OB_HIP(launch_pass(a, kModeGram, s));
+  OB_HIP(launch_pass(a, kModeGramPsi, s));
+  OB_HIP(hipEventRecord(ev.e[3], s));
+  hipLaunchKernelGGL(ob_rw_row_kernel, dim3(a.n_reps), dim3(64), 0, s, a);
+  OB_HIP(hipGetLastError());
+  OB_HIP(hipEventRecord(ev.e[4], s));
+  OB_HIP(hipEventSynchronize(ev.e[4]));
+  float m0 = 0.f, m1 = 0.f;
+  OB_HIP(hipEventElapsedTime(&m0, ev.e[2], ev.e[3]));
+  OB_HIP(hipEventElapsedTime(&m1, ev.e[3], ev.e[4]));
+  g_timing.gram_ms += m0;
+  g_timing.row_ms += m1;
+  return OB_OK;
+}
+
+// Doubles of chunk partials per replicate and chunk: the logit pass and the c w Grams share one buffer.
+size_t partial_vals(int k) { return std::max<size_t>(rw_nv(k, kModeLogit), rw_nv(k, kModeGram)); }
+size_t partial_c_vals(int k) { return rw_nv(k, kModeGramPsi); }
+
+const char* const kLogitFailed = "%sFailed to solve Information Matrix in Logit. Perfect separation?";  // logit.rs:92
+
+}  // namespace
+
+namespace ob {
+
+int reweight_check_shape(int k, int64_t n_a, int64_t n_b) {
+  if (k < 1 || n_a < 0 || n_b < 0)
+    return fail(OB_E_INVALID, "reweighted decomposition: bad shape (k = %d, n_a = %lld, n_b = %lld)", k, (long long)n_a,
+                (long long)n_b);
+  if (k > kReweightMaxK)
+    return fail(OB_E_UNSUPPORTED, "reweighted decomposition: at most %d design columns with the intercept, got %d",
+                kReweightMaxK, k);
+  if (n_a >= ((int64_t)1 << 31) || n_b >= ((int64_t)1 << 31))
+    return fail(OB_E_UNSUPPORTED, "reweighted decomposition: groups take fewer than 2^31 rows");
+  for (int64_t n : {n_a, n_b})
+    if (n <= (int64_t)k)
+      return fail(OB_E_INSUFFICIENT,
+                  "%sreweighted decomposition: a group's rows (%lld) must exceed the design columns (%d)",
+                  error_prefix(OB_E_INSUFFICIENT), (long long)n, k);
+  return OB_OK;
+}
+
+// Device side of a prepared reweighted run. The handle's ob_panel (no predictors, the outcome alone) is the
+// resampler: engine_counts draws a segment's count images for its row counts, and its chunk table is the one
+// the passes walk.
+struct ReweightState {
+  int k = 0;
+  DevBuf cols[2];  // [y | x_1 .. x_{k-1} | w] x ld
+  DevBuf chunks, gamma, flags, passes, partial, partial_c;
+  int n_chunks = 0;
+};
+
+constexpr size_t kRwPartialBudget = (size_t)1 << 30;  // bytes of chunk partials and Grams per batch
+constexpr uint64_t kRwSegReps = 4096;                 // replicates per segment of count images
+constexpr uint64_t kRwCountBudget = 8ull << 30;       // bytes of count images per segment
+
+static RwArgs rw_args(const ob_prepared* pr, const ReweightState* st) {
+  const ob_panel* p = pr->panel;
+  RwArgs h{};
+  for (int g = 0; g < 2; ++g) {
+    h.cols[g] = st->cols[g].d();
+    h.ld[g] = p->ld[g];
+    h.n[g] = p->n[g];
+  }
+  h.tiles0 = p->ntiles[0];
+  h.k = st->k;
+  h.chunks = st->chunks.as<uint32_t>();
+  h.n_chunks = st->n_chunks;
+  h.row_len = pr->row_len;
+  h.tol = 1e-6;
+  return h;
+}
+
+// Replicates per batch: 64-replicate blocks whose chunk partials stay within the budget (option hk_batch forces
+// a smaller batch, as on the Heckman path). Rows do not depend on it.
+static uint32_t rw_batch_reps(const ReweightState* st, uint32_t rep_pad) {
+  const size_t per64 = (size_t)st->n_chunks * 64 * (partial_vals(st->k) + partial_c_vals(st->k)) * sizeof(double);
+  size_t blocks = std::max<size_t>(1, kRwPartialBudget / std::max<size_t>(per64, 1));
+  const int forced = opt_int(Opt::HkBatch, 0);
+  if (forced > 0) blocks = std::min<size_t>(blocks, (size_t)forced);
+  return (uint32_t)std::min<size_t>(rep_pad, blocks * 64);
+}
+
+// Workspace for batches of hb replicates.
+static int rw_ensure(ReweightState* st, uint32_t hb) {
+  OB_HIP(st->gamma.alloc(sizeof(double) * (size_t)hb * st->k));
+  OB_HIP(st->flags.alloc(sizeof(uint32_t) * ((size_t)hb + 1)));
+  OB_HIP(st->passes.alloc(sizeof(uint32_t) * (size_t)hb));
+  OB_HIP(st->partial.alloc(sizeof(double) * (size_t)st->n_chunks * hb * partial_vals(st->k)));
+  OB_HIP(st->partial_c.alloc(sizeof(double) * (size_t)st->n_chunks * hb * partial_c_vals(st->k)));
+  return OB_OK;
+}
+
+static void rw_bind(RwArgs& h, const ReweightState* st, uint32_t hb) {
+  h.part_pad = hb;
+  h.gamma = st->gamma.d();
+  h.flags = st->flags.as<uint32_t>();
+  h.active = h.flags + hb;
+  h.passes = st->passes.as<uint32_t>();
+  h.partial = st->partial.d();
+  h.partial_c = st->partial_c.d();
+}
+
+static int rw_point(ob_prepared* pr, ReweightState* st) {
+  ob_panel* p = pr->panel;
+  OB_HIP(hipSetDevice(p->ctx->device));
+  hipStream_t s = p->ctx->stream;
+  OB_TRY(rw_ensure(st, 64));
+  DevBuf d_row, d_ok;
+  OB_HIP(d_row.alloc(sizeof(double) * pr->row_len));
+  OB_HIP(d_ok.alloc(1));
+  RwArgs h = rw_args(pr, st);
+  rw_bind(h, st, 64);
+  h.counts = nullptr;
+  h.nb_rep = 1;
+  h.n_reps = 1;
+  h.rows = d_row.d();
+  h.ok = d_ok.as<uint8_t>();
+  OB_TRY(rw_batch(h, s));
+  uint8_t okh = 0;
+  pr->point_row.assign((size_t)pr->row_len, 0.0);
+  OB_HIP(hipMemcpyAsync(pr->point_row.data(), d_row.p, sizeof(double) * pr->row_len, hipMemcpyDeviceToHost, s));
+  OB_HIP(hipMemcpyAsync(&okh, d_ok.p, 1, hipMemcpyDeviceToHost, s));
+  OB_HIP(hipStreamSynchronize(s));
+  if (!okh) return fail(OB_E_LINALG, kLogitFailed, error_prefix(OB_E_LINALG));
+  return OB_OK;
+}
+
+static int rw_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
+                          hipStream_t stream) {
+  if (!pr || !pr->reweight || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
+  if (n_reps == 0) return OB_OK;
+  if (first_rep + n_reps > 0xFFFFFFFFull)
+    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 counter word)");
+  ReweightState* st = pr->reweight;
+  ob_panel* p = pr->panel;
+  OB_HIP(hipSetDevice(p->ctx->device));
+  hipStream_t s = stream ? stream : p->ctx->stream;
+  OB_TRY(engine_order(p, s));
+  g_timing = {};
+  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
+  const uint64_t batch_bytes = (uint64_t)std::max(tiles, 1u) * 4 * kCimgWords * sizeof(uint32_t);
+  const uint64_t seg_cap = std::max<uint64_t>(64, (kRwCountBudget / batch_bytes) * 64);
+  const uint64_t seg = std::min<uint64_t>(n_reps, std::min<uint64_t>(kRwSegReps, seg_cap));
+  const uint32_t seg_pad = (uint32_t)((seg + 63) / 64 * 64);
+  const uint32_t hb = rw_batch_reps(st, seg_pad);
+  OB_TRY(rw_ensure(st, hb));
+  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
+  int rc = OB_OK;
+  for (uint64_t s0 = 0; s0 < n_reps && rc == OB_OK; s0 += seg) {
+    const uint32_t ns = (uint32_t)std::min<uint64_t>(seg, n_reps - s0);
+    uint32_t nb_rep = 0, rep_pad = 0;
+    rc = engine_counts(p, pr->seed, first_rep + s0, ns, s, &nb_rep, &rep_pad);
+    if (rc != OB_OK) break;
+    for (uint32_t b0 = 0; b0 < ns && rc == OB_OK; b0 += hb) {  // hb is a multiple of 64: whole image blocks
+      RwArgs h = rw_args(pr, st);
+      rw_bind(h, st, hb);
+      h.counts = p->d_counts + (size_t)(b0 / 64) * 4 * kCimgWords;
+      h.nb_rep = nb_rep;
+      h.n_reps = std::min(hb, ns - b0);
+      h.rows = d_rows + (s0 + b0) * pr->row_len;
+      h.ok = d_ok + s0 + b0;
+      rc = rw_batch(h, s);
+    }
+  }
+  uint32_t flag = 0;
+  if (rc == OB_OK && hipMemcpyAsync(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
+    rc = fail(OB_E_HIP, "copy of the overflow word failed");
+  if (rc == OB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(OB_E_HIP, "stream synchronize failed");
+  const int rm = engine_mark(p, s);
+  if (rc != OB_OK) return rc;
+  if (flag & 1u) return fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
+  return rm;
+}
+
+static int rw_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
+  if (!pr || !pr->reweight || (n_reps && (!rows || !ok))) return fail(OB_E_INVALID, "null pointer");
+  if (n_reps == 0) return OB_OK;
+  OB_HIP(hipSetDevice(pr->panel->ctx->device));
+  DevBuf d_rows, d_ok;
+  OB_HIP(d_rows.alloc(sizeof(double) * n_reps * pr->row_len));
+  OB_HIP(d_ok.alloc(n_reps));
+  OB_TRY(rw_boot_device(pr, first_rep, n_reps, d_rows.d(), d_ok.as<uint8_t>(), nullptr));
+  OB_HIP(hipMemcpy(rows, d_rows.p, sizeof(double) * n_reps * pr->row_len, hipMemcpyDeviceToHost));
+  OB_HIP(hipMemcpy(ok, d_ok.p, n_reps, hipMemcpyDeviceToHost));
+  return OB_OK;
+}
+
+static void rw_free(ReweightState* s) { delete s; }
+
+// installs the builder's hooks when the library loads (ob_reweight.hpp)
+static const bool g_reweight_hooks_installed = [] {
+  ReweightHooks& h = reweight_hooks();
+  h.boot_device = rw_boot_device;
+  h.boot_host = rw_boot_host;
+  h.free_state = rw_free;
+  return true;
+}();
+
+// Every check of the frame entry points, before any device work and before the context is read: settings
+// outside the scope, nulls and non-finite values in named columns, the design (ob::data_matrices), the shape.
+// On success m holds the design matrices and the groups' weights.
+static int rw_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, Config& c,
+                    ob_matrices** m) {
+  OB_TRY(config_from(cfg, c));
+  if (!c.normalize.empty())
+    return fail(OB_E_UNSUPPORTED, "reweighted decomposition: normalized categoricals are outside its scope");
+  if (c.has_selection || !c.selection_predictors.empty())
+    return fail(OB_E_UNSUPPORTED, "reweighted decomposition: Heckman selection settings are outside its scope");
+  Frame f;
+  OB_TRY(load_frame(cols, n_cols, n_rows, f));
+  std::vector<std::string> named = {c.outcome, c.group};
+  named.insert(named.end(), c.predictors.begin(), c.predictors.end());
+  named.insert(named.end(), c.categorical.begin(), c.categorical.end());
+  if (c.has_weights) named.push_back(c.weights);
+  for (const std::string& name : named) {
+    const int i = f.find(name);
+    if (i < 0) return fail(OB_E_COLUMN, "%s%s", error_prefix(OB_E_COLUMN), name.c_str());
+    const Col& col = f.cols[i];
+    for (int64_t r = 0; r < f.nrows; ++r) {
+      if (!col.valid[r])
+        return fail(OB_E_INVALID, "reweighted decomposition: column `%s` has a null in row %lld", name.c_str(), (long long)r);
+      if (col.kind == OB_COL_F64 && !std::isfinite(col.f[r]))
+        return fail(OB_E_INVALID, "reweighted decomposition: column `%s` has a non-finite value in row %lld", name.c_str(),
+                    (long long)r);
+    }
+  }
+  OB_TRY(data_matrices(cols, n_cols, n_rows, cfg, true, m));
+  int64_t n_a = 0, n_b = 0;
+  int32_t k = 0;
+  int rc = ob_matrices_dims(*m, &n_a, &n_b, &k);
+  if (rc == OB_OK && k > kReweightMaxK) rc = reweight_check_shape(k, n_a, n_b);
+  if (rc == OB_OK && (n_a == 0 || n_b == 0)) rc = fail(OB_E_GROUP, "%sOne group has no data", error_prefix(OB_E_GROUP));
+  if (rc == OB_OK) rc = reweight_check_shape(k, n_a, n_b);
+  if (rc != OB_OK) {
+    ob_matrices_free(*m);
+    *m = nullptr;
+  }
+  return rc;
+}
+
+static int rw_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                      ob_prepared** out) {
+  Config c;
+  ob_matrices* m = nullptr;
+  OB_TRY(rw_stage(cols, n_cols, n_rows, cfg, c, &m));
+  struct Guard {
+    ob_matrices* m;
+    ~Guard() { ob_matrices_free(m); }
+  } guard{m};
+  if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
+  int64_t n_a = 0, n_b = 0;
+  int32_t k = 0;
+  const double *xa, *ya, *xb, *yb;
+  OB_TRY(ob_matrices_dims(m, &n_a, &n_b, &k));
+  OB_TRY(ob_matrices_get(m, &xa, &ya, &xb, &yb));
+  ob_panel_desc pd{};  // the resampler: the groups' row counts and the outcome
+  pd.p = 0;
+  pd.n_y = 1;
+  pd.a = {n_a, nullptr, n_a, ya, nullptr};
+  pd.b = {n_b, nullptr, n_b, yb, nullptr};
+  ob_prepared* pr = new ob_prepared();
+  pr->ctx = ctx;
+  pr->cfg = c;
+  pr->ref = c.ref;
+  if (c.has_seed) {
+    pr->seed = c.seed;
+  } else {
+    std::random_device rd;
+    pr->seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
+  }
+  pr->k = k;
+  pr->n_base = 0;
+  pr->row_len = reweight_row_len(k);
+  for (int32_t j = 0; j < k; ++j) pr->names.emplace_back(ob_matrices_name(m, j));
+  pr->detail_names = pr->names;
+  pr->n_a = n_a;
+  pr->n_b = n_b;
+  pr->n_y = 1;
+  pr->n_resid = 0;
+  ReweightState* st = new ReweightState();
+  st->k = k;
+  pr->reweight = st;
+  auto build = [&]() -> int {
+    OB_TRY(ob_panel_create(ctx, &pd, &pr->panel));
+    ob_panel* p = pr->panel;
+    for (int g = 0; g < 2; ++g) {  // [y | x_1 .. | w] x ld, zero past n (x of ob_matrices: column 0 is the intercept)
+      const int64_t n = g ? n_b : n_a;
+      const double* x = g ? xb : xa;
+      const double* y = g ? yb : ya;
+      const double* w = matrices_weights(m, g);
+      const size_t bytes = sizeof(double) * (size_t)(k + 1) * p->ld[g];
+      OB_HIP(st->cols[g].alloc(bytes));
+      OB_HIP(hipMemset(st->cols[g].p, 0, bytes));
+      OB_HIP(hipMemcpy(st->cols[g].p, y, sizeof(double) * n, hipMemcpyHostToDevice));
+      if (k > 1)
+        OB_HIP(hipMemcpy2D(st->cols[g].d() + p->ld[g], sizeof(double) * p->ld[g], x + n, sizeof(double) * n,
+                           sizeof(double) * n, k - 1, hipMemcpyHostToDevice));
+      const std::vector<double> unit(w ? 0 : (size_t)n, 1.0);
+      OB_HIP(hipMemcpy(st->cols[g].d() + (size_t)k * p->ld[g], w ? w : unit.data(), sizeof(double) * n,
+                       hipMemcpyHostToDevice));
+    }
+    int32_t nc = 0;
+    OB_TRY(ob_debug_chunks(p, nullptr, 0, &nc));
+    std::vector<uint32_t> table((size_t)3 * nc);
+    OB_TRY(ob_debug_chunks(p, table.data(), nc, &nc));
+    st->n_chunks = nc;
+    OB_HIP(st->chunks.alloc(sizeof(uint32_t) * table.size()));
+    OB_HIP(hipMemcpy(st->chunks.p, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
+    g_timing = {};
+    return rw_point(pr, st);
+  };
+  const int rc = build();
+  if (rc != OB_OK) {
+    ob_prepared_destroy(pr);
+    return rc;
+  }
+  *out = pr;
+  return OB_OK;
+}
+
+// The array pieces: one launch of ob_rw_kernel in `mode` over up to two groups of rows (gx[g]: n_g x k
+// column-major with ld n_g, column 0 the intercept), every one of the n_gammas replicates counting the rows as
+// `counts` does. sums [n_gammas][rw_nv(k, mode)]: the chunk partials added in chunk order.
+static int rw_piece(ob_ctx* ctx, int mode, int k, const std::vector<double> (&gx)[2], const std::vector<double> (&gy)[2],
+                    const std::vector<double> (&gw)[2], const std::vector<uint8_t> (&gc)[2], bool counted,
+                    const double* gammas, int n_gammas, std::vector<double>& sums) {
+  OB_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  uint32_t n[2], tiles[2];
+  int64_t ld[2];
+  std::vector<uint32_t> chunks;
+  for (int g = 0; g < 2; ++g) {
+    n[g] = (uint32_t)gy[g].size();
+    tiles[g] = (n[g] + OB_TILE_ROWS - 1) / OB_TILE_ROWS;
+    ld[g] = (int64_t)tiles[g] * OB_TILE_ROWS;
+    const uint32_t nc = std::min<uint32_t>(tiles[g], 64u);
+    for (uint32_t c = 0; c < nc; ++c) {
+      chunks.push_back((uint32_t)g);
+      chunks.push_back((uint32_t)((uint64_t)tiles[g] * c / nc));
+      chunks.push_back((uint32_t)((uint64_t)tiles[g] * (c + 1) / nc));
+    }
+  }
+  const int n_chunks = (int)(chunks.size() / 3), nv = rw_nv(k, mode);
+  DevBuf d_cols[2], d_chunks, d_gamma, d_flags, d_partial, d_counts;
+  for (int g = 0; g < 2; ++g) {
+    const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(ld[g], 1) * (k + 1);
+    OB_HIP(d_cols[g].alloc(bytes));
+    OB_HIP(hipMemsetAsync(d_cols[g].p, 0, bytes, s));
+    if (!n[g]) continue;
+    OB_HIP(hipMemcpyAsync(d_cols[g].p, gy[g].data(), sizeof(double) * n[g], hipMemcpyHostToDevice, s));
+    for (int j = 1; j < k; ++j)
+      OB_HIP(hipMemcpyAsync(d_cols[g].d() + (size_t)j * ld[g], gx[g].data() + (size_t)j * n[g], sizeof(double) * n[g],
+                            hipMemcpyHostToDevice, s));
+    OB_HIP(hipMemcpyAsync(d_cols[g].d() + (size_t)k * ld[g], gw[g].data(), sizeof(double) * n[g], hipMemcpyHostToDevice, s));
+  }
+  OB_HIP(d_chunks.alloc(sizeof(uint32_t) * chunks.size()));
+  OB_HIP(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(uint32_t) * chunks.size(), hipMemcpyHostToDevice, s));
+  OB_HIP(d_gamma.alloc(sizeof(double) * (size_t)n_gammas * k));
+  OB_HIP(hipMemcpyAsync(d_gamma.p, gammas, sizeof(double) * (size_t)n_gammas * k, hipMemcpyHostToDevice, s));
+  OB_HIP(d_flags.alloc(sizeof(uint32_t) * 64));
+  OB_HIP(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t) * 64, s));
+  OB_HIP(d_partial.alloc(sizeof(double) * (size_t)n_chunks * 64 * nv));
+  OB_HIP(hipMemsetAsync(d_partial.p, 0, sizeof(double) * (size_t)n_chunks * 64 * nv, s));
+  std::vector<uint32_t> img;  // one 64-replicate block of the f64 Gram's count images (ob_engine.hpp)
+  if (counted) {
+    img.assign((size_t)(tiles[0] + tiles[1]) * 4 * kCimgWords, 0u);
+    for (int g = 0; g < 2; ++g)
+      for (uint32_t i = 0; i < n[g]; ++i) {
+        const size_t t = (g ? tiles[0] : 0u) + i / OB_TILE_ROWS, within = i % OB_TILE_ROWS, sub = within >> 6, qq = within & 63;
+        for (int r = 0; r < n_gammas; ++r)
+          img[(t * 4 + sub) * kCimgWords + (size_t)r * kCimgStride + (qq >> 2)] |= (uint32_t)gc[g][i] << (8 * (qq & 3));
+      }
+    OB_HIP(d_counts.alloc(sizeof(uint32_t) * img.size()));
+    OB_HIP(hipMemcpyAsync(d_counts.p, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice, s));
+  }
+  RwArgs h{};
+  for (int g = 0; g < 2; ++g) {
+    h.cols[g] = d_cols[g].d();
+    h.ld[g] = ld[g];
+    h.n[g] = n[g];
+  }
+  h.tiles0 = tiles[0];
+  h.k = k;
+  h.counts = counted ? d_counts.as<uint32_t>() : nullptr;
+  h.nb_rep = 1;
+  h.chunks = d_chunks.as<uint32_t>();
+  h.n_chunks = n_chunks;
+  h.n_reps = (uint32_t)n_gammas;
+  h.part_pad = 64;
+  h.gamma = d_gamma.d();
+  h.flags = d_flags.as<uint32_t>();
+  h.partial = d_partial.d();
+  h.partial_c = d_partial.d();
+  OB_HIP(launch_pass(h, mode, s));
+  std::vector<double> part((size_t)n_chunks * 64 * nv);
+  OB_HIP(hipMemcpyAsync(part.data(), d_partial.p, sizeof(double) * part.size(), hipMemcpyDeviceToHost, s));
+  OB_HIP(hipStreamSynchronize(s));
+  sums.assign((size_t)n_gammas * nv, 0.0);
+  for (int c = 0; c < n_chunks; ++c) {  // chunk order, as the step and row kernels
+    if (mode == kModeGramPsi && chunks[3 * c] == 0) continue;
+    for (int r = 0; r < n_gammas; ++r)
+      for (int e = 0; e < nv; ++e) sums[(size_t)r * nv + e] += part[((size_t)c * 64 + r) * nv + e];
+  }
+  return OB_OK;
+}
+
+// The argument checks the two array pieces share (before any device work).
+static int rw_piece_check(const char* what, const double* x, int64_t ldx, const double* second, int64_t n, int32_t k,
+                          const uint8_t* counts, const double* gammas, int32_t n_gammas, const void* out0, const void* out1) {
+  if (!x || !second || !gammas || !out0 || !out1) return fail(OB_E_INVALID, "null pointer");
+  if (n <= 0 || k < 1) return fail(OB_E_INVALID, "%s needs n > 0 rows and k >= 1 columns, got n = %lld, k = %d", what, (long long)n, k);
+  if (k > kReweightMaxK) return fail(OB_E_UNSUPPORTED, "%s takes at most %d columns, got %d", what, kReweightMaxK, k);
+  if (n_gammas < 1 || n_gammas > 64) return fail(OB_E_INVALID, "%s takes 1 to 64 coefficient vectors, got %d", what, n_gammas);
+  if (ldx < n) return fail(OB_E_INVALID, "%s: ldx = %lld is below n = %lld", what, (long long)ldx, (long long)n);
+  if (n >= ((int64_t)1 << 31)) return fail(OB_E_UNSUPPORTED, "%s takes fewer than 2^31 rows", what);
+  for (int64_t i = 0; i < n; ++i)  // the pass takes x_0 = 1 as given
+    if (x[i] != 1.0) return fail(OB_E_UNSUPPORTED, "%s: column 0 of x must be the intercept (all ones)", what);
+  (void)counts;
+  return OB_OK;
+}
+
+// Copies the rows `take` selects into group g of the piece's inputs.
+static void rw_gather(const double* x, int64_t ldx, const double* y, const double* w, const uint8_t* counts, int64_t n, int k,
+                      const std::vector<int64_t>& take, std::vector<double>& gx, std::vector<double>& gy,
+                      std::vector<double>& gw, std::vector<uint8_t>& gc) {
+  (void)n;
+  const size_t m = take.size();
+  gx.assign(m * k, 0.0);
+  gy.assign(m, 0.0);
+  gw.assign(m, 1.0);
+  gc.assign(m, 1);
+  for (size_t i = 0; i < m; ++i) {
+    const int64_t r = take[i];
+    for (int j = 0; j < k; ++j) gx[(size_t)j * m + i] = x[(size_t)j * ldx + r];
+    if (y) gy[i] = y[r];
+    if (w) gw[i] = w[r];
+    if (counts) gc[i] = counts[r];
+  }
+}
+
+}  // namespace ob
+
+extern "C" {
+
+int ob_reweight_row_len(int32_t k) { return k < 1 ? 0 : ob::reweight_row_len(k); }
+
+int ob_reweight_check_shape(int32_t k, int64_t n_a, int64_t n_b) { return ob::reweight_check_shape(k, n_a, n_b); }
+
+int ob_reweight_last_timing(ob_reweight_timing* out) {
+  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = g_timing;
+  return OB_OK;
+}
+
+int ob_builder_prepare_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                  const ob_builder_config* cfg, ob_prepared** out) {
+  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  return ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, out);
+}
+
+int ob_builder_run_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                              const ob_builder_config* cfg, ob_results** out) {
+  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  ob_prepared* pr = nullptr;
+  OB_TRY(ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, &pr));
+  const uint64_t reps = pr->cfg.reps;
+  std::vector<double> rows((size_t)reps * pr->row_len);
+  std::vector<uint8_t> ok(reps, 0);
+  int rc = OB_OK;
+  if (reps > 0) rc = ob_prepared_boot(pr, 0, reps, rows.data(), ok.data());
+  if (rc == OB_OK) rc = ob::finish(pr, 0, rows.data(), ok.data(), reps, out);
+  ob_prepared_destroy(pr);
+  return rc;
+}
+
+// One logit pass alone (include/oaxaca_boot.h). The rows with d = 1 form group A and the others group B, as the
+// stacked logit of a run sees them.
+int ob_reweight_logit_pass(ob_ctx* ctx, const double* x, int64_t ldx, const double* d, const double* w,
+                           const uint8_t* counts, int64_t n, int32_t k, const double* gammas, int32_t n_gammas,
+                           double* info, double* grad) {
+  OB_TRY(ob::rw_piece_check("ob_reweight_logit_pass", x, ldx, d, n, k, counts, gammas, n_gammas, info, grad));
+  std::vector<int64_t> take[2];
+  for (int64_t i = 0; i < n; ++i) {
+    if (d[i] != 0.0 && d[i] != 1.0) return ob::fail(OB_E_INVALID, "ob_reweight_logit_pass: d must be exactly 0.0 or 1.0, got %g", d[i]);
+    take[d[i] == 1.0 ? 0 : 1].push_back(i);
+  }
+  if (!ctx) return ob::fail(OB_E_INVALID, "null pointer: ctx");
+  std::vector<double> gx[2], gy[2], gw[2];
+  std::vector<uint8_t> gc[2];
+  for (int g = 0; g < 2; ++g) ob::rw_gather(x, ldx, nullptr, w, counts, n, k, take[g], gx[g], gy[g], gw[g], gc[g]);
+  std::vector<double> sums;
+  OB_TRY(ob::rw_piece(ctx, kModeLogit, k, gx, gy, gw, gc, counts != nullptr, gammas, n_gammas, sums));
+  const int NH = k * (k + 1) / 2, nv = NH + k;
+  for (int r = 0; r < n_gammas; ++r) {
+    for (int j = 0; j < k; ++j) {
+      for (int i = 0; i <= j; ++i) {
+        const double v = sums[(size_t)r * nv + j * (j + 1) / 2 + i];
+        info[((size_t)r * k + j) * k + i] = v;
+        info[((size_t)r * k + i) * k + j] = v;
+      }
+      grad[(size_t)r * k + j] = sums[(size_t)r * nv + NH + j];
+    }
+  }
+  return OB_OK;
+}
+
+// The psi-weighted extended Gram alone (include/oaxaca_boot.h): the rows form group B.
+int ob_reweight_gram(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, const double* w, const uint8_t* counts,
+                     int64_t n, int32_t k, const double* gammas, int32_t n_gammas, double* gram, double* ess_den) {
+  OB_TRY(ob::rw_piece_check("ob_reweight_gram", x, ldx, y, n, k, counts, gammas, n_gammas, gram, ess_den));
+  if (!ctx) return ob::fail(OB_E_INVALID, "null pointer: ctx");
+  std::vector<int64_t> take(n);
+  for (int64_t i = 0; i < n; ++i) take[i] = i;
+  std::vector<double> gx[2], gy[2], gw[2];
+  std::vector<uint8_t> gc[2];
+  ob::rw_gather(x, ldx, y, w, counts, n, k, take, gx[1], gy[1], gw[1], gc[1]);
+  std::vector<double> sums;
+  OB_TRY(ob::rw_piece(ctx, kModeGramPsi, k, gx, gy, gw, gc, counts != nullptr, gammas, n_gammas, sums));
+  const int k1 = k + 1, E = k1 * (k1 + 1) / 2, nv = E + 1;
+  for (int r = 0; r < n_gammas; ++r) {
+    for (int j = 0; j < k1; ++j)
+      for (int i = 0; i <= j; ++i) {
+        const double v = sums[(size_t)r * nv + j * (j + 1) / 2 + i];
+        gram[((size_t)r * k1 + j) * k1 + i] = v;
+        gram[((size_t)r * k1 + i) * k1 + j] = v;
+      }
+    ess_den[r] = sums[(size_t)r * nv + E];
+  }
+  return OB_OK;
+}
+
+}  // extern "C"

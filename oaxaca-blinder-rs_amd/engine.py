@@ -485,6 +485,75 @@ def binary_last_timing() -> dict:
     return {f: getattr(t, f) for f, _ in N.ob_binary_timing._fields_}
 
 
+def _reweight_args(x, second, w, counts, gammas):
+    """The arrays of the two reweighting pieces as the C ABI takes them."""
+    xf = np.asfortranarray(x, dtype=np.float64)
+    if xf.ndim != 2:
+        raise ValueError("x must be (n, k)")
+    n, k = xf.shape
+    second = np.ascontiguousarray(second, dtype=np.float64)
+    g = np.ascontiguousarray(np.atleast_2d(gammas), dtype=np.float64)
+    if second.shape != (n,) or g.ndim != 2 or g.shape[1] != k:
+        raise ValueError("d / y must have one entry per row of x and gammas must be (R, k)")
+    wv = None
+    if w is not None:
+        wv = np.ascontiguousarray(w, dtype=np.float64)
+        if wv.shape != (n,):
+            raise ValueError("w must have one entry per row of x")
+    c8 = None
+    if counts is not None:
+        c = np.ascontiguousarray(counts)
+        if c.shape != (n,) or (c < 0).any() or (c > 255).any():
+            raise ValueError("counts must be n integers in [0, 255]")
+        c8 = c.astype(np.uint8)
+    return xf, second, wv, c8, g, n, k
+
+
+def reweight_logit_pass(x, d, gammas, w=None, counts=None, device: int | None = None):
+    """One Newton pass of the reweighted decomposition's propensity logit alone (``ob_reweight_logit_pass``).
+    ``x``: (n, k) with the intercept (all ones) as column 0, ``k <= 32``; ``d``: n values 0.0 / 1.0; ``gammas``:
+    (R, k) coefficient vectors, ``R <= 64``; ``w``: n weights (``None``: 1); ``counts``: n resample counts below
+    256 (``None``: every row once). Returns ``(info, grad)``: (R, k, k) sums c w p (1 - p) x x' and (R, k) sums
+    c w (d - p) x, p the sigmoid of x'gamma clamped to [1e-10, 1 - 1e-10]."""
+    xf, dv, wv, c8, g, n, k = _reweight_args(x, d, w, counts, gammas)
+    info, grad = np.empty((len(g), k, k)), np.empty((len(g), k))
+    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
+    with_context(lambda ctx: N.lib().ob_reweight_logit_pass(ctx, _dp(xf), max(n, 1), _dp(dv), _dp(wv), cp, n, k, _dp(g),
+                                                           len(g), _dp(info), _dp(grad)), device)
+    return info, grad
+
+
+def reweight_gram(x, y, gammas, w=None, counts=None, device: int | None = None):
+    """The psi-weighted extended Gram of the reweighted decomposition alone (``ob_reweight_gram``) over one
+    group: ``(gram, ess_den)`` with gram (R, k + 1, k + 1) = sum c w psi v v', v = [x, y], psi = p / (1 - p) of the
+    clamped p at each of the (R, k) ``gammas``, and ess_den (R) = sum c (w psi)^2. Arguments as
+    ``reweight_logit_pass``."""
+    xf, yv, wv, c8, g, n, k = _reweight_args(x, y, w, counts, gammas)
+    gram, den = np.empty((len(g), k + 1, k + 1)), np.empty(len(g))
+    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
+    with_context(lambda ctx: N.lib().ob_reweight_gram(ctx, _dp(xf), max(n, 1), _dp(yv), _dp(wv), cp, n, k, _dp(g), len(g),
+                                                     _dp(gram), _dp(den)), device)
+    return gram, den
+
+
+def reweight_check_shape(k: int, n_a: int, n_b: int) -> None:
+    """ob_reweight_check_shape: raises OaxacaError where a reweighted decomposition would (host only)."""
+    N.check(N.lib().ob_reweight_check_shape(int(k), int(n_a), int(n_b)))
+
+
+def reweight_row_len(k: int) -> int:
+    """ob_reweight_row_len: 7 + 11k + 5 doubles per replicate of a reweighted decomposition."""
+    return int(N.lib().ob_reweight_row_len(int(k)))
+
+
+def reweight_last_timing() -> dict:
+    """ob_reweight_last_timing: logit passes and HIP-event ms (logit passes, Grams, rows) of this thread's last
+    reweighted boot."""
+    t = N.ob_reweight_timing()
+    N.check(N.lib().ob_reweight_last_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in N.ob_reweight_timing._fields_}
+
+
 def knn(queries, controls, k: int, device: int | None = None):
     """The min(k, n_c) nearest controls of each query (``ob_knn``): squared Euclidean distance summed
     in covariate order without FMA, ties by control position. ``queries``: (n_q, d), ``controls``:

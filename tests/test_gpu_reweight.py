@@ -1,0 +1,290 @@
+"""The reweighted Oaxaca-Blinder decomposition on the GPU (csrc/ob_reweight.hip) against the
+numpy restatement tests/reweight_ref.py: the logit pass and the psi-weighted Gram alone, the point row and the
+replicate rows on the same counts, bitwise determinism, the failure path and the builder end to end.
+
+Groups of 130 and 257 rows (a ragged last 64-row sub-tile, more than one tile, two chunks in B), K = 3, 9, 16,
+17 and 32 (both sides of a 16-column block, and the limit), weighted and unweighted, 67 replicates at first_rep 0
+and the 39 that exist from first_rep 2^32 - 40 (replicate ids stay below 2^32 - 1).
+
+The pieces' tolerance is 8 E, E the largest error of the f64 restatement against its longdouble run on the same
+inputs, relative to sqrt(G_aa G_bb); the figures are in DESIGN.md §5.14.
+
+The panel rule the issue asks for -- every replicate's step norms a factor 10 away from 1e-6 -- does not hold for
+all replicates at these row counts: Newton's norms square from pass to pass, so the band [1e-7, 1e-5] catches a
+replicate whenever its last-but-one norm falls between about 3e-4 and 3e-3, and a CPU scan over the covariate
+shift (0 .. 2.5) and scale left 8 of 67 replicates inside at best. The tests assert what the panel does give
+(every replicate converges in at most 25 passes) and print how many lie in the band; ok and the pass counts are
+still compared for equality on every replicate."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import reweight_ref as R  # noqa: E402
+from test_gpu_parity import RTOL, SEED, close  # noqa: E402  (the Heckman and binary tests' row tolerance)
+
+pytestmark = pytest.mark.gpu
+
+REPS = 64 + 3  # a ragged replicate batch
+HIGH = 2 ** 32 - 40
+KS = [3, 9, 16, 17, 32]
+
+
+def frame_of(xa, ya, xb, yb, wa, wb):
+    k = xa.shape[1]
+    f = {"y": np.concatenate([ya, yb]).tolist(), "g": ["A"] * len(ya) + ["B"] * len(yb)}
+    for j in range(1, k):
+        f[f"x{j}"] = np.concatenate([xa[:, j], xb[:, j]]).tolist()
+    if wa is not None:
+        f["w"] = np.concatenate([wa, wb]).tolist()
+    return f, [f"x{j}" for j in range(1, k)]
+
+
+def builder(ob, k, weighted, reps=REPS):
+    f, xs = frame_of(*R.panel(k, weighted))
+    b = ob.OaxacaBuilder(f, "y", "g", "B").predictors(xs).bootstrap_reps(reps).seed(SEED)
+    return b.weights("w") if weighted else b
+
+
+_ref = {}
+
+
+def ref_rows(O, k, weighted):
+    """The restatement's point row, its REPS rows from replicate 0 and its 39 from HIGH, computed once and shared
+    (read-only)."""
+    if (k, weighted) not in _ref:
+        xa, ya, xb, yb, wa, wb = R.panel(k, weighted)
+        point, pn = R.decompose(xa, ya, xb, yb, wa, wb)
+        assert point is not None
+        lo = R.boot(O, xa, ya, xb, yb, wa, wb, SEED, 0, REPS)
+        hi = R.boot(O, xa, ya, xb, yb, wa, wb, SEED, HIGH, 39)
+        norms = [pn] + lo[2] + hi[2]
+        assert lo[1].all() and hi[1].all() and max(len(v) for v in norms) <= 25
+        print(f"k={k} weighted={weighted}: {sum(not R.margin_ok(v) for v in norms)} of {len(norms)} logits have a "
+              f"step norm within a factor 10 of 1e-6")
+        for a in (point, lo[0], hi[0]):
+            a.setflags(write=False)
+        _ref[(k, weighted)] = (point, lo[0], hi[0])
+    return _ref[(k, weighted)]
+
+
+def piece_inputs(O, k, weighted):
+    """Stacked rows of a panel, a zero-weight row, and counts with a zero-count row; gammas: 0, a fitted-size one
+    and one that drives some p into the clamp."""
+    xa, ya, xb, yb, wa, wb = R.panel(k, weighted)
+    x, y = np.vstack([xa, xb]), np.concatenate([ya, yb])
+    d = np.concatenate([np.ones(len(ya)), np.zeros(len(yb))])
+    w = np.concatenate([wa, wb]) if weighted else np.ones(len(y))
+    w[7] = 0.0
+    c = np.concatenate([R.counts(O, SEED, 5, 0, len(ya)), R.counts(O, SEED, 5, 1, len(yb))])
+    c[11] = 0
+    rng = np.random.default_rng(k)
+    g1 = rng.normal(size=k) * 0.4 / np.sqrt(k)
+    g2 = g1 * 40.0 / np.abs(x @ g1).max()  # |x'gamma| up to 40: p beyond the clamp
+    gammas = np.array([np.zeros(k), g1, g2])
+    p = R.sigmoid_clamped(x @ g2)
+    assert (p == R.HI).any() or (p == R.LO).any()
+    return x, y, d, w, c, gammas
+
+
+def rel_err(got, want):
+    """The largest error relative to sqrt(G_aa G_bb) of a symmetric matrix."""
+    dg = np.sqrt(np.abs(np.diag(want)))
+    return float(np.max(np.abs(got - want) / np.outer(dg, dg)))
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+@pytest.mark.parametrize("k", KS)
+def test_pieces_match_numpy(ob, O, k, weighted):
+    x, y, d, w, c, gammas = piece_inputs(O, k, weighted)
+    L = np.longdouble
+    for counts in (None, c):
+        cf = np.ones(len(y)) if counts is None else counts.astype(float)
+        cw = cf * w
+        info, grad = ob.reweight_logit_pass(x, d, gammas, w=w, counts=counts)
+        gram, den = ob.reweight_gram(x[d == 0], y[d == 0], gammas, w=w[d == 0], counts=None if counts is None else c[d == 0])
+        for i, g in enumerate(gammas):
+            i64, g64 = R.logit_pass(x, d, cw, g)
+            iL, gL = R.logit_pass(x, d, cw, g, dtype=L)
+            e_info = rel_err(i64.astype(L), iL)
+            dev_info = rel_err(info[i].astype(L), iL)
+            gscale = np.sqrt(np.abs(np.diag(iL)) * np.sum(cw))  # |sum c w (d - p) x_j| <= sqrt(sum cw x_j^2 sum cw)
+            gscale = np.maximum(gscale, np.abs(gL))
+            e_grad = float(np.max(np.abs(g64 - gL) / gscale))
+            dev_grad = float(np.max(np.abs(grad[i] - gL) / gscale))
+            b = d == 0
+            m64, s64 = R.psi_gram(x[b], y[b], cw[b], w[b], cf[b], g)
+            mL, sL = R.psi_gram(x[b], y[b], cw[b], w[b], cf[b], g, dtype=L)
+            e_gram = rel_err(m64.astype(L), mL)
+            dev_gram = rel_err(gram[i].astype(L), mL)
+            e_den, dev_den = float(abs(s64 - sL) / sL), float(abs(den[i] - sL) / sL)
+            print(f"k={k} w={weighted} counts={counts is not None} gamma#{i}: E info {e_info:.2e} dev {dev_info:.2e} | "
+                  f"E grad {e_grad:.2e} dev {dev_grad:.2e} | E gram {e_gram:.2e} dev {dev_gram:.2e} | "
+                  f"E den {e_den:.2e} dev {dev_den:.2e}")
+            E = max(e_info, e_grad, e_gram, e_den)
+            assert E > 0.0
+            assert dev_info <= 8 * E and dev_grad <= 8 * E and dev_gram <= 8 * E and dev_den <= 8 * E
+            assert np.array_equal(info[i], info[i].T) and np.array_equal(gram[i], gram[i].T)
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+@pytest.mark.parametrize("k", KS)
+def test_rows_match_ref(ob, O, N, k, weighted):
+    point, lo, hi = ref_rows(O, k, weighted)
+    pr = builder(ob, k, weighted).prepare_reweighted()
+    try:
+        assert pr.row_len == R.row_len(k)
+        got_point = pr.point_row()
+        got_lo, ok_lo = pr.boot(0, REPS)
+        got_hi, ok_hi = pr.boot(HIGH, 39)
+    finally:
+        pr.close()
+    assert ok_lo.all() and ok_hi.all() and np.isfinite(got_point).all()
+    good, worst = close(got_point, point, point[0])
+    print(f"k={k} weighted={weighted}: point worst {worst:.3e}")
+    assert good, worst
+    assert got_point[-1] == point[-1]
+    for got, want in ((got_lo, lo), (got_hi, hi)):
+        worst_all = 0.0
+        for r in range(len(want)):
+            good, worst = close(got[r], want[r], want[r][0])
+            worst_all = max(worst_all, worst)
+            assert good, (r, worst)
+        assert np.array_equal(got[:, -1], want[:, -1])  # the pass counts
+        print(f"k={k} weighted={weighted}: replicate worst {worst_all:.3e}")
+
+
+@pytest.mark.parametrize("k", [3, 17])
+def test_rows_are_deterministic(ob, N, k):
+    """Bitwise: replicate 5 alone, in a batch of 67, at a shifted first_rep and at two batch sizes forced through
+    hk_batch; a repeated call."""
+    b = builder(ob, k, True, reps=200)
+    pr = b.prepare_reweighted()
+    try:
+        r0, k0 = pr.boot(0, 200)
+        r1, k1 = pr.boot(0, REPS)
+        r2, k2 = pr.boot(5, 1)
+        r3, k3 = pr.boot(3, 130)
+        r4, k4 = pr.boot(0, 200)
+        with N.option("hk_batch", 1):
+            r5, k5 = pr.boot(0, 200)
+        with N.option("hk_batch", 2):
+            r6, k6 = pr.boot(0, 200)
+    finally:
+        pr.close()
+    assert k0.all()
+    assert r0.tobytes() == r4.tobytes() and np.array_equal(k0, k4)
+    assert r0[:REPS].tobytes() == r1.tobytes() and np.array_equal(k0[:REPS], k1)
+    assert r0[5:6].tobytes() == r2.tobytes() and np.array_equal(k0[5:6], k2)
+    assert r0[3:133].tobytes() == r3.tobytes() and np.array_equal(k0[3:133], k3)
+    assert r0.tobytes() == r5.tobytes() == r6.tobytes() and np.array_equal(k0, k5) and np.array_equal(k0, k6)
+
+
+def test_separated_groups_fail_like_dfl(ob, N):
+    """One predictor separates the groups perfectly: the logit cannot be solved, and the call returns ob_dfl_run's
+    error for that."""
+    rng = np.random.default_rng(3)
+    n = 200
+    g = np.where(np.arange(n) < 80, "A", "B")
+    x1 = np.where(g == "A", 1.0, -1.0) * (0.5 + rng.random(n))
+    x2 = rng.normal(size=n)
+    f = {"y": (1.0 + x2 + rng.normal(size=n)).tolist(), "g": g.tolist(), "x1": x1.tolist(), "x2": x2.tolist()}
+    b = ob.OaxacaBuilder(f, "y", "g", "B").predictors(["x1", "x2"]).bootstrap_reps(8).seed(SEED)
+    with pytest.raises(N.OaxacaError) as e:
+        b.decompose_reweighted()
+    assert e.value.code == N.OB_E_LINALG
+    assert str(e.value) == "Nalgebra error: Failed to solve Information Matrix in Logit. Perfect separation?"
+
+
+def test_decompose_reweighted_end_to_end(ob, O, N):
+    """Group B's outcome is quadratic in x1: the linear model is wrong in B, and the specification error says so.
+    The aggregates are those of the restatement on the same seeds."""
+    import json
+
+    rng = np.random.default_rng(21)
+    n = 600
+    g = np.where(rng.random(n) < 0.45, "A", "B")
+    x1 = rng.normal(size=n) + 0.6 * (g == "A")
+    x2 = rng.uniform(0, 2, n)
+    cat = rng.choice(["lo", "mid", "hi"], size=n)
+    y = np.where(g == "A", 1.5 + 0.8 * x1, 1.0 + 0.8 * x1 + 0.5 * x1 ** 2) - 0.3 * x2 + 0.2 * (cat == "mid") \
+        + 0.3 * rng.normal(size=n)
+    w = rng.uniform(0.5, 2.0, n)
+    f = {"y": y.tolist(), "g": g.tolist(), "x1": x1.tolist(), "x2": x2.tolist(), "cat": cat.tolist(), "w": w.tolist()}
+    reps = 60
+    b = (ob.OaxacaBuilder(f, "y", "g", "B").predictors(["x1", "x2"]).categorical_predictors(["cat"]).weights("w")
+         .bootstrap_reps(reps).seed(SEED))
+    res = b.decompose_reweighted()
+    xa, ya, xb, yb, names = b.get_data_matrices()
+    k = xa.shape[1]
+    wa, wb = w[g == "A"], w[g == "B"]
+    assert names == ["__ob_intercept__", "x1", "x2", "cat_lo", "cat_mid"] == res.names and k == 5
+    point, _ = R.decompose(xa, ya, xb, yb, wa, wb)
+    rows, ok, _ = R.boot(O, xa, ya, xb, yb, wa, wb, SEED, 0, reps)
+    assert point is not None and ok.all()
+    scale = abs(point[0])
+    assert res.n_a == len(ya) and res.n_b == len(yb) and res.n_failed == 0
+    assert abs(res.total_gap - point[0]) <= RTOL * scale
+    tail = point[7 + 4 * k:]
+    for got, want in ((res.beta_a, tail[:k]), (res.beta_b, tail[k:2 * k]), (res.beta_c, tail[2 * k:3 * k]),
+                      (res.gamma, tail[6 * k:7 * k])):
+        assert np.all(np.abs(got - want) <= RTOL * np.maximum(np.abs(want), 1.0))
+    assert abs(res.effective_sample_size - tail[7 * k + 3]) <= RTOL * tail[7 * k + 3]
+    assert res.logit_passes == tail[7 * k + 4]
+
+    def check(comps, cols, cnames):
+        assert [c.name for c in comps] == cnames
+        for c, col in zip(comps, cols):
+            se, p, (lo, hi) = O.bootstrap_stats(rows[:, col])
+            assert abs(c.estimate - point[col]) <= RTOL * max(abs(point[col]), scale), c.name
+            for a, want in ((c.std_err, se), (c.ci_lower, lo), (c.ci_upper, hi)):
+                assert abs(a - want) <= RTOL * max(abs(want), scale), (c.name, a, want)
+
+    check(res.aggregate, range(7), list(R.AGG))
+    check(res.detailed_pure_explained, range(7, 7 + k), names)
+    check(res.detailed_specification_error, range(7 + k, 7 + 2 * k), names)
+    check(res.detailed_pure_unexplained, range(7 + 2 * k, 7 + 3 * k), names)
+    check(res.detailed_reweighting_error, range(7 + 3 * k, 7 + 4 * k), names)
+    se = res.component("specification_error")
+    print(f"specification_error {se.estimate:.4f} [{se.ci_lower:.4f}, {se.ci_upper:.4f}], "
+          f"reweighting_error {res.component('reweighting_error').estimate:.4f}")
+    assert se.ci_lower > 0.0 or se.ci_upper < 0.0
+    js = json.loads(res.to_json())
+    assert js["n_failed"] == 0 and js["names"] == names
+    assert [c["name"] for c in js["aggregate"]] == list(R.AGG)
+    assert js["aggregate"][4]["estimate"] == se.estimate and js["beta_c"] == [float(v) for v in res.beta_c]
+    assert js["effective_sample_size"] == res.effective_sample_size
+    # the C entry point that runs everything: the same tables, bitwise (same seed, same kernels)
+    cols, ncol, nrow = b._frame.as_c()
+    cfg, keep = b._config()
+    h = C.c_void_p()
+    N.check(N.lib().ob_builder_run_reweighted(N.context(None), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+    from importlib import import_module
+    r2 = import_module("oaxaca-blinder-rs_amd.api")._results_from_c(h)
+    assert r2.total_gap == res.total_gap
+    for c, d in zip(res.aggregate + res.detailed_reweighting_error, r2.two_fold.aggregate + r2.three_fold.aggregate):
+        assert (c.name, c.estimate, c.std_err, c.ci_lower, c.ci_upper) == (d.name, d.estimate, d.std_err, d.ci_lower,
+                                                                         d.ci_upper)
+    t = ob.reweight_last_timing()
+    assert t["logit_passes"] >= 2 and t["logit_launches"] >= t["logit_passes"]
+    assert t["logit_ms"] > 0.0 and t["gram_ms"] > 0.0 and t["row_ms"] > 0.0
+
+
+def test_refusals_on_a_reweighted_handle(ob, N):
+    pr = builder(ob, 3, False).prepare_reweighted()
+    try:
+        with pytest.raises(N.OaxacaError) as e:
+            pr.boot_sharded(0, 4)
+        assert e.value.code == N.OB_E_UNSUPPORTED
+        with pytest.raises(N.OaxacaError) as e:
+            pr.jackknife()
+        assert e.value.code == N.OB_E_UNSUPPORTED
+        rows, ok = pr.boot(0, 4)
+        with pytest.raises(N.OaxacaError) as e:
+            pr.finish_bca(rows, ok)
+        assert e.value.code == N.OB_E_UNSUPPORTED
+    finally:
+        pr.close()
