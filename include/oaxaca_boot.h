@@ -1120,9 +1120,10 @@ int ob_prepared_cluster_info(const ob_prepared* prep, ob_cluster_info* out);
 #define OB_RIF_VARIANCE 0
 #define OB_RIF_GINI 1
 #define OB_RIF_IQR 2
+#define OB_RIF_QUANTILE 3 /* p0 = tau; the weighted entry points only */
 typedef struct {
   int32_t stat;  /* OB_RIF_* */
-  double p0, p1; /* OB_RIF_IQR: tau_hi, tau_lo; otherwise unused */
+  double p0, p1; /* OB_RIF_IQR: tau_hi, tau_lo; OB_RIF_QUANTILE: tau, unused; otherwise unused */
 } ob_rif_spec;
 typedef struct {
   double sort_ms, scan_ms, kde_ms, scatter_ms; /* kde_ms: the quantile pieces and densities of OB_RIF_IQR */
@@ -1287,6 +1288,49 @@ int ob_builder_prepare_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_
 /* prepare + cfg->bootstrap_reps replicates + finish. */
 int ob_builder_run_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
                               const ob_builder_config* cfg, ob_results** out);
+
+/* ---- Weighted RIF pass and the reweighted decomposition of a statistic ----------------------
+ * Firpo, Fortin and Lemieux's method whole: reweight B to A's covariates, then RIF regressions in A, B and C.
+ * Weighted RIF of y[n] with weights w >= 0, W = sum w > 0: wt_i = w_i n / W; the rows ordered by y, stable; S_i
+ * the inclusive sum of wt up to the end of y_i's tie run; F_i = S_i / n; mu = sum wt y / n; Y(t), 0 < t <= n, the
+ * sorted value at the first position whose run-end S >= t (the last value if rounding leaves t above the last S).
+ *   OB_RIF_VARIANCE  RIF_i = (y_i - mu)^2, statistic sum wt (y - mu)^2 / n.
+ *   OB_RIF_GINI      GL_i = (1/n) sum_{y_j <= y_i} wt_j y_j, R = (1/n) sum wt_i GL_i, statistic G = 1 - 2R/mu,
+ *                    RIF_i = 1 + (2R/mu^2) y_i - (2/mu) [y_i (1 - F_i) + GL_i].
+ *   OB_RIF_QUANTILE  ob_rif's with every order statistic read through Y: h = (n - 1) tau, lo = floor(h), f = h - lo,
+ *                    q = Y(lo + 1) + f (Y(min(lo + 2, n)) - Y(lo + 1)); sd = sqrt(sum wt (y - mu)^2 / (n - 1)); the
+ *                    quartiles Y(min(max(ceil(p n), 1), n)); ob_rif's fallbacks and bandwidth 0.9 spread n^-0.2 with n
+ *                    the row count; density sum wt phi((q - y) / bw) / (n bw), floor 1e-8;
+ *                    RIF_i = q + (tau - 1[y_i <= q]) / density. Statistic q.
+ *   OB_RIF_IQR       the difference of two such quantiles on one bandwidth.
+ * At w = 1 these are the unweighted definitions above. Every sum is f64 in an order that depends on n alone and
+ * runs over the sorted rows (W included): a repeated call gives the same bytes, weights scaled by a power of two
+ * give the same bytes, and on distinct y a permutation of the rows gives the same statistic bytes. Inside a tie
+ * run the rows keep their input order, so with unequal weights there a permutation moves last bits.
+ * Errors, each before any device work and before the context is read: a bad spec OB_E_INVALID; n < 2
+ * OB_E_INSUFFICIENT; n > 2^28 OB_E_UNSUPPORTED; a non-finite y or w, a negative w, W = 0 OB_E_INVALID; for the Gini
+ * a negative y or no positive one among the rows with w > 0 OB_E_INVALID. ob_rif_stat and
+ * ob_builder_decompose_statistics keep refusing OB_RIF_QUANTILE. */
+int ob_rif_stat_weighted(ob_ctx* ctx, const double* y, const double* w, int64_t n, const ob_rif_spec* spec,
+                         double* rif_out, double* statistic_out);
+/* The reweighted decomposition above with the statistic's RIF as the outcome: after the point logit, the weighted RIF
+ * of A's outcome (weights w), of B's (w) and of B's under w psi-hat (the counterfactual sample C) replace y in the
+ * fits of A, B and C. Everything else is ob_builder_prepare_reweighted's: the counts, the per-replicate logit, the
+ * three Grams, the solves, the row of ob_reweight_row_len(K) doubles, the refusals, and what works on the handle.
+ * The RIFs are fixed at the point estimate: a replicate refits the logit and the three regressions but does not
+ * recompute the statistic (as the quantile path of ob_builder_decompose_quantiles does not). The row's ybar entries
+ * are the weighted means of the RIFs; the statistics themselves come from ob_prepared_reweight_statistics. */
+int ob_builder_prepare_reweighted_statistic(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                            const ob_builder_config* cfg, const ob_rif_spec* spec, ob_prepared** out);
+/* out = nu_A, nu_B, nu_C. OB_E_INVALID on a handle of the mean (or of another kind). */
+int ob_prepared_reweight_statistics(const ob_prepared* prep, double out[3]);
+#define OB_REWEIGHT_MAX_STATS 16
+/* Several statistics in one run: one resample and one logit fit per replicate serve all of them; out[t] is bitwise
+   the single-statistic run (prepare + cfg->bootstrap_reps replicates + finish) with the same seed. n_specs >
+   OB_REWEIGHT_MAX_STATS is OB_E_UNSUPPORTED. */
+int ob_builder_run_reweighted_statistics(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                         const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
+                                         ob_results** out);
 
 #ifdef __cplusplus
 }

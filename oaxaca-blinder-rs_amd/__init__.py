@@ -16,7 +16,8 @@ from .engine import (binary_check_shape, binary_last_timing, binary_means, binar
                      cluster_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
                      knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
-                     remedy_resolve_overrides, remedy_score, remedy_solve, rif, parse_rif_statistic, rif_last_timing,
+                     remedy_resolve_overrides, remedy_score, remedy_solve, rif, parse_rif_statistic, parse_weighted_rif_statistic,
+                     rif_statistic_weighted, rif_last_timing,
                      rif_scan_block, rif_statistic, reweight_check_shape, reweight_gram, reweight_last_timing,
                      reweight_logit_pass, reweight_row_len,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
@@ -38,6 +39,7 @@ __all__ = [
     "aggregate_bca",
     "cluster_index", "cluster_gram", "cluster_counts", "cluster_apply", "cluster_check_shape", "cluster_last_timing",
     "rif_statistic", "rif_last_timing", "rif_scan_block", "parse_rif_statistic",
+    "rif_statistic_weighted", "parse_weighted_rif_statistic",
     "BinaryDecompositionResults", "binary_means", "binary_check_shape", "binary_row_len", "binary_last_timing",
     "ReweightedDecompositionResults", "reweight_logit_pass", "reweight_gram", "reweight_check_shape",
     "reweight_row_len", "reweight_last_timing",

@@ -69,6 +69,8 @@ EXPORTED = (
     "ob_builder_prepare_binary", "ob_builder_run_binary", "ob_prepared_point_row",
     "ob_reweight_row_len", "ob_reweight_check_shape", "ob_reweight_last_timing", "ob_reweight_logit_pass",
     "ob_reweight_gram", "ob_builder_prepare_reweighted", "ob_builder_run_reweighted",
+    "ob_rif_stat_weighted", "ob_builder_prepare_reweighted_statistic", "ob_prepared_reweight_statistics",
+    "ob_builder_run_reweighted_statistics",
 )
 
 OB_E_CONVERGENCE = 12
@@ -86,6 +88,9 @@ OB_MATCH_MAX_DIM, OB_MATCH_MAX_K = 64, 16
 OB_MATCH_EUCLIDEAN, OB_MATCH_MAHALANOBIS, OB_MATCH_PSM = 0, 1, 2
 OB_RIF_VARIANCE, OB_RIF_GINI, OB_RIF_IQR = 0, 1, 2
 OB_RIF_STATS = {"variance": OB_RIF_VARIANCE, "gini": OB_RIF_GINI, "iqr": OB_RIF_IQR}
+OB_RIF_QUANTILE = 3  # the weighted entry points only
+OB_RIF_WSTATS = {**OB_RIF_STATS, "quantile": OB_RIF_QUANTILE}
+OB_REWEIGHT_MAX_STATS = 16
 OB_BINARY_MAX_K = 32  # design columns, the intercept included
 OB_BINARY_PROBIT, OB_BINARY_LOGIT = 0, 1
 OB_BINARY_MODELS = {"probit": OB_BINARY_PROBIT, "logit": OB_BINARY_LOGIT}
@@ -490,6 +495,14 @@ _SIGS = {
                                                 C.POINTER(ob_builder_config), C.POINTER(_P)]),
     "ob_builder_run_reweighted": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
                                             C.POINTER(ob_builder_config), C.POINTER(_P)]),
+    "ob_rif_stat_weighted": (C.c_int, [_P, _D, _D, C.c_int64, C.POINTER(ob_rif_spec), _D, _D]),
+    "ob_builder_prepare_reweighted_statistic": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                          C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec),
+                                                          C.POINTER(_P)]),
+    "ob_prepared_reweight_statistics": (C.c_int, [_P, _D]),
+    "ob_builder_run_reweighted_statistics": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                       C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec), C.c_int32,
+                                                       C.POINTER(_P)]),
 }
 
 _lib = None

@@ -348,7 +348,10 @@ class ReweightedDecompositionResults:
     Firpo 2011, section 5). ``aggregate`` holds total_gap, composition, structure, pure_explained,
     specification_error, pure_unexplained and reweighting_error; the four detailed tables their summands per
     design column. The component objects are ``OaxacaResults``' (estimate, standard error, percentile interval,
-    p-value over the bootstrap, in which the propensity logit is refitted per replicate)."""
+    p-value over the bootstrap, in which the propensity logit is refitted per replicate).
+    With a statistic (``decompose_reweighted("gini")``) the outcome of the three fits is the statistic's weighted
+    RIF in A, B and C: ``statistic`` is (name, params), ``statistics`` (nu_A, nu_B, nu_C) the statistic itself in the
+    three samples, and ``y_means`` the weighted means of the RIFs. Both are ``None`` for the mean."""
     total_gap: float
     aggregate: list
     detailed_pure_explained: list
@@ -369,6 +372,8 @@ class ReweightedDecompositionResults:
     n_a: int = 0
     n_b: int = 0
     n_failed: int = 0
+    statistic: tuple | None = None
+    statistics: tuple | None = None
 
     def component(self, name: str):
         return next(c for c in self.aggregate if c.name == name)
@@ -383,6 +388,11 @@ class ReweightedDecompositionResults:
         def vec(a):
             return [fix(float(v)) for v in a]
 
+        extra = {}
+        if self.statistic is not None:
+            extra["statistic"] = {"stat": self.statistic[0], **self.statistic[1]}
+        if self.statistics is not None:
+            extra["statistics"] = vec(self.statistics)
         return json.dumps({
             "total_gap": fix(self.total_gap), "aggregate": comps(self.aggregate),
             "detailed_pure_explained": comps(self.detailed_pure_explained),
@@ -393,7 +403,27 @@ class ReweightedDecompositionResults:
             "beta_c": vec(self.beta_c), "gamma": vec(self.gamma), "xa_mean": vec(self.xa_mean),
             "xb_mean": vec(self.xb_mean), "xc_mean": vec(self.xc_mean), "y_means": vec(self.y_means),
             "effective_sample_size": fix(self.effective_sample_size), "logit_passes": self.logit_passes,
-            "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed})
+            "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed, **extra})
+
+
+def _reweighted_results(res, point, statistic=None, statistics=None) -> ReweightedDecompositionResults:
+    """The tables of a reweighted handle's finish() and its point row."""
+    k = (len(point) - 12) // 11
+    tail = point[7 + 4 * k:]
+    sc = tail[7 * k:]
+    # the reweighted handle's five tables travel in the slots of run()'s (OB_RW_TABLE_*)
+    return ReweightedDecompositionResults(
+        total_gap=float(point[0]), aggregate=res.two_fold.aggregate,
+        detailed_pure_explained=res.two_fold.detailed_explained,
+        detailed_specification_error=res.two_fold.detailed_unexplained,
+        detailed_pure_unexplained=res.two_fold.detailed_selection,
+        detailed_reweighting_error=res.three_fold.aggregate,
+        beta_a=tail[:k].copy(), beta_b=tail[k:2 * k].copy(), beta_c=tail[2 * k:3 * k].copy(),
+        xa_mean=tail[3 * k:4 * k].copy(), xb_mean=tail[4 * k:5 * k].copy(), xc_mean=tail[5 * k:6 * k].copy(),
+        gamma=tail[6 * k:7 * k].copy(), y_means=(float(sc[0]), float(sc[1]), float(sc[2])),
+        effective_sample_size=float(sc[3]), logit_passes=int(sc[4]),
+        names=[c.name for c in res.two_fold.detailed_explained],
+        n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed, statistic=statistic, statistics=statistics)
 
 
 def _jackknife_out(k: int):
@@ -1007,9 +1037,15 @@ class OaxacaBuilder:
             xa_mean=tail[2 * k:3 * k].copy(), xb_mean=tail[3 * k:4 * k].copy(), names=names,
             n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed)
 
-    def prepare_reweighted(self) -> "PreparedRun":
-        from .engine import with_context
+    def prepare_reweighted(self, statistic=None, **params) -> "PreparedRun":
+        """The handle of ``decompose_reweighted``. ``statistic`` (with its parameters, as
+        ``parse_weighted_rif_statistic`` takes them) makes it the decomposition of that statistic; ``None`` is
+        the mean."""
+        from .engine import parse_weighted_rif_statistic, with_context
 
+        if statistic is None and params:
+            raise ValueError(f"unexpected parameter(s) {', '.join(sorted(params))} without a statistic")
+        spec = None if statistic is None else N.ob_rif_spec(*parse_weighted_rif_statistic(statistic, **params))
         if self._cluster is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED,
                                 "reweighted decomposition: the cluster bootstrap is outside its scope")
@@ -1017,14 +1053,50 @@ class OaxacaBuilder:
         cols, ncol, nrow = self._frame.as_c()
         cfg, keep = self._config()
         h = C.c_void_p()
+
+        def call(ctx):
+            if spec is None:
+                return lib.ob_builder_prepare_reweighted(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h))
+            return lib.ob_builder_prepare_reweighted_statistic(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(spec),
+                                                               C.byref(h))
+
         if self._ctx is not None:
-            N.check(lib.ob_builder_prepare_reweighted(self._ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+            N.check(call(self._ctx))
         else:
-            with_context(lambda ctx: lib.ob_builder_prepare_reweighted(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h)),
-                         self._device)
+            with_context(call, self._device)
         return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
 
-    def decompose_reweighted(self) -> "ReweightedDecompositionResults":
+    def decompose_reweighted_statistics(self, stats) -> list:
+        """Several statistics in one reweighted run (``ob_builder_run_reweighted_statistics``): every replicate's
+        resample and logit fit serve all of them. ``stats``: names, ``(name, params)`` pairs or dicts with a
+        ``stat`` key, at most 16. Element t equals ``decompose_reweighted`` of element t bitwise (same seed)."""
+        from .engine import parse_weighted_rif_statistic, weighted_rif_name, with_context
+
+        parsed = [parse_weighted_rif_statistic(s) for s in stats]
+        if not parsed:
+            raise ValueError("statistics must be a non-empty sequence")
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED,
+                                "reweighted decomposition: the cluster bootstrap is outside its scope")
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        specs = (N.ob_rif_spec * len(parsed))(*[N.ob_rif_spec(*p) for p in parsed])
+        hs = (C.c_void_p * len(parsed))()
+        out = C.cast(hs, C.POINTER(C.c_void_p))
+        with_context(lambda ctx: lib.ob_builder_run_reweighted_statistics(ctx, cols, ncol, nrow, C.byref(cfg), specs,
+                                                                          len(parsed), out), self._device)
+        results = [_results_from_c(C.c_void_p(h)) for h in hs]
+        outs = []
+        for p, res in zip(parsed, results):  # the tables came from the one run; a handle gives the point row and nu
+            pr = self.prepare_reweighted(weighted_rif_name(p))
+            try:
+                outs.append(_reweighted_results(res, pr.point_row(), weighted_rif_name(p), pr.reweight_statistics()))
+            finally:
+                pr.close()
+        return outs
+
+    def decompose_reweighted(self, statistic=None, **params) -> "ReweightedDecompositionResults":
         """Extension (no counterpart in the reference crate): the reweighted decomposition of Fortin, Lemieux and
         Firpo (2011, section 5), Stata's ``oaxaca_rif ..., rwlogit()``. A propensity logit of the non-reference
         group on the design reweights the reference group B to A's covariates (the counterfactual sample C); a
@@ -1032,30 +1104,25 @@ class OaxacaBuilder:
         error, and the structure effect into a pure unexplained part and a reweighting error. Every bootstrap
         replicate refits the logit on the GPU. Sample weights are served; ``reference_coefficients`` is ignored.
         Refused (``OB_E_UNSUPPORTED``): ``normalize``, ``cluster``, Heckman settings, more than 32 design
-        columns."""
-        pr = self.prepare_reweighted()
+        columns.
+
+        ``statistic`` ("variance", "gini", "quantile" with ``tau``, "iqr" with ``upper`` / ``lower``) decomposes the
+        gap in that statistic instead (Firpo, Fortin and Lemieux; ``oaxaca_rif ..., rwlogit()``): the statistic's
+        weighted RIF in A, in B and in the counterfactual sample C is the outcome of the three fits. The RIFs are
+        computed once, at the point estimate; replicates refit the logit and the regressions. ``None`` is the mean,
+        exactly as before."""
+        from .engine import parse_weighted_rif_statistic, weighted_rif_name
+
+        pr = self.prepare_reweighted(statistic, **params)
         try:
             rows, ok = pr.boot(0, self._bootstrap_reps)
             res = pr.finish(rows, ok)
             point = pr.point_row()
+            nu = None if statistic is None else pr.reweight_statistics()
         finally:
             pr.close()
-        k = (len(point) - 12) // 11
-        tail = point[7 + 4 * k:]
-        sc = tail[7 * k:]
-        # the reweighted handle's five tables travel in the slots of run()'s (OB_RW_TABLE_*)
-        return ReweightedDecompositionResults(
-            total_gap=float(point[0]), aggregate=res.two_fold.aggregate,
-            detailed_pure_explained=res.two_fold.detailed_explained,
-            detailed_specification_error=res.two_fold.detailed_unexplained,
-            detailed_pure_unexplained=res.two_fold.detailed_selection,
-            detailed_reweighting_error=res.three_fold.aggregate,
-            beta_a=tail[:k].copy(), beta_b=tail[k:2 * k].copy(), beta_c=tail[2 * k:3 * k].copy(),
-            xa_mean=tail[3 * k:4 * k].copy(), xb_mean=tail[4 * k:5 * k].copy(), xc_mean=tail[5 * k:6 * k].copy(),
-            gamma=tail[6 * k:7 * k].copy(), y_means=(float(sc[0]), float(sc[1]), float(sc[2])),
-            effective_sample_size=float(sc[3]), logit_passes=int(sc[4]),
-            names=[c.name for c in res.two_fold.detailed_explained],
-            n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed)
+        name = None if statistic is None else weighted_rif_name(parse_weighted_rif_statistic(statistic, **params))
+        return _reweighted_results(res, point, name, nu)
 
     def statistic_builder(self, stat, **params) -> "OaxacaBuilder":
         """A fresh builder over this frame with the outcome replaced by the statistic's RIF of each group's
@@ -1164,6 +1231,12 @@ class PreparedRun:
         n = C.c_int64()
         N.check(N.lib().ob_prepared_point_row(self._h, C.byref(ptr), C.byref(n)))
         return np.ctypeslib.as_array(ptr, shape=(n.value,)).copy() if n.value else np.zeros(0)
+
+    def reweight_statistics(self) -> tuple:
+        """ob_prepared_reweight_statistics: (nu_A, nu_B, nu_C) of a reweighted statistic's handle."""
+        out = np.zeros(3)
+        N.check(N.lib().ob_prepared_reweight_statistics(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return tuple(float(v) for v in out)
 
     def sync(self):
         N.check(N.lib().ob_panel_sync(N.lib().ob_prepared_panel(self._h)))

@@ -126,6 +126,46 @@ int rif_input_check(const double* y, int64_t n, const ob_rif_spec* specs, int n_
   return OB_OK;
 }
 
+int rif_wspec_check(const ob_rif_spec* specs, int n_specs) {
+  if (!specs || n_specs < 1) return fail(OB_E_INVALID, "no statistic given");
+  for (int s = 0; s < n_specs; ++s) {
+    const ob_rif_spec& sp = specs[s];
+    if (sp.stat == OB_RIF_QUANTILE) {
+      if (!(0.0 < sp.p0 && sp.p0 < 1.0))  // also refuses NaN
+        return fail(OB_E_INVALID, "quantile needs 0 < tau < 1, got %g", sp.p0);
+    } else {
+      OB_TRY(rif_spec_check(&sp, 1));
+    }
+  }
+  return OB_OK;
+}
+
+int rif_input_check_weighted(const double* y, const double* w, int64_t n, const ob_rif_spec* specs, int n_specs) {
+  OB_TRY(rif_wspec_check(specs, n_specs));
+  if (n < 2)
+    return fail(OB_E_INSUFFICIENT, "%sa RIF statistic needs at least 2 rows in a group, got %lld",
+                error_prefix(OB_E_INSUFFICIENT), (long long)n);
+  if (n > kRifMaxRows) return fail(OB_E_UNSUPPORTED, "RIF statistics take at most 2^28 rows per group");
+  if (!y || !w) return fail(OB_E_INVALID, "null pointer");
+  bool gini = false;
+  for (int s = 0; s < n_specs; ++s) gini = gini || specs[s].stat == OB_RIF_GINI;
+  bool positive = false;
+  double total = 0.0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!std::isfinite(y[i])) return fail(OB_E_INVALID, "outcome row %lld is not finite", (long long)i);
+    if (!std::isfinite(w[i])) return fail(OB_E_INVALID, "weight row %lld is not finite", (long long)i);
+    if (w[i] < 0.0) return fail(OB_E_INVALID, "weight row %lld is negative", (long long)i);
+    total += w[i];
+    if (!(w[i] > 0.0)) continue;
+    if (gini && y[i] < 0.0) return fail(OB_E_INVALID, "gini: outcome row %lld is negative", (long long)i);
+    positive = positive || y[i] > 0.0;
+  }
+  if (!(total > 0.0)) return fail(OB_E_INVALID, "the weights must have a positive sum");
+  if (!std::isfinite(total * (double)n)) return fail(OB_E_INVALID, "the weights' sum is not finite");
+  if (gini && !positive) return fail(OB_E_INVALID, "gini: the mean outcome must be positive");
+  return OB_OK;
+}
+
 void aggregate(const double* rows, const uint8_t* ok, uint64_t n_reps, int row_len,
                const std::vector<std::vector<int>>& groups, double* out) {
   std::vector<uint64_t> good;

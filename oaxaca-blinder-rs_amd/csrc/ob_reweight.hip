@@ -19,6 +19,16 @@
 // sums, in which it cancels.
 //
 // Panel of a reweighted run, per group [col][ld]: y | x_1 .. x_{K-1} | w (ones without sample weights).
+//
+// The decomposition of a statistic is the same code on other outcome columns: after the point
+// logit ob_rw_psi_kernel writes w psi-hat for B's rows, three weighted RIF passes (ob_rif.hip) give RIF_A, RIF_B
+// and RIF_C, and the panel of T statistics becomes
+//   A: RIF_A^0 | x_1 .. x_{K-1} | w | RIF_A^1 .. RIF_A^{T-1}
+//   B: RIF_B^0 | x_1 .. x_{K-1} | w | RIF_B^1 .. RIF_B^{T-1} | RIF_C^0 .. RIF_C^{T-1}
+// RwArgs::ycol / ycol_c name the column that ob_rw_kernel stages into the y slot under Gram / GramPsi; both are 0
+// for the mean. The RIFs are fixed at the point estimate: a replicate refits the logit and the three regressions
+// and does not recompute the statistic. Per batch the logit runs once; the two Gram modes and the row kernel run
+// once per statistic.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +44,7 @@
 #include "ob_hip.hpp"
 #include "ob_options.hpp"
 #include "ob_reweight.hpp"
+#include "ob_rif.hpp"
 #include "ob_spec.h"
 
 namespace {
@@ -69,6 +80,7 @@ struct RwArgs {
   int row_len;
   int mode;
   double tol;
+  int ycol, ycol_c;        // the column staged into the y slot under Gram / GramPsi (0: the mean's y)
 };
 
 // Values per (chunk, replicate): the packed lower triangle (entry j (j + 1) / 2 + i, i <= j) of the k x k
@@ -110,6 +122,7 @@ __global__ __launch_bounds__(kRB) void ob_rw_kernel(const RwArgs a) {
   const uint32_t chunk = blockIdx.x, g = a.chunks[3 * chunk], t0 = a.chunks[3 * chunk + 1], t1 = a.chunks[3 * chunk + 2];
   const int mode = a.mode;
   if (mode == kModeGramPsi && g == 0) return;  // the counterfactual sample is B's rows
+  const int ycol = mode == kModeGramPsi ? a.ycol_c : a.ycol;
   const int k = a.k, gs = k | 1, ncol = k + 1;
   const int ones = ncol * kRS, wcol = k * kRS;
   double* stg = rsm;                    // [ncol + 1][kRS]: y, x_1 .. x_{k-1}, w, ones
@@ -174,7 +187,7 @@ __global__ __launch_bounds__(kRB) void ob_rw_kernel(const RwArgs a) {
       __syncthreads();  // the previous sub-tile's operand reads (and the gamma loads)
       for (int i = tid; i < ncol * 64; i += kRB) {
         const int c = i >> 6, r = i & 63;
-        stg[c * kRS + r] = (uint32_t)r < nr ? X[(size_t)c * ld + r0 + r] : 0.0;
+        stg[c * kRS + r] = (uint32_t)r < nr ? X[(size_t)(c ? c : ycol) * ld + r0 + r] : 0.0;
       }
       __syncthreads();
       uint32_t word = 0;  // counts of rows 4 q .. 4 q + 3 (the f64 Gram's count-image layout, ob_engine.hpp)
@@ -253,6 +266,19 @@ __global__ __launch_bounds__(kRB) void ob_rw_kernel(const RwArgs a) {
       if (rep < a.n_reps) out[(size_t)rep * nv + NP] = v;
     }
   }
+}
+
+// out[i] = w_i psi-hat_i for the n rows of one group at the point gamma: the expression of ob_rw_kernel's tile (the
+// index summed in column order from the intercept, the clamp, psi = p / (1 - p)). The weights of sample C.
+__global__ __launch_bounds__(kRB) void ob_rw_psi_kernel(const double* X, int64_t ld, uint32_t n, int k, const double* gamma,
+                                                        double* out) {
+  const uint32_t i = blockIdx.x * kRB + threadIdx.x;
+  if (i >= n) return;
+  double z = gamma[0];
+  for (int j = 1; j < k; ++j) z += X[(size_t)j * ld + i] * gamma[j];
+  double p = 1.0 / (1.0 + exp(-z));
+  p = p < 1e-10 ? 1e-10 : (p > 1.0 - 1e-10 ? 1.0 - 1e-10 : p);
+  out[i] = X[(size_t)k * ld + i] * (p / (1.0 - p));
 }
 
 // One wave per replicate, after a logit pass: the chunk partials of both groups in chunk order, the Cholesky
@@ -420,9 +446,11 @@ hipError_t launch_pass(const RwArgs& a, int mode, hipStream_t s) {
 thread_local ob_reweight_timing g_timing = {};
 constexpr int kRwMaxPasses = 100;
 
-// The stages over one batch (or the point pass): the Newton loop, each replicate stopping on its own, the
-// Grams, the rows.
-int rw_batch(const RwArgs& a, hipStream_t s) {
+// The stages over one batch (or the point pass): the Newton loop, each replicate stopping on its own, then per
+// statistic (once for the mean, n_stats = 0) the Grams and the rows. rows / ok: one destination per statistic
+// (NULL: a's own).
+int rw_batch(const RwArgs& a, hipStream_t s, int n_stats = 0, double* const* rows = nullptr,
+             uint8_t* const* ok = nullptr) {
   if (a.k < 1 || a.k > kRMaxK || a.n_reps < 1 || a.part_pad < a.n_reps) return ob::fail(OB_E_INVALID, "reweight batch: bad shape");
   Events<5> ev;
   OB_HIP(ev.create());
@@ -448,19 +476,30 @@ int rw_batch(const RwArgs& a, hipStream_t s) {
     if (active == 0) break;
   }
   g_timing.logit_passes = std::max(g_timing.logit_passes, (int32_t)it);
-  OB_HIP(hipEventRecord(ev.e[2], s));
-  OB_HIP(launch_pass(a, kModeGram, s));
-  OB_HIP(launch_pass(a, kModeGramPsi, s));
-  OB_HIP(hipEventRecord(ev.e[3], s));
-  hipLaunchKernelGGL(ob_rw_row_kernel, dim3(a.n_reps), dim3(64), 0, s, a);
-  OB_HIP(hipGetLastError());
-  OB_HIP(hipEventRecord(ev.e[4], s));
-  OB_HIP(hipEventSynchronize(ev.e[4]));
-  float m0 = 0.f, m1 = 0.f;
-  OB_HIP(hipEventElapsedTime(&m0, ev.e[2], ev.e[3]));
-  OB_HIP(hipEventElapsedTime(&m1, ev.e[3], ev.e[4]));
-  g_timing.gram_ms += m0;
-  g_timing.row_ms += m1;
+  for (int t = 0; t < std::max(n_stats, 1); ++t) {
+    RwArgs b = a;
+    if (n_stats > 0) {
+      b.ycol = t ? a.k + t : 0;
+      b.ycol_c = a.k + n_stats + t;
+    }
+    if (rows) {
+      b.rows = rows[t];
+      b.ok = ok[t];
+    }
+    OB_HIP(hipEventRecord(ev.e[2], s));
+    OB_HIP(launch_pass(b, kModeGram, s));
+    OB_HIP(launch_pass(b, kModeGramPsi, s));
+    OB_HIP(hipEventRecord(ev.e[3], s));
+    hipLaunchKernelGGL(ob_rw_row_kernel, dim3(b.n_reps), dim3(64), 0, s, b);
+    OB_HIP(hipGetLastError());
+    OB_HIP(hipEventRecord(ev.e[4], s));
+    OB_HIP(hipEventSynchronize(ev.e[4]));
+    float m0 = 0.f, m1 = 0.f;
+    OB_HIP(hipEventElapsedTime(&m0, ev.e[2], ev.e[3]));
+    OB_HIP(hipEventElapsedTime(&m1, ev.e[3], ev.e[4]));
+    g_timing.gram_ms += m0;
+    g_timing.row_ms += m1;
+  }
   return OB_OK;
 }
 
@@ -499,6 +538,11 @@ struct ReweightState {
   DevBuf cols[2];  // [y | x_1 .. x_{k-1} | w] x ld
   DevBuf chunks, gamma, flags, passes, partial, partial_c;
   int n_chunks = 0;
+  // the decomposition of statistics (§5.15): 0 for the mean; the specs, nu_A, nu_B, nu_C and the point row of each
+  int n_stats = 0;
+  std::vector<ob_rif_spec> specs;
+  std::vector<double> nu;  // [n_stats][3]
+  std::vector<std::vector<double>> point_rows;
 };
 
 constexpr size_t kRwPartialBudget = (size_t)1 << 30;  // bytes of chunk partials and Grams per batch
@@ -557,29 +601,41 @@ static int rw_point(ob_prepared* pr, ReweightState* st) {
   OB_HIP(hipSetDevice(p->ctx->device));
   hipStream_t s = p->ctx->stream;
   OB_TRY(rw_ensure(st, 64));
+  const int nt = std::max(st->n_stats, 1);
   DevBuf d_row, d_ok;
-  OB_HIP(d_row.alloc(sizeof(double) * pr->row_len));
-  OB_HIP(d_ok.alloc(1));
+  OB_HIP(d_row.alloc(sizeof(double) * pr->row_len * nt));
+  OB_HIP(d_ok.alloc((size_t)nt));
   RwArgs h = rw_args(pr, st);
   rw_bind(h, st, 64);
   h.counts = nullptr;
   h.nb_rep = 1;
   h.n_reps = 1;
-  h.rows = d_row.d();
-  h.ok = d_ok.as<uint8_t>();
-  OB_TRY(rw_batch(h, s));
-  uint8_t okh = 0;
-  pr->point_row.assign((size_t)pr->row_len, 0.0);
-  OB_HIP(hipMemcpyAsync(pr->point_row.data(), d_row.p, sizeof(double) * pr->row_len, hipMemcpyDeviceToHost, s));
-  OB_HIP(hipMemcpyAsync(&okh, d_ok.p, 1, hipMemcpyDeviceToHost, s));
+  std::vector<double*> rows(nt);
+  std::vector<uint8_t*> oks(nt);
+  for (int t = 0; t < nt; ++t) {
+    rows[t] = d_row.d() + (size_t)t * pr->row_len;
+    oks[t] = d_ok.as<uint8_t>() + t;
+  }
+  OB_TRY(rw_batch(h, s, st->n_stats, rows.data(), oks.data()));
+  std::vector<uint8_t> okh((size_t)nt, 0);
+  std::vector<double> all((size_t)pr->row_len * nt);
+  OB_HIP(hipMemcpyAsync(all.data(), d_row.p, sizeof(double) * all.size(), hipMemcpyDeviceToHost, s));
+  OB_HIP(hipMemcpyAsync(okh.data(), d_ok.p, (size_t)nt, hipMemcpyDeviceToHost, s));
   OB_HIP(hipStreamSynchronize(s));
-  if (!okh) return fail(OB_E_LINALG, kLogitFailed, error_prefix(OB_E_LINALG));
+  for (int t = 0; t < nt; ++t)
+    if (!okh[t]) return fail(OB_E_LINALG, kLogitFailed, error_prefix(OB_E_LINALG));
+  st->point_rows.assign(nt, {});
+  for (int t = 0; t < nt; ++t) {
+    const auto r0 = all.begin() + (size_t)t * pr->row_len;
+    st->point_rows[t].assign(r0, r0 + pr->row_len);
+  }
+  pr->point_row = st->point_rows[0];
   return OB_OK;
 }
 
-static int rw_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
-                          hipStream_t stream) {
-  if (!pr || !pr->reweight || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
+// d_rows / d_ok: one destination per statistic of the handle (one for the mean).
+static int rw_boot_impl(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* const* d_rows, uint8_t* const* d_ok,
+                        hipStream_t stream) {
   if (n_reps == 0) return OB_OK;
   if (first_rep + n_reps > 0xFFFFFFFFull)
     return fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 counter word)");
@@ -609,9 +665,13 @@ static int rw_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, 
       h.counts = p->d_counts + (size_t)(b0 / 64) * 4 * kCimgWords;
       h.nb_rep = nb_rep;
       h.n_reps = std::min(hb, ns - b0);
-      h.rows = d_rows + (s0 + b0) * pr->row_len;
-      h.ok = d_ok + s0 + b0;
-      rc = rw_batch(h, s);
+      double* rows[OB_REWEIGHT_MAX_STATS];
+      uint8_t* oks[OB_REWEIGHT_MAX_STATS];
+      for (int t = 0; t < std::max(st->n_stats, 1); ++t) {
+        rows[t] = d_rows[t] + (s0 + b0) * pr->row_len;
+        oks[t] = d_ok[t] + s0 + b0;
+      }
+      rc = rw_batch(h, s, st->n_stats, rows, oks);
     }
   }
   uint32_t flag = 0;
@@ -622,6 +682,15 @@ static int rw_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, 
   if (rc != OB_OK) return rc;
   if (flag & 1u) return fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
   return rm;
+}
+
+static int rw_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
+                          hipStream_t stream) {
+  if (!pr || !pr->reweight || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
+  if (pr->reweight->n_stats > 1) return fail(OB_E_INVALID, "a handle of several statistics boots through its own driver");
+  double* const rows[1] = {d_rows};
+  uint8_t* const oks[1] = {d_ok};
+  return rw_boot_impl(pr, first_rep, n_reps, rows, oks, stream);
 }
 
 static int rw_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
@@ -690,8 +759,46 @@ static int rw_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const
   return rc;
 }
 
+// The statistics of a prepared handle: with gamma-hat of the point pass on the device, w psi-hat for B's rows, the
+// three weighted RIF passes (one sort each serves every statistic), and the RIF columns of the panel.
+static int rw_fill_statistics(ob_prepared* pr, ReweightState* st, const double* ya, const double* wa, const double* yb,
+                              const double* wb) {
+  ob_panel* p = pr->panel;
+  const int k = st->k, T = (int)st->specs.size();
+  const int64_t n_a = pr->n_a, n_b = pr->n_b;
+  hipStream_t s = p->ctx->stream;
+  DevBuf d_wc;
+  OB_HIP(d_wc.alloc(sizeof(double) * (size_t)n_b));
+  hipLaunchKernelGGL(ob_rw_psi_kernel, dim3(blocks_for(n_b)), dim3(kRB), 0, s, st->cols[1].d(), p->ld[1], (uint32_t)n_b, k,
+                     st->gamma.d(), d_wc.d());
+  OB_HIP(hipGetLastError());
+  std::vector<double> wc((size_t)n_b);
+  OB_HIP(hipMemcpyAsync(wc.data(), d_wc.p, sizeof(double) * (size_t)n_b, hipMemcpyDeviceToHost, s));
+  OB_HIP(hipStreamSynchronize(s));
+  std::vector<double> ra((size_t)T * n_a), rb((size_t)T * n_b), rc((size_t)T * n_b), nu((size_t)3 * T);
+  OB_TRY(rif_device_weighted(p->ctx, ya, wa, n_a, st->specs.data(), T, ra.data(), nu.data(), true));
+  OB_TRY(rif_device_weighted(p->ctx, yb, wb, n_b, st->specs.data(), T, rb.data(), nu.data() + T, false));
+  OB_TRY(rif_device_weighted(p->ctx, yb, wc.data(), n_b, st->specs.data(), T, rc.data(), nu.data() + 2 * T, false));
+  st->nu.assign((size_t)3 * T, 0.0);
+  for (int t = 0; t < T; ++t) {
+    for (int f = 0; f < 3; ++f) st->nu[(size_t)3 * t + f] = nu[(size_t)f * T + t];
+    const size_t col = t ? (size_t)(k + t) : 0, col_c = (size_t)(k + T + t);
+    OB_HIP(hipMemcpy(st->cols[0].d() + col * p->ld[0], ra.data() + (size_t)t * n_a, sizeof(double) * n_a, hipMemcpyHostToDevice));
+    OB_HIP(hipMemcpy(st->cols[1].d() + col * p->ld[1], rb.data() + (size_t)t * n_b, sizeof(double) * n_b, hipMemcpyHostToDevice));
+    OB_HIP(hipMemcpy(st->cols[1].d() + col_c * p->ld[1], rc.data() + (size_t)t * n_b, sizeof(double) * n_b, hipMemcpyHostToDevice));
+  }
+  return OB_OK;
+}
+
+// n_specs = 0: the mean (ob_builder_prepare_reweighted).
 static int rw_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
-                      ob_prepared** out) {
+                      const ob_rif_spec* specs, int32_t n_specs, ob_prepared** out) {
+  if (n_specs > 0) {
+    OB_TRY(rif_wspec_check(specs, n_specs));
+    if (n_specs > OB_REWEIGHT_MAX_STATS)
+      return fail(OB_E_UNSUPPORTED, "reweighted decomposition: at most %d statistics in one run, got %d",
+                  OB_REWEIGHT_MAX_STATS, n_specs);
+  }
   Config c;
   ob_matrices* m = nullptr;
   OB_TRY(rw_stage(cols, n_cols, n_rows, cfg, c, &m));
@@ -699,12 +806,23 @@ static int rw_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_
     ob_matrices* m;
     ~Guard() { ob_matrices_free(m); }
   } guard{m};
-  if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
   int64_t n_a = 0, n_b = 0;
   int32_t k = 0;
   const double *xa, *ya, *xb, *yb;
   OB_TRY(ob_matrices_dims(m, &n_a, &n_b, &k));
   OB_TRY(ob_matrices_get(m, &xa, &ya, &xb, &yb));
+  std::vector<double> unit[2];  // the RIF passes' weights of a builder without sample weights
+  const double* wrif[2] = {matrices_weights(m, 0), matrices_weights(m, 1)};
+  if (n_specs > 0) {
+    for (int g = 0; g < 2; ++g)
+      if (!wrif[g]) {
+        unit[g].assign((size_t)(g ? n_b : n_a), 1.0);
+        wrif[g] = unit[g].data();
+      }
+    OB_TRY(rif_input_check_weighted(ya, wrif[0], n_a, specs, n_specs));
+    OB_TRY(rif_input_check_weighted(yb, wrif[1], n_b, specs, n_specs));
+  }
+  if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
   ob_panel_desc pd{};  // the resampler: the groups' row counts and the outcome
   pd.p = 0;
   pd.n_y = 1;
@@ -740,7 +858,8 @@ static int rw_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_
       const double* x = g ? xb : xa;
       const double* y = g ? yb : ya;
       const double* w = matrices_weights(m, g);
-      const size_t bytes = sizeof(double) * (size_t)(k + 1) * p->ld[g];
+      const int extra = n_specs > 0 ? (g ? 2 * n_specs - 1 : n_specs - 1) : 0;  // the RIF columns (file header)
+      const size_t bytes = sizeof(double) * (size_t)(k + 1 + extra) * p->ld[g];
       OB_HIP(st->cols[g].alloc(bytes));
       OB_HIP(hipMemset(st->cols[g].p, 0, bytes));
       OB_HIP(hipMemcpy(st->cols[g].p, y, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -759,6 +878,12 @@ static int rw_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_
     OB_HIP(st->chunks.alloc(sizeof(uint32_t) * table.size()));
     OB_HIP(hipMemcpy(st->chunks.p, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
     g_timing = {};
+    OB_TRY(rw_point(pr, st));
+    if (n_specs == 0) return OB_OK;
+    // the pass above gave gamma-hat (its fits, on y itself, are dropped); now the RIF columns and the point rows
+    st->specs.assign(specs, specs + n_specs);
+    OB_TRY(rw_fill_statistics(pr, st, ya, wrif[0], yb, wrif[1]));
+    st->n_stats = n_specs;
     return rw_point(pr, st);
   };
   const int rc = build();
@@ -908,7 +1033,67 @@ int ob_builder_prepare_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_
                                   const ob_builder_config* cfg, ob_prepared** out) {
   if (!out) return ob::fail(OB_E_INVALID, "null pointer");
   *out = nullptr;
-  return ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, out);
+  return ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, nullptr, 0, out);
+}
+
+int ob_builder_prepare_reweighted_statistic(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                            const ob_builder_config* cfg, const ob_rif_spec* spec, ob_prepared** out) {
+  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  OB_TRY(ob::rif_wspec_check(spec, 1));
+  return ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, spec, 1, out);
+}
+
+int ob_prepared_reweight_statistics(const ob_prepared* prep, double out[3]) {
+  if (!prep || !out) return ob::fail(OB_E_INVALID, "null pointer");
+  if (!prep->reweight || prep->reweight->n_stats != 1)
+    return ob::fail(OB_E_INVALID, "not a handle of a reweighted statistic");
+  for (int f = 0; f < 3; ++f) out[f] = prep->reweight->nu[f];
+  return OB_OK;
+}
+
+int ob_builder_run_reweighted_statistics(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                         const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
+                                         ob_results** out) {
+  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+  for (int32_t t = 0; t < n_specs && t < OB_REWEIGHT_MAX_STATS; ++t) out[t] = nullptr;
+  OB_TRY(ob::rif_wspec_check(specs, n_specs));
+  ob_prepared* pr = nullptr;
+  OB_TRY(ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, specs, n_specs, &pr));
+  const uint64_t reps = pr->cfg.reps;
+  const size_t rl = (size_t)pr->row_len;
+  auto run = [&]() -> int {
+    std::vector<double> rows((size_t)n_specs * reps * rl);
+    std::vector<uint8_t> ok((size_t)n_specs * reps, 0);
+    if (reps > 0) {
+      OB_HIP(hipSetDevice(pr->panel->ctx->device));
+      DevBuf d_rows, d_ok;
+      OB_HIP(d_rows.alloc(sizeof(double) * rows.size()));
+      OB_HIP(d_ok.alloc(ok.size()));
+      double* rp[OB_REWEIGHT_MAX_STATS];
+      uint8_t* op[OB_REWEIGHT_MAX_STATS];
+      for (int32_t t = 0; t < n_specs; ++t) {
+        rp[t] = d_rows.d() + (size_t)t * reps * rl;
+        op[t] = d_ok.as<uint8_t>() + (size_t)t * reps;
+      }
+      OB_TRY(ob::rw_boot_impl(pr, 0, reps, rp, op, nullptr));
+      OB_HIP(hipMemcpy(rows.data(), d_rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+      OB_HIP(hipMemcpy(ok.data(), d_ok.p, ok.size(), hipMemcpyDeviceToHost));
+    }
+    for (int32_t t = 0; t < n_specs; ++t) {  // finish() reads the handle's point row: statistic t's
+      pr->point_row = pr->reweight->point_rows[t];
+      OB_TRY(ob::finish(pr, 0, rows.data() + (size_t)t * reps * rl, ok.data() + (size_t)t * reps, reps, &out[t]));
+    }
+    return OB_OK;
+  };
+  const int rc = run();
+  ob_prepared_destroy(pr);
+  if (rc != OB_OK)
+    for (int32_t t = 0; t < n_specs; ++t) {
+      delete out[t];
+      out[t] = nullptr;
+    }
+  return rc;
 }
 
 int ob_builder_run_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
@@ -916,7 +1101,7 @@ int ob_builder_run_reweighted(ob_ctx* ctx, const ob_column* cols, int32_t n_cols
   if (!out) return ob::fail(OB_E_INVALID, "null pointer");
   *out = nullptr;
   ob_prepared* pr = nullptr;
-  OB_TRY(ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, &pr));
+  OB_TRY(ob::rw_prepare(ctx, cols, n_cols, n_rows, cfg, nullptr, 0, &pr));
   const uint64_t reps = pr->cfg.reps;
   std::vector<double> rows((size_t)reps * pr->row_len);
   std::vector<uint8_t> ok(reps, 0);

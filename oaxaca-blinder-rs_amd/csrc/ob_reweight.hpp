@@ -18,6 +18,9 @@ inline int reweight_row_len(int k) { return 7 + 11 * k + 5; }
 // The checks every entry point makes before any device work. k: design columns with the intercept.
 int reweight_check_shape(int k, int64_t n_a, int64_t n_b);
 
+// The decomposition of a statistic keeps this row and these hooks: its handle is a reweighted
+// handle whose outcome columns are the weighted RIFs in A, B and C, fixed at the point estimate (a replicate
+// refits the logit and the three regressions and does not recompute the statistic).
 struct ReweightState;  // device side of a prepared reweighted run (ob_reweight.hip)
 
 // ob_builder.cpp reaches the reweighting code through these hooks only (as it does the binary code), so

@@ -360,6 +360,33 @@ def parse_rif_statistic(stat, **params) -> tuple:
     return N.OB_RIF_STATS[stat], 0.0, 0.0
 
 
+def parse_weighted_rif_statistic(stat, **params) -> tuple:
+    """``parse_rif_statistic`` for the weighted entry points (``ob_rif_stat_weighted``, the reweighted decomposition
+    of a statistic): the same statistics and forms, plus ``"quantile"`` with ``tau`` (0.5 by default)."""
+    name, kw = stat, dict(params)
+    if isinstance(stat, dict):
+        name, kw = stat.get("stat"), {**{k: v for k, v in stat.items() if k != "stat"}, **params}
+    elif isinstance(stat, (tuple, list)) and len(stat) == 2 and isinstance(stat[1], dict):
+        name, kw = stat[0], {**stat[1], **params}
+    if name != "quantile":
+        if isinstance(name, str) and name in N.OB_RIF_STATS or not isinstance(name, str):
+            return parse_rif_statistic(stat, **params)
+        raise N.OaxacaError(N.OB_E_INVALID, f"unknown RIF statistic {name!r} (variance, gini, iqr, quantile)")
+    extra = sorted(set(kw) - {"tau"})
+    if extra:
+        raise ValueError(f"quantile: unexpected parameter(s) {', '.join(extra)}")
+    return N.OB_RIF_QUANTILE, float(kw.get("tau", 0.5)), 0.0
+
+
+def weighted_rif_name(parsed) -> tuple:
+    """(code, p0, p1) -> (name, params), what ``ReweightedDecompositionResults.statistic`` holds."""
+    code, p0, p1 = parsed
+    name = {v: k for k, v in N.OB_RIF_WSTATS.items()}[code]
+    if code == N.OB_RIF_IQR:
+        return name, {"upper": p0, "lower": p1}
+    return name, ({"tau": p0} if code == N.OB_RIF_QUANTILE else {})
+
+
 def rif_specs(stats):
     """A ctypes array of ``ob_rif_spec`` for a list of statistics (``parse_rif_statistic`` each)."""
     parsed = [parse_rif_statistic(s) for s in stats]
@@ -391,6 +418,21 @@ def rif_statistic(y, stat, device: int | None = None, **params):
     spec = N.ob_rif_spec(*parse_rif_statistic(stat, **params))
     out, value = np.empty_like(y), C.c_double()
     with_context(lambda ctx: N.lib().ob_rif_stat(ctx, _dp(y), len(y), C.byref(spec), _dp(out), C.byref(value)), device)
+    return out, value.value
+
+
+def rif_statistic_weighted(y, w, stat, device: int | None = None, **params):
+    """``ob_rif_stat_weighted``: the weighted recentred influence function of ``stat`` ("variance", "gini",
+    "quantile" with ``tau``, "iqr" with ``upper`` / ``lower``) over ``y`` with weights ``w`` >= 0 on the GPU ->
+    (rif in y's order, the statistic). At w = 1 it is ``rif_statistic``'s definition."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if y.ndim != 1 or w.shape != y.shape:
+        raise ValueError("y and w must be one-dimensional and of one length")
+    spec = N.ob_rif_spec(*parse_weighted_rif_statistic(stat, **params))
+    out, value = np.empty_like(y), C.c_double()
+    with_context(lambda ctx: N.lib().ob_rif_stat_weighted(ctx, _dp(y), _dp(w), len(y), C.byref(spec), _dp(out),
+                                                          C.byref(value)), device)
     return out, value.value
 
 
