@@ -1332,6 +1332,116 @@ int ob_builder_run_reweighted_statistics(ob_ctx* ctx, const ob_column* cols, int
                                          const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
                                          ob_results** out);
 
+/* ---- Distribution-regression decomposition of quantile gaps ------------------------------------
+ * Chernozhukov, Fernandez-Val and Melly (2013), "Inference on counterfactual distributions"; Stata's `cdeco` /
+ * `counterfactual`, R's `Counterfactual`. No counterpart in the reference crate. A is the non-reference group, B
+ * cfg->reference_group; x the design row with the intercept in column 0 (K <= OB_DR_MAX_K columns); w the sample
+ * weight (1 without cfg->weights); c the replicate's OBRS-3 count of the row (1 in the point pass).
+ *   Thresholds c_1 < .. < c_T, 2 <= T <= OB_DR_MAX_T: given, or (ob_dr_config.thresholds == NULL) n_thresholds
+ *   unweighted sample quantiles of the pooled outcome (A's rows then B's) at the levels lo + (hi - lo) t / (n - 1),
+ *   t = 0 .. n - 1, by ob_rif's linear interpolation: h = (N - 1) level, s[floor h] + (h - floor h) (s[ceil h] -
+ *   s[floor h]) on the sorted outcome. Exact duplicates are removed and the number kept is T. The thresholds are
+ *   fixed at prepare time: a replicate does not move them.
+ *   Fits: for g in {A, B} and each t the logit of d = 1[y <= c_t] on x over g's rows with weights c w, by Newton
+ *   from beta = 0: p clamped to [1e-10, 1 - 1e-10], the information matrix sum c w p (1 - p) x x' solved by
+ *   Cholesky (ob::chol_factor's operation order), converged when ||step||_2 < 1e-6, at most 100 passes. Every fit
+ *   has its own done flag: once converged no later pass touches it.
+ *   Distributions: F_jg(c_t) = sum_{i in j} c_i w_i L(x_i' beta_{g,t}) / sum_{i in j} c_i w_i with the same clamped
+ *   sigmoid L, for (j, g) = AA, BB, AB and BA. F_C := F_AB, A's covariates with B's coefficients (the reading of C
+ *   of the reweighted decomposition above); BA is reported and not decomposed.
+ *   Distribution effects at every threshold: total = F_AA - F_BB, composition = F_C - F_BB, structure = F_AA - F_C.
+ *   Quantile effects: each of F_AA, F_BB and F_C is rearranged (sorted ascending over t) into F~. For each tau,
+ *   t* = min{t : F~_t >= tau} and Q = c_{t*-1} + (tau - F~_{t*-1}) (c_{t*} - c_{t*-1}) / (F~_{t*} - F~_{t*-1});
+ *   Q = c_1 if t* = 1 and Q = c_T if tau > F~_T (the two edge cases). total(tau) = Q_A - Q_B, composition(tau) =
+ *   Q_C - Q_B, structure(tau) = Q_A - Q_C.
+ * Row of a replicate, ob_dr_row_len(T, n_q) = 6 n_q + 7 T + 1 doubles:
+ *     [3][n_q] quantile effects total, composition, structure | [3][n_q] quantiles Q_A, Q_B, Q_C |
+ *     [3][T] distribution effects total, composition, structure | [4][T] F_AA, F_BB, F_AB, F_BA (not rearranged) |
+ *     the largest pass count among the replicate's 2 T fits.
+ * A replicate one of whose fits does not converge or has no Cholesky factor has ok = 0 and a NaN row, which
+ * ob_prepared_finish drops and counts; in the point pass that is OB_E_LINALG for the whole call (a threshold that
+ * nobody or everybody of a group lies under is one way it happens). Every sum is f64 in chunk order without
+ * floating-point atomics: a replicate's row has the same bytes alone, in any batch and at any first_rep. Option
+ * "hk_batch" caps a batch at n 64-replicate blocks (default: as many replicates as keep the chunk partials within
+ * 1 GiB).
+ * Errors of the frame entry points, all before any device work and before the context is read: normalize, Heckman
+ * settings, K > OB_DR_MAX_K, more than OB_DR_MAX_T thresholds, more than OB_DR_MAX_Q quantiles: OB_E_UNSUPPORTED;
+ * a null or non-finite value in a named column, thresholds that are not finite and strictly increasing, fewer than
+ * two thresholds, a tau outside (0, 1), no quantile: OB_E_INVALID; a group with rows <= K: OB_E_INSUFFICIENT.
+ * cfg->reference_coeffs is ignored. The cluster bootstrap is not served. On a handle prepared here ob_prepared_boot,
+ * ob_prepared_boot_device, ob_prepared_finish and ob_prepared_point_row work; ob_prepared_boot_sharded,
+ * ob_prepared_jackknife and ob_prepared_finish_bca are OB_E_UNSUPPORTED.
+ * Results of ob_prepared_finish / ob_builder_run_dr: the tables OB_DR_TABLE_* in row order, every component through
+ * the aggregation of the other runs (estimate, standard error, percentile interval, p); component names are
+ * "<part>@<index>" with part one of total, composition, structure (effects), A, B, C (quantiles), AA, BB, AB, BA
+ * (distributions) and index that of the quantile or threshold. */
+#define OB_DR_MAX_K 32
+#define OB_DR_MAX_T 64
+#define OB_DR_MAX_Q 32
+#define OB_DR_MAX_VECTORS 128
+#define OB_DR_TABLE_QUANTILE_EFFECTS 0
+#define OB_DR_TABLE_QUANTILES 1
+#define OB_DR_TABLE_DISTRIBUTION_EFFECTS 2
+#define OB_DR_TABLE_CDF 3
+typedef struct {
+  const double* thresholds; /* n_thresholds values, or NULL: pooled quantiles at n_thresholds levels of [lo, hi] */
+  int32_t n_thresholds;
+  double lo, hi;
+  const double* quantiles;  /* n_quantiles values in (0, 1) */
+  int32_t n_quantiles;
+} ob_dr_config;
+typedef struct {
+  int32_t passes;   /* the longest batch's Newton passes */
+  int32_t launches; /* pass kernels over all batches */
+  double pass_ms;   /* the threshold logit pass kernels (the Newton steps not included) */
+  double cdf_ms;    /* the distribution pass */
+  double row_ms;    /* the rows */
+} ob_dr_timing;
+typedef struct {
+  int32_t n_thresholds, n_quantiles, k; /* thresholds kept, quantiles, design columns */
+  int32_t n_requested;                  /* thresholds before duplicates were removed */
+  int32_t n_out_of_range;               /* (tau, distribution) pairs of the point estimate that hit an edge case */
+  const double* thresholds;             /* [T] */
+  const double* quantiles;              /* [n_q] */
+  const double* beta;                   /* [2][T][k]: the point fits of A then B */
+  const int32_t* passes;                /* [2][T] */
+  const uint8_t* out_of_range;          /* [3][n_q]: A, B, C; 1 below F~_1's threshold, 2 above F~_T */
+} ob_dr_info;
+int ob_dr_row_len(int32_t n_thresholds, int32_t n_quantiles);
+/* The shape limits above on their own (host only). k: design columns with the intercept. */
+int ob_dr_check_shape(int32_t k, int64_t n_a, int64_t n_b, int32_t n_thresholds, int32_t n_quantiles);
+/* HIP-event ms of the calling thread's last distribution-regression boot (or prepare: the point pass). */
+int ob_dr_last_timing(ob_dr_timing* out);
+/* Host only: the thresholds of a count. out [n_thresholds]; *n_kept of them are filled after duplicate removal. */
+int ob_dr_thresholds(const double* y, int64_t n, int32_t n_thresholds, double lo, double hi, double* out,
+                     int32_t* n_kept);
+/* Host only: rearrange f [T] and invert it at taus [n_q] on thresholds [T]. q [n_q]; rearranged [T] (or NULL);
+   edge [n_q] (or NULL): 0, 1 (t* = 1) or 2 (tau > F~_T). */
+int ob_dr_quantiles(const double* f, const double* thresholds, int32_t n_thresholds, const double* taus, int32_t n_q,
+                    double* q, double* rearranged, uint8_t* edge);
+/* Host only: the aggregation of ob_prepared_finish on rows of ob_dr_row_len(T, n_q) doubles and their point row. */
+int ob_dr_finish_rows(const double* point_row, int32_t n_thresholds, int32_t n_q, const double* rows, const uint8_t* ok,
+                      uint64_t n_reps, ob_results** out);
+/* One threshold logit pass alone over one group of rows: x (n x k, column-major, ldx >= n, column 0 all ones), y (n),
+   w (n weights or NULL for 1), counts (n bytes or NULL for every row once), thresholds [T] (any finite values, T <=
+   OB_DR_MAX_T), betas [T][k]. info [T][k x k] (symmetric, both triangles): sum c w p (1 - p) x x'; grad [T][k]:
+   sum c w (1[y <= c_t] - p) x. */
+int ob_dr_logit_pass(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, const double* w, const uint8_t* counts,
+                     int64_t n, int32_t k, const double* thresholds, int32_t n_thresholds, const double* betas,
+                     double* info, double* grad);
+/* The distribution pass alone: sums [m] = sum c w L(x' beta_v) for betas [m][k], m <= OB_DR_MAX_VECTORS, and
+   *wsum = sum c w. Arguments as ob_dr_logit_pass. */
+int ob_dr_cdf(ob_ctx* ctx, const double* x, int64_t ldx, const double* w, const uint8_t* counts, int64_t n, int32_t k,
+              const double* betas, int32_t m, double* sums, double* wsum);
+int ob_builder_prepare_dr(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                          const ob_builder_config* cfg, const ob_dr_config* dr, ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish. */
+int ob_builder_run_dr(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                      const ob_dr_config* dr, ob_results** out);
+/* The handle's thresholds, point fits, pass counts and edge-case counts (owned by the handle). OB_E_INVALID on a
+   handle of another kind. */
+int ob_prepared_dr_info(const ob_prepared* prep, ob_dr_info* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ hyphen). See DESIGN.md for the kernels and INTEGRATION.md for the Rust/C binding
 from . import _native
 from ._native import OaxacaError
 from .api import (Adjustment, AkmBuilder, AkmResult, BinaryDecompositionResults, BudgetAdjustment, ComponentResult, Contribution, DataSummary,
-                  DecompositionDetail, DecompositionResult, DflResult, JackknifeResult, defensibility_message, parse_rust_f64, FrontierPoint, MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder,
+                  DecompositionDetail, DecompositionResult, DflResult, DistributionDecompositionResults, dr_finish_rows, JackknifeResult, defensibility_message, parse_rust_f64, FrontierPoint, MatchingEngine, MatchResult, OaxacaBlinder, OaxacaBuilder,
                   OaxacaResults, OptimizationResult, PreparedRun,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
                   ReferenceCoefficients, ReweightedDecompositionResults, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
@@ -20,6 +20,7 @@ from .engine import (binary_check_shape, binary_last_timing, binary_means, binar
                      rif_statistic_weighted, rif_last_timing,
                      rif_scan_block, rif_statistic, reweight_check_shape, reweight_gram, reweight_last_timing,
                      reweight_logit_pass, reweight_row_len,
+                     dr_cdf, dr_check_shape, dr_last_timing, dr_logit_pass, dr_quantiles, dr_row_len, dr_thresholds,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
@@ -43,4 +44,6 @@ __all__ = [
     "BinaryDecompositionResults", "binary_means", "binary_check_shape", "binary_row_len", "binary_last_timing",
     "ReweightedDecompositionResults", "reweight_logit_pass", "reweight_gram", "reweight_check_shape",
     "reweight_row_len", "reweight_last_timing",
+    "DistributionDecompositionResults", "dr_logit_pass", "dr_cdf", "dr_thresholds", "dr_quantiles", "dr_last_timing",
+    "dr_check_shape", "dr_row_len", "dr_finish_rows",
 ]

@@ -71,6 +71,9 @@ EXPORTED = (
     "ob_reweight_gram", "ob_builder_prepare_reweighted", "ob_builder_run_reweighted",
     "ob_rif_stat_weighted", "ob_builder_prepare_reweighted_statistic", "ob_prepared_reweight_statistics",
     "ob_builder_run_reweighted_statistics",
+    "ob_dr_row_len", "ob_dr_check_shape", "ob_dr_last_timing", "ob_dr_thresholds", "ob_dr_quantiles",
+    "ob_dr_finish_rows", "ob_dr_logit_pass", "ob_dr_cdf", "ob_builder_prepare_dr", "ob_builder_run_dr",
+    "ob_prepared_dr_info",
 )
 
 OB_E_CONVERGENCE = 12
@@ -97,6 +100,8 @@ OB_BINARY_MODELS = {"probit": OB_BINARY_PROBIT, "logit": OB_BINARY_LOGIT}
 OB_REWEIGHT_MAX_K = 32  # design columns, the intercept included
 OB_RW_TABLE_AGGREGATE, OB_RW_TABLE_PURE_EXPLAINED, OB_RW_TABLE_SPECIFICATION_ERROR = 0, 1, 2
 OB_RW_TABLE_PURE_UNEXPLAINED, OB_RW_TABLE_REWEIGHTING_ERROR = 3, 4
+OB_DR_MAX_K, OB_DR_MAX_T, OB_DR_MAX_Q, OB_DR_MAX_VECTORS = 32, 64, 32, 128
+OB_DR_TABLE_QUANTILE_EFFECTS, OB_DR_TABLE_QUANTILES, OB_DR_TABLE_DISTRIBUTION_EFFECTS, OB_DR_TABLE_CDF = 0, 1, 2, 3
 
 
 class OaxacaError(RuntimeError):
@@ -263,6 +268,23 @@ class ob_binary_timing(C.Structure):
 class ob_reweight_timing(C.Structure):
     _fields_ = [("logit_passes", C.c_int32), ("logit_launches", C.c_int32), ("logit_ms", C.c_double),
                 ("gram_ms", C.c_double), ("row_ms", C.c_double)]
+
+
+class ob_dr_config(C.Structure):
+    _fields_ = [("thresholds", C.POINTER(C.c_double)), ("n_thresholds", C.c_int32), ("lo", C.c_double),
+                ("hi", C.c_double), ("quantiles", C.POINTER(C.c_double)), ("n_quantiles", C.c_int32)]
+
+
+class ob_dr_timing(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("launches", C.c_int32), ("pass_ms", C.c_double), ("cdf_ms", C.c_double),
+                ("row_ms", C.c_double)]
+
+
+class ob_dr_info(C.Structure):
+    _fields_ = [("n_thresholds", C.c_int32), ("n_quantiles", C.c_int32), ("k", C.c_int32), ("n_requested", C.c_int32),
+                ("n_out_of_range", C.c_int32), ("thresholds", C.POINTER(C.c_double)),
+                ("quantiles", C.POINTER(C.c_double)), ("beta", C.POINTER(C.c_double)),
+                ("passes", C.POINTER(C.c_int32)), ("out_of_range", C.POINTER(C.c_uint8))]
 
 
 class ob_component(C.Structure):
@@ -503,6 +525,19 @@ _SIGS = {
     "ob_builder_run_reweighted_statistics": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
                                                        C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec), C.c_int32,
                                                        C.POINTER(_P)]),
+    "ob_dr_row_len": (C.c_int, [C.c_int32, C.c_int32]),
+    "ob_dr_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "ob_dr_last_timing": (C.c_int, [C.POINTER(ob_dr_timing)]),
+    "ob_dr_thresholds": (C.c_int, [_D, C.c_int64, C.c_int32, C.c_double, C.c_double, _D, C.POINTER(C.c_int32)]),
+    "ob_dr_quantiles": (C.c_int, [_D, _D, C.c_int32, _D, C.c_int32, _D, _D, _U8]),
+    "ob_dr_finish_rows": (C.c_int, [_D, C.c_int32, C.c_int32, _D, _U8, C.c_uint64, C.POINTER(_P)]),
+    "ob_dr_logit_pass": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D, _D]),
+    "ob_dr_cdf": (C.c_int, [_P, _D, C.c_int64, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D]),
+    "ob_builder_prepare_dr": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
+                                        C.POINTER(ob_dr_config), C.POINTER(_P)]),
+    "ob_builder_run_dr": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
+                                    C.POINTER(ob_dr_config), C.POINTER(_P)]),
+    "ob_prepared_dr_info": (C.c_int, [_P, C.POINTER(ob_dr_info)]),
 }
 
 _lib = None

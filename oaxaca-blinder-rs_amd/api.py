@@ -426,6 +426,108 @@ def _reweighted_results(res, point, statistic=None, statistics=None) -> Reweight
         n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed, statistic=statistic, statistics=statistics)
 
 
+@dataclass
+class DistributionDecompositionResults:
+    """``OaxacaBuilder.decompose_distribution``: the distribution-regression decomposition of Chernozhukov,
+    Fernandez-Val and Melly (2013). ``quantile_effects`` and ``distribution_effects`` hold, under ``"total"``,
+    ``"composition"`` and ``"structure"``, one component per quantile / threshold (estimate, standard error,
+    percentile interval, p-value over the bootstrap, in which every threshold logit is refitted per replicate);
+    ``quantile_values`` the quantiles of A, B and the counterfactual C; ``cdf`` the four distributions ``"AA"``,
+    ``"BB"``, ``"AB"`` (= C: A's covariates, B's coefficients) and ``"BA"`` as fitted, and ``cdf_rearranged`` the
+    monotone rearrangement of their point estimates, which the quantiles are read from. ``beta_a`` / ``beta_b``:
+    (T, K) point fits. ``n_out_of_range``: (tau, distribution) pairs whose tau lies outside the fitted range of the
+    threshold grid, where the quantile is the grid's end."""
+    quantiles: np.ndarray
+    thresholds: np.ndarray
+    quantile_effects: dict
+    quantile_values: dict
+    distribution_effects: dict
+    cdf: dict
+    cdf_rearranged: dict = field(repr=False, default_factory=dict)
+    beta_a: np.ndarray = field(repr=False, default=None)
+    beta_b: np.ndarray = field(repr=False, default=None)
+    passes: np.ndarray = field(repr=False, default=None)
+    out_of_range: np.ndarray = field(repr=False, default=None)
+    names: list = field(default_factory=list, repr=False)
+    n_a: int = 0
+    n_b: int = 0
+    n_failed: int = 0
+    n_out_of_range: int = 0
+    n_thresholds_requested: int = 0
+
+    def to_json(self) -> str:
+        def fix(v):  # serde_json writes non-finite floats as null
+            return v if isinstance(v, str) or np.isfinite(v) else None
+
+        def comps(d):
+            return {key: [{k: fix(v) for k, v in c.__dict__.items()} for c in cs] for key, cs in d.items()}
+
+        def vec(a):
+            return [fix(float(v)) for v in np.asarray(a).ravel()]
+
+        return json.dumps({
+            "quantiles": vec(self.quantiles), "thresholds": vec(self.thresholds),
+            "quantile_effects": comps(self.quantile_effects), "quantile_values": comps(self.quantile_values),
+            "distribution_effects": comps(self.distribution_effects), "cdf": comps(self.cdf),
+            "cdf_rearranged": {key: vec(v) for key, v in self.cdf_rearranged.items()},
+            "beta_a": [vec(r) for r in self.beta_a], "beta_b": [vec(r) for r in self.beta_b],
+            "passes": [int(v) for v in np.asarray(self.passes).ravel()], "names": list(self.names),
+            "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed, "n_out_of_range": self.n_out_of_range,
+            "n_thresholds_requested": self.n_thresholds_requested})
+
+
+def _dr_tables(handle):
+    """The four tables of a distribution-regression finish() -> (dicts of component lists, n_failed); frees the
+    handle."""
+    lib = N.lib()
+
+    def table(t, parts):
+        cs = []
+        for i in range(lib.ob_results_count(handle, t)):
+            c = N.ob_component()
+            N.check(lib.ob_results_component(handle, t, i, C.byref(c)))
+            cs.append(ComponentResult(c.name.decode(), c.estimate, c.std_err, c.t_stat, c.p_value, c.ci_lower,
+                                      c.ci_upper))
+        n = len(cs) // len(parts)
+        return {p: cs[i * n:(i + 1) * n] for i, p in enumerate(parts)}
+
+    try:
+        eff = ("total", "composition", "structure")
+        return (table(N.OB_DR_TABLE_QUANTILE_EFFECTS, eff), table(N.OB_DR_TABLE_QUANTILES, ("A", "B", "C")),
+                table(N.OB_DR_TABLE_DISTRIBUTION_EFFECTS, eff), table(N.OB_DR_TABLE_CDF, ("AA", "BB", "AB", "BA")),
+                int(lib.ob_results_n_failed(handle)), int(lib.ob_results_n_a(handle)), int(lib.ob_results_n_b(handle)))
+    finally:
+        lib.ob_results_free(handle)
+
+
+def dr_finish_rows(point_row, thresholds, quantiles, rows, ok) -> DistributionDecompositionResults:
+    """ob_dr_finish_rows (host only): the aggregation of ``decompose_distribution`` on given replicate rows (each
+    ``dr_row_len(T, n_q)`` doubles) and their point row."""
+    from .engine import dr_quantiles
+
+    point = np.ascontiguousarray(point_row, dtype=np.float64)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    taus = np.ascontiguousarray(quantiles, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    T, nq = len(thr), len(taus)
+    if point.shape != (6 * nq + 7 * T + 1,) or rows.shape != (len(ok), len(point)):
+        raise ValueError("point_row and rows must have 6 n_q + 7 T + 1 entries per row")
+    h = C.c_void_p()
+    dp = C.POINTER(C.c_double)
+    N.check(N.lib().ob_dr_finish_rows(point.ctypes.data_as(dp), T, nq, rows.ctypes.data_as(dp),
+                                      ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
+    qe, qv, de, cdf, n_failed, n_a, n_b = _dr_tables(h)
+    fr = point[6 * nq + 3 * T:6 * nq + 7 * T].reshape(4, T)
+    re, edge = {}, np.zeros((3, nq), dtype=np.uint8)
+    for i, key in enumerate(("AA", "BB", "AB")):
+        _, re[key], edge[i] = dr_quantiles(fr[i], thr, taus)
+    return DistributionDecompositionResults(
+        quantiles=taus.copy(), thresholds=thr.copy(), quantile_effects=qe, quantile_values=qv,
+        distribution_effects=de, cdf=cdf, cdf_rearranged=re, out_of_range=edge, n_a=n_a, n_b=n_b,
+        n_failed=n_failed, n_out_of_range=int((edge != 0).sum()))
+
+
 def _jackknife_out(k: int):
     c = 6 + 2 * k
     bufs = (np.zeros(c), np.zeros((2, c, 3)), np.zeros((c, 3)))
@@ -1124,6 +1226,86 @@ class OaxacaBuilder:
         name = None if statistic is None else weighted_rif_name(parse_weighted_rif_statistic(statistic, **params))
         return _reweighted_results(res, point, name, nu)
 
+    def prepare_distribution(self, quantiles=(0.1, 0.25, 0.5, 0.75, 0.9), thresholds=None, n_thresholds=50, lo=0.05,
+                             hi=0.95) -> "PreparedRun":
+        """The handle of ``decompose_distribution`` (``ob_builder_prepare_dr``): the thresholds are fixed and the
+        point pass has run; ``boot`` / ``boot_device`` / ``finish`` / ``point_row`` / ``dr_info`` work on it."""
+        from .engine import with_context
+
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED,
+                                "distribution regression: the cluster bootstrap is outside its scope")
+        taus = np.ascontiguousarray(np.atleast_1d(quantiles), dtype=np.float64)
+        if taus.ndim != 1:
+            raise ValueError("quantiles must be a 1-D sequence")
+        dp = C.POINTER(C.c_double)
+        dr = N.ob_dr_config()
+        thr = None
+        if thresholds is not None:
+            thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+            if thr.ndim != 1:
+                raise ValueError("thresholds must be a 1-D sequence")
+            dr.thresholds, dr.n_thresholds = thr.ctypes.data_as(dp), len(thr)
+        else:
+            dr.thresholds, dr.n_thresholds = None, int(n_thresholds)
+        dr.lo, dr.hi = float(lo), float(hi)
+        dr.quantiles, dr.n_quantiles = taus.ctypes.data_as(dp), len(taus)
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        h = C.c_void_p()
+
+        def call(ctx):
+            return lib.ob_builder_prepare_dr(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(dr), C.byref(h))
+
+        if self._ctx is not None:
+            N.check(call(self._ctx))
+        else:
+            with_context(call, self._device)
+        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+
+    def decompose_distribution(self, quantiles=(0.1, 0.25, 0.5, 0.75, 0.9), thresholds=None, n_thresholds=50, lo=0.05,
+                               hi=0.95) -> "DistributionDecompositionResults":
+        """Extension (no counterpart in the reference crate): the distribution-regression decomposition of
+        Chernozhukov, Fernandez-Val and Melly (2013), Stata's ``cdeco`` / ``counterfactual``. A logit of
+        ``1[y <= c]`` on the design is fitted in each group at every threshold ``c`` (given, or ``n_thresholds``
+        pooled sample quantiles at evenly spaced levels of ``[lo, hi]``, duplicates removed); averaging the
+        reference group B's fitted probabilities over A's rows gives the counterfactual distribution C. The three
+        distributions are rearranged and inverted at ``quantiles``: at each tau the gap splits into
+        ``composition`` (Q_C - Q_B) and ``structure`` (Q_A - Q_C). Every bootstrap replicate refits all 2 T logits
+        on the GPU; the thresholds stay fixed. Sample weights are served; ``reference_coefficients`` is ignored.
+        Refused (``OB_E_UNSUPPORTED``): ``normalize``, ``cluster``, Heckman settings, more than 32 design columns,
+        64 thresholds or 32 quantiles. Warns when a tau lies outside the range the threshold grid covers."""
+        import warnings
+
+        pr = self.prepare_distribution(quantiles, thresholds, n_thresholds, lo, hi)
+        try:
+            rows, ok = pr.boot(0, self._bootstrap_reps)
+            h = C.c_void_p()
+            N.check(N.lib().ob_prepared_finish(pr._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                               ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
+            qe, qv, de, cdf, n_failed, n_a, n_b = _dr_tables(h)
+            info = pr.dr_info()
+            point = pr.point_row()
+        finally:
+            pr.close()
+        from .engine import dr_quantiles
+
+        T, nq = len(info["thresholds"]), len(info["quantiles"])
+        fr = point[6 * nq + 3 * T:6 * nq + 7 * T].reshape(4, T)
+        re = {key: dr_quantiles(fr[i], info["thresholds"], info["quantiles"])[1] for i, key in enumerate(("AA", "BB", "AB"))}
+        if info["n_out_of_range"]:
+            warnings.warn(f"distribution regression: {info['n_out_of_range']} (quantile, distribution) pair(s) lie "
+                          "outside the range of the threshold grid; their quantiles are the grid's end points",
+                          RuntimeWarning, stacklevel=2)
+        names = self.get_data_matrices()[4]
+        return DistributionDecompositionResults(
+            quantiles=info["quantiles"], thresholds=info["thresholds"], quantile_effects=qe, quantile_values=qv,
+            distribution_effects=de, cdf=cdf, cdf_rearranged=re, beta_a=info["beta"][0], beta_b=info["beta"][1],
+            passes=info["passes"], out_of_range=info["out_of_range"], names=list(names), n_a=n_a, n_b=n_b,
+            n_failed=n_failed, n_out_of_range=info["n_out_of_range"],
+            n_thresholds_requested=info["n_thresholds_requested"])
+
     def statistic_builder(self, stat, **params) -> "OaxacaBuilder":
         """A fresh builder over this frame with the outcome replaced by the statistic's RIF of each group's
         outcome (the rows ``run()`` would keep, group by group, as ``decompose_statistic`` forms it), so that
@@ -1237,6 +1419,21 @@ class PreparedRun:
         out = np.zeros(3)
         N.check(N.lib().ob_prepared_reweight_statistics(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
         return tuple(float(v) for v in out)
+
+    def dr_info(self) -> dict:
+        """ob_prepared_dr_info: the thresholds kept, the quantiles, the point fits beta (2, T, K: A then B), their
+        pass counts (2, T) and the edge cases of the point estimate (out_of_range (3, n_q): A, B, C)."""
+        o = N.ob_dr_info()
+        N.check(N.lib().ob_prepared_dr_info(self._h, C.byref(o)))
+        T, nq, k = o.n_thresholds, o.n_quantiles, o.k
+
+        def arr(ptr, shape):
+            return np.ctypeslib.as_array(ptr, shape=shape).copy()
+
+        return {"thresholds": arr(o.thresholds, (T,)), "quantiles": arr(o.quantiles, (nq,)),
+                "beta": arr(o.beta, (2, T, k)), "passes": arr(o.passes, (2, T)),
+                "out_of_range": arr(o.out_of_range, (3, nq)), "n_out_of_range": int(o.n_out_of_range),
+                "n_thresholds_requested": int(o.n_requested)}
 
     def sync(self):
         N.check(N.lib().ob_panel_sync(N.lib().ob_prepared_panel(self._h)))

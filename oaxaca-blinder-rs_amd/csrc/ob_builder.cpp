@@ -51,6 +51,11 @@ ReweightHooks& reweight_hooks() {
   return h;
 }
 
+DrHooks& dr_hooks() {
+  static DrHooks h;
+  return h;
+}
+
 RifHooks& rif_hooks() {
   static RifHooks h;
   return h;
@@ -574,9 +579,87 @@ static int reweight_finish(const ob_prepared* pr, const double* rows, const uint
   return OB_OK;
 }
 
+// Rearrangement and inversion of one distribution on the threshold grid (include/oaxaca_boot.h).
+int dr_quantiles(const double* f, const double* thr, int T, const double* taus, int nq, double* q, double* rearranged,
+                 uint8_t* edge) {
+  std::vector<double> s(f, f + T);
+  std::sort(s.begin(), s.end());
+  if (rearranged) std::copy(s.begin(), s.end(), rearranged);
+  int n_edge = 0;
+  for (int i = 0; i < nq; ++i) {
+    const double tau = taus[i];
+    int t = 0;
+    while (t < T && !(s[t] >= tau)) ++t;  // t* - 1
+    uint8_t e = 0;
+    if (t == T) {
+      q[i] = thr[T - 1];
+      e = 2;
+    } else if (t == 0) {
+      q[i] = thr[0];
+      e = 1;
+    } else {
+      q[i] = thr[t - 1] + (tau - s[t - 1]) * (thr[t] - thr[t - 1]) / (s[t] - s[t - 1]);
+    }
+    if (edge) edge[i] = e;
+    n_edge += e ? 1 : 0;
+  }
+  return n_edge;
+}
+
+// finish() for rows of the distribution-regression decomposition (ob_dr.hpp's row): every entry but the pass count
+// is a component of its own, through the same aggregate() as an OLS row's.
+int dr_finish_rows(const double* point, int T, int nq, const double* rows, const uint8_t* ok, uint64_t n_reps,
+                   ob_results** out) {
+  const int rl = dr_row_len(T, nq);
+  uint64_t ng = 0;
+  for (uint64_t r = 0; r < n_reps; ++r) ng += ok[r] ? 1 : 0;
+  if (ng < n_reps)
+    fprintf(stderr,
+            "Warning: %llu out of %llu bootstrap replications failed and were discarded. The analysis is based on "
+            "%llu successful replications.\n",
+            (unsigned long long)(n_reps - ng), (unsigned long long)n_reps, (unsigned long long)ng);
+  ob_results* res = new ob_results();
+  res->n_failed = (int64_t)(n_reps - ng);
+  static const char* eff[3] = {"total", "composition", "structure"};
+  static const char* smp[3] = {"A", "B", "C"};
+  static const char* cdf[4] = {"AA", "BB", "AB", "BA"};
+  std::vector<int> table;
+  std::vector<std::string> names;
+  std::vector<std::vector<int>> groups;
+  auto block = [&](int tb, const char* const* parts, int n_parts, int len) {
+    for (int p = 0; p < n_parts; ++p)
+      for (int i = 0; i < len; ++i) {
+        table.push_back(tb);
+        names.push_back(std::string(parts[p]) + "@" + std::to_string(i));
+        groups.push_back({(int)groups.size()});
+      }
+  };
+  block(OB_DR_TABLE_QUANTILE_EFFECTS, eff, 3, nq);
+  block(OB_DR_TABLE_QUANTILES, smp, 3, nq);
+  block(OB_DR_TABLE_DISTRIBUTION_EFFECTS, eff, 3, T);
+  block(OB_DR_TABLE_CDF, cdf, 4, T);
+  std::vector<double> st(4 * groups.size());
+  aggregate(rows, ok, n_reps, rl, groups, st.data());
+  for (size_t ji = 0; ji < groups.size(); ++ji) {
+    const double* s4 = st.data() + 4 * ji;
+    const double pt = point[groups[ji][0]];
+    const double t = std::fabs(s4[0]) > 1e-9 ? pt / s4[0] : 0.0;  // as finish()
+    res->tables[table[ji]].push_back({names[ji], pt, s4[0], t, s4[1], s4[2], s4[3]});
+  }
+  *out = res;
+  return OB_OK;
+}
+
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block).
 int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
   if (pr->reweight) return reweight_finish(pr, rows, ok, n_reps, out);
+  if (pr->dr) {
+    OB_TRY(dr_finish_rows(pr->point_row.data(), (int)pr->dr_info.thresholds.size(), (int)pr->dr_info.taus.size(), rows, ok,
+                          n_reps, out));
+    (*out)->n_a = pr->n_a;
+    (*out)->n_b = pr->n_b;
+    return OB_OK;
+  }
   const int k = pr->k, kd = k + pr->n_base, rl = pr->row_len;
   const double* point_row = pr->point_row.data() + (size_t)t_out * rl;
   uint64_t ng = 0;
@@ -898,6 +981,31 @@ int ob_builder_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64
   return ob::prepare(ctx, f, c, out);
 }
 
+int ob_dr_quantiles(const double* f, const double* thresholds, int32_t n_thresholds, const double* taus, int32_t n_q,
+                    double* q, double* rearranged, uint8_t* edge) {
+  if (!f || !thresholds || !q || (n_q > 0 && !taus)) return ob::fail(OB_E_INVALID, "null pointer");
+  if (n_thresholds < 2 || n_q < 0) return ob::fail(OB_E_INVALID, "ob_dr_quantiles needs at least two thresholds");
+  if (n_thresholds > OB_DR_MAX_T)
+    return ob::fail(OB_E_UNSUPPORTED, "distribution regression: at most %d thresholds, got %d", OB_DR_MAX_T, n_thresholds);
+  for (int32_t t = 0; t < n_thresholds; ++t) {
+    if (!std::isfinite(f[t]) || !std::isfinite(thresholds[t]) || (t > 0 && !(thresholds[t] > thresholds[t - 1])))
+      return ob::fail(OB_E_INVALID, "ob_dr_quantiles: f must be finite and the thresholds finite and strictly increasing");
+  }
+  for (int32_t i = 0; i < n_q; ++i)
+    if (!(taus[i] > 0.0 && taus[i] < 1.0)) return ob::fail(OB_E_INVALID, "ob_dr_quantiles: tau must lie in (0, 1)");
+  ob::dr_quantiles(f, thresholds, n_thresholds, taus, n_q, q, rearranged, edge);
+  return OB_OK;
+}
+
+int ob_dr_finish_rows(const double* point_row, int32_t n_thresholds, int32_t n_q, const double* rows, const uint8_t* ok,
+                      uint64_t n_reps, ob_results** out) {
+  if (!point_row || !out || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (n_thresholds < 2 || n_thresholds > OB_DR_MAX_T || n_q < 1 || n_q > OB_DR_MAX_Q)
+    return ob::fail(OB_E_INVALID, "ob_dr_finish_rows: bad shape (T = %d, n_q = %d)", n_thresholds, n_q);
+  return ob::dr_finish_rows(point_row, n_thresholds, n_q, rows, ok, n_reps, out);
+}
+
 int ob_prepared_row_len(const ob_prepared* p) { return p ? p->row_len : 0; }
 int ob_prepared_n_y(const ob_prepared* p) { return p ? p->n_y : 0; }
 uint64_t ob_prepared_seed(const ob_prepared* p) { return p ? p->seed : 0; }
@@ -908,6 +1016,7 @@ int ob_prepared_boot(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double
   if (p->cluster) return ob::cluster_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   if (p->binary) return ob::binary_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   if (p->reweight) return ob::reweight_hooks().boot_host(p, first_rep, n_reps, rows, ok);
+  if (p->dr) return ob::dr_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   return ob_boot_run(p->panel, p->seed, first_rep, n_reps, p->ref, rows, ok);
 }
 
@@ -916,6 +1025,7 @@ int ob_prepared_boot_sharded(ob_prepared* p, uint64_t first_rep, uint64_t n_reps
   if (p->cluster) return ob::fail(OB_E_UNSUPPORTED, "cluster bootstrap: sharded runs are outside its scope");
   if (p->binary) return ob::fail(OB_E_UNSUPPORTED, "binary decomposition: sharded runs are outside its scope");
   if (p->reweight) return ob::fail(OB_E_UNSUPPORTED, "reweighted decomposition: sharded runs are outside its scope");
+  if (p->dr) return ob::fail(OB_E_UNSUPPORTED, "distribution regression: sharded runs are outside its scope");
   // the RCCL all-gather moves only the columns finish() aggregates: two-fold, three-fold, total
   // gap, detailed [0, 6 + 2 Kd) and a Heckman row's selection terms after its 5K' tail
   const int kd = p->k + p->n_base, sel0 = 6 + 2 * kd + 5 * p->k;
@@ -941,6 +1051,8 @@ int ob_prepared_boot_device(ob_prepared* p, uint64_t first_rep, uint64_t n_reps,
     return ob::binary_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
   if (p->reweight)
     return ob::reweight_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
+  if (p->dr)
+    return ob::dr_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
   return ob_boot_run_device(p->panel, p->seed, first_rep, n_reps, p->ref, d_rows, d_ok, hip_stream);
 }
 
@@ -955,6 +1067,7 @@ void ob_prepared_destroy(ob_prepared* p) {
   if (p->cluster) ob::cluster_hooks().free_state(p->cluster);
   if (p->binary) ob::binary_hooks().free_state(p->binary);
   if (p->reweight) ob::reweight_hooks().free_state(p->reweight);
+  if (p->dr) ob::dr_hooks().free_state(p->dr);
   ob_panel_destroy(p->panel);
   delete p;
 }

@@ -8,6 +8,7 @@
 
 #include "ob_engine.hpp"
 #include "ob_frame.hpp"
+#include "ob_dr.hpp"
 #include "ob_jackknife.hpp"
 
 namespace ob {
@@ -75,6 +76,10 @@ struct ob_prepared {
   ob::BinaryState* binary = nullptr;
   // ob_builder_prepare_reweighted: the three-fit panel and workspace on the device; boots run through ob_reweight.hip
   ob::ReweightState* reweight = nullptr;
+  // ob_builder_prepare_dr: the panel, fits and workspace on the device (boots run through ob_dr.hip) and the
+  // thresholds, quantiles and point fits on the host
+  ob::DrState* dr = nullptr;
+  ob::DrInfo dr_info;
 };
 
 namespace ob {

@@ -245,6 +245,8 @@ static int prepared_jack_check(const ob_prepared* p) {
   if (p->binary) return fail(OB_E_UNSUPPORTED, "jackknife: binary decompositions (BCa included) are outside its scope");
   if (p->reweight)
     return fail(OB_E_UNSUPPORTED, "jackknife: reweighted decompositions (BCa included) are outside its scope");
+  if (p->dr)
+    return fail(OB_E_UNSUPPORTED, "jackknife: distribution-regression decompositions (BCa included) are outside its scope");
   const bool heck = !p->selection_names.empty();
   return jackknife_check_shape(heck ? p->k - 1 : p->k, p->n_a, p->n_b, p->n_base > 0 || !p->cfg.normalize.empty(),
                                p->n_y, heck, 0);

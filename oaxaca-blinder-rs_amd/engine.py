@@ -596,6 +596,100 @@ def reweight_last_timing() -> dict:
     return {f: getattr(t, f) for f, _ in N.ob_reweight_timing._fields_}
 
 
+def _dr_args(x, w, counts, betas):
+    """The arrays of the two distribution-regression pieces as the C ABI takes them."""
+    xf = np.asfortranarray(x, dtype=np.float64)
+    if xf.ndim != 2:
+        raise ValueError("x must be (n, k)")
+    n, k = xf.shape
+    b = np.ascontiguousarray(np.atleast_2d(betas), dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != k:
+        raise ValueError("betas must be (m, k)")
+    wv = None
+    if w is not None:
+        wv = np.ascontiguousarray(w, dtype=np.float64)
+        if wv.shape != (n,):
+            raise ValueError("w must have one entry per row of x")
+    c8 = None
+    if counts is not None:
+        c = np.ascontiguousarray(counts)
+        if c.shape != (n,) or (c < 0).any() or (c > 255).any():
+            raise ValueError("counts must be n integers in [0, 255]")
+        c8 = c.astype(np.uint8)
+    return xf, wv, c8, b, n, k
+
+
+def dr_logit_pass(x, y, thresholds, betas, w=None, counts=None, device: int | None = None):
+    """One Newton pass of the distribution regression's threshold logits alone (``ob_dr_logit_pass``). ``x``: (n, k)
+    with the intercept (all ones) as column 0, ``k <= 32``; ``y``: n outcomes; ``thresholds``: T <= 64 values;
+    ``betas``: (T, k), one coefficient vector per threshold; ``w``: n weights (``None``: 1); ``counts``: n resample
+    counts below 256 (``None``: every row once). Returns ``(info, grad)``: (T, k, k) sums c w p (1 - p) x x' and
+    (T, k) sums c w (1[y <= c_t] - p) x, p the sigmoid of x'beta_t clamped to [1e-10, 1 - 1e-10]."""
+    xf, wv, c8, b, n, k = _dr_args(x, w, counts, betas)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if yv.shape != (n,) or thr.ndim != 1 or len(thr) != len(b):
+        raise ValueError("y must have one entry per row of x and betas one row per threshold")
+    info, grad = np.empty((len(b), k, k)), np.empty((len(b), k))
+    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
+    with_context(lambda ctx: N.lib().ob_dr_logit_pass(ctx, _dp(xf), max(n, 1), _dp(yv), _dp(wv), cp, n, k, _dp(thr),
+                                                     len(thr), _dp(b), _dp(info), _dp(grad)), device)
+    return info, grad
+
+
+def dr_cdf(x, betas, w=None, counts=None, device: int | None = None):
+    """The distribution pass alone (``ob_dr_cdf``): ``(sums, wsum)`` with sums (m) = sum c w L(x'beta_v) for the
+    (m, k) ``betas``, m <= 128, L the clamped sigmoid, and wsum = sum c w. Arguments as ``dr_logit_pass``."""
+    xf, wv, c8, b, n, k = _dr_args(x, w, counts, betas)
+    sums, wsum = np.empty(len(b)), np.empty(1)
+    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
+    with_context(lambda ctx: N.lib().ob_dr_cdf(ctx, _dp(xf), max(n, 1), _dp(wv), cp, n, k, _dp(b), len(b), _dp(sums),
+                                              _dp(wsum)), device)
+    return sums, float(wsum[0])
+
+
+def dr_thresholds(y, n_thresholds: int = 50, lo: float = 0.05, hi: float = 0.95) -> np.ndarray:
+    """ob_dr_thresholds (host only): the sample quantiles of ``y`` at ``n_thresholds`` evenly spaced levels of
+    [lo, hi], exact duplicates removed."""
+    yv = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    out = np.empty(max(int(n_thresholds), 1))
+    kept = C.c_int32()
+    N.check(N.lib().ob_dr_thresholds(_dp(yv), len(yv), int(n_thresholds), float(lo), float(hi), _dp(out), C.byref(kept)))
+    return out[:kept.value].copy()
+
+
+def dr_quantiles(f, thresholds, taus):
+    """ob_dr_quantiles (host only): rearranges the distribution ``f`` on the threshold grid and inverts it at
+    ``taus`` -> (quantiles, rearranged f, edge codes: 0, 1 below the grid, 2 above it)."""
+    fv = np.ascontiguousarray(f, dtype=np.float64)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    tv = np.ascontiguousarray(np.atleast_1d(taus), dtype=np.float64)
+    if fv.ndim != 1 or fv.shape != thr.shape or tv.ndim != 1:
+        raise ValueError("f and thresholds must be 1-D of one length and taus 1-D")
+    q, re, edge = np.empty(len(tv)), np.empty(len(fv)), np.zeros(len(tv), dtype=np.uint8)
+    N.check(N.lib().ob_dr_quantiles(_dp(fv), _dp(thr), len(fv), _dp(tv), len(tv), _dp(q), _dp(re),
+                                    edge.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return q, re, edge
+
+
+def dr_check_shape(k: int, n_a: int, n_b: int, n_thresholds: int, n_quantiles: int) -> None:
+    """ob_dr_check_shape: raises OaxacaError where a distribution-regression decomposition would (host only)."""
+    N.check(N.lib().ob_dr_check_shape(int(k), int(n_a), int(n_b), int(n_thresholds), int(n_quantiles)))
+
+
+def dr_row_len(n_thresholds: int, n_quantiles: int) -> int:
+    """ob_dr_row_len: 6 n_q + 7 T + 1 doubles per replicate of a distribution-regression decomposition."""
+    return int(N.lib().ob_dr_row_len(int(n_thresholds), int(n_quantiles)))
+
+
+def dr_last_timing() -> dict:
+    """ob_dr_last_timing: Newton passes and HIP-event ms (logit passes, distribution pass, rows) of this thread's
+    last distribution-regression boot."""
+    t = N.ob_dr_timing()
+    N.check(N.lib().ob_dr_last_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in N.ob_dr_timing._fields_}
+
+
 def knn(queries, controls, k: int, device: int | None = None):
     """The min(k, n_c) nearest controls of each query (``ob_knn``): squared Euclidean distance summed
     in covariate order without FMA, ties by control position. ``queries``: (n_q, d), ``controls``:
