@@ -1048,7 +1048,8 @@ int ob_results_jackknife(const ob_results* r, int32_t table, int32_t i, double* 
  * Limits, each before any device work: C < 2 OB_E_INSUFFICIENT; C >= 2^24, or Q above 8 GiB
  * (C * 2 * (e_pad + 1) doubles): OB_E_UNSUPPORTED; Heckman selection, ob_prepared_boot_sharded,
  * ob_prepared_jackknife, ob_prepared_finish_bca on a clustered handle: OB_E_UNSUPPORTED (delete-one-row is
- * the wrong jackknife under clustering). Machado-Mata has no clustered entry point. */
+ * the wrong jackknife under clustering; ob_prepared_cluster_jackknife, ob_prepared_finish_cluster_bca and
+ * ob_builder_run_clustered_bca below are the delete-one-cluster forms). Machado-Mata has no clustered entry point. */
 typedef struct {
   const char* column; /* the cluster id column */
   int32_t stratified; /* 0: joint, 1: stratified */
@@ -1099,6 +1100,70 @@ int ob_builder_decompose_quantiles_clustered(ob_ctx* ctx, const ob_column* cols,
 int64_t ob_results_n_clusters(const ob_results* r);
 /* OB_E_INVALID on a handle that is not clustered. */
 int ob_prepared_cluster_info(const ob_prepared* prep, ob_cluster_info* out);
+
+/* ---- Delete-one-cluster jackknife and BCa intervals for clustered runs (the counterpart of
+ * Stata's `jackknife, cluster()`) -----------------------------------------------------------------------
+ * theta_(c), every component without cluster c, in closed form from what a clustered handle holds: with Q^xx_c,
+ * b_c = sum w x y, S_c = sum w x, W_c = sum w of cluster c in group g, M = G_g - Q^xx_c and r_c = b_c - Q^xx_c beta_g,
+ *     beta_g(c) - beta_g = -M^-1 r_c (one Cholesky of M per cluster and group),
+ *     xbar_g(c) - xbar_g = (W_c xbar_g - S_c) / (W_g - W_c), the mean outcome likewise,
+ * the same downdate of the pooled Gram for Pooled / Neumark and the Cotton weights from W_g - W_c (row counts
+ * without weights). A group the cluster has no row in stays at the point estimate exactly. In joint mode the
+ * strata are all C clusters (stratum 0), in stratified mode A's clusters and B's.
+ * A cluster is DROPPED, and counted per stratum, when n_g - rows_c,g <= K for a group it touches (the
+ * reference's InsufficientData), when W_g - W_c <= 0, or when a Cholesky pivot of M (for Pooled also of the
+ * pooled downdate) is at most 2^-40 times the same pivot of the point estimate's factor. Fewer than 2 kept
+ * clusters in a stratum that has any is OB_E_INSUFFICIENT.
+ * Sums are f64 in a fixed order that depends on C alone (no floating atomics): a repeated call returns the same
+ * bytes. It draws nothing from OBRC-1, so jack_se is an independent check of the cluster bootstrap's std_err.
+ * Limits, each OB_E_UNSUPPORTED before any device work: K > OB_CLUSTER_JACK_MAX_K, normalized categoricals,
+ * Heckman panels, more than one outcome. The delete-one-row entry points (ob_prepared_jackknife,
+ * ob_prepared_finish_bca, ob_builder_run_bca) keep refusing a clustered handle; these are their clustered forms. */
+#define OB_CLUSTER_JACK_MAX_K 32 /* design columns, the intercept included */
+/* The limits above on their own (host only): k design columns with the intercept, C clusters (C < 2 is
+   OB_E_INSUFFICIENT). Every entry point below makes exactly these checks first. */
+int ob_cluster_jackknife_check_shape(int32_t k, int64_t n_clusters, int32_t n_norm, int32_t n_y, int32_t heckman,
+                                     int32_t want_rows);
+/* The production path over a clustered handle: the power sums of d = theta_(c) - theta_hat per stratum and
+   ob_jackknife_finish's statistics (n_used / n_dropped / sums are per stratum; joint mode leaves stratum 1
+   empty). The result is kept in the handle. OB_E_INVALID on a handle that is not clustered. */
+int ob_prepared_cluster_jackknife(ob_prepared* prep, ob_jackknife_out* out);
+/* For tests and inspection: theta[C x ob_prepared_row_len(prep)] row-major, cluster c's replicate-shaped row
+   from the solve kernel itself on T_g - Q[c][g] (T_g = sum_c Q[c][g] in ob_cluster_apply's order; a group the
+   cluster has no row in takes the point estimate's Gram): the first 6 + 2 K columns are the components, then
+   beta_A, beta_B, xbar_A, xbar_B, beta*. kept[C]; a dropped cluster's row is NaN. n_dropped[2] (per stratum)
+   may be NULL. deviations (may be NULL): [C x (6 + 2 K)], every cluster's d = theta_(c) - theta_hat exactly as the
+   production path forms and sums it (NaN where that path drops the cluster). The same clusters are dropped as
+   on the production path; no statistics are formed here, so a stratum with fewer than 2 kept clusters is not an
+   error of this call. Rows go back to the host batch by batch: no more than 1 GiB of device memory beside Q. */
+int ob_prepared_cluster_jackknife_rows(ob_prepared* prep, double* theta, uint8_t* kept, int64_t* n_dropped,
+                                       double* deviations);
+/* The same two passes on arrays. q: [C][2][e_pad], cluster c's Q of group A then of group B as ob_cluster_gram
+   returns them per group (e_pad = 16 ceil((p + 2)(p + 3) / 32)); rows: [C][2] their row counts; n_clusters_a: A's
+   clusters, which come first when stratified != 0. ob_cluster_jackknife needs no panel: gram is the point
+   estimate's two extended Grams [2][e_pad] (the sum of q over the clusters serves), tail its beta_A, beta_B,
+   xbar_A, xbar_B, beta* (5 (p + 1) values; for Pooled / Neumark beta* is recomputed from gram), n_a / n_b the
+   groups' rows, weighted != 0 when the Grams carry weights; out->point is theta_hat recomputed from these.
+   ob_cluster_jackknife_rows takes the point estimate and the solve kernel from a resident panel. Both make
+   ob_cluster_jackknife_check_shape's checks and ob_cluster_check_shape's first. */
+int ob_cluster_jackknife(ob_ctx* ctx, const double* q, const uint32_t* rows, int64_t n_clusters, int64_t n_clusters_a,
+                         int32_t stratified, int32_t p, int32_t weighted, int64_t n_a, int64_t n_b, const double* gram,
+                         const double* tail, int ref_mode, ob_jackknife_out* out);
+int ob_cluster_jackknife_rows(ob_panel* panel, const double* q, const uint32_t* rows, int64_t n_clusters,
+                              int64_t n_clusters_a, int32_t stratified, int ref_mode, double* theta, uint8_t* kept,
+                              int64_t* n_dropped, double* deviations);
+/* ob_prepared_finish with ci_lower / ci_upper of every component replaced by the BCa endpoints at `level`
+   through ob_bca_stats with the delete-one-cluster accelerations (estimate, std_err, t_stat and p_value are
+   untouched). Runs ob_prepared_cluster_jackknife if the handle has none yet. */
+int ob_prepared_finish_cluster_bca(ob_prepared* prep, const double* rows, const uint8_t* ok, uint64_t n_reps,
+                                   double level, ob_results** out);
+/* ob_builder_run_clustered with BCa intervals: prepare + every replicate + the pass + the finish above.
+   ob_results_jackknife serves its result. */
+int ob_builder_run_clustered_bca(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                 const ob_builder_config* cfg, const ob_cluster_config* ccfg, double level,
+                                 ob_results** out);
+/* The calling thread's last cluster jackknife pass: HIP-event ms of the kernel with its ordered sums. */
+int ob_cluster_jackknife_last_timing(double* pass_ms);
 
 /* ---- RIF decompositions of the variance, the Gini and quantile ranges -------------------
  * The recentred influence function of a distributional statistic as the outcome of the mean decomposition

@@ -13,7 +13,7 @@ from .api import (Adjustment, AkmBuilder, AkmResult, BinaryDecompositionResults,
                   ReferenceCoefficients, ReweightedDecompositionResults, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
                   parse_formula, run_dfl, run_dfl_from_csv)
 from .engine import (binary_check_shape, binary_last_timing, binary_means, binary_row_len, cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
-                     cluster_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
+                     cluster_last_timing, cluster_jackknife, cluster_jackknife_rows, cluster_jackknife_check_shape, cluster_jackknife_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
                      knn, logit, match_logistic, normal_inverse_cdf, probit, remedy_allocate, remedy_apply_adjustments, remedy_defend_rows,
                      remedy_resolve_overrides, remedy_score, remedy_solve, rif, parse_rif_statistic, parse_weighted_rif_statistic,
@@ -39,6 +39,7 @@ __all__ = [
     "JackknifeResult", "jackknife_rows", "jackknife_finish", "jackknife_check_shape", "jackknife_last_timing", "bca_stats",
     "aggregate_bca",
     "cluster_index", "cluster_gram", "cluster_counts", "cluster_apply", "cluster_check_shape", "cluster_last_timing",
+    "cluster_jackknife", "cluster_jackknife_rows", "cluster_jackknife_check_shape", "cluster_jackknife_last_timing",
     "rif_statistic", "rif_last_timing", "rif_scan_block", "parse_rif_statistic",
     "rif_statistic_weighted", "parse_weighted_rif_statistic",
     "BinaryDecompositionResults", "binary_means", "binary_check_shape", "binary_row_len", "binary_last_timing",

@@ -63,6 +63,9 @@ EXPORTED = (
     "ob_cluster_check_shape", "ob_cluster_index", "ob_cluster_gram", "ob_cluster_counts", "ob_cluster_apply",
     "ob_cluster_last_timing", "ob_builder_prepare_clustered", "ob_builder_run_clustered",
     "ob_builder_decompose_quantiles_clustered", "ob_prepared_cluster_info", "ob_results_n_clusters",
+    "ob_cluster_jackknife", "ob_cluster_jackknife_rows",
+    "ob_cluster_jackknife_check_shape", "ob_prepared_cluster_jackknife", "ob_prepared_cluster_jackknife_rows",
+    "ob_prepared_finish_cluster_bca", "ob_builder_run_clustered_bca", "ob_cluster_jackknife_last_timing",
     "ob_rif_stat", "ob_rif_scan_block", "ob_rif_last_timing", "ob_builder_decompose_statistics",
     "ob_builder_decompose_statistics_clustered",
     "ob_binary_row_len", "ob_binary_check_shape", "ob_binary_means", "ob_binary_last_timing",
@@ -84,6 +87,7 @@ OB_VIF_MAX_K = 120
 OB_REMEDY_MAX_K = 120  # design columns, the intercept included
 OB_REMEDY_MAX_STEPS = 127
 OB_JACK_MAX_K = 119  # design columns, the intercept included
+OB_CLUSTER_JACK_MAX_K = 32  # design columns, the intercept included
 OB_REMEDY_TARGETS = {"reference": 0, "pooled": 1}
 OB_REMEDY_STRATEGIES = {"greedy": 0, "equitable": 1}
 OB_REMEDY_RANGE_TARGETS = {"midpoint": 0, "lower": 1, "upper": 2}
@@ -489,6 +493,18 @@ _SIGS = {
                                                            _D, C.c_int32, C.POINTER(_P)]),
     "ob_prepared_cluster_info": (C.c_int, [_P, C.POINTER(ob_cluster_info)]),
     "ob_results_n_clusters": (C.c_int64, [_P]),
+    "ob_cluster_jackknife_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ob_prepared_cluster_jackknife": (C.c_int, [_P, C.POINTER(ob_jackknife_out)]),
+    "ob_prepared_cluster_jackknife_rows": (C.c_int, [_P, _D, _U8, C.POINTER(C.c_int64), _D]),
+    "ob_cluster_jackknife": (C.c_int, [_P, _D, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int64, C.c_int64, _D, _D, C.c_int, C.POINTER(ob_jackknife_out)]),
+    "ob_cluster_jackknife_rows": (C.c_int, [_P, _D, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.c_int32, C.c_int,
+                                            _D, _U8, C.POINTER(C.c_int64), _D]),
+    "ob_prepared_finish_cluster_bca": (C.c_int, [_P, _D, _U8, C.c_uint64, C.c_double, C.POINTER(_P)]),
+    "ob_builder_run_clustered_bca": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                               C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config), C.c_double,
+                                               C.POINTER(_P)]),
+    "ob_cluster_jackknife_last_timing": (C.c_int, [_D]),
     "ob_rif_stat": (C.c_int, [_P, _D, C.c_int64, C.POINTER(ob_rif_spec), _D, _D]),
     "ob_rif_scan_block": (C.c_int32, []),
     "ob_rif_last_timing": (C.c_int, [C.POINTER(ob_rif_timing)]),

@@ -1023,6 +1023,36 @@ class OaxacaBuilder:
         finally:
             pr.close()
 
+    def _require_clustered(self, what: str):
+        if self._cluster is None:
+            raise N.OaxacaError(N.OB_E_INVALID, f"{what}: this builder is not clustered (call .cluster(column) first)")
+
+    def run_cluster_bca(self, confidence_level: float = 0.95) -> OaxacaResults:
+        """The clustered ``run()`` with every component's interval replaced by the BCa one: z0 from the cluster
+        bootstrap's replicates, the acceleration from one delete-one-cluster pass. Estimates,
+        standard errors and p-values are those of ``run()`` with the same seed; ``.jackknife`` holds, per
+        (table, name), the acceleration, the cluster jackknife standard error and bias, z0 and the BCa flag."""
+        self._require_clustered("run_cluster_bca")
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        cc = self._cluster_config()
+        h = C.c_void_p()
+        N.check(lib.ob_builder_run_clustered_bca(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(cc),
+                                                 float(confidence_level), C.byref(h)))
+        return _results_from_c(h, jackknife=True)
+
+    def cluster_jackknife(self) -> "JackknifeResult":
+        """The delete-one-cluster pass alone (Stata's ``jackknife, cluster()``): acceleration, cluster-robust
+        jackknife standard error and bias of every component. ``n_used`` / ``n_dropped`` count clusters per
+        stratum: all clusters as stratum 0 in joint mode, A's and B's clusters in stratified mode."""
+        self._require_clustered("cluster_jackknife")
+        pr = self.prepare()
+        try:
+            return pr.cluster_jackknife()
+        finally:
+            pr.close()
+
     def decompose_quantile(self, quantile: float) -> OaxacaResults:
         """builder.rs:711-757: RIF-regression decomposition at ``quantile``."""
         lib = N.lib()
@@ -1466,6 +1496,44 @@ class PreparedRun:
         N.check(N.lib().ob_prepared_finish_bca(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
                                                ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok),
                                                float(confidence_level), C.byref(h)))
+        return _results_from_c(h, jackknife=True)
+
+    def cluster_jackknife(self) -> "JackknifeResult":
+        """ob_prepared_cluster_jackknife: the delete-one-cluster pass over the resident per-cluster Grams (kept in
+        the handle); ``n_used`` / ``n_dropped`` are clusters per stratum."""
+        panel = N.lib().ob_prepared_panel(self._h)
+        o, bufs = _jackknife_out(N.lib().ob_panel_k(panel))
+        N.check(N.lib().ob_prepared_cluster_jackknife(self._h, C.byref(o)))
+        return _jackknife_result(o, bufs, None)
+
+    def cluster_jackknife_rows(self, full: bool = False, deviations: bool = False):
+        """ob_prepared_cluster_jackknife_rows -> (theta (C, 6 + 2K), kept (C,), n_dropped per stratum): theta_(c)
+        from the solve kernel itself, NaN for a dropped cluster. ``full=True`` keeps the whole replicate-shaped
+        rows (C, row_len): the components, then beta_A, beta_B, xbar_A, xbar_B, beta*. ``deviations=True`` appends
+        d (C, 6 + 2K): every cluster's theta_(c) - theta_hat exactly as the production path forms and sums it."""
+        if self.cluster_info is None:
+            raise N.OaxacaError(N.OB_E_INVALID, "this prepared run is not clustered")
+        nc = self.cluster_info["n_clusters"]
+        k = N.lib().ob_panel_k(N.lib().ob_prepared_panel(self._h))
+        theta = np.empty((nc, self.row_len), dtype=np.float64)
+        kept = np.zeros(nc, dtype=np.uint8)
+        dev = np.empty((nc, 6 + 2 * k), dtype=np.float64) if deviations else None
+        nd = (C.c_int64 * 2)()
+        dp = C.POINTER(C.c_double)
+        N.check(N.lib().ob_prepared_cluster_jackknife_rows(self._h, theta.ctypes.data_as(dp),
+                                                           kept.ctypes.data_as(C.POINTER(C.c_uint8)), nd,
+                                                           dev.ctypes.data_as(dp) if deviations else None))
+        out = ((theta if full else theta[:, :6 + 2 * k].copy()), kept.astype(bool), (int(nd[0]), int(nd[1])))
+        return out + (dev,) if deviations else out
+
+    def finish_cluster_bca(self, rows: np.ndarray, ok: np.ndarray, confidence_level: float = 0.95) -> OaxacaResults:
+        """``finish`` with BCa intervals from the delete-one-cluster accelerations (ob_prepared_finish_cluster_bca)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        h = C.c_void_p()
+        N.check(N.lib().ob_prepared_finish_cluster_bca(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok),
+                                                       float(confidence_level), C.byref(h)))
         return _results_from_c(h, jackknife=True)
 
     def close(self):

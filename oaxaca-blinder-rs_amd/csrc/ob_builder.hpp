@@ -89,6 +89,10 @@ int config_from(const ob_builder_config* c, Config& out);
 int prepare(ob_ctx* ctx, const Frame& input, const Config& c, ob_prepared** out);
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block)
 int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out);
+// ob_jackknife.cpp: finish(), then every component's interval through bca_stats with the accelerations of
+// pr->jack_stats ([C][3], filled by a jackknife pass over the handle)
+int finish_bca(const ob_prepared* pr, const double* rows, const uint8_t* ok, uint64_t n_reps, double level,
+               ob_results** out);
 // ob_builder_data_matrices, with the groups' sample weights kept where want_w (matrices_weights: NULL without
 // a weights column; the weight column's dtype and sign are checked as prepare() checks them)
 int data_matrices(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, bool want_w,

@@ -104,9 +104,144 @@ int cluster_index(const Col& ids, const int32_t* group, int64_t n_rows, bool str
   return OB_OK;
 }
 
+// ---- the delete-one-cluster jackknife: the checks, the handle's pass and its statistics -------
+static thread_local double g_cluster_jack_ms = 0.0;
+void cluster_jack_set_timing(double ms) { g_cluster_jack_ms = ms; }
+
+int cluster_jack_check_shape(int k, int64_t n_clusters, int n_norm, int n_y, int heckman, int want_rows) {
+  if (k < 1 || n_clusters < 0 || n_norm < 0 || n_y < 0) return fail(OB_E_INVALID, "bad cluster jackknife dimensions");
+  if (heckman) return fail(OB_E_UNSUPPORTED, "cluster jackknife: Heckman selection panels are outside its scope");
+  if (n_norm > 0) return fail(OB_E_UNSUPPORTED, "cluster jackknife: normalized categoricals are outside its scope");
+  if (n_y > 1) return fail(OB_E_UNSUPPORTED, "cluster jackknife: one outcome at a time");
+  if (k > kClusterJackMaxK)
+    return fail(OB_E_UNSUPPORTED, "cluster jackknife: %d design columns exceed OB_CLUSTER_JACK_MAX_K = %d", k,
+                kClusterJackMaxK);
+  if (n_clusters >= kClusterMax)
+    return fail(OB_E_UNSUPPORTED, "cluster jackknife: %lld clusters; the limit is 2^24 - 1", (long long)n_clusters);
+  (void)want_rows;  // the rows output goes back batch by batch into the caller's C x row_len array: no further limit
+  if (n_clusters < 2)
+    return fail(OB_E_INSUFFICIENT, "%scluster jackknife: %lld cluster(s); deleting one needs at least 2",
+                error_prefix(OB_E_INSUFFICIENT), (long long)n_clusters);
+  return OB_OK;
+}
+
+// The checks of the prepared entry points, before any device work.
+static int prepared_cluster_jack_check(const ob_prepared* p, int want_rows) {
+  if (!p) return fail(OB_E_INVALID, "null pointer");
+  if (!p->cluster) return fail(OB_E_INVALID, "this prepared run is not clustered");
+  // no clustered handle of these kinds exists today; BCa for them stays out of scope when one does
+  if (p->binary || p->reweight || p->dr)
+    return fail(OB_E_UNSUPPORTED, "cluster jackknife: binary, reweighted and distribution-regression decompositions "
+                                  "(BCa included) are outside its scope");
+  if (!cluster_hooks().jack || !cluster_hooks().info) return fail(OB_E_UNSUPPORTED, "this build carries no cluster jackknife");
+  ob_cluster_info ci;
+  cluster_hooks().info(p->cluster, &ci);
+  const bool heck = !p->selection_names.empty();
+  return cluster_jack_check_shape(heck ? p->k - 1 : p->k, ci.n_clusters, p->n_base > 0 || !p->cfg.normalize.empty(), p->n_y,
+                                  heck, want_rows);
+}
+
+// Fewer than 2 kept clusters in a stratum that has any leaves no jackknife variance there.
+int cluster_jack_enough(const JackResult& r) {
+  for (int s = 0; s < 2; ++s)
+    if (r.kept[s] + r.dropped[s] > 0 && r.kept[s] < 2)
+      return fail(OB_E_INSUFFICIENT, "%scluster jackknife: %lld of %lld clusters of stratum %d have a fit without them; 2 are needed",
+                  error_prefix(OB_E_INSUFFICIENT), (long long)r.kept[s], (long long)(r.kept[s] + r.dropped[s]), s);
+  return OB_OK;
+}
+
+static int prepared_cluster_jack_run(ob_prepared* p) {
+  if (p->has_jack) return OB_OK;
+  JackResult r;
+  OB_TRY(cluster_hooks().jack(p, r, nullptr, nullptr, nullptr));
+  g_cluster_jack_ms = r.ms;
+  OB_TRY(cluster_jack_enough(r));
+  p->jack_stats.assign((size_t)3 * r.c, 0.0);
+  jackknife_finish(r.sums.data(), r.kept, r.c, p->jack_stats.data());  // a stratum is a group to it
+  p->jack = r;
+  p->has_jack = true;
+  return OB_OK;
+}
+
 }  // namespace ob
 
 extern "C" {
+
+int ob_cluster_jackknife_check_shape(int32_t k, int64_t n_clusters, int32_t n_norm, int32_t n_y, int32_t heckman,
+                                     int32_t want_rows) {
+  return ob::cluster_jack_check_shape(k, n_clusters, n_norm, n_y, heckman, want_rows);
+}
+
+int ob_prepared_cluster_jackknife(ob_prepared* p, ob_jackknife_out* out) {
+  if (!out) return ob::fail(OB_E_INVALID, "null pointer");
+  OB_TRY(ob::prepared_cluster_jack_check(p, 0));
+  const int c = 6 + 2 * p->k;
+  if (out->capacity < c || !out->point || !out->sums || !out->stats)
+    return ob::fail(OB_E_INVALID, "cluster jackknife: the output arrays must hold %d components", c);
+  OB_TRY(ob::prepared_cluster_jack_run(p));
+  out->n_components = c;
+  for (int s = 0; s < 2; ++s) {
+    out->n_used[s] = p->jack.kept[s];
+    out->n_dropped[s] = p->jack.dropped[s];
+  }
+  std::copy(p->jack.point.begin(), p->jack.point.end(), out->point);
+  std::copy(p->jack.sums.begin(), p->jack.sums.end(), out->sums);
+  std::copy(p->jack_stats.begin(), p->jack_stats.end(), out->stats);
+  return OB_OK;
+}
+
+int ob_prepared_cluster_jackknife_rows(ob_prepared* p, double* theta, uint8_t* kept, int64_t* n_dropped,
+                                       double* deviations) {
+  OB_TRY(ob::prepared_cluster_jack_check(p, 1));
+  if (!theta || !kept) return ob::fail(OB_E_INVALID, "null pointer");
+  ob::JackResult r;
+  OB_TRY(ob::cluster_hooks().jack(p, r, theta, kept, deviations));
+  ob::g_cluster_jack_ms = r.ms;
+  if (n_dropped) {
+    n_dropped[0] = r.dropped[0];
+    n_dropped[1] = r.dropped[1];
+  }
+  return OB_OK;  // no statistics are formed here: a stratum with fewer than 2 kept clusters is there to be inspected
+}
+
+int ob_prepared_finish_cluster_bca(ob_prepared* p, const double* rows, const uint8_t* ok, uint64_t n_reps, double level,
+                                   ob_results** out) {
+  if (!p || !out || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (!(level > 0.0 && level < 1.0)) return ob::fail(OB_E_INVALID, "the confidence level must lie in (0, 1)");
+  OB_TRY(ob::prepared_cluster_jack_check(p, 0));
+  OB_TRY(ob::prepared_cluster_jack_run(p));
+  return ob::finish_bca(p, rows, ok, n_reps, level, out);
+}
+
+int ob_builder_run_clustered_bca(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                 const ob_builder_config* cfg, const ob_cluster_config* ccfg, double level,
+                                 ob_results** out) {
+  if (!ctx || !out) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (!(level > 0.0 && level < 1.0)) return ob::fail(OB_E_INVALID, "the confidence level must lie in (0, 1)");
+  ob::Config c;
+  OB_TRY(ob::config_from(cfg, c));
+  if (c.has_selection) return ob::fail(OB_E_UNSUPPORTED, "cluster jackknife: Heckman selection panels are outside its scope");
+  if (!c.normalize.empty())
+    return ob::fail(OB_E_UNSUPPORTED, "cluster jackknife: normalized categoricals are outside its scope");
+  ob_prepared* pr = nullptr;
+  OB_TRY(ob_builder_prepare_clustered(ctx, cols, n_cols, n_rows, cfg, ccfg, &pr));
+  int rc = ob::prepared_cluster_jack_check(pr, 0);
+  const uint64_t reps = pr->cfg.reps;
+  std::vector<double> rows((size_t)reps * pr->row_len);
+  std::vector<uint8_t> ok(reps, 0);
+  if (rc == OB_OK && reps > 0) rc = ob_prepared_boot(pr, 0, reps, rows.data(), ok.data());
+  if (rc == OB_OK) rc = ob::prepared_cluster_jack_run(pr);
+  if (rc == OB_OK) rc = ob::finish_bca(pr, rows.data(), ok.data(), reps, level, out);
+  ob_prepared_destroy(pr);
+  return rc;
+}
+
+int ob_cluster_jackknife_last_timing(double* pass_ms) {
+  if (pass_ms) *pass_ms = ob::g_cluster_jack_ms;
+  return OB_OK;
+}
 
 int ob_cluster_check_shape(int64_t n_clusters, int32_t k1) { return ob::cluster_check_shape(n_clusters, k1); }
 

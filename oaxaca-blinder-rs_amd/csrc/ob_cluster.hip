@@ -343,25 +343,12 @@ int cluster_attach(ob_prepared* pr, const ClusterIndex& idx) {
   return OB_OK;
 }
 
-static int cluster_boot(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
-                        hipStream_t stream, bool timed) {
+// Q and the clusters' row counts: one pass over the panel, the first time a clustered handle needs them.
+static int cluster_ensure_q(ob_prepared* pr, hipStream_t s, bool timed, ob_cluster_timing& tm) {
   ob_panel* p = pr->panel;
   ClusterState* cs = pr->cluster;
-  if (n_reps == 0) return OB_OK;
-  if (first_rep + n_reps > 0x100000000ull)
-    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 (OBRC-1 counter word)");
-  OB_HIP(hipSetDevice(p->ctx->device));
-  hipStream_t s = stream ? stream : p->ctx->stream;
-  OB_TRY(engine_order(p, s));
-  if (!p->timing_pending) std::memset(&p->timing, 0, sizeof(p->timing));
-  if (timed && !cs->ev_ready) {
-    OB_HIP(cs->ev.create());
-    cs->ev_ready = true;
-  }
-  const uint32_t nc = cs->n_clusters, runs = apply_runs(nc);
-  const int width = 2 * p->e_pad;
-  ob_cluster_timing tm = {};
-  if (!cs->q_ready) {  // one pass over the panel: Q and the clusters' row counts
+  const uint32_t nc = cs->n_clusters;
+  if (!cs->q_ready) {
     CgArgs ga{};
     for (int g = 0; g < 2; ++g) {
       ga.cols[g] = p->d_cols[g];
@@ -390,6 +377,28 @@ static int cluster_boot(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, do
     }
     cs->q_ready = true;
   }
+  return OB_OK;
+}
+
+static int cluster_boot(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
+                        hipStream_t stream, bool timed) {
+  ob_panel* p = pr->panel;
+  ClusterState* cs = pr->cluster;
+  if (n_reps == 0) return OB_OK;
+  if (first_rep + n_reps > 0x100000000ull)
+    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 (OBRC-1 counter word)");
+  OB_HIP(hipSetDevice(p->ctx->device));
+  hipStream_t s = stream ? stream : p->ctx->stream;
+  OB_TRY(engine_order(p, s));
+  if (!p->timing_pending) std::memset(&p->timing, 0, sizeof(p->timing));
+  if (timed && !cs->ev_ready) {
+    OB_HIP(cs->ev.create());
+    cs->ev_ready = true;
+  }
+  const uint32_t nc = cs->n_clusters, runs = apply_runs(nc);
+  const int width = 2 * p->e_pad;
+  ob_cluster_timing tm = {};
+  OB_TRY(cluster_ensure_q(pr, s, timed, tm));
   // batch: counts, partial sums and Grams within kClBatchBudget, so a run of any length needs bounded memory
   const uint64_t per_rep = (uint64_t)nc * 4 + (uint64_t)width * 8 * (runs > 1 ? runs + 1 : 1) + 8;
   const uint64_t batch = std::min<uint64_t>(std::min(n_reps, kClBatchMax),
@@ -457,6 +466,38 @@ int cluster_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, doub
   OB_TRY(engine_collect(p));
   OB_HIP(hipMemcpy(rows, cs->rows_tmp.p, sizeof(double) * nrow * p->row_len, hipMemcpyDeviceToHost));
   OB_HIP(hipMemcpy(ok, cs->ok_tmp.p, nrow, hipMemcpyDeviceToHost));
+  return OB_OK;
+}
+
+// ---- what the delete-one-cluster jackknife reads of a clustered handle (ob_cluster_jack.hip) -------------------
+int cluster_view(ob_prepared* pr, hipStream_t s, ClusterView& out) {
+  ClusterState* cs = pr->cluster;
+  ob_cluster_timing tm = {};
+  OB_TRY(cluster_ensure_q(pr, s, false, tm));
+  out.q = cs->q.d();
+  out.qrows = cs->qrows.as<uint32_t>();
+  out.n_clusters = cs->n_clusters;
+  out.n_clusters_a = (uint32_t)cs->info.n_clusters_a;
+  out.stratified = cs->info.stratified;
+  return OB_OK;
+}
+
+int cluster_sum_q(const double* d_q, uint32_t nc, int width, double* d_total, hipStream_t s) {
+  const std::vector<uint32_t> ones(nc, 1u);  // every cluster once: ob_cluster_apply's sum, one replicate wide
+  DevBuf counts, partial;
+  OB_HIP(counts.alloc(sizeof(uint32_t) * nc));
+  OB_HIP(hipMemcpyAsync(counts.p, ones.data(), sizeof(uint32_t) * nc, hipMemcpyHostToDevice, s));
+  if (apply_runs(nc) > 1) OB_HIP(partial.alloc(sizeof(double) * width * apply_runs(nc)));
+  OB_TRY(launch_apply(counts.as<uint32_t>(), d_q, 1, nc, width, partial.d(), d_total, s));
+  OB_HIP(hipStreamSynchronize(s));  // `ones` and the buffers are in use until here
+  return OB_OK;
+}
+
+int cluster_guard(const ob_panel* p, const uint32_t* d_rep_rows, uint32_t ns, uint64_t n_reps, uint64_t s0, double* d_rows,
+                  uint8_t* d_ok, hipStream_t s) {
+  hipLaunchKernelGGL(ob_cluster_guard_kernel, dim3((ns * (uint32_t)p->n_y + 255) / 256), dim3(256), 0, s, d_rep_rows,
+                     (uint32_t)p->k, ns, p->n_y, n_reps, s0, p->row_len, d_rows, d_ok);
+  OB_HIP(hipGetLastError());
   return OB_OK;
 }
 

@@ -199,8 +199,8 @@ namespace ob {
 
 // ob::finish, then every component's interval through bca_stats over the same pooled values that aggregate()
 // gave bootstrap_stats (a detailed component pools the columns that share its name, builder.rs:963-971).
-static int finish_bca(const ob_prepared* pr, const double* rows, const uint8_t* ok, uint64_t n_reps, double level,
-                      ob_results** out) {
+int finish_bca(const ob_prepared* pr, const double* rows, const uint8_t* ok, uint64_t n_reps, double level,
+               ob_results** out) {
   OB_TRY(finish(pr, 0, rows, ok, n_reps, out));
   ob_results* res = *out;
   const int k = pr->k, rl = pr->row_len;  // n_norm = 0: kd = k
@@ -241,7 +241,8 @@ static int finish_bca(const ob_prepared* pr, const double* rows, const uint8_t* 
 static int prepared_jack_check(const ob_prepared* p) {
   if (!p) return fail(OB_E_INVALID, "null pointer");
   if (p->cluster)  // delete-one-row is the wrong jackknife under clustering
-    return fail(OB_E_UNSUPPORTED, "jackknife: a clustered run needs a delete-one-cluster pass, which is not built");
+    return fail(OB_E_UNSUPPORTED, "jackknife: a clustered run takes the delete-one-cluster pass "
+                                  "(ob_prepared_cluster_jackknife, ob_prepared_finish_cluster_bca)");
   if (p->binary) return fail(OB_E_UNSUPPORTED, "jackknife: binary decompositions (BCa included) are outside its scope");
   if (p->reweight)
     return fail(OB_E_UNSUPPORTED, "jackknife: reweighted decompositions (BCa included) are outside its scope");

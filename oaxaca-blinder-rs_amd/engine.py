@@ -1159,3 +1159,77 @@ def cluster_last_timing() -> dict:
     t = N.ob_cluster_timing()
     N.check(N.lib().ob_cluster_last_timing(C.byref(t)))
     return {f: getattr(t, f) for f, _ in N.ob_cluster_timing._fields_}
+
+
+# ---- delete-one-cluster jackknife ---------------------------------------------
+def cluster_jackknife_check_shape(k: int, n_clusters: int, n_norm: int = 0, n_y: int = 1, heckman: bool = False,
+                                  want_rows: bool = False) -> None:
+    """ob_cluster_jackknife_check_shape: raises OaxacaError where the cluster jackknife entry points would
+    (host only). ``k``: design columns with the intercept."""
+    N.check(N.lib().ob_cluster_jackknife_check_shape(int(k), int(n_clusters), int(n_norm), int(n_y), int(heckman),
+                                                     int(want_rows)))
+
+
+def cluster_jackknife_last_timing() -> float:
+    """ob_cluster_jackknife_last_timing: HIP-event ms of this thread's last delete-one-cluster pass."""
+    ms = C.c_double()
+    N.check(N.lib().ob_cluster_jackknife_last_timing(C.byref(ms)))
+    return ms.value
+
+
+def _cluster_q(q_a, q_b, rows_a, rows_b):
+    """The two groups' ``cluster_gram`` outputs interleaved into Q (C, 2, e_pad) and rows (C, 2)."""
+    q_a, q_b = np.asarray(q_a, dtype=np.float64), np.asarray(q_b, dtype=np.float64)
+    if q_a.ndim != 2 or q_a.shape != q_b.shape or len(rows_a) != len(q_a) or len(rows_b) != len(q_a):
+        raise ValueError("cluster_jackknife: q_a / q_b (C, E) and rows_a / rows_b (C,) of the same clusters")
+    e = q_a.shape[1]
+    q = np.zeros((len(q_a), 2, (e + 15) // 16 * 16))
+    q[:, 0, :e], q[:, 1, :e] = q_a, q_b
+    rows = np.ascontiguousarray(np.stack([rows_a, rows_b], axis=1), dtype=np.uint32)
+    return q, rows, e
+
+
+def cluster_jackknife(q_a, q_b, rows_a, rows_b, tail, n_a: int, n_b: int, weighted: bool,
+                      ref_mode=ReferenceCoefficients.GroupA, n_clusters_a=None, gram=None, device=None):
+    """ob_cluster_jackknife: the delete-one-cluster pass on arrays. ``q_a`` / ``q_b`` (C, E) and ``rows_a`` /
+    ``rows_b`` (C,) from ``cluster_gram`` per group over the same C clusters; ``tail``: the point estimate's beta_A,
+    beta_B, xbar_A, xbar_B, beta* (5K values, a point-estimate row's columns after its 6 + 2K components); ``gram``
+    (2, E): its extended Grams, by default the sum of Q over the clusters; ``n_clusters_a``: A's clusters (they come
+    first) for the stratified strata, ``None`` for joint mode. -> api.JackknifeResult, counts per stratum."""
+    from .api import _jackknife_out, _jackknife_result
+
+    q, rows, e = _cluster_q(q_a, q_b, rows_a, rows_b)
+    k1 = int(round((np.sqrt(8 * e + 1) - 1) / 2))
+    if k1 * (k1 + 1) // 2 != e or k1 < 2:
+        raise ValueError("cluster_jackknife: E is not (p + 2)(p + 3) / 2")
+    g = q.sum(0) if gram is None else np.zeros((2, q.shape[2]))
+    if gram is not None:
+        g[:, :e] = np.asarray(gram, dtype=np.float64)
+    tail = np.ascontiguousarray(tail, dtype=np.float64)
+    if tail.size != 5 * (k1 - 1):
+        raise ValueError("cluster_jackknife: tail holds 5 K values")
+    o, bufs = _jackknife_out(k1 - 1)
+    N.check(N.lib().ob_cluster_jackknife(N.context(device), _dp(q), rows.ctypes.data_as(C.POINTER(C.c_uint32)), len(q),
+                                         len(q) if n_clusters_a is None else int(n_clusters_a),
+                                         0 if n_clusters_a is None else 1, k1 - 2, int(bool(weighted)), int(n_a), int(n_b),
+                                         _dp(np.ascontiguousarray(g)), _dp(tail), int(ref_mode), C.byref(o)))
+    return _jackknife_result(o, bufs, None)
+
+
+def cluster_jackknife_rows(panel, q_a, q_b, rows_a, rows_b, ref_mode=ReferenceCoefficients.GroupA, n_clusters_a=None,
+                           deviations: bool = False):
+    """ob_cluster_jackknife_rows on a resident ``Panel`` (its point estimate and solve kernel) and the two groups'
+    ``cluster_gram`` outputs -> (theta (C, row_len), kept, n_dropped per stratum[, d (C, 6 + 2K)])."""
+    q, rows, e = _cluster_q(q_a, q_b, rows_a, rows_b)
+    lib = N.lib()
+    nc, k = len(q), lib.ob_panel_k(panel._h)
+    theta = np.empty((nc, lib.ob_panel_row_len(panel._h)), dtype=np.float64)
+    kept = np.zeros(nc, dtype=np.uint8)
+    dev = np.empty((nc, 6 + 2 * k), dtype=np.float64) if deviations else None
+    nd = (C.c_int64 * 2)()
+    N.check(lib.ob_cluster_jackknife_rows(panel._h, _dp(q), rows.ctypes.data_as(C.POINTER(C.c_uint32)), nc,
+                                          nc if n_clusters_a is None else int(n_clusters_a),
+                                          0 if n_clusters_a is None else 1, int(ref_mode), _dp(theta),
+                                          kept.ctypes.data_as(C.POINTER(C.c_uint8)), nd, _dp(dev) if deviations else None))
+    out = (theta, kept.astype(bool), (int(nd[0]), int(nd[1])))
+    return out + (dev,) if deviations else out
