@@ -1507,6 +1507,83 @@ int ob_builder_run_dr(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_
    handle of another kind. */
 int ob_prepared_dr_info(const ob_prepared* prep, ob_dr_info* out);
 
+/* ---- Per-replicate RIF of a quantile over resample counts --------------------------------------
+ * decompose_quantile(s) computes the RIF once and bootstraps with it held fixed, so every replicate reuses the
+ * point estimate's quantile and density. This pass refits both on the resample (Firpo, Fortin, Lemieux 2009; Stata's
+ * `oaxaca_rif` under `bootstrap`) without a sort per replicate. A group's rows stand in stable ascending order of
+ * y; a replicate is its counts c_i over those rows (sum c_i = n). With Y(k) the y of the first position whose
+ * inclusive count prefix exceeds k, the values are rif.rs:14-88 on the expanded resample:
+ *     h = (n - 1) tau;  q = Y(floor h) when h is whole, else Y(floor h) + frac (Y(ceil h) - Y(floor h)), the multiply
+ *         and the add rounded separately (no FMA): q is bitwise the reference's
+ *     mean, sd (over n - 1) of the resample;  iqr = Y(ceil(0.75 n) - 1) - Y(ceil(0.25 n) - 1)
+ *     spread = iqr > 1e-8 ? min(sd, iqr / 1.34) : sd;  spread < 1e-8 -> 1.0;  bw = 0.9 spread n^-0.2
+ *     f = sum c_i phi((q - y_i) / bw) / (n bw), floored at 1e-8 (floored = 1)
+ *     RIF_i = A - B [y_i <= q],  B = 1 / f,  A = q + tau B;  p = upper_bound(y, q): y_i <= q is the row prefix [0, p)
+ * and, over v = [1, x_1 .. x_P] (K = P + 1), the y-pairs of the replicate's extended Gram:
+ *     T_a = sum_{i < p} c_i v_ia (T_0 = N_le, an exact integer);  G[a, y] = A G[0, a] - B T_a;
+ *     G[y, y] = A^2 n - (2 A B - B^2) N_le
+ * Limits: K > OB_RIFQ_MAX_K or more than OB_RIFQ_MAX_TAUS quantiles: OB_E_UNSUPPORTED; tau outside (0, 1) or not
+ * strictly increasing, y not finite or not ascending, x not finite, counts that do not sum to n: OB_E_INVALID; fewer
+ * than 2 rows (or, for a decomposition's shape, a group with rows <= K): OB_E_INSUFFICIENT. All before any device
+ * work. Every sum is f64 in an order fixed by n, without atomics: a replicate's values have the same bytes alone, in
+ * any batch, and for tau_t alone or among other quantiles. */
+#define OB_RIFQ_MAX_K 32
+#define OB_RIFQ_MAX_TAUS 8
+typedef struct {
+  double search_ms;  /* order statistics, quantiles, spread, bandwidth */
+  double density_ms; /* the density and column sums over every row: the hot pass */
+  double patch_ms;   /* masked sums, f, the Gram's y-pairs */
+  double gram_ms;    /* a prepared refit's boots: resample counts, the f64 Gram and its reduce (0 for ob_rifq_pass) */
+  double solve_ms;   /* a prepared refit's boots: y-pairs stored, the solves and the rows of every tau (0 likewise) */
+} ob_rifq_timing;
+typedef struct {
+  int32_t n_taus, k;
+  int64_t n_a, n_b;
+  int64_t n_density_floored; /* floored densities (replicate, group, tau) of the point pass and every boot since */
+  const double* taus;        /* [n_taus] */
+  const int32_t* perm_a;     /* [n_a] sorted position -> row of group A's cleaned rows (stable ascending y) */
+  const int32_t* perm_b;     /* [n_b] */
+  const double* q;           /* [2][n_taus] point quantiles, A then B */
+  const double* f;           /* [2][n_taus] point densities after the floor */
+} ob_rifq_info;
+/* The row of ob_builder_prepare_quantiles_refit's handle: the OLS row (ob_row_len) followed by q_A, q_B, f_A, f_B, N_le,A,
+   N_le,B. */
+int ob_rifq_row_len(int32_t k, int32_t n_base);
+/* The shape limits above on their own (host only). k: design columns with the intercept. */
+int ob_rifq_check_shape(int32_t k, int32_t n_taus, const double* taus, int64_t n_a, int64_t n_b);
+/* The pass over one group. y_sorted [n] ascending; counts [n_reps][n] bytes, or NULL for the point pass (every row
+   once, n_reps = 1); x [p][ldx] predictor columns in y's row order (NULL when p = 0). Outputs: q, f, n_le
+   [n_reps][n_taus]; bw [n_reps]; t [n_reps][n_taus][p + 1]; gy [n_reps][n_taus][p + 2] = G[a, y] for a <= p, then
+   G[y, y] (may be NULL); floored [n_reps][n_taus] (may be NULL). */
+int ob_rifq_pass(ob_ctx* ctx, const double* y_sorted, int64_t n, const uint8_t* counts, int32_t n_reps,
+                 const double* taus, int32_t n_taus, const double* x, int64_t ldx, int32_t p, double* q, double* bw,
+                 double* f, double* n_le, double* t, double* gy, uint8_t* floored);
+/* HIP-event ms of the calling thread's last ob_rifq_pass, prepare or boot of a refit handle. */
+int ob_rifq_last_timing(ob_rifq_timing* out);
+/* decompose_quantiles with the RIF refitted on every replicate. Row-order convention: the handle holds each group's
+   cleaned rows in stable ascending order of y, and OBRS-3 position i of group g is the i-th row in that order, so the
+   same seed draws other rows than the fixed-RIF run. The Gram is the engine's f64 one over that panel; its y-pairs
+   are replaced by the pass above, once per tau, before the engine's solve. Rows are outcome-major [n_taus][n_reps],
+   each ob_rifq_row_len(K, 0) doubles. The handle serves ob_prepared_boot, ob_prepared_boot_device (which
+   synchronizes), ob_prepared_finish (tau 0) and ob_prepared_point_row ([n_taus][row_len]); residuals are empty.
+   Refused before any device work: sample weights, normalize, Heckman settings, a cluster setting, K or n_taus over
+   the limits: OB_E_UNSUPPORTED; bad taus, a null or non-finite value in a named column: OB_E_INVALID; a group with
+   rows <= K or fewer than 2: OB_E_INSUFFICIENT. ob_prepared_boot_sharded, the jackknives and finish_bca on the
+   handle: OB_E_UNSUPPORTED. */
+int ob_builder_prepare_quantiles_refit(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                       const ob_builder_config* cfg, const double* taus, int32_t n_taus,
+                                       ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish per tau: out[n_taus]. */
+int ob_builder_decompose_quantiles_refit(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                         const ob_builder_config* cfg, const double* taus, int32_t n_taus,
+                                         ob_results** out);
+/* The sort permutations, the point q and f and the floor count (owned by the handle). OB_E_INVALID on a handle of
+   another kind. */
+int ob_prepared_rifq_info(const ob_prepared* prep, ob_rifq_info* out);
+/* ob_prepared_finish for quantile t of a refit handle: rows / ok are t's block of a boot. */
+int ob_prepared_finish_tau(ob_prepared* prep, int32_t t, const double* rows, const uint8_t* ok, uint64_t n_reps,
+                           ob_results** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,10 +77,14 @@ EXPORTED = (
     "ob_dr_row_len", "ob_dr_check_shape", "ob_dr_last_timing", "ob_dr_thresholds", "ob_dr_quantiles",
     "ob_dr_finish_rows", "ob_dr_logit_pass", "ob_dr_cdf", "ob_builder_prepare_dr", "ob_builder_run_dr",
     "ob_prepared_dr_info",
+    "ob_rifq_row_len", "ob_rifq_check_shape", "ob_rifq_pass", "ob_rifq_last_timing",
+    "ob_builder_prepare_quantiles_refit", "ob_builder_decompose_quantiles_refit", "ob_prepared_rifq_info",
+    "ob_prepared_finish_tau",
 )
 
 OB_E_CONVERGENCE = 12
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
+OB_RIFQ_MAX_K, OB_RIFQ_MAX_TAUS = 32, 8
 OB_HECKMAN_MAX_ZSEL = 31
 OB_AKM_MAX_CONTROLS = 64
 OB_VIF_MAX_K = 120
@@ -282,6 +286,17 @@ class ob_dr_config(C.Structure):
 class ob_dr_timing(C.Structure):
     _fields_ = [("passes", C.c_int32), ("launches", C.c_int32), ("pass_ms", C.c_double), ("cdf_ms", C.c_double),
                 ("row_ms", C.c_double)]
+
+
+class ob_rifq_timing(C.Structure):
+    _fields_ = [("search_ms", C.c_double), ("density_ms", C.c_double), ("patch_ms", C.c_double),
+                ("gram_ms", C.c_double), ("solve_ms", C.c_double)]
+
+
+class ob_rifq_info(C.Structure):
+    _fields_ = [("n_taus", C.c_int32), ("k", C.c_int32), ("n_a", C.c_int64), ("n_b", C.c_int64),
+                ("n_density_floored", C.c_int64), ("taus", C.POINTER(C.c_double)), ("perm_a", C.POINTER(C.c_int32)),
+                ("perm_b", C.POINTER(C.c_int32)), ("q", C.POINTER(C.c_double)), ("f", C.POINTER(C.c_double))]
 
 
 class ob_dr_info(C.Structure):
@@ -554,6 +569,17 @@ _SIGS = {
     "ob_builder_run_dr": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
                                     C.POINTER(ob_dr_config), C.POINTER(_P)]),
     "ob_prepared_dr_info": (C.c_int, [_P, C.POINTER(ob_dr_info)]),
+    "ob_rifq_row_len": (C.c_int, [C.c_int32, C.c_int32]),
+    "ob_rifq_check_shape": (C.c_int, [C.c_int32, C.c_int32, _D, C.c_int64, C.c_int64]),
+    "ob_rifq_pass": (C.c_int, [_P, _D, C.c_int64, _U8, C.c_int32, _D, C.c_int32, _D, C.c_int64, C.c_int32, _D, _D, _D, _D,
+                               _D, _D, _U8]),
+    "ob_rifq_last_timing": (C.c_int, [C.POINTER(ob_rifq_timing)]),
+    "ob_builder_prepare_quantiles_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                     C.POINTER(ob_builder_config), _D, C.c_int32, C.POINTER(_P)]),
+    "ob_builder_decompose_quantiles_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                       C.POINTER(ob_builder_config), _D, C.c_int32, C.POINTER(_P)]),
+    "ob_prepared_rifq_info": (C.c_int, [_P, C.POINTER(ob_rifq_info)]),
+    "ob_prepared_finish_tau": (C.c_int, [_P, C.c_int32, _D, _U8, C.c_uint64, C.POINTER(_P)]),
 }
 
 _lib = None

@@ -212,6 +212,11 @@ class OaxacaResults:
     n_failed: int = 0
     jackknife: dict = None  # run_bca / finish_bca: (table, name) -> {accel, std_err, bias, z0, flag}
     n_clusters: int = None  # a cluster bootstrap's C (OaxacaBuilder.cluster), else None
+    # decompose_quantile(s)(refit=True) only: the point (q_A, q_B), the point (f_A, f_B) after the floor and the
+    # floored densities over the point pass and every replicate, group and quantile of the run
+    quantile_values: tuple = None
+    density_values: tuple = None
+    n_density_floored: int = None
 
     def explained(self):
         return next((c for c in self.two_fold.aggregate if c.name == "explained"), None)
@@ -266,6 +271,10 @@ class OaxacaResults:
         }
         if self.n_clusters is not None:  # absent without clustering: the JSON of a row bootstrap is unchanged
             d["n_clusters"] = self.n_clusters
+        if self.quantile_values is not None:  # absent without the refit
+            d["quantile_values"] = list(self.quantile_values)
+            d["density_values"] = list(self.density_values)
+            d["n_density_floored"] = self.n_density_floored
         return json.dumps(d)
 
     def summary(self) -> str:
@@ -1053,8 +1062,11 @@ class OaxacaBuilder:
         finally:
             pr.close()
 
-    def decompose_quantile(self, quantile: float) -> OaxacaResults:
-        """builder.rs:711-757: RIF-regression decomposition at ``quantile``."""
+    def decompose_quantile(self, quantile: float, refit: bool = False) -> OaxacaResults:
+        """builder.rs:711-757: RIF-regression decomposition at ``quantile``. ``refit=True``: see
+        ``decompose_quantiles``."""
+        if refit:
+            return self.decompose_quantiles([float(quantile)], refit=True)[0]
         lib = N.lib()
         cols, ncol, nrow = self._frame.as_c()
         cfg, keep = self._config()
@@ -1065,10 +1077,52 @@ class OaxacaBuilder:
                                                   float(quantile), C.byref(h)))
         return _results_from_c(h)
 
-    def decompose_quantiles(self, quantiles) -> list:
+    def prepare_quantiles_refit(self, quantiles) -> "PreparedRun":
+        """ob_builder_prepare_quantiles_refit: a handle whose replicates refit the quantile, the bandwidth, the
+        density and so the RIF on every resample. ``boot`` returns rows (T, n_reps, row_len) and
+        ok (T, n_reps); ``point_row()`` is (T * row_len,). Each group's rows stand in stable ascending order of y,
+        so the same seed draws other rows than the fixed-RIF run."""
+        from .engine import with_context
+
+        taus = np.ascontiguousarray(quantiles, dtype=np.float64)
+        if taus.ndim != 1 or taus.size == 0:
+            raise ValueError("quantiles must be a non-empty 1-D sequence")
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, "quantile refit: the cluster bootstrap is outside its scope")
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        h = C.c_void_p()
+        tp = taus.ctypes.data_as(C.POINTER(C.c_double))
+        with_context(lambda ctx: lib.ob_builder_prepare_quantiles_refit(ctx, cols, ncol, nrow, C.byref(cfg), tp,
+                                                                        int(taus.size), C.byref(h)), self._device)
+        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+
+    def _decompose_quantiles_refit(self, quantiles) -> list:
+        pr = self.prepare_quantiles_refit(quantiles)
+        try:
+            rows, ok = pr.boot(0, pr.bootstrap_reps)
+            info = pr.rifq_info()
+            out = []
+            for t in range(pr.n_taus):
+                r = pr.finish_tau(t, rows[t], ok[t])
+                r.quantile_values = (float(info["q"][0, t]), float(info["q"][1, t]))
+                r.density_values = (float(info["f"][0, t]), float(info["f"][1, t]))
+                r.n_density_floored = info["n_density_floored"]
+                out.append(r)
+            return out
+        finally:
+            pr.close()
+
+    def decompose_quantiles(self, quantiles, refit: bool = False) -> list:
         """RIF decompositions at several quantiles in one run: one panel
         whose outcomes are the RIF columns, so every replicate's resample and Gram pass serve all
-        quantiles. Element t equals ``decompose_quantile(quantiles[t])`` bitwise (same seed)."""
+        quantiles. Element t equals ``decompose_quantile(quantiles[t])`` bitwise (same seed).
+        ``refit=True``: every replicate refits the quantile, the bandwidth and the density of its
+        own resample, so the standard errors carry their sampling error; the results gain ``quantile_values``,
+        ``density_values`` and ``n_density_floored``. Unweighted, no ``normalize``, Heckman or ``cluster``."""
+        if refit:
+            return self._decompose_quantiles_refit(quantiles)
         lib = N.lib()
         taus = np.ascontiguousarray(quantiles, dtype=np.float64)
         if taus.ndim != 1 or taus.size == 0:
@@ -1411,10 +1465,14 @@ class PreparedRun:
         self.cluster_info = None  # a clustered run: n_clusters, n_clusters_a, n_clusters_b, max_cluster_rows, stratified
         if N.lib().ob_prepared_cluster_info(handle, C.byref(info)) == N.OB_OK:
             self.cluster_info = {f: int(getattr(info, f)) for f, _ in N.ob_cluster_info._fields_}
+        # a refit handle (prepare_quantiles_refit): its quantiles; boot then returns (n_taus, n_reps, ...) blocks
+        rq = N.ob_rifq_info()
+        self.n_taus = int(rq.n_taus) if N.lib().ob_prepared_rifq_info(handle, C.byref(rq)) == N.OB_OK else 0
 
     def boot(self, first_rep: int, n_reps: int):
-        rows = np.empty((n_reps, self.row_len), dtype=np.float64)
-        ok = np.zeros(n_reps, dtype=np.uint8)
+        shape = (self.n_taus, n_reps) if self.n_taus else (n_reps,)
+        rows = np.empty(shape + (self.row_len,), dtype=np.float64)
+        ok = np.zeros(shape, dtype=np.uint8)
         if n_reps:
             N.check(N.lib().ob_prepared_boot(self._h, first_rep, n_reps,
                                              rows.ctypes.data_as(C.POINTER(C.c_double)),
@@ -1465,6 +1523,28 @@ class PreparedRun:
                 "out_of_range": arr(o.out_of_range, (3, nq)), "n_out_of_range": int(o.n_out_of_range),
                 "n_thresholds_requested": int(o.n_requested)}
 
+    def rifq_info(self) -> dict:
+        """ob_prepared_rifq_info: the quantiles, each group's sort permutation, the point q and f (2, T: A then B)
+        and the floored densities of the point pass and every boot since."""
+        o = N.ob_rifq_info()
+        N.check(N.lib().ob_prepared_rifq_info(self._h, C.byref(o)))
+        T = o.n_taus
+
+        def arr(ptr, shape):
+            return np.ctypeslib.as_array(ptr, shape=shape).copy()
+
+        return {"taus": arr(o.taus, (T,)), "k": int(o.k), "perm_a": arr(o.perm_a, (o.n_a,)),
+                "perm_b": arr(o.perm_b, (o.n_b,)), "q": arr(o.q, (2, T)), "f": arr(o.f, (2, T)),
+                "n_density_floored": int(o.n_density_floored)}
+
+    def finish_tau(self, t: int, rows: np.ndarray, ok: np.ndarray) -> OaxacaResults:
+        """ob_prepared_finish_tau: ``finish`` for quantile t of a refit handle (rows / ok: its block)."""
+        rows, ok = self._flat_block(rows, ok)
+        h = C.c_void_p()
+        N.check(N.lib().ob_prepared_finish_tau(self._h, int(t), rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                               ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
+        return _results_from_c(h)
+
     def sync(self):
         N.check(N.lib().ob_panel_sync(N.lib().ob_prepared_panel(self._h)))
 
@@ -1473,9 +1553,18 @@ class PreparedRun:
         N.check(N.lib().ob_panel_last_timing(N.lib().ob_prepared_panel(self._h), C.byref(t)))
         return {f: getattr(t, f) for f, _ in N.ob_timing._fields_}
 
-    def finish(self, rows: np.ndarray, ok: np.ndarray) -> OaxacaResults:
+    def _flat_block(self, rows, ok):
+        """rows (n_reps, row_len) and ok (n_reps,) of one outcome: a refit handle's (T, n_reps, ...) blocks go
+        through ``finish_tau`` one quantile at a time."""
         rows = np.ascontiguousarray(rows, dtype=np.float64)
         ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        if rows.ndim != 2 or ok.ndim != 1 or len(rows) != len(ok):
+            raise ValueError("rows must be (n_reps, row_len) and ok (n_reps,); pass one quantile's block of a refit "
+                             "handle's boot to finish_tau")
+        return rows, ok
+
+    def finish(self, rows: np.ndarray, ok: np.ndarray) -> OaxacaResults:
+        rows, ok = self._flat_block(rows, ok)
         h = C.c_void_p()
         N.check(N.lib().ob_prepared_finish(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
                                            ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
@@ -1490,8 +1579,7 @@ class PreparedRun:
 
     def finish_bca(self, rows: np.ndarray, ok: np.ndarray, confidence_level: float = 0.95) -> OaxacaResults:
         """``finish`` with BCa intervals (ob_prepared_finish_bca); rows of ``boot`` or ``boot_sharded``."""
-        rows = np.ascontiguousarray(rows, dtype=np.float64)
-        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        rows, ok = self._flat_block(rows, ok)
         h = C.c_void_p()
         N.check(N.lib().ob_prepared_finish_bca(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
                                                ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok),
@@ -1581,7 +1669,9 @@ class OaxacaBlinder:
     def fit(self) -> OaxacaResults:
         return self._create_builder().run()
 
-    def fit_quantile(self, quantile: float) -> OaxacaResults:
+    def fit_quantile(self, quantile: float, refit: bool = False) -> OaxacaResults:
+        if refit:
+            return self._create_builder().decompose_quantile(quantile, refit=True)
         return self._create_builder().decompose_quantile(quantile)
 
     def fit_quantiles(self, quantiles) -> list:

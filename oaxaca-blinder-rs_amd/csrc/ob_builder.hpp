@@ -35,6 +35,7 @@ struct Config {
 struct ClusterState;
 struct BinaryState;
 struct ReweightState;
+struct RifqState;
 
 }  // namespace ob
 
@@ -79,6 +80,8 @@ struct ob_prepared {
   // ob_builder_prepare_dr: the panel, fits and workspace on the device (boots run through ob_dr.hip) and the
   // thresholds, quantiles and point fits on the host
   ob::DrState* dr = nullptr;
+  // ob_builder_prepare_quantiles_refit: the y-sorted panel and the refit's workspace; boots run through ob_rifq.hip
+  ob::RifqState* rifq = nullptr;
   ob::DrInfo dr_info;
 };
 

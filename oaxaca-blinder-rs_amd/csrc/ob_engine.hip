@@ -2156,6 +2156,63 @@ int engine_solve_grams(ob_panel* p, const double* d_gram, const uint32_t* d_rep_
   return OB_OK;
 }
 
+// The f64 Gram and its reduce over the count images that are in d_counts (engine_counts, or
+// engine_unit_counts): the reduced extended Grams [replicate][2][e_pad] of n_reps replicates into d_gram, without a
+// solve (ob_rifq.hip patches the y-pairs first). The kernels and their launch shapes are engine_boot's f64 path.
+int engine_gram_f64(ob_panel* p, uint32_t n_reps, hipStream_t s) {
+  if (n_reps == 0) return OB_OK;
+  if (p->heckman || p->weighted) return ob::fail(OB_E_UNSUPPORTED, "engine_gram_f64 takes plain unweighted panels");
+  const Plan pl = make_plan(p, n_reps, false);
+  const int nch = pl.n_chunks();
+  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
+  OB_TRY(ensure_buf(&p->d_partial, p->cap_partial, (size_t)nch * pl.rep_pad * p->e_pad));
+  OB_TRY(ensure_buf(&p->d_gram, p->cap_gram, (size_t)2 * pl.rep_pad * p->e_pad));
+  if (!p->chunks_ready) {
+    p->chunks = pl.chunks;
+    OB_TRY(ensure_buf(&p->d_chunks, p->cap_chunks, p->chunks.size()));
+    OB_HIP(hipMemcpyAsync(p->d_chunks, p->chunks.data(), sizeof(uint32_t) * p->chunks.size(), hipMemcpyHostToDevice, s));
+    p->chunks_ready = true;
+  }
+  if (pl.chunks != p->chunks) return ob::fail(OB_E_INVALID, "internal: the chunk table changed with the replicate count");
+  GramArgs ga = gram_args(p, pl);
+  ga.chunks = p->d_chunks;
+  ga.m1 = p->d_m1;
+  ga.n_reps = n_reps;
+  ga.partial = p->d_partial;
+  ga.counts = p->d_counts;
+  ga.tiles_total = tiles;
+  OB_HIP(launch_gram(p, pl.cb, false, ga, pl.nb_rep * pl.n_cg * (uint32_t)nch, s));
+  const size_t nred = (size_t)n_reps * p->e_pad;
+  hipLaunchKernelGGL(ob_reduce_kernel, dim3((unsigned)((nred + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                     (const double*)p->d_partial, (const uint32_t*)p->d_chunks, nch, pl.rep_pad, p->e_pad, n_reps,
+                     p->d_gram);
+  OB_HIP(hipGetLastError());
+  return OB_OK;
+}
+
+// One batch of count images and level-1 counts in which replicate 0 counts every row once: the point pass of a
+// caller that runs the boot's own kernels over it.
+int engine_unit_counts(ob_panel* p, hipStream_t s, uint32_t* nb_rep, uint32_t* rep_pad) {
+  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
+  OB_TRY(ensure_buf(&p->d_m1, p->cap_m1, (size_t)tiles * 64));
+  OB_TRY(ensure_buf(&p->d_counts, p->cap_counts, (size_t)tiles * 4 * kCimgWords));
+  std::vector<uint32_t> m1((size_t)tiles * 64, 0u), img((size_t)tiles * 4 * kCimgWords, 0u);
+  for (int g = 0; g < 2; ++g) {
+    const uint32_t t0 = g ? p->ntiles[0] : 0u;
+    for (uint32_t i = 0; i < p->n[g]; ++i) {
+      const uint32_t t = t0 + i / OB_TILE_ROWS, within = i % OB_TILE_ROWS, sub = within >> 6, q = within & 63u;
+      img[((size_t)t * 4 + sub) * kCimgWords + (q >> 2)] |= 1u << (8 * (q & 3u));
+      m1[t] += 1u;
+    }
+  }
+  OB_HIP(hipMemcpyAsync(p->d_m1, m1.data(), sizeof(uint32_t) * m1.size(), hipMemcpyHostToDevice, s));
+  OB_HIP(hipMemcpyAsync(p->d_counts, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice, s));
+  OB_HIP(hipStreamSynchronize(s));  // the host images go out of scope
+  *nb_rep = 1;
+  *rep_pad = 64;
+  return OB_OK;
+}
+
 // Synchronize the last boot run, sum its per-segment kernel timings and check the
 // count-overflow flag.
 int engine_collect(ob_panel* p) {

@@ -169,6 +169,10 @@ int engine_order(ob_panel* p, hipStream_t s);
 int engine_mark(ob_panel* p, hipStream_t s, bool scratch = true);
 int engine_counts(ob_panel* p, uint64_t seed, uint64_t first_rep, uint32_t n_reps, hipStream_t s,
                   uint32_t* nb_rep, uint32_t* rep_pad);
+// ob_rifq.hip: the f64 Gram + reduce over the count images in d_counts into d_gram (no solve); one batch of unit
+// counts (replicate 0) in d_m1 / d_counts; the solve stage over reduced Grams (also ob_cluster.hip)
+int engine_gram_f64(ob_panel* p, uint32_t n_reps, hipStream_t s);
+int engine_unit_counts(ob_panel* p, hipStream_t s, uint32_t* nb_rep, uint32_t* rep_pad);
 // ob_gram_i8.hip
 int oz_prepare(ob_panel* p, hipStream_t s);
 int oz_gram(ob_panel* p, const uint32_t* d_chunks, int n_chunks, const uint32_t* counts, uint32_t nb_rep,

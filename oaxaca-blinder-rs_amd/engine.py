@@ -527,6 +527,61 @@ def binary_last_timing() -> dict:
     return {f: getattr(t, f) for f, _ in N.ob_binary_timing._fields_}
 
 
+def rifq_pass(y_sorted, taus, counts=None, x=None, device: int | None = None) -> dict:
+    """The RIF of quantiles refitted on resamples of one group (``ob_rifq_pass``). ``y_sorted``: the
+    group's outcome in ascending order; ``taus``: up to 8 strictly increasing quantiles in (0, 1); ``counts``:
+    (n_reps, n) resample counts below 256 over the sorted rows, each replicate summing to n (``None``: the point
+    pass, every row once); ``x``: (n, p) predictors in y's row order, ``p <= 31``. Returns ``q``, ``f``, ``n_le``,
+    ``floored`` (n_reps, T), ``bw`` (n_reps), ``t`` (n_reps, T, p + 1) = the sums of c v over the rows with
+    y <= q, v = [1, x], and ``gy`` (n_reps, T, p + 2) = the y-pairs G[a, y], then G[y, y], of the extended Gram."""
+    y = np.ascontiguousarray(y_sorted, dtype=np.float64)
+    tq = np.ascontiguousarray(np.atleast_1d(taus), dtype=np.float64)
+    if y.ndim != 1 or tq.ndim != 1:
+        raise ValueError("y_sorted and taus must be one-dimensional")
+    n, nt = len(y), len(tq)
+    xf, p = None, 0
+    if x is not None:
+        xf = np.asfortranarray(x, dtype=np.float64)
+        if xf.ndim != 2 or xf.shape[0] != n:
+            raise ValueError("x must be (n, p)")
+        p = xf.shape[1]
+        if p == 0:
+            xf = None
+    cp, reps = None, 1
+    if counts is not None:
+        c = np.atleast_2d(np.ascontiguousarray(counts))
+        if c.ndim != 2 or c.shape[1] != n or (c < 0).any() or (c > 255).any():
+            raise ValueError("counts must be (n_reps, n) integers in [0, 255]")
+        c8 = np.ascontiguousarray(c.astype(np.uint8))
+        cp, reps = c8.ctypes.data_as(C.POINTER(C.c_uint8)), c.shape[0]
+    q, f, nle = np.empty((reps, nt)), np.empty((reps, nt)), np.empty((reps, nt))
+    bw, t, gy = np.empty(reps), np.empty((reps, nt, p + 1)), np.empty((reps, nt, p + 2))
+    fl = np.zeros((reps, nt), dtype=np.uint8)
+    with_context(lambda ctx: N.lib().ob_rifq_pass(ctx, _dp(y), n, cp, reps, _dp(tq), nt, _dp(xf), max(n, 1), p, _dp(q),
+                                                  _dp(bw), _dp(f), _dp(nle), _dp(t), _dp(gy),
+                                                  fl.ctypes.data_as(C.POINTER(C.c_uint8))), device)
+    return {"q": q, "bw": bw, "f": f, "n_le": nle, "t": t, "gy": gy, "floored": fl.astype(bool)}
+
+
+def rifq_check_shape(k: int, taus, n_a: int, n_b: int) -> None:
+    """ob_rifq_check_shape: raises OaxacaError where a refitted quantile decomposition would (host only)."""
+    tq = np.ascontiguousarray(np.atleast_1d(taus), dtype=np.float64)
+    N.check(N.lib().ob_rifq_check_shape(int(k), len(tq), _dp(tq), int(n_a), int(n_b)))
+
+
+def rifq_row_len(k: int, n_base: int = 0) -> int:
+    """ob_rifq_row_len: the OLS row followed by q_A, q_B, f_A, f_B, N_le,A, N_le,B."""
+    return int(N.lib().ob_rifq_row_len(int(k), int(n_base)))
+
+
+def rifq_last_timing() -> dict:
+    """ob_rifq_last_timing: HIP-event ms of this thread's last rifq_pass, or prepare / boot of a refit handle: search,
+    density, patch, and for a handle gram (resample, f64 Gram, reduce) and solve (y-pairs, solves, rows)."""
+    t = N.ob_rifq_timing()
+    N.check(N.lib().ob_rifq_last_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in N.ob_rifq_timing._fields_}
+
+
 def _reweight_args(x, second, w, counts, gammas):
     """The arrays of the two reweighting pieces as the C ABI takes them."""
     xf = np.asfortranarray(x, dtype=np.float64)
