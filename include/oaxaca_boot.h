@@ -1580,9 +1580,90 @@ int ob_builder_decompose_quantiles_refit(ob_ctx* ctx, const ob_column* cols, int
 /* The sort permutations, the point q and f and the floor count (owned by the handle). OB_E_INVALID on a handle of
    another kind. */
 int ob_prepared_rifq_info(const ob_prepared* prep, ob_rifq_info* out);
-/* ob_prepared_finish for quantile t of a refit handle: rows / ok are t's block of a boot. */
+/* ob_prepared_finish for quantile t of a refit handle (or statistic t of ob_builder_prepare_statistics_refit's):
+   rows / ok are t's block of a boot. */
 int ob_prepared_finish_tau(ob_prepared* prep, int32_t t, const double* rows, const uint8_t* ok, uint64_t n_reps,
                            ob_results** out);
+
+/* ---- Per-replicate RIF of the variance, the Gini and quantile ranges over resample counts ------
+ * The refit above for the statistics of ob_builder_decompose_statistics, without a sort or an n-length column per
+ * replicate. Setting as above: rows in stable ascending order of y, a replicate is its counts c_i (sum c_i = n),
+ * v = [1, x_1 .. x_P], K = P + 1. Per statistic the pass gives its value nu on the expanded resample and the y-pairs
+ * G[a, RIF] = sum c v_a RIF, G[RIF, RIF] = sum c RIF^2 of the replicate's extended Gram, with RIF as in 5.12:
+ *   OB_RIF_VARIANCE  d = y - mu0 (mu0 the sample's own mean), M0_a = sum c v_a, M1_a = sum c v_a d,
+ *                    M2_a = sum c v_a d^2, M3 = sum c d^3, M4 = sum c d^4, delta = M1_0 / n:
+ *                    nu = (M2_0 - n delta^2) / n;  G[a, RIF] = M2_a - 2 delta M1_a + delta^2 M0_a;
+ *                    G[RIF, RIF] = M4 - 4 delta M3 + 6 delta^2 M2_0 - 4 delta^3 M1_0 + delta^4 n
+ *   OB_RIF_GINI      Cin_i, Sin_i the inclusive prefixes of c and c y in row order, mu = Sin_{n-1} / n,
+ *                    z_i = y_i (1 - Cin_i / n) + Sin_i / n (the same at a row and at the end of its tie run),
+ *                    R = (sum c_i Sin_i + E) / n^2, E = sum over tie runs of more than one row of
+ *                    y_run (m_run^2 - sum_{i in run} c_i^2) / 2, m_run = sum_{i in run} c_i; alpha = 2R / mu^2,
+ *                    beta = 2 / mu: nu = 1 - 2R / mu;  G[a, RIF] = M0_a + alpha sum c v_a y - beta sum c v_a z;
+ *                    G[RIF, RIF] = n + alpha^2 sum c y^2 + beta^2 sum c z^2 + 2 alpha sum c y - 2 beta sum c z
+ *                                  - 2 alpha beta sum c y z.  A replicate whose mu is 0 is flagged not ok.
+ *   OB_RIF_IQR       RIF_hi - RIF_lo of the pass above (one bandwidth): nu = q_hi - q_lo, G[a, RIF] the difference of
+ *                    the two G[a, y], G[RIF, RIF] = G_hh + G_ll - 2 (A_h A_l n - A_h B_l N_le,lo - A_l B_h N_le,hi
+ *                    + B_h B_l N_le,lo).
+ * Limits, each before any device work and with a NULL context too: K > OB_RIFQ_MAX_K, more than OB_RIFS_MAX_STATS
+ * statistics, more than OB_RIFQ_MAX_TAUS distinct quantiles over all ranges, more than 16384 replicates a call:
+ * OB_E_UNSUPPORTED; y not finite or not ascending, x not finite, counts that do not sum to n, bad range parameters, for
+ * the Gini a negative y or no positive one: OB_E_INVALID; n < 2 (or, for a decomposition's shape, a group with rows
+ * <= K): OB_E_INSUFFICIENT. Every sum is f64 in an order fixed by n and the chunk table, without atomics: a
+ * replicate's values have the same bytes alone, in any batch, and for a statistic alone or among others. */
+#define OB_RIFS_MAX_STATS 8
+typedef struct {
+  double moment_ms; /* the variance sums and the chunk totals over every row */
+  double scan_ms;   /* chunk totals into chunk carries */
+  double gini_ms;   /* the Gini's prefix pass over every row */
+  double tie_ms;    /* the Gini's tie-run term E */
+  double finish_ms; /* chunk partials in chunk order, nu and the y-pairs */
+  double gram_ms;   /* a prepared refit's boots: resample counts, the f64 Gram and its reduce (0 for ob_rifs_pass) */
+  double solve_ms;  /* a prepared refit's boots: y-pairs stored, the solves and the rows of every statistic */
+  double rifq_ms;   /* the quantile pass's three kernels for the ranges */
+} ob_rifs_timing;
+typedef struct {
+  int32_t n_specs, k;
+  int64_t n_a, n_b;
+  int64_t n_density_floored; /* floored densities (replicate, group, range) of the point pass and every boot since */
+  const ob_rif_spec* specs;  /* [n_specs] */
+  const int32_t* perm_a;     /* [n_a] sorted position -> row of group A's cleaned rows (stable ascending y) */
+  const int32_t* perm_b;     /* [n_b] */
+  const double* nu;          /* [2][n_specs] point statistics, A then B */
+} ob_rifs_info;
+/* The row of ob_builder_prepare_statistics_refit's handle: the OLS row (ob_row_len) followed by nu_A, nu_B. */
+int ob_rifs_row_len(int32_t k, int32_t n_base);
+/* The shape limits above on their own (host only). k: design columns with the intercept. */
+int ob_rifs_check_shape(int32_t k, const ob_rif_spec* specs, int32_t n_specs, int64_t n_a, int64_t n_b);
+/* The pass over one group. y_sorted [n] ascending; counts [n_reps][n] bytes, or NULL for the point pass (every row
+   once, n_reps = 1); x [p][ldx] predictor columns in y's row order (NULL when p = 0). Outputs: nu [n_reps][n_specs];
+   gy [n_reps][n_specs][p + 2] = G[a, RIF] for a <= p, then G[RIF, RIF]; floored [n_reps][n_specs], 1 where a range's
+   density was floored (may be NULL); ok [n_reps][n_specs], 0 where a Gini's mu is 0 (nu is then NaN and the pairs 0;
+   may be NULL). */
+int ob_rifs_pass(ob_ctx* ctx, const double* y_sorted, int64_t n, const uint8_t* counts, int32_t n_reps,
+                 const ob_rif_spec* specs, int32_t n_specs, const double* x, int64_t ldx, int32_t p, double* nu,
+                 double* gy, uint8_t* floored, uint8_t* ok);
+/* HIP-event ms of the calling thread's last ob_rifs_pass, prepare or boot of a statistics refit handle. */
+int ob_rifs_last_timing(ob_rifs_timing* out);
+/* decompose_statistics with the RIF refitted on every replicate: ob_builder_prepare_quantiles_refit step by step,
+   with the same row-order convention (OBRS-3 position i of group g is the i-th row in stable ascending order of y, so
+   the same seed draws other rows than the fixed-RIF run). Rows are outcome-major [n_specs][n_reps], each
+   ob_rifs_row_len(K, 0) doubles. The handle serves ob_prepared_boot, ob_prepared_boot_device (which synchronizes),
+   ob_prepared_finish (statistic 0), ob_prepared_finish_tau (statistic t) and ob_prepared_point_row
+   ([n_specs][row_len]); residuals are empty. Refused before any device work: sample weights, normalize, Heckman
+   settings, a cluster setting, the limits above: OB_E_UNSUPPORTED; bad specs, a null or non-finite value in a named
+   column, for the Gini a negative outcome or a group with no positive one: OB_E_INVALID; a group with rows <= K or
+   fewer than 2: OB_E_INSUFFICIENT. ob_prepared_boot_sharded, the jackknives and finish_bca on the handle:
+   OB_E_UNSUPPORTED. */
+int ob_builder_prepare_statistics_refit(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                        const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
+                                        ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish per statistic: out[n_specs]. */
+int ob_builder_decompose_statistics_refit(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                                          const ob_builder_config* cfg, const ob_rif_spec* specs, int32_t n_specs,
+                                          ob_results** out);
+/* The statistics, the sort permutations, the point nu and the floor count (owned by the handle). OB_E_INVALID on a
+   handle of another kind. */
+int ob_prepared_rifs_info(const ob_prepared* prep, ob_rifs_info* out);
 
 #ifdef __cplusplus
 }

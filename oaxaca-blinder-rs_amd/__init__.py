@@ -22,6 +22,7 @@ from .engine import (binary_check_shape, binary_last_timing, binary_means, binar
                      reweight_logit_pass, reweight_row_len,
                      dr_cdf, dr_check_shape, dr_last_timing, dr_logit_pass, dr_quantiles, dr_row_len, dr_thresholds,
                      rifq_check_shape, rifq_last_timing, rifq_pass, rifq_row_len,
+                     rifs_check_shape, rifs_last_timing, rifs_pass, rifs_row_len,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
@@ -49,4 +50,5 @@ __all__ = [
     "DistributionDecompositionResults", "dr_logit_pass", "dr_cdf", "dr_thresholds", "dr_quantiles", "dr_last_timing",
     "dr_check_shape", "dr_row_len", "dr_finish_rows",
     "rifq_pass", "rifq_check_shape", "rifq_row_len", "rifq_last_timing",
+    "rifs_pass", "rifs_check_shape", "rifs_row_len", "rifs_last_timing",
 ]

@@ -80,11 +80,14 @@ EXPORTED = (
     "ob_rifq_row_len", "ob_rifq_check_shape", "ob_rifq_pass", "ob_rifq_last_timing",
     "ob_builder_prepare_quantiles_refit", "ob_builder_decompose_quantiles_refit", "ob_prepared_rifq_info",
     "ob_prepared_finish_tau",
+    "ob_rifs_row_len", "ob_rifs_check_shape", "ob_rifs_pass", "ob_rifs_last_timing",
+    "ob_builder_prepare_statistics_refit", "ob_builder_decompose_statistics_refit", "ob_prepared_rifs_info",
 )
 
 OB_E_CONVERGENCE = 12
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
 OB_RIFQ_MAX_K, OB_RIFQ_MAX_TAUS = 32, 8
+OB_RIFS_MAX_STATS = 8
 OB_HECKMAN_MAX_ZSEL = 31
 OB_AKM_MAX_CONTROLS = 64
 OB_VIF_MAX_K = 120
@@ -291,6 +294,17 @@ class ob_dr_timing(C.Structure):
 class ob_rifq_timing(C.Structure):
     _fields_ = [("search_ms", C.c_double), ("density_ms", C.c_double), ("patch_ms", C.c_double),
                 ("gram_ms", C.c_double), ("solve_ms", C.c_double)]
+
+
+class ob_rifs_timing(C.Structure):
+    _fields_ = [("moment_ms", C.c_double), ("scan_ms", C.c_double), ("gini_ms", C.c_double), ("tie_ms", C.c_double),
+                ("finish_ms", C.c_double), ("gram_ms", C.c_double), ("solve_ms", C.c_double), ("rifq_ms", C.c_double)]
+
+
+class ob_rifs_info(C.Structure):
+    _fields_ = [("n_specs", C.c_int32), ("k", C.c_int32), ("n_a", C.c_int64), ("n_b", C.c_int64),
+                ("n_density_floored", C.c_int64), ("specs", C.POINTER(ob_rif_spec)), ("perm_a", C.POINTER(C.c_int32)),
+                ("perm_b", C.POINTER(C.c_int32)), ("nu", C.POINTER(C.c_double))]
 
 
 class ob_rifq_info(C.Structure):
@@ -580,6 +594,18 @@ _SIGS = {
                                                        C.POINTER(ob_builder_config), _D, C.c_int32, C.POINTER(_P)]),
     "ob_prepared_rifq_info": (C.c_int, [_P, C.POINTER(ob_rifq_info)]),
     "ob_prepared_finish_tau": (C.c_int, [_P, C.c_int32, _D, _U8, C.c_uint64, C.POINTER(_P)]),
+    "ob_rifs_row_len": (C.c_int, [C.c_int32, C.c_int32]),
+    "ob_rifs_check_shape": (C.c_int, [C.c_int32, C.POINTER(ob_rif_spec), C.c_int32, C.c_int64, C.c_int64]),
+    "ob_rifs_pass": (C.c_int, [_P, _D, C.c_int64, _U8, C.c_int32, C.POINTER(ob_rif_spec), C.c_int32, _D, C.c_int64,
+                               C.c_int32, _D, _D, _U8, _U8]),
+    "ob_rifs_last_timing": (C.c_int, [C.POINTER(ob_rifs_timing)]),
+    "ob_builder_prepare_statistics_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                      C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec), C.c_int32,
+                                                      C.POINTER(_P)]),
+    "ob_builder_decompose_statistics_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
+                                                        C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec),
+                                                        C.c_int32, C.POINTER(_P)]),
+    "ob_prepared_rifs_info": (C.c_int, [_P, C.POINTER(ob_rifs_info)]),
 }
 
 _lib = None

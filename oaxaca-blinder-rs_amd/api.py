@@ -217,6 +217,8 @@ class OaxacaResults:
     quantile_values: tuple = None
     density_values: tuple = None
     n_density_floored: int = None
+    # decompose_statistic(s)(refit=True) only: the point (nu_A, nu_B); a range also sets n_density_floored
+    statistic_values: tuple = None
 
     def explained(self):
         return next((c for c in self.two_fold.aggregate if c.name == "explained"), None)
@@ -275,6 +277,10 @@ class OaxacaResults:
             d["quantile_values"] = list(self.quantile_values)
             d["density_values"] = list(self.density_values)
             d["n_density_floored"] = self.n_density_floored
+        if self.statistic_values is not None:  # absent without the refit
+            d["statistic_values"] = list(self.statistic_values)
+            if self.n_density_floored is not None:
+                d["n_density_floored"] = self.n_density_floored
         return json.dumps(d)
 
     def summary(self) -> str:
@@ -1141,26 +1147,69 @@ class OaxacaBuilder:
                                                    C.cast(hs, C.POINTER(C.c_void_p))))
         return [_results_from_c(C.c_void_p(h)) for h in hs]
 
-    def decompose_statistic(self, stat, **params) -> OaxacaResults:
+    def decompose_statistic(self, stat, refit: bool = False, **params) -> OaxacaResults:
         """RIF-regression decomposition of the gap in a distributional statistic (Firpo, Fortin, Lemieux):
         ``"variance"``, ``"gini"`` or ``"iqr"`` (``upper=0.9, lower=0.1``). The statistic's recentred influence
         function of each group's outcome, computed on the GPU (``ob_rif_stat``), is the outcome of ``run()``:
-        ``total_gap`` is the gap in mean RIF, the statistic's gap up to the identities of DESIGN.md §5.12."""
+        ``total_gap`` is the gap in mean RIF, the statistic's gap up to the identities of DESIGN.md §5.12.
+        ``refit=True``: see ``decompose_statistics``."""
         from .engine import parse_rif_statistic
 
-        return self.decompose_statistics([parse_rif_statistic(stat, **params)])[0]
+        return self.decompose_statistics([parse_rif_statistic(stat, **params)], refit=refit)[0]
 
-    def decompose_statistics(self, stats) -> list:
+    def prepare_statistics_refit(self, stats) -> "PreparedRun":
+        """ob_builder_prepare_statistics_refit: a handle whose replicates refit the statistic and so its RIF on every
+        resample. ``boot`` returns rows (S, n_reps, row_len) and ok (S, n_reps); ``point_row()``
+        is (S * row_len,). Row-order convention of §5.18: each group's rows stand in stable ascending order of y and
+        OBRS-3 position i is the i-th row in that order, so the same seed draws other rows than the fixed-RIF
+        run."""
+        from .engine import _rif_specs, with_context
+
+        specs, parsed = _rif_specs(stats)
+        if not parsed:
+            raise ValueError("statistics must be a non-empty sequence")
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, "statistics refit: the cluster bootstrap is outside its scope")
+        lib = N.lib()
+        cols, ncol, nrow = self._frame.as_c()
+        cfg, keep = self._config()
+        h = C.c_void_p()
+        with_context(lambda ctx: lib.ob_builder_prepare_statistics_refit(ctx, cols, ncol, nrow, C.byref(cfg), specs,
+                                                                         len(parsed), C.byref(h)), self._device)
+        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+
+    def _decompose_statistics_refit(self, stats) -> list:
+        pr = self.prepare_statistics_refit(stats)
+        try:
+            rows, ok = pr.boot(0, pr.bootstrap_reps)
+            info = pr.rifs_info()
+            out = []
+            for t in range(pr.n_taus):
+                r = pr.finish_tau(t, rows[t], ok[t])
+                r.statistic_values = (float(info["nu"][0, t]), float(info["nu"][1, t]))
+                if info["specs"][t][0] == N.OB_RIF_IQR:
+                    r.n_density_floored = info["n_density_floored"]
+                out.append(r)
+            return out
+        finally:
+            pr.close()
+
+    def decompose_statistics(self, stats, refit: bool = False) -> list:
         """Several statistics in one run: one panel whose outcomes are the RIF columns, so every replicate's
         resample and Gram pass serve all of them. ``stats``: names, ``(name, params)`` pairs or dicts with a
         ``stat`` key. Element t equals ``decompose_statistic`` of element t bitwise (same seed). Honours
-        ``.cluster(...)`` the way ``decompose_quantiles`` does."""
+        ``.cluster(...)`` the way ``decompose_quantiles`` does.
+        ``refit=True``: every replicate refits the statistic on its own resample, so the standard
+        errors carry its sampling error; the results gain ``statistic_values`` and, for a range,
+        ``n_density_floored``. Unweighted, no ``normalize``, Heckman or ``cluster``."""
         from .engine import parse_rif_statistic, with_context
 
         stats = list(stats)
         parsed = [s if isinstance(s, tuple) and len(s) == 3 else parse_rif_statistic(s) for s in stats]
         if not parsed:
             raise ValueError("statistics must be a non-empty sequence")
+        if refit:
+            return self._decompose_statistics_refit(parsed)
         specs = (N.ob_rif_spec * len(parsed))(*[N.ob_rif_spec(*p) for p in parsed])
         lib = N.lib()
         cols, ncol, nrow = self._frame.as_c()
@@ -1468,6 +1517,9 @@ class PreparedRun:
         # a refit handle (prepare_quantiles_refit): its quantiles; boot then returns (n_taus, n_reps, ...) blocks
         rq = N.ob_rifq_info()
         self.n_taus = int(rq.n_taus) if N.lib().ob_prepared_rifq_info(handle, C.byref(rq)) == N.OB_OK else 0
+        if not self.n_taus:  # a statistics refit handle (prepare_statistics_refit): its statistics, likewise
+            rs = N.ob_rifs_info()
+            self.n_taus = int(rs.n_specs) if N.lib().ob_prepared_rifs_info(handle, C.byref(rs)) == N.OB_OK else 0
 
     def boot(self, first_rep: int, n_reps: int):
         shape = (self.n_taus, n_reps) if self.n_taus else (n_reps,)
@@ -1537,8 +1589,23 @@ class PreparedRun:
                 "perm_b": arr(o.perm_b, (o.n_b,)), "q": arr(o.q, (2, T)), "f": arr(o.f, (2, T)),
                 "n_density_floored": int(o.n_density_floored)}
 
+    def rifs_info(self) -> dict:
+        """ob_prepared_rifs_info: the statistics as (code, p0, p1), each group's sort permutation, the point nu
+        (2, S: A then B) and the floored densities of the point pass and every boot since."""
+        o = N.ob_rifs_info()
+        N.check(N.lib().ob_prepared_rifs_info(self._h, C.byref(o)))
+        S = o.n_specs
+
+        def arr(ptr, shape):
+            return np.ctypeslib.as_array(ptr, shape=shape).copy()
+
+        return {"specs": [(int(o.specs[t].stat), float(o.specs[t].p0), float(o.specs[t].p1)) for t in range(S)],
+                "k": int(o.k), "perm_a": arr(o.perm_a, (o.n_a,)), "perm_b": arr(o.perm_b, (o.n_b,)),
+                "nu": arr(o.nu, (2, S)), "n_density_floored": int(o.n_density_floored)}
+
     def finish_tau(self, t: int, rows: np.ndarray, ok: np.ndarray) -> OaxacaResults:
-        """ob_prepared_finish_tau: ``finish`` for quantile t of a refit handle (rows / ok: its block)."""
+        """ob_prepared_finish_tau: ``finish`` for quantile t of a refit handle, or statistic t of a statistics refit
+        handle (rows / ok: its block)."""
         rows, ok = self._flat_block(rows, ok)
         h = C.c_void_p()
         N.check(N.lib().ob_prepared_finish_tau(self._h, int(t), rows.ctypes.data_as(C.POINTER(C.c_double)),
@@ -1678,12 +1745,16 @@ class OaxacaBlinder:
         """Several RIF quantiles sharing one bootstrap (``OaxacaBuilder.decompose_quantiles``)."""
         return self._create_builder().decompose_quantiles(quantiles)
 
-    def fit_statistic(self, stat, **params) -> OaxacaResults:
+    def fit_statistic(self, stat, refit: bool = False, **params) -> OaxacaResults:
         """The RIF decomposition of a distributional statistic (``OaxacaBuilder.decompose_statistic``)."""
+        if refit:
+            return self._create_builder().decompose_statistic(stat, refit=True, **params)
         return self._create_builder().decompose_statistic(stat, **params)
 
-    def fit_statistics(self, stats) -> list:
+    def fit_statistics(self, stats, refit: bool = False) -> list:
         """Several statistics sharing one bootstrap (``OaxacaBuilder.decompose_statistics``)."""
+        if refit:
+            return self._create_builder().decompose_statistics(stats, refit=True)
         return self._create_builder().decompose_statistics(stats)
 
     def optimize_budget(self, budget: float, target_gap: float):

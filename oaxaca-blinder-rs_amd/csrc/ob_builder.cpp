@@ -33,6 +33,7 @@
 #include "ob_mm.hpp"
 #include "ob_rif.hpp"
 #include "ob_rifq.hpp"
+#include "ob_rifs.hpp"
 #include "ob_spec.h"
 
 namespace ob {
@@ -59,6 +60,10 @@ DrHooks& dr_hooks() {
 
 RifqHooks& rifq_hooks() {
   static RifqHooks h;
+  return h;
+}
+RifsHooks& rifs_hooks() {
+  static RifsHooks h;
   return h;
 }
 RifHooks& rif_hooks() {
@@ -1023,6 +1028,7 @@ int ob_prepared_boot(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double
   if (p->reweight) return ob::reweight_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   if (p->dr) return ob::dr_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   if (p->rifq) return ob::rifq_hooks().boot_host(p, first_rep, n_reps, rows, ok);
+  if (p->rifs) return ob::rifs_hooks().boot_host(p, first_rep, n_reps, rows, ok);
   return ob_boot_run(p->panel, p->seed, first_rep, n_reps, p->ref, rows, ok);
 }
 
@@ -1033,6 +1039,7 @@ int ob_prepared_boot_sharded(ob_prepared* p, uint64_t first_rep, uint64_t n_reps
   if (p->reweight) return ob::fail(OB_E_UNSUPPORTED, "reweighted decomposition: sharded runs are outside its scope");
   if (p->dr) return ob::fail(OB_E_UNSUPPORTED, "distribution regression: sharded runs are outside its scope");
   if (p->rifq) return ob::fail(OB_E_UNSUPPORTED, "quantile refit: sharded runs are outside its scope");
+  if (p->rifs) return ob::fail(OB_E_UNSUPPORTED, "statistics refit: sharded runs are outside its scope");
   // the RCCL all-gather moves only the columns finish() aggregates: two-fold, three-fold, total
   // gap, detailed [0, 6 + 2 Kd) and a Heckman row's selection terms after its 5K' tail
   const int kd = p->k + p->n_base, sel0 = 6 + 2 * kd + 5 * p->k;
@@ -1062,6 +1069,8 @@ int ob_prepared_boot_device(ob_prepared* p, uint64_t first_rep, uint64_t n_reps,
     return ob::dr_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
   if (p->rifq)
     return ob::rifq_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
+  if (p->rifs)
+    return ob::rifs_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
   return ob_boot_run_device(p->panel, p->seed, first_rep, n_reps, p->ref, d_rows, d_ok, hip_stream);
 }
 
@@ -1078,6 +1087,7 @@ void ob_prepared_destroy(ob_prepared* p) {
   if (p->reweight) ob::reweight_hooks().free_state(p->reweight);
   if (p->dr) ob::dr_hooks().free_state(p->dr);
   if (p->rifq) ob::rifq_hooks().free_state(p->rifq);
+  if (p->rifs) ob::rifs_hooks().free_state(p->rifs);
   ob_panel_destroy(p->panel);
   delete p;
 }

@@ -36,6 +36,7 @@ struct ClusterState;
 struct BinaryState;
 struct ReweightState;
 struct RifqState;
+struct RifsState;
 
 }  // namespace ob
 
@@ -82,6 +83,8 @@ struct ob_prepared {
   ob::DrState* dr = nullptr;
   // ob_builder_prepare_quantiles_refit: the y-sorted panel and the refit's workspace; boots run through ob_rifq.hip
   ob::RifqState* rifq = nullptr;
+  // ob_builder_prepare_statistics_refit: the y-sorted panel and the refit's workspace; boots run through ob_rifs.hip
+  ob::RifsState* rifs = nullptr;
   ob::DrInfo dr_info;
 };
 

@@ -245,6 +245,7 @@ static int prepared_jack_check(const ob_prepared* p) {
                                   "(ob_prepared_cluster_jackknife, ob_prepared_finish_cluster_bca)");
   if (p->binary) return fail(OB_E_UNSUPPORTED, "jackknife: binary decompositions (BCa included) are outside its scope");
   if (p->rifq) return fail(OB_E_UNSUPPORTED, "jackknife: refitted quantile decompositions (BCa included) are outside its scope");
+  if (p->rifs) return fail(OB_E_UNSUPPORTED, "jackknife: refitted statistic decompositions (BCa included) are outside its scope");
   if (p->reweight)
     return fail(OB_E_UNSUPPORTED, "jackknife: reweighted decompositions (BCa included) are outside its scope");
   if (p->dr)

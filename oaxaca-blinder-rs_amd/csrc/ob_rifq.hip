@@ -46,33 +46,7 @@ constexpr int kQRound = 8;   // sums reduced per round of the block's final orde
 constexpr int kQRanks = 2 * ob::kRifqMaxTaus + 2;
 static_assert(kQVals == ob::kRifqMaxTaus + ob::kRifqMaxK && kQVals % kQRound == 0, "sum slots");
 
-struct RifqArgs {
-  const double* cols[2];  // per group [k][ld]: y (ascending) | x_1 .. x_{k-1}
-  int64_t ld[2];
-  uint32_t n[2];
-  uint32_t tile0[2];      // first tile of the group in m1 / the count images
-  double mu0[2];          // the original sample's mean: the centre of the spread sums
-  double npow[2];         // n_g^-0.2
-  double taus[ob::kRifqMaxTaus];
-  int k, n_taus, n_groups;
-  uint32_t tiles_total;
-  const uint32_t* m1;      // [replicate][tile] level-1 counts
-  const uint32_t* counts;  // level-2 count images (ob_engine.hpp, the f64 Gram's layout); NULL: every row once
-  uint32_t nb_rep, part_pad, n_reps;
-  const uint32_t* chunks;  // [chunk][3] = (g, t0, t1)
-  int n_chunks;
-  // search -> density, patch: per (replicate, group)
-  double* sq;     // [rep][g][T] quantiles
-  uint32_t* sp;   // [rep][g][T] p_t
-  double* sbw;    // [rep][g][3] bandwidth, mean, sd
-  double* partial;  // [chunk][part_pad][kRifqMaxTaus + k]
-  // patch outputs, per (replicate, group, tau)
-  double* of;     // density after the floor
-  double* onle;   // N_le
-  uint8_t* ofl;   // 1 = the density was floored
-  double* ot;     // [..][k] masked sums T_a
-  double* ogy;    // [..][k + 1] G[a, y] for a < k, then G[y, y]
-};
+using ob::RifqArgs;  // ob_rifq.hpp
 
 // c of sorted position `row` of group g in replicate rep.
 __device__ __forceinline__ uint32_t rifq_count(const RifqArgs& a, int g, uint32_t rep, uint32_t row) {
@@ -404,6 +378,15 @@ int rifq_times(hipEvent_t* e) {
 }  // namespace
 
 namespace ob {
+
+// ob_rifs.hip runs the same kernels for its quantile ranges.
+int rifq_run(const RifqArgs& a, hipStream_t s, hipEvent_t* e) { return rifq_launch(a, s, e); }
+
+int rifq_store(const RifqArgs& a, int t, double* gram, int e_pad, hipStream_t s) {
+  hipLaunchKernelGGL(rifq_store_kernel, dim3(blocks_for((int64_t)a.n_reps * 2 * (a.k + 1))), dim3(256), 0, s, a, t, gram, e_pad);
+  OB_HIP(hipGetLastError());
+  return OB_OK;
+}
 
 int rifq_check_taus(const double* taus, int n_taus) {
   if (!taus || n_taus < 1) return fail(OB_E_INVALID, "quantile refit: no quantiles");
@@ -943,8 +926,9 @@ int ob_prepared_finish_tau(ob_prepared* prep, int32_t t, const double* rows, con
                            ob_results** out) {
   if (!prep || !out || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
   *out = nullptr;
-  if (!prep->rifq) return ob::fail(OB_E_INVALID, "the handle was not prepared for a quantile refit");
-  if (t < 0 || t >= prep->rifq->n_taus) return ob::fail(OB_E_INVALID, "quantile index %d out of range", t);
+  if (!prep->rifq && !prep->rifs) return ob::fail(OB_E_INVALID, "the handle was not prepared for a quantile refit");
+  const int n_out = prep->rifq ? prep->rifq->n_taus : prep->n_y;  // a statistics refit handle: its statistics
+  if (t < 0 || t >= n_out) return ob::fail(OB_E_INVALID, "quantile index %d out of range", t);
   return ob::finish(prep, t, rows, ok, n_reps, out);
 }
 

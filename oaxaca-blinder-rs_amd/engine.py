@@ -582,6 +582,69 @@ def rifq_last_timing() -> dict:
     return {f: getattr(t, f) for f, _ in N.ob_rifq_timing._fields_}
 
 
+def _rif_specs(stats):
+    """names, (name, params) pairs, dicts or parsed (code, p0, p1) triples -> (ctypes array of ob_rif_spec, triples)."""
+    stats = [stats] if isinstance(stats, (str, dict)) else list(stats)
+    parsed = [s if isinstance(s, tuple) and len(s) == 3 else parse_rif_statistic(s) for s in stats]
+    return (N.ob_rif_spec * max(len(parsed), 1))(*[N.ob_rif_spec(*p) for p in parsed]), parsed
+
+
+def rifs_pass(y_sorted, stats, counts=None, x=None, device: int | None = None) -> dict:
+    """The RIFs of the variance, the Gini and quantile ranges refitted on resamples of one group (``ob_rifs_pass``,
+    DESIGN.md §5.19). ``y_sorted``: the group's outcome in ascending order; ``stats``: up to 8 statistics as
+    ``decompose_statistics`` lists them (the ranges share at most 8 distinct quantiles); ``counts``: (n_reps, n)
+    resample counts below 256 over the sorted rows, each replicate summing to n (``None``: the point pass, every row
+    once); ``x``: (n, p) predictors in y's row order, ``p <= 31``. Returns ``nu`` (n_reps, S) = the statistics on the
+    expanded resamples, ``gy`` (n_reps, S, p + 2) = the y-pairs G[a, RIF], then G[RIF, RIF], of the extended Gram,
+    ``floored`` (n_reps, S) = a range's density floor flags and ``ok`` (n_reps, S), False where a Gini's resample has
+    mean 0."""
+    y = np.ascontiguousarray(y_sorted, dtype=np.float64)
+    if y.ndim != 1:
+        raise ValueError("y_sorted must be one-dimensional")
+    specs, parsed = _rif_specs(stats)
+    n, ns = len(y), len(parsed)
+    xf, p = None, 0
+    if x is not None:
+        xf = np.asfortranarray(x, dtype=np.float64)
+        if xf.ndim != 2 or xf.shape[0] != n:
+            raise ValueError("x must be (n, p)")
+        p = xf.shape[1]
+        if p == 0:
+            xf = None
+    cp, reps = None, 1
+    if counts is not None:
+        c = np.atleast_2d(np.ascontiguousarray(counts))
+        if c.ndim != 2 or c.shape[1] != n or (c < 0).any() or (c > 255).any():
+            raise ValueError("counts must be (n_reps, n) integers in [0, 255]")
+        c8 = np.ascontiguousarray(c.astype(np.uint8))
+        cp, reps = c8.ctypes.data_as(C.POINTER(C.c_uint8)), c.shape[0]
+    nu, gy = np.empty((reps, ns)), np.empty((reps, ns, p + 2))
+    fl, ok = np.zeros((reps, ns), dtype=np.uint8), np.zeros((reps, ns), dtype=np.uint8)
+    with_context(lambda ctx: N.lib().ob_rifs_pass(ctx, _dp(y), n, cp, reps, specs, ns, _dp(xf), max(n, 1), p, _dp(nu),
+                                                  _dp(gy), fl.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  ok.ctypes.data_as(C.POINTER(C.c_uint8))), device)
+    return {"nu": nu, "gy": gy, "floored": fl.astype(bool), "ok": ok.astype(bool)}
+
+
+def rifs_check_shape(k: int, stats, n_a: int, n_b: int) -> None:
+    """ob_rifs_check_shape: raises OaxacaError where a refitted statistics decomposition would (host only)."""
+    specs, parsed = _rif_specs(stats)
+    N.check(N.lib().ob_rifs_check_shape(int(k), specs, len(parsed), int(n_a), int(n_b)))
+
+
+def rifs_row_len(k: int, n_base: int = 0) -> int:
+    """ob_rifs_row_len: the OLS row followed by nu_A, nu_B."""
+    return int(N.lib().ob_rifs_row_len(int(k), int(n_base)))
+
+
+def rifs_last_timing() -> dict:
+    """ob_rifs_last_timing: HIP-event ms of this thread's last rifs_pass, or prepare / boot of a statistics refit
+    handle: moment, scan, gini, tie, finish, rifq (the ranges' quantile pass), and for a handle gram and solve."""
+    t = N.ob_rifs_timing()
+    N.check(N.lib().ob_rifs_last_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in N.ob_rifs_timing._fields_}
+
+
 def _reweight_args(x, second, w, counts, gammas):
     """The arrays of the two reweighting pieces as the C ABI takes them."""
     xf = np.asfortranarray(x, dtype=np.float64)
