@@ -17,7 +17,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -26,6 +25,7 @@
 #include "ob_engine.hpp"
 #include "ob_heckman.hpp"
 #include "ob_hip.hpp"
+#include "ob_model.hpp"
 #include "ob_normal.hpp"
 #include "ob_options.hpp"
 #include "ob_spec.h"
@@ -349,9 +349,7 @@ struct BinaryState {
   int n_chunks = 0;
 };
 
-constexpr size_t kBinaryPartialBudget = (size_t)1 << 30;  // bytes of chunk partials per batch (as heck_batch)
-constexpr uint64_t kBinarySegReps = 4096;                 // replicates per segment of count images
-constexpr uint64_t kBinaryCountBudget = 8ull << 30;       // bytes of count images per segment
+static BinaryState* binary_state(const ob_prepared* pr) { return model_state<BinaryState>(pr, kModelBinary); }
 
 static ob_heck_seg binary_seg(const ob_prepared* pr, const BinaryState* st) {
   const ob_panel* p = pr->panel;
@@ -384,15 +382,10 @@ static int binary_ensure(BinaryState* st, uint32_t rep_pad, uint32_t hb) {
 }
 
 // Replicates per batch: the register-resident probit kernels (k <= 8) take a segment whole (their
-// partials are [chunk][rep_pad]); the wide ones run batches of 64-replicate blocks within the budget
-// (option hk_batch forces a smaller batch, as on the Heckman path). Rows do not depend on it.
+// partials are [chunk][rep_pad]); the wide ones run boot_batch_reps' batches. Rows do not depend on it.
 static uint32_t binary_batch_reps(const BinaryState* st, uint32_t rep_pad) {
   if (st->k <= kHeckMaxKs) return rep_pad;
-  const size_t per64 = (size_t)st->n_chunks * 64 * partial_vals(st->k) * sizeof(double);
-  size_t blocks = std::max<size_t>(1, kBinaryPartialBudget / std::max<size_t>(per64, 1));
-  const int forced = opt_int(Opt::HkBatch, 0);
-  if (forced > 0) blocks = std::min<size_t>(blocks, (size_t)forced);
-  return (uint32_t)std::min<size_t>(rep_pad, blocks * 64);
+  return boot_batch_reps((size_t)st->n_chunks * partial_vals(st->k) * sizeof(double), rep_pad);
 }
 
 static int binary_point(ob_prepared* pr, BinaryState* st) {
@@ -427,29 +420,16 @@ static int binary_point(ob_prepared* pr, BinaryState* st) {
 
 static int binary_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
                               hipStream_t stream) {
-  if (!pr || !pr->binary || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  if (first_rep + n_reps > 0xFFFFFFFFull)
-    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 counter word)");
-  BinaryState* st = pr->binary;
-  ob_panel* p = pr->panel;
-  OB_HIP(hipSetDevice(p->ctx->device));
-  hipStream_t s = stream ? stream : p->ctx->stream;
-  OB_TRY(engine_order(p, s));
-  g_timing = {};
-  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
-  const uint64_t batch_bytes = (uint64_t)std::max(tiles, 1u) * 4 * kCimgWords * sizeof(uint32_t);
-  const uint64_t seg_cap = std::max<uint64_t>(64, (kBinaryCountBudget / batch_bytes) * 64);
-  const uint64_t seg = std::min<uint64_t>(n_reps, std::min<uint64_t>(kBinarySegReps, seg_cap));
-  const uint32_t seg_pad = (uint32_t)((seg + 63) / 64 * 64);
-  OB_TRY(binary_ensure(st, seg_pad, binary_batch_reps(st, seg_pad)));
-  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
-  int rc = OB_OK;
-  for (uint64_t s0 = 0; s0 < n_reps && rc == OB_OK; s0 += seg) {
-    const uint32_t ns = (uint32_t)std::min<uint64_t>(seg, n_reps - s0);
-    uint32_t nb_rep = 0, rep_pad = 0;
-    rc = engine_counts(p, pr->seed, first_rep + s0, ns, s, &nb_rep, &rep_pad);
-    if (rc != OB_OK) break;
+  BinaryState* st = binary_state(pr);
+  ob_panel* p = pr ? pr->panel : nullptr;
+  uint32_t seg_pad = 0;  // the flags are laid out for the longest segment (binary alone keeps per-segment flags)
+  const BootPlan plan{kFitSegReps, kCountBudget, true, [&](uint32_t pad) {
+                        g_timing = {};
+                        seg_pad = pad;
+                        return binary_ensure(st, pad, binary_batch_reps(st, pad));
+                      }};
+  return boot_segmented(pr, kModelBinary, plan, first_rep, n_reps, d_rows && d_ok, stream,
+                        [&](uint64_t s0, uint32_t ns, uint32_t nb_rep, uint32_t rep_pad, hipStream_t s) {
     ob_heck_seg hs = binary_seg(pr, st);
     hs.counts = p->d_counts;
     hs.counts_i8 = 0;
@@ -458,184 +438,74 @@ static int binary_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_re
     hs.active = st->flags.as<uint32_t>() + 2 * (size_t)seg_pad;
     hs.partial = st->partial.d();
     const uint32_t hb = binary_batch_reps(st, rep_pad);
-    for (uint32_t b0 = 0; b0 < ns && rc == OB_OK; b0 += hb) {  // every per-replicate base moved to b0
+    return boot_batches(ns, hb, [&](uint32_t b0, uint32_t nb) {  // every per-replicate base moved to b0
       ob_heck_seg hb_seg = hs;
-      hb_seg.n_reps = std::min(hb, ns - b0);
+      hb_seg.n_reps = nb;
       hb_seg.part_pad = hb;
       hb_seg.counts = hs.counts + (size_t)(b0 / 64) * 4 * kCimgWords;
       hb_seg.gamma = st->gamma.d() + (size_t)b0 * st->k;
       hb_seg.hflags = st->flags.as<uint32_t>() + b0;
       hb_seg.rows = d_rows + (s0 + b0) * pr->row_len;
       hb_seg.ok = d_ok + s0 + b0;
-      rc = binary_batch(hb_seg, st->betas.d() + (size_t)b0 * 3 * st->k, s);
-    }
-  }
-  uint32_t flag = 0;
-  if (rc == OB_OK && hipMemcpyAsync(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = fail(OB_E_HIP, "copy of the overflow word failed");
-  if (rc == OB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(OB_E_HIP, "stream synchronize failed");
-  const int rm = engine_mark(p, s);
-  if (rc != OB_OK) return rc;
-  if (flag & 1u) return fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
-  return rm;
+      return binary_batch(hb_seg, st->betas.d() + (size_t)b0 * 3 * st->k, s);
+    });
+  });
 }
 
-static int binary_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
-  if (!pr || !pr->binary || (n_reps && (!rows || !ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  OB_HIP(hipSetDevice(pr->panel->ctx->device));
-  DevBuf d_rows, d_ok;
-  OB_HIP(d_rows.alloc(sizeof(double) * n_reps * pr->row_len));
-  OB_HIP(d_ok.alloc(n_reps));
-  OB_TRY(binary_boot_device(pr, first_rep, n_reps, d_rows.d(), d_ok.as<uint8_t>(), nullptr));
-  OB_HIP(hipMemcpy(rows, d_rows.p, sizeof(double) * n_reps * pr->row_len, hipMemcpyDeviceToHost));
-  OB_HIP(hipMemcpy(ok, d_ok.p, n_reps, hipMemcpyDeviceToHost));
-  return OB_OK;
-}
-
-static void binary_free(BinaryState* s) { delete s; }
-
-// installs the builder's hooks when the library loads (ob_binary.hpp)
-static const bool g_binary_hooks_installed = [] {
-  BinaryHooks& h = binary_hooks();
-  h.boot_device = binary_boot_device;
-  h.boot_host = binary_boot_host;
-  h.free_state = binary_free;
-  return true;
-}();
+// installs the builder's hooks when the library loads (ob_model.hpp)
+static const bool g_binary_hooks_installed = model_install(
+    kModelBinary, {binary_boot_device, model_boot_host, [](void* s) { delete static_cast<BinaryState*>(s); }});
 
 // Every check of the frame entry points, before any device work and before the context is read:
-// settings outside the scope, nulls in named columns, the design (ob_builder_data_matrices), the
+// settings outside the scope, nulls in named columns, the design (ob::data_matrices), the
 // outcome's values, the shape. On success m holds the design matrices.
 static int binary_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
-                        int32_t model, Config& c, ob_matrices** m) {
+                        int32_t model, Config& c, Matrices& m) {
   OB_TRY(config_from(cfg, c));
   if (model == OB_BINARY_LOGIT)
     return fail(OB_E_UNSUPPORTED, "binary decomposition: the logit link is outside the engine's scope (the "
                                   "per-replicate fit kernels are probit's)");
   if (model != OB_BINARY_PROBIT) return fail(OB_E_INVALID, "binary decomposition: unknown model %d", model);
-  if (c.has_weights) return fail(OB_E_UNSUPPORTED, "binary decomposition: sample weights are outside its scope");
-  if (!c.normalize.empty())
-    return fail(OB_E_UNSUPPORTED, "binary decomposition: normalized categoricals are outside its scope");
-  if (c.has_selection || !c.selection_predictors.empty())
-    return fail(OB_E_UNSUPPORTED, "binary decomposition: Heckman selection settings are outside its scope");
+  if (c.has_weights) return model_refuse(kModelBinary, "sample weights are");
+  if (!c.normalize.empty()) return model_refuse(kModelBinary, "normalized categoricals are");
+  if (c.has_selection || !c.selection_predictors.empty()) return model_refuse(kModelBinary, "Heckman selection settings are");
   if (c.ref == OB_REF_POOLED || c.ref == OB_REF_NEUMARK)
-    return fail(OB_E_UNSUPPORTED, "binary decomposition: pooled reference coefficients need a third, stacked probit "
-                                  "and are outside its scope");
-  Frame f;
-  OB_TRY(load_frame(cols, n_cols, n_rows, f));
-  std::vector<std::string> named = {c.outcome, c.group};
-  named.insert(named.end(), c.predictors.begin(), c.predictors.end());
-  named.insert(named.end(), c.categorical.begin(), c.categorical.end());
-  for (const std::string& name : named) {
-    const int i = f.find(name);
-    if (i < 0) return fail(OB_E_COLUMN, "%s%s", error_prefix(OB_E_COLUMN), name.c_str());
-    for (int64_t r = 0; r < f.nrows; ++r)
-      if (!f.cols[i].valid[r])
-        return fail(OB_E_INVALID, "binary decomposition: column `%s` has a null in row %lld", name.c_str(), (long long)r);
-  }
-  OB_TRY(ob_builder_data_matrices(cols, n_cols, n_rows, cfg, m));
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  const double *xa, *ya, *xb, *yb;
-  int rc = ob_matrices_dims(*m, &n_a, &n_b, &k);
-  if (rc == OB_OK) rc = ob_matrices_get(*m, &xa, &ya, &xb, &yb);
-  if (rc == OB_OK && k > kBinaryMaxK) rc = binary_check_shape(k, n_a, n_b);
-  for (int g = 0; g < 2 && rc == OB_OK; ++g) {
-    const double* y = g ? yb : ya;
-    const int64_t n = g ? n_b : n_a;
+    return model_refuse(kModelBinary, "pooled reference coefficients need a third, stacked probit and are");
+  OB_TRY(stage_named(cols, n_cols, n_rows, c, kModelBinary, false, false));
+  OB_TRY(m.load(cols, n_cols, n_rows, cfg, false));
+  if (m.k > kBinaryMaxK) OB_TRY(binary_check_shape(m.k, m.n[0], m.n[1]));
+  for (int g = 0; g < 2; ++g) {
+    const int64_t n = m.n[g];
     int64_t ones = 0;
-    for (int64_t i = 0; i < n && rc == OB_OK; ++i) {
-      if (y[i] != 0.0 && y[i] != 1.0)
-        rc = fail(OB_E_INVALID, "binary decomposition: the outcome must be exactly 0.0 or 1.0, got %g", y[i]);
-      ones += y[i] == 1.0 ? 1 : 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const double y = m.y[g][i];
+      if (y != 0.0 && y != 1.0) return fail(OB_E_INVALID, "binary decomposition: the outcome must be exactly 0.0 or 1.0, got %g", y);
+      ones += y == 1.0 ? 1 : 0;
     }
-    if (rc == OB_OK && n == 0) rc = fail(OB_E_GROUP, "%sOne group has no data", error_prefix(OB_E_GROUP));
-    if (rc == OB_OK && (ones == 0 || ones == n))
-      rc = fail(OB_E_INVALID, "binary decomposition: the outcome of group %c is constant", g ? 'B' : 'A');
+    if (n == 0) return fail(OB_E_GROUP, "%sOne group has no data", error_prefix(OB_E_GROUP));
+    if (ones == 0 || ones == n)
+      return fail(OB_E_INVALID, "binary decomposition: the outcome of group %c is constant", g ? 'B' : 'A');
   }
-  if (rc == OB_OK) rc = binary_check_shape(k, n_a, n_b);
-  if (rc != OB_OK) {
-    ob_matrices_free(*m);
-    *m = nullptr;
-  }
-  return rc;
+  return binary_check_shape(m.k, m.n[0], m.n[1]);
 }
 
 static int binary_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
                           const ob_builder_config* cfg, int32_t model, ob_prepared** out) {
   Config c;
-  ob_matrices* m = nullptr;
-  OB_TRY(binary_stage(cols, n_cols, n_rows, cfg, model, c, &m));
-  struct Guard {
-    ob_matrices* m;
-    ~Guard() { ob_matrices_free(m); }
-  } guard{m};
+  Matrices m;
+  OB_TRY(binary_stage(cols, n_cols, n_rows, cfg, model, c, m));
   if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  const double *xa, *ya, *xb, *yb;
-  OB_TRY(ob_matrices_dims(m, &n_a, &n_b, &k));
-  OB_TRY(ob_matrices_get(m, &xa, &ya, &xb, &yb));
-  ob_panel_desc pd{};  // the resampler: the groups' row counts and the outcome
-  pd.p = 0;
-  pd.n_y = 1;
-  pd.a = {n_a, nullptr, n_a, ya, nullptr};
-  pd.b = {n_b, nullptr, n_b, yb, nullptr};
-  ob_prepared* pr = new ob_prepared();
-  pr->ctx = ctx;
-  pr->cfg = c;
-  pr->ref = c.ref;
-  if (c.has_seed) {
-    pr->seed = c.seed;
-  } else {
-    std::random_device rd;
-    pr->seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
-  }
-  pr->k = k;
-  pr->n_base = 0;
-  pr->row_len = binary_row_len(k);
-  for (int32_t j = 0; j < k; ++j) pr->names.emplace_back(ob_matrices_name(m, j));
-  pr->detail_names = pr->names;
-  pr->n_a = n_a;
-  pr->n_b = n_b;
-  pr->n_y = 1;
-  pr->n_resid = 0;
   BinaryState* st = new BinaryState();
-  st->k = k;
-  pr->binary = st;
+  st->k = m.k;
+  ob_prepared* pr = model_handle(ctx, c, m, kModelBinary, st, binary_row_len(m.k), 1);
   auto build = [&]() -> int {
-    OB_TRY(ob_panel_create(ctx, &pd, &pr->panel));
-    ob_panel* p = pr->panel;
-    for (int g = 0; g < 2; ++g) {  // [y | x_1 ..] x ld, zero past n (x of ob_matrices: column 0 is the intercept)
-      const int64_t n = g ? n_b : n_a;
-      const double* x = g ? xb : xa;
-      const double* y = g ? yb : ya;
-      const size_t bytes = sizeof(double) * (size_t)k * p->ld[g];
-      OB_HIP(st->cols[g].alloc(bytes));
-      OB_HIP(hipMemset(st->cols[g].p, 0, bytes));
-      OB_HIP(hipMemcpy(st->cols[g].p, y, sizeof(double) * n, hipMemcpyHostToDevice));
-      if (k > 1)
-        OB_HIP(hipMemcpy2D(st->cols[g].d() + p->ld[g], sizeof(double) * p->ld[g], x + n, sizeof(double) * n,
-                           sizeof(double) * n, k - 1, hipMemcpyHostToDevice));
-    }
-    int32_t nc = 0;
-    OB_TRY(ob_debug_chunks(p, nullptr, 0, &nc));
-    std::vector<uint32_t> table((size_t)3 * nc);
-    OB_TRY(ob_debug_chunks(p, table.data(), nc, &nc));
-    st->n_chunks = nc;
-    OB_HIP(st->chunks.alloc(sizeof(uint32_t) * table.size()));
-    OB_HIP(hipMemcpy(st->chunks.p, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
+    OB_TRY(outcome_panel(ctx, m, &pr->panel));
+    for (int g = 0; g < 2; ++g) OB_TRY(upload_group(st->cols[g], pr->panel->ld[g], m.n[g], m.k, 0, m.y[g], m.x[g]));
+    OB_TRY(upload_chunks(pr->panel, st->chunks, &st->n_chunks));
     g_timing = {};
     return binary_point(pr, st);
   };
-  const int rc = build();
-  if (rc != OB_OK) {
-    ob_prepared_destroy(pr);
-    return rc;
-  }
-  *out = pr;
-  return OB_OK;
+  return model_built(pr, build(), out);
 }
 
 }  // namespace ob

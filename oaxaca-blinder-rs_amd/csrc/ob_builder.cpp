@@ -27,13 +27,10 @@
 #include "ob_frame.hpp"
 #include "ob_host.hpp"
 #include "ob_builder.hpp"
-#include "ob_binary.hpp"
-#include "ob_reweight.hpp"
 #include "ob_cluster.hpp"
 #include "ob_mm.hpp"
+#include "ob_model.hpp"
 #include "ob_rif.hpp"
-#include "ob_rifq.hpp"
-#include "ob_rifs.hpp"
 #include "ob_spec.h"
 
 namespace ob {
@@ -43,29 +40,11 @@ ClusterHooks& cluster_hooks() {
   return h;
 }
 
-BinaryHooks& binary_hooks() {
-  static BinaryHooks h;
-  return h;
+ModelHooks& model_hooks(int kind) {
+  static ModelHooks h[kModelKinds];
+  return h[kind];
 }
 
-ReweightHooks& reweight_hooks() {
-  static ReweightHooks h;
-  return h;
-}
-
-DrHooks& dr_hooks() {
-  static DrHooks h;
-  return h;
-}
-
-RifqHooks& rifq_hooks() {
-  static RifqHooks h;
-  return h;
-}
-RifsHooks& rifs_hooks() {
-  static RifsHooks h;
-  return h;
-}
 RifHooks& rif_hooks() {
   static RifHooks h;
   return h;
@@ -662,8 +641,8 @@ int dr_finish_rows(const double* point, int T, int nq, const double* rows, const
 
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block).
 int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
-  if (pr->reweight) return reweight_finish(pr, rows, ok, n_reps, out);
-  if (pr->dr) {
+  if (pr->model_kind == kModelReweight) return reweight_finish(pr, rows, ok, n_reps, out);
+  if (pr->model_kind == kModelDr) {
     OB_TRY(dr_finish_rows(pr->point_row.data(), (int)pr->dr_info.thresholds.size(), (int)pr->dr_info.taus.size(), rows, ok,
                           n_reps, out));
     (*out)->n_a = pr->n_a;
@@ -1024,22 +1003,14 @@ ob_panel* ob_prepared_panel(ob_prepared* p) { return p ? p->panel : nullptr; }
 int ob_prepared_boot(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
   if (p->cluster) return ob::cluster_hooks().boot_host(p, first_rep, n_reps, rows, ok);
-  if (p->binary) return ob::binary_hooks().boot_host(p, first_rep, n_reps, rows, ok);
-  if (p->reweight) return ob::reweight_hooks().boot_host(p, first_rep, n_reps, rows, ok);
-  if (p->dr) return ob::dr_hooks().boot_host(p, first_rep, n_reps, rows, ok);
-  if (p->rifq) return ob::rifq_hooks().boot_host(p, first_rep, n_reps, rows, ok);
-  if (p->rifs) return ob::rifs_hooks().boot_host(p, first_rep, n_reps, rows, ok);
+  if (p->model) return ob::model_hooks(p->model_kind).boot_host(p, first_rep, n_reps, rows, ok);
   return ob_boot_run(p->panel, p->seed, first_rep, n_reps, p->ref, rows, ok);
 }
 
 int ob_prepared_boot_sharded(ob_prepared* p, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
   if (!p) return ob::fail(OB_E_INVALID, "null pointer");
   if (p->cluster) return ob::fail(OB_E_UNSUPPORTED, "cluster bootstrap: sharded runs are outside its scope");
-  if (p->binary) return ob::fail(OB_E_UNSUPPORTED, "binary decomposition: sharded runs are outside its scope");
-  if (p->reweight) return ob::fail(OB_E_UNSUPPORTED, "reweighted decomposition: sharded runs are outside its scope");
-  if (p->dr) return ob::fail(OB_E_UNSUPPORTED, "distribution regression: sharded runs are outside its scope");
-  if (p->rifq) return ob::fail(OB_E_UNSUPPORTED, "quantile refit: sharded runs are outside its scope");
-  if (p->rifs) return ob::fail(OB_E_UNSUPPORTED, "statistics refit: sharded runs are outside its scope");
+  if (p->model) return ob::model_refuse(p->model_kind, "sharded runs are");
   // the RCCL all-gather moves only the columns finish() aggregates: two-fold, three-fold, total
   // gap, detailed [0, 6 + 2 Kd) and a Heckman row's selection terms after its 5K' tail
   const int kd = p->k + p->n_base, sel0 = 6 + 2 * kd + 5 * p->k;
@@ -1061,16 +1032,9 @@ int ob_prepared_boot_device(ob_prepared* p, uint64_t first_rep, uint64_t n_reps,
   if (p->cluster)
     return ob::cluster_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok,
                                            reinterpret_cast<hipStream_t>(hip_stream));
-  if (p->binary)
-    return ob::binary_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
-  if (p->reweight)
-    return ob::reweight_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
-  if (p->dr)
-    return ob::dr_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
-  if (p->rifq)
-    return ob::rifq_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
-  if (p->rifs)
-    return ob::rifs_hooks().boot_device(p, first_rep, n_reps, d_rows, d_ok, reinterpret_cast<hipStream_t>(hip_stream));
+  if (p->model)
+    return ob::model_hooks(p->model_kind).boot_device(p, first_rep, n_reps, d_rows, d_ok,
+                                                      reinterpret_cast<hipStream_t>(hip_stream));
   return ob_boot_run_device(p->panel, p->seed, first_rep, n_reps, p->ref, d_rows, d_ok, hip_stream);
 }
 
@@ -1083,11 +1047,7 @@ int ob_prepared_finish(ob_prepared* p, const double* rows, const uint8_t* ok, ui
 void ob_prepared_destroy(ob_prepared* p) {
   if (!p) return;
   if (p->cluster) ob::cluster_hooks().free_state(p->cluster);
-  if (p->binary) ob::binary_hooks().free_state(p->binary);
-  if (p->reweight) ob::reweight_hooks().free_state(p->reweight);
-  if (p->dr) ob::dr_hooks().free_state(p->dr);
-  if (p->rifq) ob::rifq_hooks().free_state(p->rifq);
-  if (p->rifs) ob::rifs_hooks().free_state(p->rifs);
+  if (p->model) ob::model_hooks(p->model_kind).free_state(p->model);
   ob_panel_destroy(p->panel);
   delete p;
 }

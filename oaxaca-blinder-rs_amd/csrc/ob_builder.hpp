@@ -33,10 +33,6 @@ struct Config {
 };
 
 struct ClusterState;
-struct BinaryState;
-struct ReweightState;
-struct RifqState;
-struct RifsState;
 
 }  // namespace ob
 
@@ -74,17 +70,11 @@ struct ob_prepared {
   bool has_jack = false;
   // ob_builder_prepare_clustered: the cluster index and Q on the device; boots run through ob_cluster.hip
   ob::ClusterState* cluster = nullptr;
-  // ob_builder_prepare_binary: the probit panel and workspace on the device; boots run through ob_binary.hip
-  ob::BinaryState* binary = nullptr;
-  // ob_builder_prepare_reweighted: the three-fit panel and workspace on the device; boots run through ob_reweight.hip
-  ob::ReweightState* reweight = nullptr;
-  // ob_builder_prepare_dr: the panel, fits and workspace on the device (boots run through ob_dr.hip) and the
-  // thresholds, quantiles and point fits on the host
-  ob::DrState* dr = nullptr;
-  // ob_builder_prepare_quantiles_refit: the y-sorted panel and the refit's workspace; boots run through ob_rifq.hip
-  ob::RifqState* rifq = nullptr;
-  // ob_builder_prepare_statistics_refit: the y-sorted panel and the refit's workspace; boots run through ob_rifs.hip
-  ob::RifsState* rifs = nullptr;
+  // a model front end's handle (ob_model.hpp): its ob::ModelKind and its state on the device; boots run through the
+  // kind's hooks
+  int model_kind = 0;
+  void* model = nullptr;
+  // ob_builder_prepare_dr: the thresholds, quantiles and point fits on the host
   ob::DrInfo dr_info;
 };
 

@@ -130,7 +130,7 @@ static int prepared_cluster_jack_check(const ob_prepared* p, int want_rows) {
   if (!p) return fail(OB_E_INVALID, "null pointer");
   if (!p->cluster) return fail(OB_E_INVALID, "this prepared run is not clustered");
   // no clustered handle of these kinds exists today; BCa for them stays out of scope when one does
-  if (p->binary || p->reweight || p->dr || p->rifq || p->rifs)
+  if (p->model)
     return fail(OB_E_UNSUPPORTED, "cluster jackknife: binary, reweighted and distribution-regression decompositions "
                                   "(BCa included) are outside its scope");
   if (!cluster_hooks().jack || !cluster_hooks().info) return fail(OB_E_UNSUPPORTED, "this build carries no cluster jackknife");

@@ -22,7 +22,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -31,6 +30,7 @@
 #include "ob_dr.hpp"
 #include "ob_engine.hpp"
 #include "ob_hip.hpp"
+#include "ob_model.hpp"
 #include "ob_options.hpp"
 #include "ob_spec.h"
 
@@ -598,9 +598,7 @@ struct DrState {
   int n_chunks = 0;
 };
 
-constexpr size_t kDrPartialBudget = (size_t)1 << 30;  // bytes of chunk partials per batch
-constexpr uint64_t kDrSegReps = 4096;                 // replicates per segment of count images
-constexpr uint64_t kDrCountBudget = 8ull << 30;       // bytes of count images per segment
+static DrState* dr_state(const ob_prepared* pr) { return model_state<DrState>(pr, kModelDr); }
 
 static DrArgs dr_args(const ob_prepared* pr, const DrState* st) {
   const ob_panel* p = pr->panel;
@@ -628,15 +626,10 @@ static size_t dr_rep_bytes(const DrState* st) {  // chunk partials of one replic
   return (size_t)st->n_chunks * ((size_t)st->T * dr_nv(st->k) + 2 * st->T + 1) * sizeof(double);
 }
 
-// Replicates per batch: as many as keep the chunk partials within the budget, in whole 64-replicate blocks where
-// more than one fits (option hk_batch forces at most that many blocks, as on the Heckman path). Rows do not depend
-// on it.
+// Replicates per batch (boot_batch_reps), below 64 where one replicate's partials are that large (the kernels take
+// any batch through img0), and at most the grid's z extent.
 static uint32_t dr_batch_reps(const DrState* st, uint32_t rep_pad) {
-  size_t reps = std::max<size_t>(1, kDrPartialBudget / std::max<size_t>(dr_rep_bytes(st), 1));
-  if (reps >= 64) reps = reps / 64 * 64;
-  const int forced = opt_int(Opt::HkBatch, 0);
-  if (forced > 0) reps = std::min<size_t>(reps, (size_t)forced * 64);
-  return (uint32_t)std::min<size_t>(std::min<size_t>(rep_pad, reps), kDrMaxBatch);
+  return std::min(boot_batch_reps(dr_rep_bytes(st), rep_pad, true), kDrMaxBatch);
 }
 
 static int dr_ensure(DrState* st, uint32_t hb) {
@@ -703,204 +696,84 @@ static int dr_point(ob_prepared* pr, DrState* st) {
 
 static int dr_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
                           hipStream_t stream) {
-  if (!pr || !pr->dr || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  if (first_rep + n_reps > 0xFFFFFFFFull)
-    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 counter word)");
-  DrState* st = pr->dr;
-  ob_panel* p = pr->panel;
-  OB_HIP(hipSetDevice(p->ctx->device));
-  hipStream_t s = stream ? stream : p->ctx->stream;
-  OB_TRY(engine_order(p, s));
-  g_timing = {};
-  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
-  const uint64_t batch_bytes = (uint64_t)std::max(tiles, 1u) * 4 * kCimgWords * sizeof(uint32_t);
-  const uint64_t seg_cap = std::max<uint64_t>(64, (kDrCountBudget / batch_bytes) * 64);
-  const uint64_t seg = std::min<uint64_t>(n_reps, std::min<uint64_t>(kDrSegReps, seg_cap));
-  const uint32_t seg_pad = (uint32_t)((seg + 63) / 64 * 64);
-  const uint32_t hb = dr_batch_reps(st, seg_pad);
-  OB_TRY(dr_ensure(st, hb));
-  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
-  int rc = OB_OK;
-  for (uint64_t s0 = 0; s0 < n_reps && rc == OB_OK; s0 += seg) {
-    const uint32_t ns = (uint32_t)std::min<uint64_t>(seg, n_reps - s0);
-    uint32_t nb_rep = 0, rep_pad = 0;
-    rc = engine_counts(p, pr->seed, first_rep + s0, ns, s, &nb_rep, &rep_pad);
-    if (rc != OB_OK) break;
-    for (uint32_t b0 = 0; b0 < ns && rc == OB_OK; b0 += hb) {
+  DrState* st = dr_state(pr);
+  uint32_t hb = 0;
+  const BootPlan plan{kFitSegReps, kCountBudget, true, [&](uint32_t seg_pad) {
+                        g_timing = {};
+                        hb = dr_batch_reps(st, seg_pad);
+                        return dr_ensure(st, hb);
+                      }};
+  return boot_segmented(pr, kModelDr, plan, first_rep, n_reps, d_rows && d_ok, stream,
+                        [&](uint64_t s0, uint32_t ns, uint32_t nb_rep, uint32_t, hipStream_t s) {
+    return boot_batches(ns, hb, [&](uint32_t b0, uint32_t nb) {
       DrArgs h = dr_args(pr, st);
       dr_bind(h, st, hb);
-      h.counts = p->d_counts;
+      h.counts = pr->panel->d_counts;
       h.nb_rep = nb_rep;
       h.img0 = b0;
-      h.n_reps = std::min(hb, ns - b0);
+      h.n_reps = nb;
       h.rows = d_rows + (s0 + b0) * pr->row_len;
       h.ok = d_ok + s0 + b0;
-      rc = dr_batch(h, s);
-    }
-  }
-  uint32_t flag = 0;
-  if (rc == OB_OK && hipMemcpyAsync(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = fail(OB_E_HIP, "copy of the overflow word failed");
-  if (rc == OB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(OB_E_HIP, "stream synchronize failed");
-  const int rm = engine_mark(p, s);
-  if (rc != OB_OK) return rc;
-  if (flag & 1u) return fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
-  return rm;
+      return dr_batch(h, s);
+    });
+  });
 }
 
-static int dr_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
-  if (!pr || !pr->dr || (n_reps && (!rows || !ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  OB_HIP(hipSetDevice(pr->panel->ctx->device));
-  DevBuf d_rows, d_ok;
-  OB_HIP(d_rows.alloc(sizeof(double) * n_reps * pr->row_len));
-  OB_HIP(d_ok.alloc(n_reps));
-  OB_TRY(dr_boot_device(pr, first_rep, n_reps, d_rows.d(), d_ok.as<uint8_t>(), nullptr));
-  OB_HIP(hipMemcpy(rows, d_rows.p, sizeof(double) * n_reps * pr->row_len, hipMemcpyDeviceToHost));
-  OB_HIP(hipMemcpy(ok, d_ok.p, n_reps, hipMemcpyDeviceToHost));
-  return OB_OK;
-}
-
-static void dr_free(DrState* s) { delete s; }
-
-// installs the builder's hooks when the library loads (ob_dr.hpp)
-static const bool g_dr_hooks_installed = [] {
-  DrHooks& h = dr_hooks();
-  h.boot_device = dr_boot_device;
-  h.boot_host = dr_boot_host;
-  h.free_state = dr_free;
-  return true;
-}();
+// installs the builder's hooks when the library loads (ob_model.hpp)
+static const bool g_dr_hooks_installed =
+    model_install(kModelDr, {dr_boot_device, model_boot_host, [](void* s) { delete static_cast<DrState*>(s); }});
 
 // Every check of the frame entry points, before any device work and before the context is read: the thresholds
 // and quantiles, settings outside the scope, nulls and non-finite values in named columns, the design
 // (ob::data_matrices), the shape. On success m holds the design matrices and the groups' weights.
 static int dr_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
-                    const ob_dr_config* dr, Config& c, ob_matrices** m) {
+                    const ob_dr_config* dr, Config& c, Matrices& m) {
   OB_TRY(config_from(cfg, c));
-  if (!c.normalize.empty())
-    return fail(OB_E_UNSUPPORTED, "distribution regression: normalized categoricals are outside its scope");
-  if (c.has_selection || !c.selection_predictors.empty())
-    return fail(OB_E_UNSUPPORTED, "distribution regression: Heckman selection settings are outside its scope");
-  if (c.has_cluster) return fail(OB_E_UNSUPPORTED, "distribution regression: the cluster bootstrap is outside its scope");
+  if (!c.normalize.empty()) return model_refuse(kModelDr, "normalized categoricals are");
+  if (c.has_selection || !c.selection_predictors.empty()) return model_refuse(kModelDr, "Heckman selection settings are");
+  if (c.has_cluster) return model_refuse(kModelDr, "the cluster bootstrap is");
   OB_TRY(dr_config_check(dr));
-  Frame f;
-  OB_TRY(load_frame(cols, n_cols, n_rows, f));
-  std::vector<std::string> named = {c.outcome, c.group};
-  named.insert(named.end(), c.predictors.begin(), c.predictors.end());
-  named.insert(named.end(), c.categorical.begin(), c.categorical.end());
-  if (c.has_weights) named.push_back(c.weights);
-  for (const std::string& name : named) {
-    const int i = f.find(name);
-    if (i < 0) return fail(OB_E_COLUMN, "%s%s", error_prefix(OB_E_COLUMN), name.c_str());
-    const Col& col = f.cols[i];
-    for (int64_t r = 0; r < f.nrows; ++r) {
-      if (!col.valid[r])
-        return fail(OB_E_INVALID, "distribution regression: column `%s` has a null in row %lld", name.c_str(), (long long)r);
-      if (col.kind == OB_COL_F64 && !std::isfinite(col.f[r]))
-        return fail(OB_E_INVALID, "distribution regression: column `%s` has a non-finite value in row %lld", name.c_str(),
-                    (long long)r);
-    }
-  }
-  OB_TRY(data_matrices(cols, n_cols, n_rows, cfg, true, m));
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  int rc = ob_matrices_dims(*m, &n_a, &n_b, &k);
-  if (rc == OB_OK && k > kDrMaxK) rc = dr_check_shape(k, n_a, n_b, dr->n_thresholds, dr->n_quantiles);
-  if (rc == OB_OK && (n_a == 0 || n_b == 0)) rc = fail(OB_E_GROUP, "%sOne group has no data", error_prefix(OB_E_GROUP));
-  if (rc == OB_OK) rc = dr_check_shape(k, n_a, n_b, dr->n_thresholds, dr->n_quantiles);
-  if (rc != OB_OK) {
-    ob_matrices_free(*m);
-    *m = nullptr;
-  }
-  return rc;
+  OB_TRY(stage_named(cols, n_cols, n_rows, c, kModelDr, true, true));
+  OB_TRY(m.load(cols, n_cols, n_rows, cfg, true));
+  if (m.k > kDrMaxK) OB_TRY(dr_check_shape(m.k, m.n[0], m.n[1], dr->n_thresholds, dr->n_quantiles));
+  if (m.n[0] == 0 || m.n[1] == 0) return fail(OB_E_GROUP, "%sOne group has no data", error_prefix(OB_E_GROUP));
+  return dr_check_shape(m.k, m.n[0], m.n[1], dr->n_thresholds, dr->n_quantiles);
 }
 
 static int dr_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
                       const ob_dr_config* dr, ob_prepared** out) {
   Config c;
-  ob_matrices* m = nullptr;
-  OB_TRY(dr_stage(cols, n_cols, n_rows, cfg, dr, c, &m));
-  struct Guard {
-    ob_matrices* m;
-    ~Guard() { ob_matrices_free(m); }
-  } guard{m};
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  const double *xa, *ya, *xb, *yb;
-  OB_TRY(ob_matrices_dims(m, &n_a, &n_b, &k));
-  OB_TRY(ob_matrices_get(m, &xa, &ya, &xb, &yb));
+  Matrices m;
+  OB_TRY(dr_stage(cols, n_cols, n_rows, cfg, dr, c, m));
+  const int k = m.k;
   std::vector<double> thr;
   if (dr->thresholds) {
     thr.assign(dr->thresholds, dr->thresholds + dr->n_thresholds);
   } else {
-    std::vector<double> pooled(ya, ya + n_a);
-    pooled.insert(pooled.end(), yb, yb + n_b);
+    std::vector<double> pooled(m.y[0], m.y[0] + m.n[0]);
+    pooled.insert(pooled.end(), m.y[1], m.y[1] + m.n[1]);
     OB_TRY(dr_count_thresholds(std::move(pooled), dr->n_thresholds, dr->lo, dr->hi, thr));
     if (thr.size() < 2)
       return fail(OB_E_INVALID, "distribution regression: fewer than two distinct thresholds are left of %d", dr->n_thresholds);
   }
   const int T = (int)thr.size(), nq = dr->n_quantiles;
   if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
-  ob_panel_desc pd{};  // the resampler: the groups' row counts and the outcome
-  pd.p = 0;
-  pd.n_y = 1;
-  pd.a = {n_a, nullptr, n_a, ya, nullptr};
-  pd.b = {n_b, nullptr, n_b, yb, nullptr};
-  ob_prepared* pr = new ob_prepared();
-  pr->ctx = ctx;
-  pr->cfg = c;
-  pr->ref = c.ref;
-  if (c.has_seed) {
-    pr->seed = c.seed;
-  } else {
-    std::random_device rd;
-    pr->seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
-  }
-  pr->k = k;
-  pr->n_base = 0;
-  pr->row_len = dr_row_len(T, nq);
-  for (int32_t j = 0; j < k; ++j) pr->names.emplace_back(ob_matrices_name(m, j));
-  pr->detail_names = pr->names;
-  pr->n_a = n_a;
-  pr->n_b = n_b;
-  pr->n_y = 1;
-  pr->n_resid = 0;
-  pr->dr_info.thresholds = thr;
-  pr->dr_info.taus.assign(dr->quantiles, dr->quantiles + nq);
-  pr->dr_info.n_requested = dr->n_thresholds;
   DrState* st = new DrState();
   st->k = k;
   st->T = T;
   st->nq = nq;
-  pr->dr = st;
+  ob_prepared* pr = model_handle(ctx, c, m, kModelDr, st, dr_row_len(T, nq), 1);
+  pr->dr_info.thresholds = thr;
+  pr->dr_info.taus.assign(dr->quantiles, dr->quantiles + nq);
+  pr->dr_info.n_requested = dr->n_thresholds;
   auto build = [&]() -> int {
-    OB_TRY(ob_panel_create(ctx, &pd, &pr->panel));
+    OB_TRY(outcome_panel(ctx, m, &pr->panel));
     ob_panel* p = pr->panel;
-    for (int g = 0; g < 2; ++g) {  // [y | x_1 .. | w] x ld, zero past n (x of ob_matrices: column 0 is the intercept)
-      const int64_t n = g ? n_b : n_a;
-      const double* x = g ? xb : xa;
-      const double* y = g ? yb : ya;
-      const double* w = matrices_weights(m, g);
-      const size_t bytes = sizeof(double) * (size_t)(k + 1) * p->ld[g];
-      OB_HIP(st->cols[g].alloc(bytes));
-      OB_HIP(hipMemset(st->cols[g].p, 0, bytes));
-      OB_HIP(hipMemcpy(st->cols[g].p, y, sizeof(double) * n, hipMemcpyHostToDevice));
-      if (k > 1)
-        OB_HIP(hipMemcpy2D(st->cols[g].d() + p->ld[g], sizeof(double) * p->ld[g], x + n, sizeof(double) * n,
-                           sizeof(double) * n, k - 1, hipMemcpyHostToDevice));
-      const std::vector<double> unit(w ? 0 : (size_t)n, 1.0);
-      OB_HIP(hipMemcpy(st->cols[g].d() + (size_t)k * p->ld[g], w ? w : unit.data(), sizeof(double) * n,
-                       hipMemcpyHostToDevice));
+    for (int g = 0; g < 2; ++g) {  // [y | x_1 .. | w] x ld
+      OB_TRY(upload_group(st->cols[g], p->ld[g], m.n[g], k, 1, m.y[g], m.x[g]));
+      OB_TRY(upload_weights(st->cols[g], p->ld[g], m.n[g], k, m.w(g)));
     }
-    int32_t nc = 0;
-    OB_TRY(ob_debug_chunks(p, nullptr, 0, &nc));
-    std::vector<uint32_t> table((size_t)3 * nc);
-    OB_TRY(ob_debug_chunks(p, table.data(), nc, &nc));
-    st->n_chunks = nc;
-    OB_HIP(st->chunks.alloc(sizeof(uint32_t) * table.size()));
-    OB_HIP(hipMemcpy(st->chunks.p, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
+    OB_TRY(upload_chunks(p, st->chunks, &st->n_chunks));
     OB_HIP(st->thr.alloc(sizeof(double) * T));
     OB_HIP(hipMemcpy(st->thr.p, thr.data(), sizeof(double) * T, hipMemcpyHostToDevice));
     OB_HIP(st->taus.alloc(sizeof(double) * nq));
@@ -908,13 +781,7 @@ static int dr_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_
     g_timing = {};
     return dr_point(pr, st);
   };
-  const int rc = build();
-  if (rc != OB_OK) {
-    ob_prepared_destroy(pr);
-    return rc;
-  }
-  *out = pr;
-  return OB_OK;
+  return model_built(pr, build(), out);
 }
 
 // The array pieces: one launch of a pass kernel over one group of n rows (x: n x k column-major with ld ldx, column
@@ -929,13 +796,8 @@ static int dr_piece(ob_ctx* ctx, bool cdf, int k, const double* x, int64_t ldx, 
   const uint32_t n = (uint32_t)n64, tiles = (n + OB_TILE_ROWS - 1) / OB_TILE_ROWS;
   const int64_t ld = (int64_t)tiles * OB_TILE_ROWS;
   std::vector<uint32_t> chunks;
-  const uint32_t nc = std::min<uint32_t>(tiles, 64u);
-  for (uint32_t c = 0; c < nc; ++c) {
-    chunks.push_back(0u);
-    chunks.push_back((uint32_t)((uint64_t)tiles * c / nc));
-    chunks.push_back((uint32_t)((uint64_t)tiles * (c + 1) / nc));
-  }
-  const int n_chunks = (int)nc, nv = dr_nv(k);
+  group_chunks(0u, tiles, 64u, chunks);
+  const int n_chunks = (int)(chunks.size() / 3), nv = dr_nv(k);
   const int n_vec = cdf ? m : T;
   const size_t per = cdf ? (size_t)m + 1 : (size_t)T * nv;
   DevBuf d_cols, d_chunks, d_beta, d_flags, d_partial, d_counts, d_thr;
@@ -963,10 +825,7 @@ static int dr_piece(ob_ctx* ctx, bool cdf, int k, const double* x, int64_t ldx, 
   std::vector<uint32_t> img;  // one 64-replicate block of the f64 Gram's count images (ob_engine.hpp), slot 0
   if (counts) {
     img.assign((size_t)tiles * 4 * kCimgWords, 0u);
-    for (uint32_t i = 0; i < n; ++i) {
-      const size_t t = i / OB_TILE_ROWS, within = i % OB_TILE_ROWS, sub = within >> 6, qq = within & 63;
-      img[(t * 4 + sub) * kCimgWords + (qq >> 2)] |= (uint32_t)counts[i] << (8 * (qq & 3));
-    }
+    pack_count_images(counts, n, n, 1, 1, img.data(), nullptr, 0);
     OB_HIP(d_counts.alloc(sizeof(uint32_t) * img.size()));
     OB_HIP(hipMemcpyAsync(d_counts.p, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice, s));
   }
@@ -1074,7 +933,7 @@ int ob_builder_run_dr(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_
 
 int ob_prepared_dr_info(const ob_prepared* prep, ob_dr_info* out) {
   if (!prep || !out) return ob::fail(OB_E_INVALID, "null pointer");
-  if (!prep->dr) return ob::fail(OB_E_INVALID, "not a handle of a distribution-regression decomposition");
+  if (prep->model_kind != ob::kModelDr) return ob::fail(OB_E_INVALID, "not a handle of a distribution-regression decomposition");
   const ob::DrInfo& i = prep->dr_info;
   out->n_thresholds = (int32_t)i.thresholds.size();
   out->n_quantiles = (int32_t)i.taus.size();

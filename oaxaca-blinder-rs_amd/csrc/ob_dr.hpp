@@ -1,6 +1,6 @@
 // ob_dr.hpp -- the distribution-regression decomposition of quantile gaps (Chernozhukov, Fernandez-Val and Melly
-// 2013): limits, row layout, what a prepared handle keeps on the host, and the hooks through which
-// ob_builder.cpp routes a handle that ob_builder_prepare_dr made (ob_dr.hip holds the rest).
+// 2013): limits, row layout, and what a prepared handle keeps on the host (ob_dr.hip
+// holds the rest; ob_builder.cpp routes a handle through the hooks of ob_model.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,8 +22,6 @@ inline int dr_row_len(int T, int nq) { return 6 * nq + 7 * T + 1; }
 // The checks every entry point makes before any device work.
 int dr_check_shape(int k, int64_t n_a, int64_t n_b, int T, int nq);
 
-struct DrState;  // device side of a prepared run (ob_dr.hip)
-
 // Host side of a prepared run: what dr_finish and ob_prepared_dr_info read.
 struct DrInfo {
   std::vector<double> thresholds, taus, beta;  // [T], [n_q], [2][T][k]
@@ -40,15 +38,5 @@ int dr_quantiles(const double* f, const double* thr, int T, const double* taus, 
 // finish() on rows of dr_row_len(T, nq) doubles and their point row (ob_builder.cpp).
 int dr_finish_rows(const double* point, int T, int nq, const double* rows, const uint8_t* ok, uint64_t n_reps,
                    ob_results** out);
-
-// ob_builder.cpp reaches the device code through these hooks only, so that it links without ob_dr.hip, which
-// installs them when the library loads.
-struct DrHooks {
-  int (*boot_device)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
-                     hipStream_t stream) = nullptr;
-  int (*boot_host)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) = nullptr;
-  void (*free_state)(DrState* s) = nullptr;
-};
-DrHooks& dr_hooks();  // ob_builder.cpp
 
 }  // namespace ob

@@ -16,8 +16,6 @@
                       __LINE__);                                                         \
   } while (0)
 
-namespace {
-
 // One hipMalloc that frees itself. alloc keeps an allocation that is already large enough.
 struct DevBuf {
   void* p = nullptr;
@@ -61,5 +59,3 @@ struct Events {
 
 // Blocks of 256 threads that cover n items.
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-}  // namespace

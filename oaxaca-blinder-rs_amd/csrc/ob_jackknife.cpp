@@ -10,6 +10,7 @@
 #include "ob_common.hpp"
 #include "ob_host.hpp"
 #include "ob_jackknife.hpp"
+#include "ob_model.hpp"
 
 namespace ob {
 
@@ -243,13 +244,8 @@ static int prepared_jack_check(const ob_prepared* p) {
   if (p->cluster)  // delete-one-row is the wrong jackknife under clustering
     return fail(OB_E_UNSUPPORTED, "jackknife: a clustered run takes the delete-one-cluster pass "
                                   "(ob_prepared_cluster_jackknife, ob_prepared_finish_cluster_bca)");
-  if (p->binary) return fail(OB_E_UNSUPPORTED, "jackknife: binary decompositions (BCa included) are outside its scope");
-  if (p->rifq) return fail(OB_E_UNSUPPORTED, "jackknife: refitted quantile decompositions (BCa included) are outside its scope");
-  if (p->rifs) return fail(OB_E_UNSUPPORTED, "jackknife: refitted statistic decompositions (BCa included) are outside its scope");
-  if (p->reweight)
-    return fail(OB_E_UNSUPPORTED, "jackknife: reweighted decompositions (BCa included) are outside its scope");
-  if (p->dr)
-    return fail(OB_E_UNSUPPORTED, "jackknife: distribution-regression decompositions (BCa included) are outside its scope");
+  if (p->model)
+    return fail(OB_E_UNSUPPORTED, "jackknife: %s (BCa included) are outside its scope", model_name(p->model_kind).plural);
   const bool heck = !p->selection_names.empty();
   return jackknife_check_shape(heck ? p->k - 1 : p->k, p->n_a, p->n_b, p->n_base > 0 || !p->cfg.normalize.empty(),
                                p->n_y, heck, 0);

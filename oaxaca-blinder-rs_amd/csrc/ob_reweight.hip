@@ -34,7 +34,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -42,6 +41,7 @@
 #include "ob_device.hpp"
 #include "ob_engine.hpp"
 #include "ob_hip.hpp"
+#include "ob_model.hpp"
 #include "ob_options.hpp"
 #include "ob_reweight.hpp"
 #include "ob_rif.hpp"
@@ -545,9 +545,7 @@ struct ReweightState {
   std::vector<std::vector<double>> point_rows;
 };
 
-constexpr size_t kRwPartialBudget = (size_t)1 << 30;  // bytes of chunk partials and Grams per batch
-constexpr uint64_t kRwSegReps = 4096;                 // replicates per segment of count images
-constexpr uint64_t kRwCountBudget = 8ull << 30;       // bytes of count images per segment
+static ReweightState* reweight_state(const ob_prepared* pr) { return model_state<ReweightState>(pr, kModelReweight); }
 
 static RwArgs rw_args(const ob_prepared* pr, const ReweightState* st) {
   const ob_panel* p = pr->panel;
@@ -566,14 +564,9 @@ static RwArgs rw_args(const ob_prepared* pr, const ReweightState* st) {
   return h;
 }
 
-// Replicates per batch: 64-replicate blocks whose chunk partials stay within the budget (option hk_batch forces
-// a smaller batch, as on the Heckman path). Rows do not depend on it.
+// Replicates per batch (boot_batch_reps) for the chunk partials and Grams of a replicate.
 static uint32_t rw_batch_reps(const ReweightState* st, uint32_t rep_pad) {
-  const size_t per64 = (size_t)st->n_chunks * 64 * (partial_vals(st->k) + partial_c_vals(st->k)) * sizeof(double);
-  size_t blocks = std::max<size_t>(1, kRwPartialBudget / std::max<size_t>(per64, 1));
-  const int forced = opt_int(Opt::HkBatch, 0);
-  if (forced > 0) blocks = std::min<size_t>(blocks, (size_t)forced);
-  return (uint32_t)std::min<size_t>(rep_pad, blocks * 64);
+  return boot_batch_reps((size_t)st->n_chunks * (partial_vals(st->k) + partial_c_vals(st->k)) * sizeof(double), rep_pad);
 }
 
 // Workspace for batches of hb replicates.
@@ -633,130 +626,63 @@ static int rw_point(ob_prepared* pr, ReweightState* st) {
   return OB_OK;
 }
 
-// d_rows / d_ok: one destination per statistic of the handle (one for the mean).
+// d_rows / d_ok: one destination per statistic of the handle (one for the mean); the multi-destination form is
+// reweight's alone, so the driver sees only whether the first pair is set.
 static int rw_boot_impl(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* const* d_rows, uint8_t* const* d_ok,
                         hipStream_t stream) {
-  if (n_reps == 0) return OB_OK;
-  if (first_rep + n_reps > 0xFFFFFFFFull)
-    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 counter word)");
-  ReweightState* st = pr->reweight;
-  ob_panel* p = pr->panel;
-  OB_HIP(hipSetDevice(p->ctx->device));
-  hipStream_t s = stream ? stream : p->ctx->stream;
-  OB_TRY(engine_order(p, s));
-  g_timing = {};
-  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
-  const uint64_t batch_bytes = (uint64_t)std::max(tiles, 1u) * 4 * kCimgWords * sizeof(uint32_t);
-  const uint64_t seg_cap = std::max<uint64_t>(64, (kRwCountBudget / batch_bytes) * 64);
-  const uint64_t seg = std::min<uint64_t>(n_reps, std::min<uint64_t>(kRwSegReps, seg_cap));
-  const uint32_t seg_pad = (uint32_t)((seg + 63) / 64 * 64);
-  const uint32_t hb = rw_batch_reps(st, seg_pad);
-  OB_TRY(rw_ensure(st, hb));
-  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
-  int rc = OB_OK;
-  for (uint64_t s0 = 0; s0 < n_reps && rc == OB_OK; s0 += seg) {
-    const uint32_t ns = (uint32_t)std::min<uint64_t>(seg, n_reps - s0);
-    uint32_t nb_rep = 0, rep_pad = 0;
-    rc = engine_counts(p, pr->seed, first_rep + s0, ns, s, &nb_rep, &rep_pad);
-    if (rc != OB_OK) break;
-    for (uint32_t b0 = 0; b0 < ns && rc == OB_OK; b0 += hb) {  // hb is a multiple of 64: whole image blocks
+  ReweightState* st = reweight_state(pr);
+  uint32_t hb = 0;
+  const BootPlan plan{kFitSegReps, kCountBudget, true, [&](uint32_t seg_pad) {
+                        g_timing = {};
+                        hb = rw_batch_reps(st, seg_pad);
+                        return rw_ensure(st, hb);
+                      }};
+  return boot_segmented(pr, kModelReweight, plan, first_rep, n_reps, d_rows[0] && d_ok[0], stream,
+                        [&](uint64_t s0, uint32_t ns, uint32_t nb_rep, uint32_t, hipStream_t s) {
+    return boot_batches(ns, hb, [&](uint32_t b0, uint32_t nb) {  // hb is a multiple of 64: whole image blocks
       RwArgs h = rw_args(pr, st);
       rw_bind(h, st, hb);
-      h.counts = p->d_counts + (size_t)(b0 / 64) * 4 * kCimgWords;
+      h.counts = pr->panel->d_counts + (size_t)(b0 / 64) * 4 * kCimgWords;
       h.nb_rep = nb_rep;
-      h.n_reps = std::min(hb, ns - b0);
+      h.n_reps = nb;
       double* rows[OB_REWEIGHT_MAX_STATS];
       uint8_t* oks[OB_REWEIGHT_MAX_STATS];
       for (int t = 0; t < std::max(st->n_stats, 1); ++t) {
         rows[t] = d_rows[t] + (s0 + b0) * pr->row_len;
         oks[t] = d_ok[t] + s0 + b0;
       }
-      rc = rw_batch(h, s, st->n_stats, rows, oks);
-    }
-  }
-  uint32_t flag = 0;
-  if (rc == OB_OK && hipMemcpyAsync(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = fail(OB_E_HIP, "copy of the overflow word failed");
-  if (rc == OB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(OB_E_HIP, "stream synchronize failed");
-  const int rm = engine_mark(p, s);
-  if (rc != OB_OK) return rc;
-  if (flag & 1u) return fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
-  return rm;
+      return rw_batch(h, s, st->n_stats, rows, oks);
+    });
+  });
 }
 
 static int rw_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
                           hipStream_t stream) {
-  if (!pr || !pr->reweight || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
-  if (pr->reweight->n_stats > 1) return fail(OB_E_INVALID, "a handle of several statistics boots through its own driver");
+  const ReweightState* st = reweight_state(pr);
+  if (!st || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
+  if (st->n_stats > 1) return fail(OB_E_INVALID, "a handle of several statistics boots through its own driver");
   double* const rows[1] = {d_rows};
   uint8_t* const oks[1] = {d_ok};
   return rw_boot_impl(pr, first_rep, n_reps, rows, oks, stream);
 }
 
-static int rw_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
-  if (!pr || !pr->reweight || (n_reps && (!rows || !ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  OB_HIP(hipSetDevice(pr->panel->ctx->device));
-  DevBuf d_rows, d_ok;
-  OB_HIP(d_rows.alloc(sizeof(double) * n_reps * pr->row_len));
-  OB_HIP(d_ok.alloc(n_reps));
-  OB_TRY(rw_boot_device(pr, first_rep, n_reps, d_rows.d(), d_ok.as<uint8_t>(), nullptr));
-  OB_HIP(hipMemcpy(rows, d_rows.p, sizeof(double) * n_reps * pr->row_len, hipMemcpyDeviceToHost));
-  OB_HIP(hipMemcpy(ok, d_ok.p, n_reps, hipMemcpyDeviceToHost));
-  return OB_OK;
-}
-
-static void rw_free(ReweightState* s) { delete s; }
-
-// installs the builder's hooks when the library loads (ob_reweight.hpp)
-static const bool g_reweight_hooks_installed = [] {
-  ReweightHooks& h = reweight_hooks();
-  h.boot_device = rw_boot_device;
-  h.boot_host = rw_boot_host;
-  h.free_state = rw_free;
-  return true;
-}();
+// installs the builder's hooks when the library loads (ob_model.hpp)
+static const bool g_reweight_hooks_installed = model_install(
+    kModelReweight, {rw_boot_device, model_boot_host, [](void* s) { delete static_cast<ReweightState*>(s); }});
 
 // Every check of the frame entry points, before any device work and before the context is read: settings
 // outside the scope, nulls and non-finite values in named columns, the design (ob::data_matrices), the shape.
 // On success m holds the design matrices and the groups' weights.
 static int rw_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, Config& c,
-                    ob_matrices** m) {
+                    Matrices& m) {
   OB_TRY(config_from(cfg, c));
-  if (!c.normalize.empty())
-    return fail(OB_E_UNSUPPORTED, "reweighted decomposition: normalized categoricals are outside its scope");
-  if (c.has_selection || !c.selection_predictors.empty())
-    return fail(OB_E_UNSUPPORTED, "reweighted decomposition: Heckman selection settings are outside its scope");
-  Frame f;
-  OB_TRY(load_frame(cols, n_cols, n_rows, f));
-  std::vector<std::string> named = {c.outcome, c.group};
-  named.insert(named.end(), c.predictors.begin(), c.predictors.end());
-  named.insert(named.end(), c.categorical.begin(), c.categorical.end());
-  if (c.has_weights) named.push_back(c.weights);
-  for (const std::string& name : named) {
-    const int i = f.find(name);
-    if (i < 0) return fail(OB_E_COLUMN, "%s%s", error_prefix(OB_E_COLUMN), name.c_str());
-    const Col& col = f.cols[i];
-    for (int64_t r = 0; r < f.nrows; ++r) {
-      if (!col.valid[r])
-        return fail(OB_E_INVALID, "reweighted decomposition: column `%s` has a null in row %lld", name.c_str(), (long long)r);
-      if (col.kind == OB_COL_F64 && !std::isfinite(col.f[r]))
-        return fail(OB_E_INVALID, "reweighted decomposition: column `%s` has a non-finite value in row %lld", name.c_str(),
-                    (long long)r);
-    }
-  }
-  OB_TRY(data_matrices(cols, n_cols, n_rows, cfg, true, m));
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  int rc = ob_matrices_dims(*m, &n_a, &n_b, &k);
-  if (rc == OB_OK && k > kReweightMaxK) rc = reweight_check_shape(k, n_a, n_b);
-  if (rc == OB_OK && (n_a == 0 || n_b == 0)) rc = fail(OB_E_GROUP, "%sOne group has no data", error_prefix(OB_E_GROUP));
-  if (rc == OB_OK) rc = reweight_check_shape(k, n_a, n_b);
-  if (rc != OB_OK) {
-    ob_matrices_free(*m);
-    *m = nullptr;
-  }
-  return rc;
+  if (!c.normalize.empty()) return model_refuse(kModelReweight, "normalized categoricals are");
+  if (c.has_selection || !c.selection_predictors.empty()) return model_refuse(kModelReweight, "Heckman selection settings are");
+  OB_TRY(stage_named(cols, n_cols, n_rows, c, kModelReweight, true, true));
+  OB_TRY(m.load(cols, n_cols, n_rows, cfg, true));
+  if (m.k > kReweightMaxK) OB_TRY(reweight_check_shape(m.k, m.n[0], m.n[1]));
+  if (m.n[0] == 0 || m.n[1] == 0) return fail(OB_E_GROUP, "%sOne group has no data", error_prefix(OB_E_GROUP));
+  return reweight_check_shape(m.k, m.n[0], m.n[1]);
 }
 
 // The statistics of a prepared handle: with gamma-hat of the point pass on the device, w psi-hat for B's rows, the
@@ -800,99 +726,43 @@ static int rw_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_
                   OB_REWEIGHT_MAX_STATS, n_specs);
   }
   Config c;
-  ob_matrices* m = nullptr;
-  OB_TRY(rw_stage(cols, n_cols, n_rows, cfg, c, &m));
-  struct Guard {
-    ob_matrices* m;
-    ~Guard() { ob_matrices_free(m); }
-  } guard{m};
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  const double *xa, *ya, *xb, *yb;
-  OB_TRY(ob_matrices_dims(m, &n_a, &n_b, &k));
-  OB_TRY(ob_matrices_get(m, &xa, &ya, &xb, &yb));
+  Matrices m;
+  OB_TRY(rw_stage(cols, n_cols, n_rows, cfg, c, m));
+  const int k = m.k;
   std::vector<double> unit[2];  // the RIF passes' weights of a builder without sample weights
-  const double* wrif[2] = {matrices_weights(m, 0), matrices_weights(m, 1)};
+  const double* wrif[2] = {m.w(0), m.w(1)};
   if (n_specs > 0) {
     for (int g = 0; g < 2; ++g)
       if (!wrif[g]) {
-        unit[g].assign((size_t)(g ? n_b : n_a), 1.0);
+        unit[g].assign((size_t)m.n[g], 1.0);
         wrif[g] = unit[g].data();
       }
-    OB_TRY(rif_input_check_weighted(ya, wrif[0], n_a, specs, n_specs));
-    OB_TRY(rif_input_check_weighted(yb, wrif[1], n_b, specs, n_specs));
+    OB_TRY(rif_input_check_weighted(m.y[0], wrif[0], m.n[0], specs, n_specs));
+    OB_TRY(rif_input_check_weighted(m.y[1], wrif[1], m.n[1], specs, n_specs));
   }
   if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
-  ob_panel_desc pd{};  // the resampler: the groups' row counts and the outcome
-  pd.p = 0;
-  pd.n_y = 1;
-  pd.a = {n_a, nullptr, n_a, ya, nullptr};
-  pd.b = {n_b, nullptr, n_b, yb, nullptr};
-  ob_prepared* pr = new ob_prepared();
-  pr->ctx = ctx;
-  pr->cfg = c;
-  pr->ref = c.ref;
-  if (c.has_seed) {
-    pr->seed = c.seed;
-  } else {
-    std::random_device rd;
-    pr->seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
-  }
-  pr->k = k;
-  pr->n_base = 0;
-  pr->row_len = reweight_row_len(k);
-  for (int32_t j = 0; j < k; ++j) pr->names.emplace_back(ob_matrices_name(m, j));
-  pr->detail_names = pr->names;
-  pr->n_a = n_a;
-  pr->n_b = n_b;
-  pr->n_y = 1;
-  pr->n_resid = 0;
   ReweightState* st = new ReweightState();
   st->k = k;
-  pr->reweight = st;
+  ob_prepared* pr = model_handle(ctx, c, m, kModelReweight, st, reweight_row_len(k), 1);
   auto build = [&]() -> int {
-    OB_TRY(ob_panel_create(ctx, &pd, &pr->panel));
+    OB_TRY(outcome_panel(ctx, m, &pr->panel));
     ob_panel* p = pr->panel;
-    for (int g = 0; g < 2; ++g) {  // [y | x_1 .. | w] x ld, zero past n (x of ob_matrices: column 0 is the intercept)
-      const int64_t n = g ? n_b : n_a;
-      const double* x = g ? xb : xa;
-      const double* y = g ? yb : ya;
-      const double* w = matrices_weights(m, g);
-      const int extra = n_specs > 0 ? (g ? 2 * n_specs - 1 : n_specs - 1) : 0;  // the RIF columns (file header)
-      const size_t bytes = sizeof(double) * (size_t)(k + 1 + extra) * p->ld[g];
-      OB_HIP(st->cols[g].alloc(bytes));
-      OB_HIP(hipMemset(st->cols[g].p, 0, bytes));
-      OB_HIP(hipMemcpy(st->cols[g].p, y, sizeof(double) * n, hipMemcpyHostToDevice));
-      if (k > 1)
-        OB_HIP(hipMemcpy2D(st->cols[g].d() + p->ld[g], sizeof(double) * p->ld[g], x + n, sizeof(double) * n,
-                           sizeof(double) * n, k - 1, hipMemcpyHostToDevice));
-      const std::vector<double> unit(w ? 0 : (size_t)n, 1.0);
-      OB_HIP(hipMemcpy(st->cols[g].d() + (size_t)k * p->ld[g], w ? w : unit.data(), sizeof(double) * n,
-                       hipMemcpyHostToDevice));
+    for (int g = 0; g < 2; ++g) {  // [y | x_1 .. | w | the RIF columns (file header)] x ld
+      const int extra = n_specs > 0 ? (g ? 2 * n_specs - 1 : n_specs - 1) : 0;
+      OB_TRY(upload_group(st->cols[g], p->ld[g], m.n[g], k, 1 + extra, m.y[g], m.x[g]));
+      OB_TRY(upload_weights(st->cols[g], p->ld[g], m.n[g], k, m.w(g)));
     }
-    int32_t nc = 0;
-    OB_TRY(ob_debug_chunks(p, nullptr, 0, &nc));
-    std::vector<uint32_t> table((size_t)3 * nc);
-    OB_TRY(ob_debug_chunks(p, table.data(), nc, &nc));
-    st->n_chunks = nc;
-    OB_HIP(st->chunks.alloc(sizeof(uint32_t) * table.size()));
-    OB_HIP(hipMemcpy(st->chunks.p, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
+    OB_TRY(upload_chunks(p, st->chunks, &st->n_chunks));
     g_timing = {};
     OB_TRY(rw_point(pr, st));
     if (n_specs == 0) return OB_OK;
     // the pass above gave gamma-hat (its fits, on y itself, are dropped); now the RIF columns and the point rows
     st->specs.assign(specs, specs + n_specs);
-    OB_TRY(rw_fill_statistics(pr, st, ya, wrif[0], yb, wrif[1]));
+    OB_TRY(rw_fill_statistics(pr, st, m.y[0], wrif[0], m.y[1], wrif[1]));
     st->n_stats = n_specs;
     return rw_point(pr, st);
   };
-  const int rc = build();
-  if (rc != OB_OK) {
-    ob_prepared_destroy(pr);
-    return rc;
-  }
-  *out = pr;
-  return OB_OK;
+  return model_built(pr, build(), out);
 }
 
 // The array pieces: one launch of ob_rw_kernel in `mode` over up to two groups of rows (gx[g]: n_g x k
@@ -910,12 +780,7 @@ static int rw_piece(ob_ctx* ctx, int mode, int k, const std::vector<double> (&gx
     n[g] = (uint32_t)gy[g].size();
     tiles[g] = (n[g] + OB_TILE_ROWS - 1) / OB_TILE_ROWS;
     ld[g] = (int64_t)tiles[g] * OB_TILE_ROWS;
-    const uint32_t nc = std::min<uint32_t>(tiles[g], 64u);
-    for (uint32_t c = 0; c < nc; ++c) {
-      chunks.push_back((uint32_t)g);
-      chunks.push_back((uint32_t)((uint64_t)tiles[g] * c / nc));
-      chunks.push_back((uint32_t)((uint64_t)tiles[g] * (c + 1) / nc));
-    }
+    group_chunks((uint32_t)g, tiles[g], 64u, chunks);
   }
   const int n_chunks = (int)(chunks.size() / 3), nv = rw_nv(k, mode);
   DevBuf d_cols[2], d_chunks, d_gamma, d_flags, d_partial, d_counts;
@@ -941,12 +806,9 @@ static int rw_piece(ob_ctx* ctx, int mode, int k, const std::vector<double> (&gx
   std::vector<uint32_t> img;  // one 64-replicate block of the f64 Gram's count images (ob_engine.hpp)
   if (counted) {
     img.assign((size_t)(tiles[0] + tiles[1]) * 4 * kCimgWords, 0u);
-    for (int g = 0; g < 2; ++g)
-      for (uint32_t i = 0; i < n[g]; ++i) {
-        const size_t t = (g ? tiles[0] : 0u) + i / OB_TILE_ROWS, within = i % OB_TILE_ROWS, sub = within >> 6, qq = within & 63;
-        for (int r = 0; r < n_gammas; ++r)
-          img[(t * 4 + sub) * kCimgWords + (size_t)r * kCimgStride + (qq >> 2)] |= (uint32_t)gc[g][i] << (8 * (qq & 3));
-      }
+    for (int g = 0; g < 2; ++g)  // every replicate counts the rows alike
+      pack_count_images(gc[g].data(), n[g], 0, (uint32_t)n_gammas, 1, img.data() + (size_t)(g ? tiles[0] : 0u) * 4 * kCimgWords,
+                        nullptr, 0);
     OB_HIP(d_counts.alloc(sizeof(uint32_t) * img.size()));
     OB_HIP(hipMemcpyAsync(d_counts.p, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice, s));
   }
@@ -1046,9 +908,9 @@ int ob_builder_prepare_reweighted_statistic(ob_ctx* ctx, const ob_column* cols, 
 
 int ob_prepared_reweight_statistics(const ob_prepared* prep, double out[3]) {
   if (!prep || !out) return ob::fail(OB_E_INVALID, "null pointer");
-  if (!prep->reweight || prep->reweight->n_stats != 1)
-    return ob::fail(OB_E_INVALID, "not a handle of a reweighted statistic");
-  for (int f = 0; f < 3; ++f) out[f] = prep->reweight->nu[f];
+  const ob::ReweightState* st = ob::reweight_state(prep);
+  if (!st || st->n_stats != 1) return ob::fail(OB_E_INVALID, "not a handle of a reweighted statistic");
+  for (int f = 0; f < 3; ++f) out[f] = st->nu[f];
   return OB_OK;
 }
 
@@ -1081,7 +943,7 @@ int ob_builder_run_reweighted_statistics(ob_ctx* ctx, const ob_column* cols, int
       OB_HIP(hipMemcpy(ok.data(), d_ok.p, ok.size(), hipMemcpyDeviceToHost));
     }
     for (int32_t t = 0; t < n_specs; ++t) {  // finish() reads the handle's point row: statistic t's
-      pr->point_row = pr->reweight->point_rows[t];
+      pr->point_row = ob::reweight_state(pr)->point_rows[t];
       OB_TRY(ob::finish(pr, 0, rows.data() + (size_t)t * reps * rl, ok.data() + (size_t)t * reps, reps, &out[t]));
     }
     return OB_OK;

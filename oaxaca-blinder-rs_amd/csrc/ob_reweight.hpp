@@ -1,7 +1,6 @@
 // ob_reweight.hpp -- the reweighted Oaxaca-Blinder decomposition with a bootstrapped propensity logit
-// (Fortin, Lemieux and Firpo 2011, section 5): limits, row layout and the hooks through
-// which ob_builder.cpp routes a handle that ob_builder_prepare_reweighted made (ob_reweight.hip holds the
-// rest).
+// (Fortin, Lemieux and Firpo 2011, section 5): limits and row layout (ob_reweight.hip holds the
+// rest; ob_builder.cpp routes a handle through the hooks of ob_model.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,19 +17,8 @@ inline int reweight_row_len(int k) { return 7 + 11 * k + 5; }
 // The checks every entry point makes before any device work. k: design columns with the intercept.
 int reweight_check_shape(int k, int64_t n_a, int64_t n_b);
 
-// The decomposition of a statistic keeps this row and these hooks: its handle is a reweighted
+// The decomposition of a statistic keeps this row and the same hooks: its handle is a reweighted
 // handle whose outcome columns are the weighted RIFs in A, B and C, fixed at the point estimate (a replicate
 // refits the logit and the three regressions and does not recompute the statistic).
-struct ReweightState;  // device side of a prepared reweighted run (ob_reweight.hip)
-
-// ob_builder.cpp reaches the reweighting code through these hooks only (as it does the binary code), so
-// that it links without ob_reweight.hip. ob_reweight.hip installs them when the library loads.
-struct ReweightHooks {
-  int (*boot_device)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
-                     hipStream_t stream) = nullptr;
-  int (*boot_host)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) = nullptr;
-  void (*free_state)(ReweightState* s) = nullptr;
-};
-ReweightHooks& reweight_hooks();  // ob_builder.cpp
 
 }  // namespace ob

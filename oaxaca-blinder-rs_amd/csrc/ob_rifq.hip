@@ -24,8 +24,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <numeric>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -33,6 +31,7 @@
 #include "ob_cluster.hpp"
 #include "ob_engine.hpp"
 #include "ob_hip.hpp"
+#include "ob_model.hpp"
 #include "ob_rifq.hpp"
 #include "ob_spec.h"
 
@@ -382,8 +381,13 @@ namespace ob {
 // ob_rifs.hip runs the same kernels for its quantile ranges.
 int rifq_run(const RifqArgs& a, hipStream_t s, hipEvent_t* e) { return rifq_launch(a, s, e); }
 
-int rifq_store(const RifqArgs& a, int t, double* gram, int e_pad, hipStream_t s) {
-  hipLaunchKernelGGL(rifq_store_kernel, dim3(blocks_for((int64_t)a.n_reps * 2 * (a.k + 1))), dim3(256), 0, s, a, t, gram, e_pad);
+int rifq_store(const double* gy, int k, uint32_t n_reps, int n_out, int t, double* gram, int e_pad, hipStream_t s) {
+  RifqArgs a{};  // rifq_store_kernel reads these four
+  a.k = k;
+  a.n_reps = n_reps;
+  a.n_taus = n_out;
+  a.ogy = const_cast<double*>(gy);
+  hipLaunchKernelGGL(rifq_store_kernel, dim3(blocks_for((int64_t)n_reps * 2 * (k + 1))), dim3(256), 0, s, a, t, gram, e_pad);
   OB_HIP(hipGetLastError());
   return OB_OK;
 }
@@ -440,69 +444,20 @@ int ob_rifq_pass(ob_ctx* ctx, const double* y_sorted, int64_t n, const uint8_t* 
   if (k > ob::kRifqMaxK)
     return ob::fail(OB_E_UNSUPPORTED, "ob_rifq_pass: at most %d design columns with the intercept, got %d", ob::kRifqMaxK, k);
   OB_TRY(ob::rifq_check_taus(taus, n_taus));
+  // the order of the shared checks differs from ob_rifs_pass in this one place: the rows before the replicates
   if (n < 2) return ob::fail(OB_E_INSUFFICIENT, "ob_rifq_pass needs at least 2 rows, got %lld", (long long)n);
   if (n >= ((int64_t)1 << 31)) return ob::fail(OB_E_UNSUPPORTED, "ob_rifq_pass takes fewer than 2^31 rows");
   if (p > 0 && ldx < n) return ob::fail(OB_E_INVALID, "ob_rifq_pass: ldx = %lld is below n = %lld", (long long)ldx, (long long)n);
   if (n_reps < 1 || n_reps > 16384) return ob::fail(OB_E_INVALID, "ob_rifq_pass takes 1 to 16384 replicates, got %d", n_reps);
-  if (!counts && n_reps != 1) return ob::fail(OB_E_INVALID, "ob_rifq_pass: the point pass (no counts) is one replicate");
-  for (int64_t i = 0; i < n; ++i) {
-    if (!std::isfinite(y_sorted[i])) return ob::fail(OB_E_INVALID, "ob_rifq_pass: y must be finite");
-    if (i && y_sorted[i] < y_sorted[i - 1]) return ob::fail(OB_E_INVALID, "ob_rifq_pass: y must be in ascending order");
-  }
-  for (int64_t j = 0; j < (int64_t)p; ++j)
-    for (int64_t i = 0; i < n; ++i)
-      if (!std::isfinite(x[j * ldx + i])) return ob::fail(OB_E_INVALID, "ob_rifq_pass: x must be finite");
-  if (counts)
-    for (int32_t r = 0; r < n_reps; ++r) {  // a replicate is a resample of n draws: the ranks are those of n
-      int64_t sum = 0;
-      for (int64_t i = 0; i < n; ++i) sum += counts[(size_t)r * n + i];
-      if (sum != n)
-        return ob::fail(OB_E_INVALID, "ob_rifq_pass: the counts of replicate %d sum to %lld, not to n = %lld", r,
-                        (long long)sum, (long long)n);
-    }
+  OB_TRY(ob::refit_pass_check("ob_rifq_pass", y_sorted, n, counts, n_reps, x, ldx, p, false));
   if (!ctx) return ob::fail(OB_E_INVALID, "null pointer: ctx");
   OB_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const uint32_t tiles = (uint32_t)((n + OB_TILE_ROWS - 1) / OB_TILE_ROWS), nc = std::min<uint32_t>(tiles, 128u);
-  const int64_t ld = (int64_t)tiles * OB_TILE_ROWS;
-  const uint32_t nb_rep = ((uint32_t)n_reps + 63u) / 64u, rep_pad = nb_rep * 64u;
+  ob::RefitPassInput in;
+  OB_TRY(in.upload(y_sorted, n, counts, n_reps, x, ldx, k, s));
   const int T = n_taus, nv = ob::rifq_sums_len(k);
-  std::vector<uint32_t> chunks;
-  for (uint32_t c = 0; c < nc; ++c) {
-    chunks.push_back(0u);
-    chunks.push_back((uint32_t)((uint64_t)tiles * c / nc));
-    chunks.push_back((uint32_t)((uint64_t)tiles * (c + 1) / nc));
-  }
-  double mu0 = 0.0;
-  for (int64_t i = 0; i < n; ++i) mu0 += y_sorted[i];
-  mu0 /= (double)n;
-  DevBuf d_cols, d_chunks, d_partial, d_counts, d_m1, d_sq, d_sp, d_sbw, d_f, d_nle, d_fl, d_t, d_gy;
-  OB_HIP(d_cols.alloc(sizeof(double) * (size_t)ld * k));
-  OB_HIP(hipMemsetAsync(d_cols.p, 0, sizeof(double) * (size_t)ld * k, s));
-  OB_HIP(hipMemcpyAsync(d_cols.p, y_sorted, sizeof(double) * n, hipMemcpyHostToDevice, s));
-  for (int j = 1; j < k; ++j)
-    OB_HIP(hipMemcpyAsync(d_cols.d() + (size_t)j * ld, x + (size_t)(j - 1) * ldx, sizeof(double) * n, hipMemcpyHostToDevice, s));
-  OB_HIP(d_chunks.alloc(sizeof(uint32_t) * chunks.size()));
-  OB_HIP(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(uint32_t) * chunks.size(), hipMemcpyHostToDevice, s));
-  OB_HIP(d_partial.alloc(sizeof(double) * (size_t)nc * rep_pad * nv));
-  std::vector<uint32_t> img, m1;  // the engine's layouts: f64-Gram count images and [replicate][tile] counts
-  if (counts) {
-    img.assign((size_t)tiles * nb_rep * 4 * kCimgWords, 0u);
-    m1.assign((size_t)n_reps * tiles, 0u);
-    for (int32_t r = 0; r < n_reps; ++r)
-      for (int64_t i = 0; i < n; ++i) {
-        const uint32_t c = counts[(size_t)r * n + i];
-        if (!c) continue;
-        const size_t tl = (size_t)(i / OB_TILE_ROWS), within = (size_t)(i % OB_TILE_ROWS), sub = within >> 6, qq = within & 63;
-        img[((tl * nb_rep + ((uint32_t)r >> 6)) * 4 + sub) * kCimgWords + ((uint32_t)r & 63u) * kCimgStride + (qq >> 2)] |=
-            c << (8 * (qq & 3));
-        m1[(size_t)r * tiles + tl] += c;
-      }
-    OB_HIP(d_counts.alloc(sizeof(uint32_t) * img.size()));
-    OB_HIP(hipMemcpyAsync(d_counts.p, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice, s));
-    OB_HIP(d_m1.alloc(sizeof(uint32_t) * m1.size()));
-    OB_HIP(hipMemcpyAsync(d_m1.p, m1.data(), sizeof(uint32_t) * m1.size(), hipMemcpyHostToDevice, s));
-  }
+  DevBuf d_partial, d_sq, d_sp, d_sbw, d_f, d_nle, d_fl, d_t, d_gy;
+  OB_HIP(d_partial.alloc(sizeof(double) * (size_t)in.n_chunks * in.rep_pad * nv));
   const size_t nrt = (size_t)n_reps * T;
   OB_HIP(d_sq.alloc(sizeof(double) * nrt));
   OB_HIP(d_sp.alloc(sizeof(uint32_t) * nrt));
@@ -513,24 +468,24 @@ int ob_rifq_pass(ob_ctx* ctx, const double* y_sorted, int64_t n, const uint8_t* 
   OB_HIP(d_t.alloc(sizeof(double) * nrt * k));
   OB_HIP(d_gy.alloc(sizeof(double) * nrt * (k + 1)));
   RifqArgs a{};
-  a.cols[0] = d_cols.d();
-  a.ld[0] = ld;
+  a.cols[0] = in.cols.d();
+  a.ld[0] = in.ld;
   a.n[0] = (uint32_t)n;
   a.tile0[0] = 0;
-  a.mu0[0] = mu0;
+  a.mu0[0] = in.mu0;
   a.npow[0] = std::pow((double)n, -0.2);
   for (int i = 0; i < T; ++i) a.taus[i] = taus[i];
   a.k = k;
   a.n_taus = T;
   a.n_groups = 1;
-  a.tiles_total = tiles;
-  a.m1 = counts ? d_m1.as<uint32_t>() : nullptr;
-  a.counts = counts ? d_counts.as<uint32_t>() : nullptr;
-  a.nb_rep = nb_rep;
-  a.part_pad = rep_pad;
+  a.tiles_total = in.tiles;
+  a.m1 = counts ? in.m1.as<uint32_t>() : nullptr;
+  a.counts = counts ? in.counts.as<uint32_t>() : nullptr;
+  a.nb_rep = in.nb_rep;
+  a.part_pad = in.rep_pad;
   a.n_reps = (uint32_t)n_reps;
-  a.chunks = d_chunks.as<uint32_t>();
-  a.n_chunks = (int)nc;
+  a.chunks = in.chunks.as<uint32_t>();
+  a.n_chunks = (int)in.n_chunks;
   a.sq = d_sq.d();
   a.sp = d_sp.as<uint32_t>();
   a.sbw = d_sbw.d();
@@ -572,292 +527,137 @@ struct RifqState {
   double taus[kRifqMaxTaus] = {};
   DevBuf cols[2];  // [y | x_1 .. x_{k-1}] x ld
   DevBuf sq, sp, sbw, partial, of, onle, ofl, ot, ogy, solved, sok;
-  double mu0[2] = {0.0, 0.0}, npow[2] = {0.0, 0.0};
-  std::vector<int32_t> perm[2];       // sorted position -> row of the group before the sort
+  SortedGroups sorted;                   // perm, mu0, npow (x and y are dropped once uploaded)
   std::vector<double> point_q, point_f;  // [2][T]
-  int64_t n_floored = 0;              // floored densities of the point pass and of every boot since
+  int64_t n_floored = 0;                 // floored densities of the point pass and of every boot since
 };
 
-constexpr uint64_t kRifqSegReps = 2048;
-constexpr uint64_t kRifqCountBudget = 8ull << 30;  // bytes of count images per segment
+static RifqState* rifq_state(const ob_prepared* pr) { return model_state<RifqState>(pr, kModelRifq); }
 
-// One segment: counts (the OBRS-3 stream, or unit counts for the point pass), the f64 Gram and its reduce, the three
-// refit kernels, then per tau the y-pairs patched into the Grams, the engine's solve and the row with its tail.
-// rows / ok: [T][n_total] blocks, this segment at s0.
-static int rifq_segment(ob_prepared* pr, RifqState* st, bool point, uint64_t first_rep, uint32_t ns, uint64_t n_total,
-                        uint64_t s0, double* d_rows, uint8_t* d_ok, hipStream_t s) {
+// One segment (refit_segment) with the three refit kernels and rifq_tail_kernel.
+static int rifq_segment(ob_prepared* pr, const RefitSegment& sg, hipStream_t s) {
+  RifqState* st = rifq_state(pr);
   ob_panel* p = pr->panel;
-  const int k = st->k, T = st->n_taus, rl0 = p->row_len, rl = pr->row_len;
-  Events<6> ev;  // start | Gram end = search start | search, density, patch end | solve end
+  const int k = st->k, T = st->n_taus, rl0 = p->row_len;
+  Events<4> ev;
   OB_HIP(ev.create());
-  OB_HIP(hipEventRecord(ev.e[0], s));
-  uint32_t nb_rep = 0, rep_pad = 0;
-  if (point) OB_TRY(engine_unit_counts(p, s, &nb_rep, &rep_pad));
-  else OB_TRY(engine_counts(p, pr->seed, first_rep, ns, s, &nb_rep, &rep_pad));
-  OB_TRY(engine_gram_f64(p, ns, s));
-  const int n_chunks = (int)(p->chunks.size() / 3);
-  const size_t nrt = (size_t)rep_pad * 2 * T;
-  OB_HIP(st->sq.alloc(sizeof(double) * nrt));
-  OB_HIP(st->sp.alloc(sizeof(uint32_t) * nrt));
-  OB_HIP(st->sbw.alloc(sizeof(double) * 3 * 2 * rep_pad));
-  OB_HIP(st->partial.alloc(sizeof(double) * (size_t)n_chunks * rep_pad * rifq_sums_len(k)));
-  OB_HIP(st->of.alloc(sizeof(double) * nrt));
-  OB_HIP(st->onle.alloc(sizeof(double) * nrt));
-  OB_HIP(st->ofl.alloc(nrt));
-  OB_HIP(st->ot.alloc(sizeof(double) * nrt * k));
-  OB_HIP(st->ogy.alloc(sizeof(double) * nrt * (k + 1)));
-  OB_HIP(st->solved.alloc(sizeof(double) * (size_t)rep_pad * rl0));
-  OB_HIP(st->sok.alloc(rep_pad));
   RifqArgs a{};
-  for (int g = 0; g < 2; ++g) {
-    a.cols[g] = st->cols[g].d();
-    a.ld[g] = p->ld[g];
-    a.n[g] = p->n[g];
-    a.mu0[g] = st->mu0[g];
-    a.npow[g] = st->npow[g];
-  }
-  a.tile0[0] = 0;
-  a.tile0[1] = p->ntiles[0];
-  for (int t = 0; t < T; ++t) a.taus[t] = st->taus[t];
-  a.k = k;
-  a.n_taus = T;
-  a.n_groups = 2;
-  a.tiles_total = p->ntiles[0] + p->ntiles[1];
-  a.m1 = p->d_m1;
-  a.counts = p->d_counts;
-  a.nb_rep = nb_rep;
-  a.part_pad = rep_pad;
-  a.n_reps = ns;
-  a.chunks = p->d_chunks;
-  a.n_chunks = n_chunks;
-  a.sq = st->sq.d();
-  a.sp = st->sp.as<uint32_t>();
-  a.sbw = st->sbw.d();
-  a.partial = st->partial.d();
-  a.of = st->of.d();
-  a.onle = st->onle.d();
-  a.ofl = st->ofl.as<uint8_t>();
-  a.ot = st->ot.d();
-  a.ogy = st->ogy.d();
-  OB_TRY(rifq_launch(a, s, ev.e + 1));
-  for (int t = 0; t < T; ++t) {
-    hipLaunchKernelGGL(rifq_store_kernel, dim3(blocks_for((int64_t)ns * 2 * (k + 1))), dim3(256), 0, s, a, t, p->d_gram,
-                       p->e_pad);
-    OB_HIP(hipGetLastError());
-    OB_TRY(engine_solve_grams(p, p->d_gram, nullptr, ns, ns, 0, pr->ref, st->solved.d(), st->sok.as<uint8_t>(), s));
-    hipLaunchKernelGGL(rifq_tail_kernel, dim3(ns), dim3(64), 0, s, a, t, (const double*)st->solved.d(),
-                       (const uint8_t*)st->sok.p, rl0, d_rows + ((size_t)t * n_total + s0) * rl,
-                       d_ok + (size_t)t * n_total + s0);
-    OB_HIP(hipGetLastError());
-  }
-  OB_HIP(hipEventRecord(ev.e[5], s));
-  std::vector<uint8_t> fl((size_t)ns * 2 * T);
-  OB_HIP(hipMemcpyAsync(fl.data(), st->ofl.p, fl.size(), hipMemcpyDeviceToHost, s));
-  OB_HIP(hipStreamSynchronize(s));  // the one host wait of a segment: the floor flags and the timings
-  float gram_ms = 0.f, solve_ms = 0.f;
-  OB_HIP(hipEventElapsedTime(&gram_ms, ev.e[0], ev.e[1]));
-  OB_HIP(hipEventElapsedTime(&solve_ms, ev.e[4], ev.e[5]));
-  g_timing.gram_ms += gram_ms;
-  g_timing.solve_ms += solve_ms;
-  OB_TRY(rifq_times(ev.e + 1));
-  for (uint8_t v : fl) st->n_floored += v ? 1 : 0;
-  return OB_OK;
+  RefitModel md{T, &st->solved, &st->sok, &st->n_floored, nullptr, nullptr};
+  md.launch = [&](uint32_t nb_rep, uint32_t rep_pad, RefitOut* out) -> int {
+    const int n_chunks = (int)(p->chunks.size() / 3);
+    const size_t nrt = (size_t)rep_pad * 2 * T;
+    OB_HIP(st->sq.alloc(sizeof(double) * nrt));
+    OB_HIP(st->sp.alloc(sizeof(uint32_t) * nrt));
+    OB_HIP(st->sbw.alloc(sizeof(double) * 3 * 2 * rep_pad));
+    OB_HIP(st->partial.alloc(sizeof(double) * (size_t)n_chunks * rep_pad * rifq_sums_len(k)));
+    OB_HIP(st->of.alloc(sizeof(double) * nrt));
+    OB_HIP(st->onle.alloc(sizeof(double) * nrt));
+    OB_HIP(st->ofl.alloc(nrt));
+    OB_HIP(st->ot.alloc(sizeof(double) * nrt * k));
+    OB_HIP(st->ogy.alloc(sizeof(double) * nrt * (k + 1)));
+    for (int g = 0; g < 2; ++g) {
+      a.cols[g] = st->cols[g].d();
+      a.ld[g] = p->ld[g];
+      a.n[g] = p->n[g];
+      a.mu0[g] = st->sorted.mu0[g];
+      a.npow[g] = st->sorted.npow[g];
+    }
+    a.tile0[0] = 0;
+    a.tile0[1] = p->ntiles[0];
+    for (int t = 0; t < T; ++t) a.taus[t] = st->taus[t];
+    a.k = k;
+    a.n_taus = T;
+    a.n_groups = 2;
+    a.tiles_total = p->ntiles[0] + p->ntiles[1];
+    a.m1 = p->d_m1;
+    a.counts = p->d_counts;
+    a.nb_rep = nb_rep;
+    a.part_pad = rep_pad;
+    a.n_reps = sg.ns;
+    a.chunks = p->d_chunks;
+    a.n_chunks = n_chunks;
+    a.sq = st->sq.d();
+    a.sp = st->sp.as<uint32_t>();
+    a.sbw = st->sbw.d();
+    a.partial = st->partial.d();
+    a.of = st->of.d();
+    a.onle = st->onle.d();
+    a.ofl = st->ofl.as<uint8_t>();
+    a.ot = st->ot.d();
+    a.ogy = st->ogy.d();
+    *out = {a.ogy, a.ofl};
+    return rifq_launch(a, s, ev.e);
+  };
+  md.tail = [&](int t, const double* solved, const uint8_t* sok, double* rows, uint8_t* ok) {
+    hipLaunchKernelGGL(rifq_tail_kernel, dim3(sg.ns), dim3(64), 0, s, a, t, solved, sok, rl0, rows, ok);
+  };
+  RefitTimes tm;
+  OB_TRY(refit_segment(pr, sg, md, s, &tm));
+  g_timing.gram_ms += tm.gram_ms;
+  g_timing.solve_ms += tm.solve_ms;
+  return rifq_times(ev.e);
 }
 
 static int rifq_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
                             hipStream_t stream) {
-  if (!pr || !pr->rifq || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  if (first_rep + n_reps > 0xFFFFFFFFull)
-    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 counter word)");
-  RifqState* st = pr->rifq;
-  ob_panel* p = pr->panel;
-  OB_HIP(hipSetDevice(p->ctx->device));
-  hipStream_t s = stream ? stream : p->ctx->stream;
-  OB_TRY(engine_order(p, s));
-  g_timing = {};
-  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
-  const uint64_t batch_bytes = (uint64_t)std::max(tiles, 1u) * 4 * kCimgWords * sizeof(uint32_t);
-  const uint64_t seg_cap = std::max<uint64_t>(64, (kRifqCountBudget / batch_bytes) * 64);
-  const uint64_t seg = std::min<uint64_t>(n_reps, std::min<uint64_t>(kRifqSegReps, seg_cap));
-  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
-  int rc = OB_OK;
-  for (uint64_t s0 = 0; s0 < n_reps && rc == OB_OK; s0 += seg)
-    rc = rifq_segment(pr, st, false, first_rep + s0, (uint32_t)std::min<uint64_t>(seg, n_reps - s0), n_reps, s0, d_rows,
-                      d_ok, s);
-  uint32_t flag = 0;
-  if (rc == OB_OK && hipMemcpyAsync(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = fail(OB_E_HIP, "copy of the overflow word failed");
-  if (rc == OB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(OB_E_HIP, "stream synchronize failed");
-  const int rm = engine_mark(p, s);
-  if (rc != OB_OK) return rc;
-  if (flag & 1u) return fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
-  return rm;
+  const BootPlan plan{kRefitSegReps, kCountBudget, false, [](uint32_t) {
+                        g_timing = {};
+                        return OB_OK;
+                      }};
+  return boot_segmented(pr, kModelRifq, plan, first_rep, n_reps, d_rows && d_ok, stream,
+                        [&](uint64_t s0, uint32_t ns, uint32_t, uint32_t, hipStream_t s) {
+                          return rifq_segment(pr, {false, first_rep + s0, ns, n_reps, s0, d_rows, d_ok}, s);
+                        });
 }
 
-static int rifq_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
-  if (!pr || !pr->rifq || (n_reps && (!rows || !ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  OB_HIP(hipSetDevice(pr->panel->ctx->device));
-  const size_t T = (size_t)pr->rifq->n_taus;
-  DevBuf d_rows, d_ok;
-  OB_HIP(d_rows.alloc(sizeof(double) * T * n_reps * pr->row_len));
-  OB_HIP(d_ok.alloc(T * n_reps));
-  OB_TRY(rifq_boot_device(pr, first_rep, n_reps, d_rows.d(), d_ok.as<uint8_t>(), nullptr));
-  OB_HIP(hipMemcpy(rows, d_rows.p, sizeof(double) * T * n_reps * pr->row_len, hipMemcpyDeviceToHost));
-  OB_HIP(hipMemcpy(ok, d_ok.p, T * n_reps, hipMemcpyDeviceToHost));
-  return OB_OK;
-}
-
-static void rifq_free(RifqState* s) { delete s; }
-
-static const bool g_rifq_hooks_installed = [] {
-  RifqHooks& h = rifq_hooks();
-  h.boot_device = rifq_boot_device;
-  h.boot_host = rifq_boot_host;
-  h.free_state = rifq_free;
-  return true;
-}();
+static const bool g_rifq_hooks_installed = model_install(
+    kModelRifq, {rifq_boot_device, model_boot_host, [](void* s) { delete static_cast<RifqState*>(s); }});
 
 // Every check of the frame entry points, before any device work and before the context is read.
 static int rifq_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
-                      const double* taus, int32_t n_taus, Config& c, ob_matrices** m) {
+                      const double* taus, int32_t n_taus, Config& c, Matrices& m) {
   OB_TRY(config_from(cfg, c));
   OB_TRY(rifq_check_taus(taus, n_taus));
-  if (c.has_weights) return fail(OB_E_UNSUPPORTED, "quantile refit: sample weights are outside its scope");
-  if (!c.normalize.empty()) return fail(OB_E_UNSUPPORTED, "quantile refit: normalized categoricals are outside its scope");
-  if (c.has_selection || !c.selection_predictors.empty())
-    return fail(OB_E_UNSUPPORTED, "quantile refit: Heckman selection settings are outside its scope");
-  if (c.has_cluster) return fail(OB_E_UNSUPPORTED, "quantile refit: a cluster bootstrap is outside its scope");
-  Frame f;
-  OB_TRY(load_frame(cols, n_cols, n_rows, f));
-  std::vector<std::string> named = {c.outcome, c.group};
-  named.insert(named.end(), c.predictors.begin(), c.predictors.end());
-  named.insert(named.end(), c.categorical.begin(), c.categorical.end());
-  for (const std::string& name : named) {
-    const int i = f.find(name);
-    if (i < 0) return fail(OB_E_COLUMN, "%s%s", error_prefix(OB_E_COLUMN), name.c_str());
-    for (int64_t r = 0; r < f.nrows; ++r)
-      if (!f.cols[i].valid[r])
-        return fail(OB_E_INVALID, "quantile refit: column `%s` has a null in row %lld", name.c_str(), (long long)r);
+  if (c.has_weights) return model_refuse(kModelRifq, "sample weights are");
+  if (!c.normalize.empty()) return model_refuse(kModelRifq, "normalized categoricals are");
+  if (c.has_selection || !c.selection_predictors.empty()) return model_refuse(kModelRifq, "Heckman selection settings are");
+  if (c.has_cluster) return model_refuse(kModelRifq, "a cluster bootstrap is");
+  OB_TRY(stage_named(cols, n_cols, n_rows, c, kModelRifq, false, false));
+  OB_TRY(m.load(cols, n_cols, n_rows, cfg, false));
+  OB_TRY(rifq_check_shape(m.k, n_taus, taus, m.n[0], m.n[1]));
+  for (int g = 0; g < 2; ++g) {
+    for (int64_t i = 0; i < m.n[g]; ++i)
+      if (!std::isfinite(m.y[g][i])) return fail(OB_E_INVALID, "quantile refit: a non-finite value in the outcome");
+    for (int64_t i = 0; i < m.n[g] * m.k; ++i)
+      if (!std::isfinite(m.x[g][i])) return fail(OB_E_INVALID, "quantile refit: a non-finite value in a predictor");
   }
-  OB_TRY(ob_builder_data_matrices(cols, n_cols, n_rows, cfg, m));
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  const double *xa, *ya, *xb, *yb;
-  int rc = ob_matrices_dims(*m, &n_a, &n_b, &k);
-  if (rc == OB_OK) rc = ob_matrices_get(*m, &xa, &ya, &xb, &yb);
-  if (rc == OB_OK) rc = rifq_check_shape(k, n_taus, taus, n_a, n_b);
-  for (int g = 0; g < 2 && rc == OB_OK; ++g) {
-    const double* x = g ? xb : xa;
-    const double* y = g ? yb : ya;
-    const int64_t n = g ? n_b : n_a;
-    for (int64_t i = 0; i < n && rc == OB_OK; ++i)
-      if (!std::isfinite(y[i])) rc = fail(OB_E_INVALID, "quantile refit: a non-finite value in the outcome");
-    for (int64_t i = 0; i < n * k && rc == OB_OK; ++i)
-      if (!std::isfinite(x[i])) rc = fail(OB_E_INVALID, "quantile refit: a non-finite value in a predictor");
-  }
-  if (rc != OB_OK) {
-    ob_matrices_free(*m);
-    *m = nullptr;
-  }
-  return rc;
+  return OB_OK;
 }
 
 static int rifq_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
                         const double* taus, int32_t n_taus, ob_prepared** out) {
   Config c;
-  ob_matrices* m = nullptr;
-  OB_TRY(rifq_stage(cols, n_cols, n_rows, cfg, taus, n_taus, c, &m));
-  struct Guard {
-    ob_matrices* m;
-    ~Guard() { ob_matrices_free(m); }
-  } guard{m};
+  Matrices m;
+  OB_TRY(rifq_stage(cols, n_cols, n_rows, cfg, taus, n_taus, c, m));
   if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
-  int64_t nn[2] = {0, 0};
-  int32_t k = 0;
-  const double *xg[2], *yg[2];
-  OB_TRY(ob_matrices_dims(m, &nn[0], &nn[1], &k));
-  OB_TRY(ob_matrices_get(m, &xg[0], &yg[0], &xg[1], &yg[1]));
-  ob_prepared* pr = new ob_prepared();
+  const int k = m.k;
   RifqState* st = new RifqState();
-  pr->rifq = st;
-  pr->ctx = ctx;
-  pr->cfg = c;
-  pr->ref = c.ref;
-  if (c.has_seed) {
-    pr->seed = c.seed;
-  } else {
-    std::random_device rd;
-    pr->seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
-  }
-  pr->k = k;
-  pr->n_base = 0;
-  pr->row_len = ob_row_len(k, 0) + 6;
-  for (int32_t j = 0; j < k; ++j) pr->names.emplace_back(ob_matrices_name(m, j));
-  pr->detail_names = pr->names;
-  pr->n_a = nn[0];
-  pr->n_b = nn[1];
-  pr->n_y = n_taus;
-  pr->n_resid = 0;
+  ob_prepared* pr = model_handle(ctx, c, m, kModelRifq, st, ob_row_len(k, 0) + 6, n_taus);
   st->k = k;
   st->n_taus = n_taus;
   for (int t = 0; t < n_taus; ++t) st->taus[t] = taus[t];
-  // each group's rows in stable ascending order of y: [x_0 = 1 | x_1 ..] and y, column-major n x k
-  std::vector<double> xs[2], ys[2];
-  for (int g = 0; g < 2; ++g) {
-    const int64_t n = nn[g];
-    st->perm[g].resize((size_t)n);
-    std::iota(st->perm[g].begin(), st->perm[g].end(), 0);
-    const double* y = yg[g];
-    std::stable_sort(st->perm[g].begin(), st->perm[g].end(), [y](int32_t a, int32_t b) { return y[a] < y[b]; });
-    xs[g].resize((size_t)n * k);
-    ys[g].resize((size_t)n);
-    double mu = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t r = st->perm[g][(size_t)i];
-      ys[g][(size_t)i] = y[r];
-      mu += y[r];
-      for (int32_t j = 0; j < k; ++j) xs[g][(size_t)j * n + i] = xg[g][(size_t)j * n + r];
-    }
-    st->mu0[g] = mu / (double)n;
-    st->npow[g] = std::pow((double)n, -0.2);
-  }
-  ob_panel_desc pd{};
-  pd.p = k - 1;
-  pd.n_num = (int32_t)c.predictors.size();
-  pd.n_y = 1;
-  pd.a = {nn[0], xs[0].data() + nn[0], nn[0], ys[0].data(), nullptr};
-  pd.b = {nn[1], xs[1].data() + nn[1], nn[1], ys[1].data(), nullptr};
+  SortedGroups& sg = st->sorted;
+  sort_groups(m, sg);
   auto build = [&]() -> int {
-    OB_TRY(ob_panel_create(ctx, &pd, &pr->panel));
-    ob_panel* p = pr->panel;
-    for (int g = 0; g < 2; ++g) {  // [y | x_1 ..] x ld, zero past n
-      const int64_t n = nn[g];
-      const size_t bytes = sizeof(double) * (size_t)k * p->ld[g];
-      OB_HIP(st->cols[g].alloc(bytes));
-      OB_HIP(hipMemset(st->cols[g].p, 0, bytes));
-      OB_HIP(hipMemcpy(st->cols[g].p, ys[g].data(), sizeof(double) * n, hipMemcpyHostToDevice));
-      if (k > 1)
-        OB_HIP(hipMemcpy2D(st->cols[g].d() + p->ld[g], sizeof(double) * p->ld[g], xs[g].data() + n, sizeof(double) * n,
-                           sizeof(double) * n, k - 1, hipMemcpyHostToDevice));
-    }
+    OB_TRY(refit_panel(ctx, c, m, sg, &pr->panel));
+    for (int g = 0; g < 2; ++g)
+      OB_TRY(upload_group(st->cols[g], pr->panel->ld[g], m.n[g], k, 0, sg.y[g].data(), sg.x[g].data()));
     // the point pass: the boot's own kernels over unit counts
-    hipStream_t s = ctx->stream;
-    const size_t T = (size_t)n_taus;
-    DevBuf d_rows, d_ok;
-    OB_HIP(d_rows.alloc(sizeof(double) * T * pr->row_len));
-    OB_HIP(d_ok.alloc(T));
     g_timing = {};
-    OB_TRY(engine_order(p, s));
-    OB_TRY(rifq_segment(pr, st, true, 0, 1, 1, 0, d_rows.d(), d_ok.as<uint8_t>(), s));
-    OB_TRY(engine_mark(p, s));
-    pr->point_row.assign(T * pr->row_len, 0.0);
-    std::vector<uint8_t> okh(T, 0);
-    OB_HIP(hipMemcpy(pr->point_row.data(), d_rows.p, sizeof(double) * T * pr->row_len, hipMemcpyDeviceToHost));
-    OB_HIP(hipMemcpy(okh.data(), d_ok.p, T, hipMemcpyDeviceToHost));
-    for (uint8_t v : okh)
-      if (!v) return fail(OB_E_LINALG, "%squantile refit: the point estimate's regression could not be solved", error_prefix(OB_E_LINALG));
+    OB_TRY(refit_point(pr, [&](double* d_rows, uint8_t* d_ok, hipStream_t s) {
+      return rifq_segment(pr, {true, 0, 1, 1, 0, d_rows, d_ok}, s);
+    }));
+    const size_t T = (size_t)n_taus;
     const int rl0 = pr->row_len - 6;
     st->point_q.resize(2 * T);
     st->point_f.resize(2 * T);
@@ -869,12 +669,11 @@ static int rifq_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int6
     return OB_OK;
   };
   const int rc = build();
-  if (rc != OB_OK) {
-    ob_prepared_destroy(pr);
-    return rc;
+  for (int g = 0; g < 2; ++g) {
+    sg.x[g] = {};
+    sg.y[g] = {};
   }
-  *out = pr;
-  return OB_OK;
+  return model_built(pr, rc, out);
 }
 
 }  // namespace ob
@@ -915,10 +714,10 @@ int ob_builder_decompose_quantiles_refit(ob_ctx* ctx, const ob_column* cols, int
 
 int ob_prepared_rifq_info(const ob_prepared* prep, ob_rifq_info* out) {
   if (!prep || !out) return ob::fail(OB_E_INVALID, "null pointer");
-  if (!prep->rifq) return ob::fail(OB_E_INVALID, "the handle was not prepared for a quantile refit");
-  const ob::RifqState* st = prep->rifq;
-  *out = {st->n_taus, st->k, prep->n_a, prep->n_b, st->n_floored, st->taus, st->perm[0].data(), st->perm[1].data(),
-          st->point_q.data(), st->point_f.data()};
+  const ob::RifqState* st = ob::rifq_state(prep);
+  if (!st) return ob::fail(OB_E_INVALID, "the handle was not prepared for a quantile refit");
+  *out = {st->n_taus, st->k, prep->n_a, prep->n_b, st->n_floored, st->taus, st->sorted.perm[0].data(),
+          st->sorted.perm[1].data(), st->point_q.data(), st->point_f.data()};
   return OB_OK;
 }
 
@@ -926,9 +725,10 @@ int ob_prepared_finish_tau(ob_prepared* prep, int32_t t, const double* rows, con
                            ob_results** out) {
   if (!prep || !out || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
   *out = nullptr;
-  if (!prep->rifq && !prep->rifs) return ob::fail(OB_E_INVALID, "the handle was not prepared for a quantile refit");
-  const int n_out = prep->rifq ? prep->rifq->n_taus : prep->n_y;  // a statistics refit handle: its statistics
-  if (t < 0 || t >= n_out) return ob::fail(OB_E_INVALID, "quantile index %d out of range", t);
+  if (prep->model_kind != ob::kModelRifq && prep->model_kind != ob::kModelRifs)
+    return ob::fail(OB_E_INVALID, "the handle was not prepared for a quantile refit");
+  // n_y: a quantile refit's taus, a statistics refit's statistics
+  if (t < 0 || t >= prep->n_y) return ob::fail(OB_E_INVALID, "quantile index %d out of range", t);
   return ob::finish(prep, t, rows, ok, n_reps, out);
 }
 

@@ -50,19 +50,5 @@ struct RifqArgs {
 // The search, density and patch kernels over the replicates of `a` (every buffer set), enqueued on s; e[0] .. e[3]
 // are recorded before the search and after each kernel.
 int rifq_run(const RifqArgs& a, hipStream_t s, hipEvent_t* e);
-// rifq_store_kernel: output t's y-pairs a.ogy [rep][2][a.n_taus][k + 1] over those of the reduced Grams [rep][2][e_pad].
-int rifq_store(const RifqArgs& a, int t, double* gram, int e_pad, hipStream_t s);
-
-struct RifqState;  // device side of a prepared refit run (ob_rifq.hip)
-
-// ob_builder.cpp reaches the refit through these hooks only (as it does the binary code), so that it links without
-// ob_rifq.hip. ob_rifq.hip installs them when the library loads.
-struct RifqHooks {
-  int (*boot_device)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
-                     hipStream_t stream) = nullptr;
-  int (*boot_host)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) = nullptr;
-  void (*free_state)(RifqState* s) = nullptr;
-};
-RifqHooks& rifq_hooks();  // ob_builder.cpp
 
 }  // namespace ob

@@ -22,8 +22,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <numeric>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -31,6 +29,7 @@
 #include "ob_cluster.hpp"
 #include "ob_engine.hpp"
 #include "ob_hip.hpp"
+#include "ob_model.hpp"
 #include "ob_rif.hpp"
 #include "ob_rifq.hpp"
 #include "ob_rifs.hpp"
@@ -636,91 +635,35 @@ int ob_rifs_pass(ob_ctx* ctx, const double* y_sorted, int64_t n, const uint8_t* 
   if (n_reps > ob::kRifsMaxReps)
     return ob::fail(OB_E_UNSUPPORTED, "ob_rifs_pass takes at most %d replicates a call, got %d", ob::kRifsMaxReps, n_reps);
   if (n_reps < 1) return ob::fail(OB_E_INVALID, "ob_rifs_pass takes at least one replicate, got %d", n_reps);
-  if (!counts && n_reps != 1) return ob::fail(OB_E_INVALID, "ob_rifs_pass: the point pass (no counts) is one replicate");
-  if (n < 2) return ob::fail(OB_E_INSUFFICIENT, "ob_rifs_pass needs at least 2 rows, got %lld", (long long)n);
-  if (n >= ((int64_t)1 << 31)) return ob::fail(OB_E_UNSUPPORTED, "ob_rifs_pass takes fewer than 2^31 rows");
-  if (p > 0 && ldx < n) return ob::fail(OB_E_INVALID, "ob_rifs_pass: ldx = %lld is below n = %lld", (long long)ldx, (long long)n);
-  bool positive = false;
-  for (int64_t i = 0; i < n; ++i) {
-    if (!std::isfinite(y_sorted[i])) return ob::fail(OB_E_INVALID, "ob_rifs_pass: y must be finite");
-    if (i && y_sorted[i] < y_sorted[i - 1]) return ob::fail(OB_E_INVALID, "ob_rifs_pass: y must be in ascending order");
-    if (pl.gini && y_sorted[i] < 0.0) return ob::fail(OB_E_INVALID, "ob_rifs_pass: the Gini takes no negative y");
-    positive = positive || y_sorted[i] > 0.0;
-  }
-  if (pl.gini && !positive) return ob::fail(OB_E_INVALID, "ob_rifs_pass: the Gini needs a positive y");
-  for (int64_t j = 0; j < (int64_t)p; ++j)
-    for (int64_t i = 0; i < n; ++i)
-      if (!std::isfinite(x[j * ldx + i])) return ob::fail(OB_E_INVALID, "ob_rifs_pass: x must be finite");
-  if (counts)
-    for (int32_t r = 0; r < n_reps; ++r) {
-      int64_t sum = 0;
-      for (int64_t i = 0; i < n; ++i) sum += counts[(size_t)r * n + i];
-      if (sum != n)
-        return ob::fail(OB_E_INVALID, "ob_rifs_pass: the counts of replicate %d sum to %lld, not to n = %lld", r,
-                        (long long)sum, (long long)n);
-    }
+  OB_TRY(ob::refit_pass_check("ob_rifs_pass", y_sorted, n, counts, n_reps, x, ldx, p, pl.gini));
   if (!ctx) return ob::fail(OB_E_INVALID, "null pointer: ctx");
   OB_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const uint32_t tiles = (uint32_t)((n + OB_TILE_ROWS - 1) / OB_TILE_ROWS), nc = std::min<uint32_t>(tiles, 128u);
-  const int64_t ld = (int64_t)tiles * OB_TILE_ROWS;
-  const uint32_t nb_rep = ((uint32_t)n_reps + 63u) / 64u, rep_pad = nb_rep * 64u;
+  ob::RefitPassInput in;
+  OB_TRY(in.upload(y_sorted, n, counts, n_reps, x, ldx, k, s));
   const int S = n_specs;
-  std::vector<uint32_t> chunks, runs;
-  for (uint32_t c = 0; c < nc; ++c) {
-    chunks.push_back(0u);
-    chunks.push_back((uint32_t)((uint64_t)tiles * c / nc));
-    chunks.push_back((uint32_t)((uint64_t)tiles * (c + 1) / nc));
-  }
+  std::vector<uint32_t> runs;
   if (pl.gini) tie_runs(y_sorted, n, 0u, runs);
-  double mu0 = 0.0;
-  for (int64_t i = 0; i < n; ++i) mu0 += y_sorted[i];
-  mu0 /= (double)n;
-  DevBuf d_cols, d_chunks, d_runs, d_counts, d_m1;
-  OB_HIP(d_cols.alloc(sizeof(double) * (size_t)ld * k));
-  OB_HIP(hipMemsetAsync(d_cols.p, 0, sizeof(double) * (size_t)ld * k, s));
-  OB_HIP(hipMemcpyAsync(d_cols.p, y_sorted, sizeof(double) * n, hipMemcpyHostToDevice, s));
-  for (int j = 1; j < k; ++j)
-    OB_HIP(hipMemcpyAsync(d_cols.d() + (size_t)j * ld, x + (size_t)(j - 1) * ldx, sizeof(double) * n, hipMemcpyHostToDevice, s));
-  OB_HIP(d_chunks.alloc(sizeof(uint32_t) * chunks.size()));
-  OB_HIP(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(uint32_t) * chunks.size(), hipMemcpyHostToDevice, s));
+  DevBuf d_runs;
   OB_HIP(d_runs.alloc(sizeof(uint32_t) * runs.size()));
   if (!runs.empty()) OB_HIP(hipMemcpyAsync(d_runs.p, runs.data(), sizeof(uint32_t) * runs.size(), hipMemcpyHostToDevice, s));
-  std::vector<uint32_t> img, m1;  // the engine's layouts: f64-Gram count images and [replicate][tile] counts
-  if (counts) {
-    img.assign((size_t)tiles * nb_rep * 4 * kCimgWords, 0u);
-    m1.assign((size_t)n_reps * tiles, 0u);
-    for (int32_t r = 0; r < n_reps; ++r)
-      for (int64_t i = 0; i < n; ++i) {
-        const uint32_t c = counts[(size_t)r * n + i];
-        if (!c) continue;
-        const size_t tl = (size_t)(i / OB_TILE_ROWS), within = (size_t)(i % OB_TILE_ROWS), sub = within >> 6, qq = within & 63;
-        img[((tl * nb_rep + ((uint32_t)r >> 6)) * 4 + sub) * kCimgWords + ((uint32_t)r & 63u) * kCimgStride + (qq >> 2)] |=
-            c << (8 * (qq & 3));
-        m1[(size_t)r * tiles + tl] += c;
-      }
-    OB_HIP(d_counts.alloc(sizeof(uint32_t) * img.size()));
-    OB_HIP(hipMemcpyAsync(d_counts.p, img.data(), sizeof(uint32_t) * img.size(), hipMemcpyHostToDevice, s));
-    OB_HIP(d_m1.alloc(sizeof(uint32_t) * m1.size()));
-    OB_HIP(hipMemcpyAsync(d_m1.p, m1.data(), sizeof(uint32_t) * m1.size(), hipMemcpyHostToDevice, s));
-  }
   RifsArgs a{};
   ob::RifqArgs qa{};
-  a.cols[0] = qa.cols[0] = d_cols.d();
-  a.ld[0] = qa.ld[0] = ld;
+  a.cols[0] = qa.cols[0] = in.cols.d();
+  a.ld[0] = qa.ld[0] = in.ld;
   a.n[0] = qa.n[0] = (uint32_t)n;
-  a.mu0[0] = qa.mu0[0] = mu0;
+  a.mu0[0] = qa.mu0[0] = in.mu0;
   qa.npow[0] = std::pow((double)n, -0.2);
   a.k = qa.k = k;
   a.n_groups = qa.n_groups = 1;
-  qa.tiles_total = tiles;
-  qa.m1 = counts ? d_m1.as<uint32_t>() : nullptr;
-  a.counts = qa.counts = counts ? d_counts.as<uint32_t>() : nullptr;
-  a.nb_rep = qa.nb_rep = nb_rep;
-  a.part_pad = qa.part_pad = rep_pad;
+  qa.tiles_total = in.tiles;
+  qa.m1 = counts ? in.m1.as<uint32_t>() : nullptr;
+  a.counts = qa.counts = counts ? in.counts.as<uint32_t>() : nullptr;
+  a.nb_rep = qa.nb_rep = in.nb_rep;
+  a.part_pad = qa.part_pad = in.rep_pad;
   a.n_reps = qa.n_reps = (uint32_t)n_reps;
-  a.chunks = qa.chunks = d_chunks.as<uint32_t>();
-  a.n_chunks = qa.n_chunks = (int)nc;
+  a.chunks = qa.chunks = in.chunks.as<uint32_t>();
+  a.n_chunks = qa.n_chunks = (int)in.n_chunks;
   a.runs = d_runs.as<uint32_t>();
   a.n_runs = (int)(runs.size() / 3);
   g_timing = {};
@@ -757,287 +700,130 @@ struct RifsState {
   DevBuf runs, solved, sok;
   int n_runs = 0;
   RifsWork work;
-  double mu0[2] = {0.0, 0.0}, npow[2] = {0.0, 0.0};
-  std::vector<int32_t> perm[2];  // sorted position -> row of the group before the sort
+  SortedGroups sorted;           // perm, mu0, npow (x and y are dropped once uploaded)
   std::vector<double> point_nu;  // [2][S]
   int64_t n_floored = 0;         // floored densities of the point pass and of every boot since
 };
 
-constexpr uint64_t kRifsSegReps = 2048;
-constexpr uint64_t kRifsCountBudget = 8ull << 30;  // bytes of count images per segment
+static RifsState* rifs_state(const ob_prepared* pr) { return model_state<RifsState>(pr, kModelRifs); }
 
-// One segment: counts (the OBRS-3 stream, or unit counts for the point pass), the f64 Gram and its reduce, the refit
-// kernels, then per statistic the y-pairs patched into the Grams, the engine's solve and the row with its tail.
-// rows / ok: [S][n_total] blocks, this segment at s0.
-static int rifs_segment(ob_prepared* pr, RifsState* st, bool point, uint64_t first_rep, uint32_t ns, uint64_t n_total,
-                        uint64_t s0, double* d_rows, uint8_t* d_ok, hipStream_t s) {
+// One segment (refit_segment) with the plan's kernels and rifs_tail_kernel.
+static int rifs_segment(ob_prepared* pr, const RefitSegment& sg, hipStream_t s) {
+  RifsState* st = rifs_state(pr);
   ob_panel* p = pr->panel;
-  const int k = st->k, S = st->plan.n_specs, rl0 = p->row_len, rl = pr->row_len;
-  Events<13> ev;  // [0] start | [1 .. 11] rifs_launch's | [12] solve end
+  const int k = st->k, rl0 = p->row_len;
+  Events<11> ev;  // rifs_launch's
   OB_HIP(ev.create());
-  OB_HIP(hipEventRecord(ev.e[0], s));
-  uint32_t nb_rep = 0, rep_pad = 0;
-  if (point) OB_TRY(engine_unit_counts(p, s, &nb_rep, &rep_pad));
-  else OB_TRY(engine_counts(p, pr->seed, first_rep, ns, s, &nb_rep, &rep_pad));
-  OB_TRY(engine_gram_f64(p, ns, s));
-  OB_HIP(st->solved.alloc(sizeof(double) * (size_t)rep_pad * rl0));
-  OB_HIP(st->sok.alloc(rep_pad));
   RifsArgs a{};
-  RifqArgs qa{};
-  for (int g = 0; g < 2; ++g) {
-    a.cols[g] = qa.cols[g] = st->cols[g].d();
-    a.ld[g] = qa.ld[g] = p->ld[g];
-    a.n[g] = qa.n[g] = p->n[g];
-    a.mu0[g] = qa.mu0[g] = st->mu0[g];
-    qa.npow[g] = st->npow[g];
-  }
-  a.tile0[1] = qa.tile0[1] = p->ntiles[0];
-  a.k = qa.k = k;
-  a.n_groups = qa.n_groups = 2;
-  qa.tiles_total = p->ntiles[0] + p->ntiles[1];
-  qa.m1 = p->d_m1;
-  a.counts = qa.counts = p->d_counts;
-  a.nb_rep = qa.nb_rep = nb_rep;
-  a.part_pad = qa.part_pad = rep_pad;
-  a.n_reps = qa.n_reps = ns;
-  a.chunks = qa.chunks = p->d_chunks;
-  a.n_chunks = qa.n_chunks = (int)(p->chunks.size() / 3);
-  a.runs = st->runs.as<uint32_t>();
-  a.n_runs = st->n_runs;
-  OB_TRY(rifs_launch(a, qa, st->plan, st->work, s, ev.e + 1));
-  RifqArgs sa{};  // rifq_store_kernel reads these four
-  sa.k = k;
-  sa.n_reps = ns;
-  sa.n_taus = S;
-  sa.ogy = a.gy;
-  for (int t = 0; t < S; ++t) {
-    OB_TRY(rifq_store(sa, t, p->d_gram, p->e_pad, s));
-    OB_TRY(engine_solve_grams(p, p->d_gram, nullptr, ns, ns, 0, pr->ref, st->solved.d(), st->sok.as<uint8_t>(), s));
-    hipLaunchKernelGGL(rifs_tail_kernel, dim3(ns), dim3(64), 0, s, a, t, (const double*)st->solved.d(),
-                       (const uint8_t*)st->sok.p, rl0, d_rows + ((size_t)t * n_total + s0) * rl,
-                       d_ok + (size_t)t * n_total + s0);
-    OB_HIP(hipGetLastError());
-  }
-  OB_HIP(hipEventRecord(ev.e[12], s));
-  std::vector<uint8_t> fl((size_t)ns * 2 * S);
-  OB_HIP(hipMemcpyAsync(fl.data(), a.fl, fl.size(), hipMemcpyDeviceToHost, s));
-  OB_HIP(hipStreamSynchronize(s));  // the one host wait of a segment: the floor flags and the timings
-  float gram_ms = 0.f, solve_ms = 0.f;
-  OB_HIP(hipEventElapsedTime(&gram_ms, ev.e[0], ev.e[1]));
-  OB_HIP(hipEventElapsedTime(&solve_ms, ev.e[7], ev.e[12]));
-  g_timing.gram_ms += gram_ms;
-  g_timing.solve_ms += solve_ms;
-  OB_TRY(rifs_times(ev.e + 1, st->plan));
-  for (uint8_t v : fl) st->n_floored += v ? 1 : 0;
-  return OB_OK;
+  RefitModel md{st->plan.n_specs, &st->solved, &st->sok, &st->n_floored, nullptr, nullptr};
+  md.launch = [&](uint32_t nb_rep, uint32_t rep_pad, RefitOut* out) -> int {
+    RifqArgs qa{};
+    for (int g = 0; g < 2; ++g) {
+      a.cols[g] = qa.cols[g] = st->cols[g].d();
+      a.ld[g] = qa.ld[g] = p->ld[g];
+      a.n[g] = qa.n[g] = p->n[g];
+      a.mu0[g] = qa.mu0[g] = st->sorted.mu0[g];
+      qa.npow[g] = st->sorted.npow[g];
+    }
+    a.tile0[1] = qa.tile0[1] = p->ntiles[0];
+    a.k = qa.k = k;
+    a.n_groups = qa.n_groups = 2;
+    qa.tiles_total = p->ntiles[0] + p->ntiles[1];
+    qa.m1 = p->d_m1;
+    a.counts = qa.counts = p->d_counts;
+    a.nb_rep = qa.nb_rep = nb_rep;
+    a.part_pad = qa.part_pad = rep_pad;
+    a.n_reps = qa.n_reps = sg.ns;
+    a.chunks = qa.chunks = p->d_chunks;
+    a.n_chunks = qa.n_chunks = (int)(p->chunks.size() / 3);
+    a.runs = st->runs.as<uint32_t>();
+    a.n_runs = st->n_runs;
+    OB_TRY(rifs_launch(a, qa, st->plan, st->work, s, ev.e));
+    *out = {a.gy, a.fl};
+    return OB_OK;
+  };
+  md.tail = [&](int t, const double* solved, const uint8_t* sok, double* rows, uint8_t* ok) {
+    hipLaunchKernelGGL(rifs_tail_kernel, dim3(sg.ns), dim3(64), 0, s, a, t, solved, sok, rl0, rows, ok);
+  };
+  RefitTimes tm;
+  OB_TRY(refit_segment(pr, sg, md, s, &tm));
+  g_timing.gram_ms += tm.gram_ms;
+  g_timing.solve_ms += tm.solve_ms;
+  return rifs_times(ev.e, st->plan);
 }
 
 static int rifs_boot_device(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
                             hipStream_t stream) {
-  if (!pr || !pr->rifs || (n_reps && (!d_rows || !d_ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  if (first_rep + n_reps > 0xFFFFFFFFull)
-    return fail(OB_E_INVALID, "replicate ids must stay below 2^32 - 1 (OBRS-3 counter word)");
-  RifsState* st = pr->rifs;
-  ob_panel* p = pr->panel;
-  OB_HIP(hipSetDevice(p->ctx->device));
-  hipStream_t s = stream ? stream : p->ctx->stream;
-  OB_TRY(engine_order(p, s));
-  g_timing = {};
-  const uint32_t tiles = p->ntiles[0] + p->ntiles[1];
-  const uint64_t batch_bytes = (uint64_t)std::max(tiles, 1u) * 4 * kCimgWords * sizeof(uint32_t);
-  const uint64_t seg_cap = std::max<uint64_t>(64, (kRifsCountBudget / batch_bytes) * 64);
-  const uint64_t seg = std::min<uint64_t>(n_reps, std::min<uint64_t>(kRifsSegReps, seg_cap));
-  OB_HIP(hipMemsetAsync(p->d_flags + 2, 0, sizeof(uint32_t), s));  // engine_counts' overflow word
-  int rc = OB_OK;
-  for (uint64_t s0 = 0; s0 < n_reps && rc == OB_OK; s0 += seg)
-    rc = rifs_segment(pr, st, false, first_rep + s0, (uint32_t)std::min<uint64_t>(seg, n_reps - s0), n_reps, s0, d_rows,
-                      d_ok, s);
-  uint32_t flag = 0;
-  if (rc == OB_OK && hipMemcpyAsync(&flag, p->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = fail(OB_E_HIP, "copy of the overflow word failed");
-  if (rc == OB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(OB_E_HIP, "stream synchronize failed");
-  const int rm = engine_mark(p, s);
-  if (rc != OB_OK) return rc;
-  if (flag & 1u) return fail(OB_E_OVERFLOW, "a resampled row was drawn more than 255 times in one replicate");
-  return rm;
+  const BootPlan plan{kRefitSegReps, kCountBudget, false, [](uint32_t) {
+                        g_timing = {};
+                        return OB_OK;
+                      }};
+  return boot_segmented(pr, kModelRifs, plan, first_rep, n_reps, d_rows && d_ok, stream,
+                        [&](uint64_t s0, uint32_t ns, uint32_t, uint32_t, hipStream_t s) {
+                          return rifs_segment(pr, {false, first_rep + s0, ns, n_reps, s0, d_rows, d_ok}, s);
+                        });
 }
 
-static int rifs_boot_host(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) {
-  if (!pr || !pr->rifs || (n_reps && (!rows || !ok))) return fail(OB_E_INVALID, "null pointer");
-  if (n_reps == 0) return OB_OK;
-  OB_HIP(hipSetDevice(pr->panel->ctx->device));
-  const size_t S = (size_t)pr->rifs->plan.n_specs;
-  DevBuf d_rows, d_ok;
-  OB_HIP(d_rows.alloc(sizeof(double) * S * n_reps * pr->row_len));
-  OB_HIP(d_ok.alloc(S * n_reps));
-  OB_TRY(rifs_boot_device(pr, first_rep, n_reps, d_rows.d(), d_ok.as<uint8_t>(), nullptr));
-  OB_HIP(hipMemcpy(rows, d_rows.p, sizeof(double) * S * n_reps * pr->row_len, hipMemcpyDeviceToHost));
-  OB_HIP(hipMemcpy(ok, d_ok.p, S * n_reps, hipMemcpyDeviceToHost));
-  return OB_OK;
-}
-
-static void rifs_free(RifsState* s) { delete s; }
-
-static const bool g_rifs_hooks_installed = [] {
-  RifsHooks& h = rifs_hooks();
-  h.boot_device = rifs_boot_device;
-  h.boot_host = rifs_boot_host;
-  h.free_state = rifs_free;
-  return true;
-}();
+static const bool g_rifs_hooks_installed = model_install(
+    kModelRifs, {rifs_boot_device, model_boot_host, [](void* s) { delete static_cast<RifsState*>(s); }});
 
 // Every check of the frame entry points, before any device work and before the context is read.
 static int rifs_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
-                      const ob_rif_spec* specs, int32_t n_specs, Config& c, RifsPlan& pl, ob_matrices** m) {
+                      const ob_rif_spec* specs, int32_t n_specs, Config& c, RifsPlan& pl, Matrices& m) {
   OB_TRY(config_from(cfg, c));
   OB_TRY(rifs_plan(specs, n_specs, pl));
-  if (c.has_weights) return fail(OB_E_UNSUPPORTED, "statistics refit: sample weights are outside its scope");
-  if (!c.normalize.empty()) return fail(OB_E_UNSUPPORTED, "statistics refit: normalized categoricals are outside its scope");
-  if (c.has_selection || !c.selection_predictors.empty())
-    return fail(OB_E_UNSUPPORTED, "statistics refit: Heckman selection settings are outside its scope");
-  if (c.has_cluster) return fail(OB_E_UNSUPPORTED, "statistics refit: a cluster bootstrap is outside its scope");
-  Frame f;
-  OB_TRY(load_frame(cols, n_cols, n_rows, f));
-  std::vector<std::string> named = {c.outcome, c.group};
-  named.insert(named.end(), c.predictors.begin(), c.predictors.end());
-  named.insert(named.end(), c.categorical.begin(), c.categorical.end());
-  for (const std::string& name : named) {
-    const int i = f.find(name);
-    if (i < 0) return fail(OB_E_COLUMN, "%s%s", error_prefix(OB_E_COLUMN), name.c_str());
-    for (int64_t r = 0; r < f.nrows; ++r)
-      if (!f.cols[i].valid[r])
-        return fail(OB_E_INVALID, "statistics refit: column `%s` has a null in row %lld", name.c_str(), (long long)r);
-  }
-  OB_TRY(ob_builder_data_matrices(cols, n_cols, n_rows, cfg, m));
-  int64_t n_a = 0, n_b = 0;
-  int32_t k = 0;
-  const double *xa, *ya, *xb, *yb;
-  int rc = ob_matrices_dims(*m, &n_a, &n_b, &k);
-  if (rc == OB_OK) rc = ob_matrices_get(*m, &xa, &ya, &xb, &yb);
-  if (rc == OB_OK) rc = rifs_check_shape(k, specs, n_specs, n_a, n_b);
-  for (int g = 0; g < 2 && rc == OB_OK; ++g) {
-    const double* x = g ? xb : xa;
-    const double* y = g ? yb : ya;
-    const int64_t n = g ? n_b : n_a;
+  if (c.has_weights) return model_refuse(kModelRifs, "sample weights are");
+  if (!c.normalize.empty()) return model_refuse(kModelRifs, "normalized categoricals are");
+  if (c.has_selection || !c.selection_predictors.empty()) return model_refuse(kModelRifs, "Heckman selection settings are");
+  if (c.has_cluster) return model_refuse(kModelRifs, "a cluster bootstrap is");
+  OB_TRY(stage_named(cols, n_cols, n_rows, c, kModelRifs, false, false));
+  OB_TRY(m.load(cols, n_cols, n_rows, cfg, false));
+  OB_TRY(rifs_check_shape(m.k, specs, n_specs, m.n[0], m.n[1]));
+  for (int g = 0; g < 2; ++g) {
     bool positive = false;
-    for (int64_t i = 0; i < n && rc == OB_OK; ++i) {
-      if (!std::isfinite(y[i])) rc = fail(OB_E_INVALID, "statistics refit: a non-finite value in the outcome");
-      else if (pl.gini && y[i] < 0.0) rc = fail(OB_E_INVALID, "statistics refit: the Gini takes no negative outcome");
-      positive = positive || y[i] > 0.0;
+    for (int64_t i = 0; i < m.n[g]; ++i) {
+      const double y = m.y[g][i];
+      if (!std::isfinite(y)) return fail(OB_E_INVALID, "statistics refit: a non-finite value in the outcome");
+      if (pl.gini && y < 0.0) return fail(OB_E_INVALID, "statistics refit: the Gini takes no negative outcome");
+      positive = positive || y > 0.0;
     }
-    if (rc == OB_OK && pl.gini && !positive)
-      rc = fail(OB_E_INVALID, "statistics refit: the Gini needs a positive outcome in each group");
-    for (int64_t i = 0; i < n * k && rc == OB_OK; ++i)
-      if (!std::isfinite(x[i])) rc = fail(OB_E_INVALID, "statistics refit: a non-finite value in a predictor");
+    if (pl.gini && !positive) return fail(OB_E_INVALID, "statistics refit: the Gini needs a positive outcome in each group");
+    for (int64_t i = 0; i < m.n[g] * m.k; ++i)
+      if (!std::isfinite(m.x[g][i])) return fail(OB_E_INVALID, "statistics refit: a non-finite value in a predictor");
   }
-  if (rc != OB_OK) {
-    ob_matrices_free(*m);
-    *m = nullptr;
-  }
-  return rc;
+  return OB_OK;
 }
 
 static int rifs_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
                         const ob_rif_spec* specs, int32_t n_specs, ob_prepared** out) {
   Config c;
   RifsPlan pl;
-  ob_matrices* m = nullptr;
-  OB_TRY(rifs_stage(cols, n_cols, n_rows, cfg, specs, n_specs, c, pl, &m));
-  struct Guard {
-    ob_matrices* m;
-    ~Guard() { ob_matrices_free(m); }
-  } guard{m};
+  Matrices m;
+  OB_TRY(rifs_stage(cols, n_cols, n_rows, cfg, specs, n_specs, c, pl, m));
   if (!ctx) return fail(OB_E_INVALID, "null pointer: ctx");
-  int64_t nn[2] = {0, 0};
-  int32_t k = 0;
-  const double *xg[2], *yg[2];
-  OB_TRY(ob_matrices_dims(m, &nn[0], &nn[1], &k));
-  OB_TRY(ob_matrices_get(m, &xg[0], &yg[0], &xg[1], &yg[1]));
-  ob_prepared* pr = new ob_prepared();
+  const int k = m.k;
   RifsState* st = new RifsState();
-  pr->rifs = st;
-  pr->ctx = ctx;
-  pr->cfg = c;
-  pr->ref = c.ref;
-  if (c.has_seed) {
-    pr->seed = c.seed;
-  } else {
-    std::random_device rd;
-    pr->seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
-  }
-  pr->k = k;
-  pr->n_base = 0;
-  pr->row_len = ob_row_len(k, 0) + 2;
-  for (int32_t j = 0; j < k; ++j) pr->names.emplace_back(ob_matrices_name(m, j));
-  pr->detail_names = pr->names;
-  pr->n_a = nn[0];
-  pr->n_b = nn[1];
-  pr->n_y = n_specs;
-  pr->n_resid = 0;
+  ob_prepared* pr = model_handle(ctx, c, m, kModelRifs, st, ob_row_len(k, 0) + 2, n_specs);
   st->k = k;
   st->plan = pl;
   st->specs.assign(specs, specs + n_specs);
-  // each group's rows in stable ascending order of y: [x_0 = 1 | x_1 ..] and y, column-major n x k
-  std::vector<double> xs[2], ys[2];
+  SortedGroups& sg = st->sorted;
+  sort_groups(m, sg);
   std::vector<uint32_t> runs;
-  for (int g = 0; g < 2; ++g) {
-    const int64_t n = nn[g];
-    st->perm[g].resize((size_t)n);
-    std::iota(st->perm[g].begin(), st->perm[g].end(), 0);
-    const double* y = yg[g];
-    std::stable_sort(st->perm[g].begin(), st->perm[g].end(), [y](int32_t a, int32_t b) { return y[a] < y[b]; });
-    xs[g].resize((size_t)n * k);
-    ys[g].resize((size_t)n);
-    double mu = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t r = st->perm[g][(size_t)i];
-      ys[g][(size_t)i] = y[r];
-      mu += y[r];
-      for (int32_t j = 0; j < k; ++j) xs[g][(size_t)j * n + i] = xg[g][(size_t)j * n + r];
-    }
-    st->mu0[g] = mu / (double)n;
-    st->npow[g] = std::pow((double)n, -0.2);
-    if (pl.gini) tie_runs(ys[g].data(), n, (uint32_t)g, runs);
-  }
+  for (int g = 0; g < 2 && pl.gini; ++g) tie_runs(sg.y[g].data(), m.n[g], (uint32_t)g, runs);
   st->n_runs = (int)(runs.size() / 3);
-  ob_panel_desc pd{};
-  pd.p = k - 1;
-  pd.n_num = (int32_t)c.predictors.size();
-  pd.n_y = 1;
-  pd.a = {nn[0], xs[0].data() + nn[0], nn[0], ys[0].data(), nullptr};
-  pd.b = {nn[1], xs[1].data() + nn[1], nn[1], ys[1].data(), nullptr};
   auto build = [&]() -> int {
-    OB_TRY(ob_panel_create(ctx, &pd, &pr->panel));
-    ob_panel* p = pr->panel;
-    for (int g = 0; g < 2; ++g) {  // [y | x_1 ..] x ld, zero past n
-      const int64_t n = nn[g];
-      const size_t bytes = sizeof(double) * (size_t)k * p->ld[g];
-      OB_HIP(st->cols[g].alloc(bytes));
-      OB_HIP(hipMemset(st->cols[g].p, 0, bytes));
-      OB_HIP(hipMemcpy(st->cols[g].p, ys[g].data(), sizeof(double) * n, hipMemcpyHostToDevice));
-      if (k > 1)
-        OB_HIP(hipMemcpy2D(st->cols[g].d() + p->ld[g], sizeof(double) * p->ld[g], xs[g].data() + n, sizeof(double) * n,
-                           sizeof(double) * n, k - 1, hipMemcpyHostToDevice));
-    }
+    OB_TRY(refit_panel(ctx, c, m, sg, &pr->panel));
+    for (int g = 0; g < 2; ++g)
+      OB_TRY(upload_group(st->cols[g], pr->panel->ld[g], m.n[g], k, 0, sg.y[g].data(), sg.x[g].data()));
     OB_HIP(st->runs.alloc(sizeof(uint32_t) * runs.size()));
     if (!runs.empty()) OB_HIP(hipMemcpy(st->runs.p, runs.data(), sizeof(uint32_t) * runs.size(), hipMemcpyHostToDevice));
     // the point pass: the boot's own kernels over unit counts
-    hipStream_t s = ctx->stream;
-    const size_t S = (size_t)n_specs;
-    DevBuf d_rows, d_ok;
-    OB_HIP(d_rows.alloc(sizeof(double) * S * pr->row_len));
-    OB_HIP(d_ok.alloc(S));
     g_timing = {};
-    OB_TRY(engine_order(p, s));
-    OB_TRY(rifs_segment(pr, st, true, 0, 1, 1, 0, d_rows.d(), d_ok.as<uint8_t>(), s));
-    OB_TRY(engine_mark(p, s));
-    pr->point_row.assign(S * pr->row_len, 0.0);
-    std::vector<uint8_t> okh(S, 0);
-    OB_HIP(hipMemcpy(pr->point_row.data(), d_rows.p, sizeof(double) * S * pr->row_len, hipMemcpyDeviceToHost));
-    OB_HIP(hipMemcpy(okh.data(), d_ok.p, S, hipMemcpyDeviceToHost));
-    for (uint8_t v : okh)
-      if (!v) return fail(OB_E_LINALG, "%sstatistics refit: the point estimate's regression could not be solved", error_prefix(OB_E_LINALG));
+    OB_TRY(refit_point(pr, [&](double* d_rows, uint8_t* d_ok, hipStream_t s) {
+      return rifs_segment(pr, {true, 0, 1, 1, 0, d_rows, d_ok}, s);
+    }));
+    const size_t S = (size_t)n_specs;
     const int rl0 = pr->row_len - 2;
     st->point_nu.resize(2 * S);
     for (size_t t = 0; t < S; ++t)
@@ -1045,12 +831,11 @@ static int rifs_prepare(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int6
     return OB_OK;
   };
   const int rc = build();
-  if (rc != OB_OK) {
-    ob_prepared_destroy(pr);
-    return rc;
+  for (int g = 0; g < 2; ++g) {
+    sg.x[g] = {};
+    sg.y[g] = {};
   }
-  *out = pr;
-  return OB_OK;
+  return model_built(pr, rc, out);
 }
 
 }  // namespace ob
@@ -1091,10 +876,10 @@ int ob_builder_decompose_statistics_refit(ob_ctx* ctx, const ob_column* cols, in
 
 int ob_prepared_rifs_info(const ob_prepared* prep, ob_rifs_info* out) {
   if (!prep || !out) return ob::fail(OB_E_INVALID, "null pointer");
-  if (!prep->rifs) return ob::fail(OB_E_INVALID, "the handle was not prepared for a statistics refit");
-  const ob::RifsState* st = prep->rifs;
-  *out = {st->plan.n_specs, st->k, prep->n_a, prep->n_b, st->n_floored, st->specs.data(), st->perm[0].data(),
-          st->perm[1].data(), st->point_nu.data()};
+  const ob::RifsState* st = ob::rifs_state(prep);
+  if (!st) return ob::fail(OB_E_INVALID, "the handle was not prepared for a statistics refit");
+  *out = {st->plan.n_specs, st->k, prep->n_a, prep->n_b, st->n_floored, st->specs.data(), st->sorted.perm[0].data(),
+          st->sorted.perm[1].data(), st->point_nu.data()};
   return OB_OK;
 }
 

@@ -31,16 +31,4 @@ int rifs_plan(const ob_rif_spec* specs, int n_specs, RifsPlan& out);
 // k: design columns with the intercept; a group needs more than k rows and at least two.
 int rifs_check_shape(int k, const ob_rif_spec* specs, int n_specs, int64_t n_a, int64_t n_b);
 
-struct RifsState;  // device side of a prepared refit run (ob_rifs.hip)
-
-// ob_builder.cpp reaches the refit through these hooks only (as it does the quantile refit), so that it links
-// without ob_rifs.hip. ob_rifs.hip installs them when the library loads.
-struct RifsHooks {
-  int (*boot_device)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* d_rows, uint8_t* d_ok,
-                     hipStream_t stream) = nullptr;
-  int (*boot_host)(ob_prepared* pr, uint64_t first_rep, uint64_t n_reps, double* rows, uint8_t* ok) = nullptr;
-  void (*free_state)(RifsState* s) = nullptr;
-};
-RifsHooks& rifs_hooks();  // ob_builder.cpp
-
 }  // namespace ob

@@ -15,6 +15,7 @@
 
 #include "../../include/oaxaca_boot.h"
 #include "../../oaxaca-blinder-rs_amd/csrc/ob_linalg.hpp"
+#include "../../oaxaca-blinder-rs_amd/csrc/ob_model.hpp"
 #include "../../oaxaca-blinder-rs_amd/csrc/ob_shard_layout.h"
 
 static int failures = 0;
@@ -272,6 +273,61 @@ static void linalg() {
   CHECK(!ob::try_inverse(std::vector<double>(36, 0.0), 6, inv));
 }
 
+// pack_count_images (ob_model.hpp): decoded with the kernels' index formula the images give the counts back, m1 holds
+// the tile sums, and no word beyond the valid rows is set.
+static void count_images() {
+  for (int64_t n : {1, 255, 256, 257, 600})
+    for (uint32_t reps : {1u, 64u, 65u}) {
+      const uint32_t tiles = (uint32_t)((n + OB_TILE_ROWS - 1) / OB_TILE_ROWS), nb_rep = (reps + 63u) / 64u;
+      std::vector<uint8_t> c((size_t)reps * n);
+      for (size_t i = 0; i < c.size(); ++i) c[i] = i % 7 == 0 ? 0 : i % 11 == 0 ? 255 : (uint8_t)(1 + (i * 2654435761u >> 13) % 254);
+      c[0] = 255;
+      c.back() = 0;
+      std::vector<uint32_t> img((size_t)tiles * nb_rep * 4 * kCimgWords, 0u), m1((size_t)reps * tiles, 0u);
+      ob::pack_count_images(c.data(), n, n, reps, nb_rep, img.data(), m1.data(), tiles);
+      std::vector<uint8_t> addressed(img.size() * 4, 0);
+      bool same = true, sums = true;
+      for (uint32_t rep = 0; rep < reps; ++rep) {
+        std::vector<uint32_t> want(tiles, 0u);
+        for (int64_t row = 0; row < n; ++row) {
+          const size_t tile = (size_t)(row / OB_TILE_ROWS), within = (size_t)(row % OB_TILE_ROWS), sub = within >> 6, q = within & 63;
+          const size_t word = ((tile * nb_rep + rep / 64) * 4 + sub) * kCimgWords + (rep % 64) * kCimgStride + q / 4;
+          same = same && ((img[word] >> (8 * (q % 4))) & 255u) == c[(size_t)rep * n + row];
+          addressed[word * 4 + q % 4] = 1;
+          want[tile] += c[(size_t)rep * n + row];
+        }
+        for (uint32_t tl = 0; tl < tiles; ++tl) sums = sums && m1[(size_t)rep * tiles + tl] == want[tl];
+      }
+      bool clean = true;
+      for (size_t b = 0; b < addressed.size(); ++b)
+        if (!addressed[b]) clean = clean && ((img[b / 4] >> (8 * (b % 4))) & 255u) == 0u;
+      CHECK(same);
+      CHECK(sums);
+      CHECK(clean);
+    }
+}
+
+// One dispatch answers a handle of each model kind (ob_builder.cpp): the sharded refusal keeps the parent's code and
+// text, copied from its ladder.
+static void model_refusals() {
+  const char* sharded[] = {"binary decomposition: sharded runs are outside its scope",
+                           "reweighted decomposition: sharded runs are outside its scope",
+                           "distribution regression: sharded runs are outside its scope",
+                           "quantile refit: sharded runs are outside its scope",
+                           "statistics refit: sharded runs are outside its scope"};
+  const int kinds[] = {ob::kModelBinary, ob::kModelReweight, ob::kModelDr, ob::kModelRifq, ob::kModelRifs};
+  for (int i = 0; i < 5; ++i) {
+    ob_prepared pr;
+    int state = 0;
+    pr.model_kind = kinds[i];
+    pr.model = &state;
+    double row = 0.0;
+    uint8_t ok = 0;
+    CHECK(ob_prepared_boot_sharded(&pr, 0, 1, &row, &ok) == OB_E_UNSUPPORTED);
+    CHECK(std::strcmp(ob_last_error(), sharded[i]) == 0);
+  }
+}
+
 int main(int argc, char** argv) {
   const char* dir = argc > 1 ? argv[1] : "/tmp";
   csv_and_frames(dir);
@@ -279,6 +335,8 @@ int main(int argc, char** argv) {
   no_gpu();
   shard_layout();
   linalg();
+  count_images();
+  model_refusals();
   std::printf("host_asan: %s (%d failed checks)\n", failures ? "FAIL" : "ok", failures);
   return failures ? 1 : 0;
 }
