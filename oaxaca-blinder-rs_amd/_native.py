@@ -12,6 +12,8 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # OB_LIB_PATH: an alternative build for A/B timing runs (tools/build_alt.sh); never set in tests.
 LIB_PATH = os.environ.get("OB_LIB_PATH") or os.path.join(_HERE, "liboaxaca_boot.so")
@@ -24,65 +26,6 @@ OB_COL_F64, OB_COL_I64, OB_COL_STR = 0, 1, 2
 OB_TABLE_TWO_FOLD, OB_TABLE_DETAILED_EXPLAINED, OB_TABLE_DETAILED_UNEXPLAINED = 0, 1, 2
 OB_TABLE_DETAILED_SELECTION, OB_TABLE_THREE_FOLD = 3, 4
 OB_VEC_RESIDUALS, OB_VEC_XA_MEAN, OB_VEC_XB_MEAN, OB_VEC_BETA_STAR = 0, 1, 2, 3
-
-# Every exported entry point of include/oaxaca_boot.h (tests/test_capi_host.py checks both ways).
-EXPORTED = (
-    "ob_last_error", "ob_version", "ob_device_count", "ob_ctx_create", "ob_ctx_destroy",
-    "ob_panel_create", "ob_panel_destroy", "ob_panel_row_len", "ob_panel_k", "ob_panel_n_base", "ob_panel_n_y",
-    "ob_point_estimate", "ob_boot_run", "ob_boot_run_device", "ob_panel_last_timing", "ob_panel_sync",
-    "ob_bootstrap_stats", "ob_aggregate", "ob_rif",
-    "ob_builder_prepare", "ob_prepared_row_len", "ob_prepared_n_y", "ob_prepared_seed", "ob_prepared_panel",
-    "ob_prepared_boot", "ob_prepared_boot_device", "ob_prepared_finish", "ob_prepared_destroy",
-    "ob_builder_run", "ob_builder_decompose_quantile", "ob_builder_decompose_quantiles",
-    "ob_builder_data_matrices", "ob_csv_read", "ob_csv_dims", "ob_csv_column", "ob_csv_free",
-    "ob_results_total_gap", "ob_results_n_a", "ob_results_n_b", "ob_results_n_failed",
-    "ob_results_count", "ob_results_component", "ob_results_vector", "ob_results_free",
-    "ob_matrices_dims", "ob_matrices_get", "ob_matrices_name", "ob_matrices_free",
-    "ob_mm_run", "ob_quantile_decomposition_run", "ob_qd_results_dims", "ob_qd_results_get",
-    "ob_qd_results_n_failed", "ob_qd_results_free",
-    "ob_get_unique_id", "ob_ctx_create_rank", "ob_ctx_rank", "ob_boot_run_sharded", "ob_boot_run_sharded_device",
-    "ob_boot_run_multi", "ob_debug_counts", "ob_prepared_boot_sharded", "ob_debug_gram",
-    "ob_debug_gram_exceptions", "ob_panel_set_gather_columns", "ob_debug_shard_sim", "ob_debug_mm_fail",
-    "ob_debug_chunks", "ob_debug_mm_betas", "ob_set_option", "ob_get_option", "ob_tuning_build",
-    "ob_debug_normal",
-    "ob_logit", "ob_probit", "ob_kde", "ob_silverman_bandwidth", "ob_dfl_run", "ob_dfl_results_get", "ob_dfl_results_info",
-    "ob_dfl_results_free",
-    "ob_knn", "ob_match_logistic", "ob_match_run", "ob_match_results_get", "ob_match_results_info",
-    "ob_match_results_free",
-    "ob_akm_connected_set", "ob_akm_set_get", "ob_akm_set_id", "ob_akm_set_free", "ob_akm_demean",
-    "ob_akm_recover_fe", "ob_akm_run", "ob_akm_results_get", "ob_akm_results_info", "ob_akm_results_free",
-    "ob_vif_gram", "ob_vif_solve", "ob_vif_sums", "ob_vif", "ob_vif_run", "ob_vif_last_timing",
-    "ob_normal_inverse_cdf", "ob_remedy_solve", "ob_remedy_score", "ob_remedy_allocate", "ob_remedy_results_info",
-    "ob_remedy_results_get", "ob_remedy_results_free", "ob_remedy_results_model", "ob_remedy_run",
-    "ob_remedy_frontier",
-    "ob_remedy_defend_rows", "ob_remedy_defend", "ob_remedy_resolve_overrides", "ob_remedy_results_defensible",
-    "ob_remedy_results_defend_info", "ob_remedy_apply_adjustments", "ob_remedy_verify",
-    "ob_jackknife_check_shape", "ob_jackknife", "ob_jackknife_rows", "ob_jackknife_last_timing", "ob_jackknife_finish",
-    "ob_bca_stats", "ob_aggregate_bca", "ob_prepared_jackknife", "ob_prepared_finish_bca", "ob_builder_run_bca",
-    "ob_results_jackknife",
-    "ob_cluster_check_shape", "ob_cluster_index", "ob_cluster_gram", "ob_cluster_counts", "ob_cluster_apply",
-    "ob_cluster_last_timing", "ob_builder_prepare_clustered", "ob_builder_run_clustered",
-    "ob_builder_decompose_quantiles_clustered", "ob_prepared_cluster_info", "ob_results_n_clusters",
-    "ob_cluster_jackknife", "ob_cluster_jackknife_rows",
-    "ob_cluster_jackknife_check_shape", "ob_prepared_cluster_jackknife", "ob_prepared_cluster_jackknife_rows",
-    "ob_prepared_finish_cluster_bca", "ob_builder_run_clustered_bca", "ob_cluster_jackknife_last_timing",
-    "ob_rif_stat", "ob_rif_scan_block", "ob_rif_last_timing", "ob_builder_decompose_statistics",
-    "ob_builder_decompose_statistics_clustered",
-    "ob_binary_row_len", "ob_binary_check_shape", "ob_binary_means", "ob_binary_last_timing",
-    "ob_builder_prepare_binary", "ob_builder_run_binary", "ob_prepared_point_row",
-    "ob_reweight_row_len", "ob_reweight_check_shape", "ob_reweight_last_timing", "ob_reweight_logit_pass",
-    "ob_reweight_gram", "ob_builder_prepare_reweighted", "ob_builder_run_reweighted",
-    "ob_rif_stat_weighted", "ob_builder_prepare_reweighted_statistic", "ob_prepared_reweight_statistics",
-    "ob_builder_run_reweighted_statistics",
-    "ob_dr_row_len", "ob_dr_check_shape", "ob_dr_last_timing", "ob_dr_thresholds", "ob_dr_quantiles",
-    "ob_dr_finish_rows", "ob_dr_logit_pass", "ob_dr_cdf", "ob_builder_prepare_dr", "ob_builder_run_dr",
-    "ob_prepared_dr_info",
-    "ob_rifq_row_len", "ob_rifq_check_shape", "ob_rifq_pass", "ob_rifq_last_timing",
-    "ob_builder_prepare_quantiles_refit", "ob_builder_decompose_quantiles_refit", "ob_prepared_rifq_info",
-    "ob_prepared_finish_tau",
-    "ob_rifs_row_len", "ob_rifs_check_shape", "ob_rifs_pass", "ob_rifs_last_timing",
-    "ob_builder_prepare_statistics_refit", "ob_builder_decompose_statistics_refit", "ob_prepared_rifs_info",
-)
 
 OB_E_CONVERGENCE = 12
 OB_LOGIT_MAX_K = 64  # include/oaxaca_boot.h
@@ -329,6 +272,12 @@ class ob_component(C.Structure):
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _U8 = C.POINTER(C.c_uint8)
+_H = C.POINTER(_P)  # a handle out parameter
+# the prefix of every entry point that takes a frame: ctx, cols, n_cols, n_rows (then the builder's config)
+_FRAME = [_P, C.POINTER(ob_column), C.c_int32, C.c_int64]
+_FRAME_CFG = _FRAME + [C.POINTER(ob_builder_config)]
+_CLUSTER = C.POINTER(ob_cluster_config)
+_SPEC = C.POINTER(ob_rif_spec)
 _SIGS = {
     "ob_last_error": (C.c_char_p, []),
     "ob_version": (C.c_char_p, []),
@@ -349,8 +298,7 @@ _SIGS = {
     "ob_bootstrap_stats": (C.c_int, [_D, C.c_int64, C.c_double, _D]),
     "ob_aggregate": (C.c_int, [_D, _U8, C.c_uint64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _D]),
     "ob_rif": (C.c_int, [_D, C.c_int64, C.c_double, _D]),
-    "ob_builder_prepare": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                     C.POINTER(ob_builder_config), C.POINTER(_P)]),
+    "ob_builder_prepare": (C.c_int, _FRAME_CFG + [_H]),
     "ob_prepared_row_len": (C.c_int, [_P]),
     "ob_prepared_n_y": (C.c_int, [_P]),
     "ob_prepared_seed": (C.c_uint64, [_P]),
@@ -359,14 +307,10 @@ _SIGS = {
     "ob_prepared_boot_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P]),
     "ob_prepared_finish": (C.c_int, [_P, _D, _U8, C.c_uint64, C.POINTER(_P)]),
     "ob_prepared_destroy": (None, [_P]),
-    "ob_builder_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                 C.POINTER(ob_builder_config), C.POINTER(_P)]),
-    "ob_builder_decompose_quantile": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                C.POINTER(ob_builder_config), C.c_double, C.POINTER(_P)]),
-    "ob_builder_decompose_quantiles": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                 C.POINTER(ob_builder_config), _D, C.c_int32, C.POINTER(_P)]),
-    "ob_builder_data_matrices": (C.c_int, [C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                           C.POINTER(ob_builder_config), C.POINTER(_P)]),
+    "ob_builder_run": (C.c_int, _FRAME_CFG + [_H]),
+    "ob_builder_decompose_quantile": (C.c_int, _FRAME_CFG + [C.c_double, _H]),
+    "ob_builder_decompose_quantiles": (C.c_int, _FRAME_CFG + [_D, C.c_int32, _H]),
+    "ob_builder_data_matrices": (C.c_int, _FRAME_CFG[1:] + [_H]),  # host only: no ctx
     "ob_csv_read": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "ob_csv_dims": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "ob_csv_column": (C.c_int, [_P, C.c_int32, C.POINTER(ob_column)]),
@@ -384,8 +328,7 @@ _SIGS = {
     "ob_matrices_name": (C.c_char_p, [_P, C.c_int32]),
     "ob_matrices_free": (None, [_P]),
     "ob_mm_run": (C.c_int, [_P, C.c_uint64, C.c_int32, _D, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, _D, _U8]),
-    "ob_quantile_decomposition_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                C.POINTER(ob_qd_config), C.POINTER(_P)]),
+    "ob_quantile_decomposition_run": (C.c_int, _FRAME + [C.POINTER(ob_qd_config), _H]),
     "ob_qd_results_dims": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ob_qd_results_get": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(ob_component)]),
     "ob_qd_results_n_failed": (C.c_int64, [_P]),
@@ -416,8 +359,7 @@ _SIGS = {
                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ob_kde": (C.c_int, [_P, _D, _D, C.c_int64, _D, C.c_int64, C.c_double, _D]),
     "ob_silverman_bandwidth": (C.c_int, [_D, C.c_int64, _D]),
-    "ob_dfl_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_dfl_config),
-                             C.POINTER(_P)]),
+    "ob_dfl_run": (C.c_int, _FRAME + [C.POINTER(ob_dfl_config), _H]),
     "ob_dfl_results_get": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D),
                                      C.POINTER(_D)]),
     "ob_dfl_results_info": (C.c_int, [_P, C.POINTER(ob_dfl_info)]),
@@ -426,15 +368,13 @@ _SIGS = {
                          C.POINTER(C.c_int64), _D]),
     "ob_match_logistic": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int32, C.c_int32, C.c_double, _D, _D,
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "ob_match_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_match_config),
-                               C.POINTER(_P)]),
+    "ob_match_run": (C.c_int, _FRAME + [C.POINTER(ob_match_config), _H]),
     "ob_match_results_get": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(_D), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int64)),
                                        C.POINTER(C.POINTER(C.c_int64)), C.POINTER(_D)]),
     "ob_match_results_info": (C.c_int, [_P, C.POINTER(ob_match_info)]),
     "ob_match_results_free": (None, [_P]),
-    "ob_akm_connected_set": (C.c_int, [C.POINTER(ob_column), C.c_int32, C.c_int64, C.c_char_p, C.c_char_p,
-                                       C.POINTER(_P)]),
+    "ob_akm_connected_set": (C.c_int, _FRAME[1:] + [C.c_char_p, C.c_char_p, _H]),  # host only: no ctx
     "ob_akm_set_get": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(_U8), C.POINTER(C.c_int64),
                                  C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -446,8 +386,7 @@ _SIGS = {
     "ob_akm_recover_fe": (C.c_int, [_P, _D, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64,
                                     C.c_int64, C.c_double, C.c_int64, _D, _D, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32)]),
-    "ob_akm_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_akm_config),
-                             C.POINTER(_P)]),
+    "ob_akm_run": (C.c_int, _FRAME + [C.POINTER(ob_akm_config), _H]),
     "ob_akm_results_get": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(_D), C.POINTER(C.c_int64),
                                      C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(_D), C.POINTER(C.c_int64),
                                      C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(_D), C.POINTER(C.c_double)]),
@@ -458,7 +397,7 @@ _SIGS = {
     "ob_vif_sums": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _D]),
     "ob_vif": (C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int32, _D]),
     "ob_vif_last_timing": (C.c_int, [_D, _D, _D]),
-    "ob_vif_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.c_int32, _D]),
+    "ob_vif_run": (C.c_int, _FRAME + [C.POINTER(C.c_char_p), C.c_int32, _D]),
     "ob_normal_inverse_cdf": (C.c_double, [C.c_double]),
     "ob_remedy_solve": (C.c_int, [_D, _D, C.c_int32, _D, _D]),
     "ob_remedy_score": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _D, _D, _D]),
@@ -471,15 +410,12 @@ _SIGS = {
     "ob_remedy_results_free": (None, [_P]),
     "ob_remedy_results_model": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(_D),
                                           C.POINTER(_D)]),
-    "ob_remedy_frontier": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
-                                     C.c_int32, C.c_double, _D, _D, _D, C.POINTER(C.c_int32), _D]),
-    "ob_remedy_run": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
-                                C.POINTER(ob_remedy_request), C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ob_remedy_frontier": (C.c_int, _FRAME_CFG + [C.c_int32, C.c_double, _D, _D, _D, C.POINTER(C.c_int32), _D]),
+    "ob_remedy_run": (C.c_int, _FRAME_CFG + [C.POINTER(ob_remedy_request), C.c_int32, C.c_int32, _H]),
     "ob_remedy_defend_rows": (C.c_int, [_P, _D, _D, _D, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _D, C.c_int64,
                                         C.c_double, C.c_double, C.POINTER(_P)]),
-    "ob_remedy_defend": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
-                                   C.POINTER(C.c_int64), _D, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_char_p), _D,
-                                   C.c_int64, C.c_double, C.c_int32, C.POINTER(_P)]),
+    "ob_remedy_defend": (C.c_int, _FRAME_CFG + [C.POINTER(C.c_int64), _D, C.c_int64, C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_char_p), _D, C.c_int64, C.c_double, C.c_int32, _H]),
     "ob_remedy_resolve_overrides": (C.c_int, [C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64),
                                               C.POINTER(C.c_char_p), _D, C.c_int64, C.POINTER(C.c_char_p), C.c_int32,
                                               C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _D,
@@ -487,8 +423,7 @@ _SIGS = {
     "ob_remedy_results_defensible": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_int32))]),
     "ob_remedy_results_defend_info": (C.c_int, [_P, C.POINTER(ob_defend_info)]),
     "ob_remedy_apply_adjustments": (C.c_int, [_D, _U8, C.c_int64, C.POINTER(C.c_int64), _D, C.c_int64, _D]),
-    "ob_remedy_verify": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
-                                   C.POINTER(C.c_int64), _D, C.c_int64, C.POINTER(_P)]),
+    "ob_remedy_verify": (C.c_int, _FRAME_CFG + [C.POINTER(C.c_int64), _D, C.c_int64, _H]),
     "ob_jackknife_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "ob_jackknife": (C.c_int, [_P, C.c_int, C.POINTER(ob_jackknife_out)]),
     "ob_jackknife_rows": (C.c_int, [_P, C.c_int, _D, _U8, C.POINTER(C.c_int64)]),
@@ -499,8 +434,7 @@ _SIGS = {
                                    _D]),
     "ob_prepared_jackknife": (C.c_int, [_P, C.POINTER(ob_jackknife_out)]),
     "ob_prepared_finish_bca": (C.c_int, [_P, _D, _U8, C.c_uint64, C.c_double, C.POINTER(_P)]),
-    "ob_builder_run_bca": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
-                                     C.c_double, C.POINTER(_P)]),
+    "ob_builder_run_bca": (C.c_int, _FRAME_CFG + [C.c_double, _H]),
     "ob_results_jackknife": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "ob_cluster_check_shape": (C.c_int, [C.c_int64, C.c_int32]),
     "ob_cluster_index": (C.c_int, [C.POINTER(ob_column), C.POINTER(C.c_int32), C.c_int64, C.c_int32,
@@ -512,14 +446,9 @@ _SIGS = {
                                     C.POINTER(C.c_uint32)]),
     "ob_cluster_apply": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_uint32, C.c_int64, _D, C.c_int32, _D]),
     "ob_cluster_last_timing": (C.c_int, [C.POINTER(ob_cluster_timing)]),
-    "ob_builder_prepare_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                               C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config),
-                                               C.POINTER(_P)]),
-    "ob_builder_run_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                           C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config), C.POINTER(_P)]),
-    "ob_builder_decompose_quantiles_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                           C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config),
-                                                           _D, C.c_int32, C.POINTER(_P)]),
+    "ob_builder_prepare_clustered": (C.c_int, _FRAME_CFG + [_CLUSTER, _H]),
+    "ob_builder_run_clustered": (C.c_int, _FRAME_CFG + [_CLUSTER, _H]),
+    "ob_builder_decompose_quantiles_clustered": (C.c_int, _FRAME_CFG + [_CLUSTER, _D, C.c_int32, _H]),
     "ob_prepared_cluster_info": (C.c_int, [_P, C.POINTER(ob_cluster_info)]),
     "ob_results_n_clusters": (C.c_int64, [_P]),
     "ob_cluster_jackknife_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
@@ -530,46 +459,31 @@ _SIGS = {
     "ob_cluster_jackknife_rows": (C.c_int, [_P, _D, C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.c_int32, C.c_int,
                                             _D, _U8, C.POINTER(C.c_int64), _D]),
     "ob_prepared_finish_cluster_bca": (C.c_int, [_P, _D, _U8, C.c_uint64, C.c_double, C.POINTER(_P)]),
-    "ob_builder_run_clustered_bca": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                               C.POINTER(ob_builder_config), C.POINTER(ob_cluster_config), C.c_double,
-                                               C.POINTER(_P)]),
+    "ob_builder_run_clustered_bca": (C.c_int, _FRAME_CFG + [_CLUSTER, C.c_double, _H]),
     "ob_cluster_jackknife_last_timing": (C.c_int, [_D]),
     "ob_rif_stat": (C.c_int, [_P, _D, C.c_int64, C.POINTER(ob_rif_spec), _D, _D]),
     "ob_rif_scan_block": (C.c_int32, []),
     "ob_rif_last_timing": (C.c_int, [C.POINTER(ob_rif_timing)]),
-    "ob_builder_decompose_statistics": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                  C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec), C.c_int32,
-                                                  C.POINTER(_P)]),
-    "ob_builder_decompose_statistics_clustered": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                            C.POINTER(ob_builder_config),
-                                                            C.POINTER(ob_cluster_config), C.POINTER(ob_rif_spec),
-                                                            C.c_int32, C.POINTER(_P)]),
+    "ob_builder_decompose_statistics": (C.c_int, _FRAME_CFG + [_SPEC, C.c_int32, _H]),
+    "ob_builder_decompose_statistics_clustered": (C.c_int, _FRAME_CFG + [_CLUSTER, _SPEC, C.c_int32, _H]),
     "ob_binary_row_len": (C.c_int, [C.c_int32]),
     "ob_binary_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64]),
     "ob_binary_means": (C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int32, _U8, _D, _D]),
     "ob_binary_last_timing": (C.c_int, [C.POINTER(ob_binary_timing)]),
-    "ob_builder_prepare_binary": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                            C.POINTER(ob_builder_config), C.c_int32, C.POINTER(_P)]),
-    "ob_builder_run_binary": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                        C.POINTER(ob_builder_config), C.c_int32, C.POINTER(_P)]),
+    "ob_builder_prepare_binary": (C.c_int, _FRAME_CFG + [C.c_int32, _H]),
+    "ob_builder_run_binary": (C.c_int, _FRAME_CFG + [C.c_int32, _H]),
     "ob_prepared_point_row": (C.c_int, [_P, C.POINTER(_D), C.POINTER(C.c_int64)]),
     "ob_reweight_row_len": (C.c_int, [C.c_int32]),
     "ob_reweight_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64]),
     "ob_reweight_last_timing": (C.c_int, [C.POINTER(ob_reweight_timing)]),
     "ob_reweight_logit_pass": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D]),
     "ob_reweight_gram": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D]),
-    "ob_builder_prepare_reweighted": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                C.POINTER(ob_builder_config), C.POINTER(_P)]),
-    "ob_builder_run_reweighted": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                            C.POINTER(ob_builder_config), C.POINTER(_P)]),
-    "ob_rif_stat_weighted": (C.c_int, [_P, _D, _D, C.c_int64, C.POINTER(ob_rif_spec), _D, _D]),
-    "ob_builder_prepare_reweighted_statistic": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                          C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec),
-                                                          C.POINTER(_P)]),
+    "ob_builder_prepare_reweighted": (C.c_int, _FRAME_CFG + [_H]),
+    "ob_builder_run_reweighted": (C.c_int, _FRAME_CFG + [_H]),
+    "ob_rif_stat_weighted": (C.c_int, [_P, _D, _D, C.c_int64, _SPEC, _D, _D]),
+    "ob_builder_prepare_reweighted_statistic": (C.c_int, _FRAME_CFG + [_SPEC, _H]),
     "ob_prepared_reweight_statistics": (C.c_int, [_P, _D]),
-    "ob_builder_run_reweighted_statistics": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                       C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec), C.c_int32,
-                                                       C.POINTER(_P)]),
+    "ob_builder_run_reweighted_statistics": (C.c_int, _FRAME_CFG + [_SPEC, C.c_int32, _H]),
     "ob_dr_row_len": (C.c_int, [C.c_int32, C.c_int32]),
     "ob_dr_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "ob_dr_last_timing": (C.c_int, [C.POINTER(ob_dr_timing)]),
@@ -578,20 +492,16 @@ _SIGS = {
     "ob_dr_finish_rows": (C.c_int, [_D, C.c_int32, C.c_int32, _D, _U8, C.c_uint64, C.POINTER(_P)]),
     "ob_dr_logit_pass": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D, _D]),
     "ob_dr_cdf": (C.c_int, [_P, _D, C.c_int64, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D]),
-    "ob_builder_prepare_dr": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
-                                        C.POINTER(ob_dr_config), C.POINTER(_P)]),
-    "ob_builder_run_dr": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64, C.POINTER(ob_builder_config),
-                                    C.POINTER(ob_dr_config), C.POINTER(_P)]),
+    "ob_builder_prepare_dr": (C.c_int, _FRAME_CFG + [C.POINTER(ob_dr_config), _H]),
+    "ob_builder_run_dr": (C.c_int, _FRAME_CFG + [C.POINTER(ob_dr_config), _H]),
     "ob_prepared_dr_info": (C.c_int, [_P, C.POINTER(ob_dr_info)]),
     "ob_rifq_row_len": (C.c_int, [C.c_int32, C.c_int32]),
     "ob_rifq_check_shape": (C.c_int, [C.c_int32, C.c_int32, _D, C.c_int64, C.c_int64]),
     "ob_rifq_pass": (C.c_int, [_P, _D, C.c_int64, _U8, C.c_int32, _D, C.c_int32, _D, C.c_int64, C.c_int32, _D, _D, _D, _D,
                                _D, _D, _U8]),
     "ob_rifq_last_timing": (C.c_int, [C.POINTER(ob_rifq_timing)]),
-    "ob_builder_prepare_quantiles_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                     C.POINTER(ob_builder_config), _D, C.c_int32, C.POINTER(_P)]),
-    "ob_builder_decompose_quantiles_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                       C.POINTER(ob_builder_config), _D, C.c_int32, C.POINTER(_P)]),
+    "ob_builder_prepare_quantiles_refit": (C.c_int, _FRAME_CFG + [_D, C.c_int32, _H]),
+    "ob_builder_decompose_quantiles_refit": (C.c_int, _FRAME_CFG + [_D, C.c_int32, _H]),
     "ob_prepared_rifq_info": (C.c_int, [_P, C.POINTER(ob_rifq_info)]),
     "ob_prepared_finish_tau": (C.c_int, [_P, C.c_int32, _D, _U8, C.c_uint64, C.POINTER(_P)]),
     "ob_rifs_row_len": (C.c_int, [C.c_int32, C.c_int32]),
@@ -599,14 +509,45 @@ _SIGS = {
     "ob_rifs_pass": (C.c_int, [_P, _D, C.c_int64, _U8, C.c_int32, C.POINTER(ob_rif_spec), C.c_int32, _D, C.c_int64,
                                C.c_int32, _D, _D, _U8, _U8]),
     "ob_rifs_last_timing": (C.c_int, [C.POINTER(ob_rifs_timing)]),
-    "ob_builder_prepare_statistics_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                      C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec), C.c_int32,
-                                                      C.POINTER(_P)]),
-    "ob_builder_decompose_statistics_refit": (C.c_int, [_P, C.POINTER(ob_column), C.c_int32, C.c_int64,
-                                                        C.POINTER(ob_builder_config), C.POINTER(ob_rif_spec),
-                                                        C.c_int32, C.POINTER(_P)]),
+    "ob_builder_prepare_statistics_refit": (C.c_int, _FRAME_CFG + [_SPEC, C.c_int32, _H]),
+    "ob_builder_decompose_statistics_refit": (C.c_int, _FRAME_CFG + [_SPEC, C.c_int32, _H]),
     "ob_prepared_rifs_info": (C.c_int, [_P, C.POINTER(ob_rifs_info)]),
 }
+
+# Every exported entry point of include/oaxaca_boot.h (tests/test_capi_host.py checks both ways).
+EXPORTED = tuple(_SIGS)
+
+
+def _pointer_to(ctype):
+    ptr = C.POINTER(ctype)
+    return lambda a: None if a is None else a.ctypes.data_as(ptr)
+
+
+# A numpy array's buffer as the C ABI takes it (None stays NULL). The array must outlive the call.
+dp, u8p, u32p = _pointer_to(C.c_double), _pointer_to(C.c_uint8), _pointer_to(C.c_uint32)
+i32p, i64p = _pointer_to(C.c_int32), _pointer_to(C.c_int64)
+
+
+def strs(names):
+    """A ``char**`` of the encoded names -> (pointer, the array behind it). The pointer is only good while the
+    array is alive: hold the array until the C call has returned (``api._frame_call`` does)."""
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    return C.cast(arr, C.POINTER(C.c_char_p)), arr
+
+
+def struct_dict(s) -> dict:
+    """A ctypes struct's fields by name."""
+    return {f: getattr(s, f) for f, _ in s._fields_}
+
+
+def array_copy(ptr, shape):
+    """A copy of the library-owned array at the typed pointer ``ptr``. Zero elements never touch the pointer (it
+    may be NULL): they give zeros of the shape in the pointer's type."""
+    shape = tuple(int(v) for v in shape)
+    if not math.prod(shape):
+        return np.zeros(shape, dtype=np.dtype(ptr._type_))
+    return np.ctypeslib.as_array(ptr, shape=shape).copy()
+
 
 _lib = None
 _lib_lock = threading.Lock()

@@ -529,9 +529,7 @@ def dr_finish_rows(point_row, thresholds, quantiles, rows, ok) -> DistributionDe
     if point.shape != (6 * nq + 7 * T + 1,) or rows.shape != (len(ok), len(point)):
         raise ValueError("point_row and rows must have 6 n_q + 7 T + 1 entries per row")
     h = C.c_void_p()
-    dp = C.POINTER(C.c_double)
-    N.check(N.lib().ob_dr_finish_rows(point.ctypes.data_as(dp), T, nq, rows.ctypes.data_as(dp),
-                                      ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
+    N.check(N.lib().ob_dr_finish_rows(N.dp(point), T, nq, N.dp(rows), N.u8p(ok), len(ok), C.byref(h)))
     qe, qv, de, cdf, n_failed, n_a, n_b = _dr_tables(h)
     fr = point[6 * nq + 3 * T:6 * nq + 7 * T].reshape(4, T)
     re, edge = {}, np.zeros((3, nq), dtype=np.uint8)
@@ -548,7 +546,7 @@ def _jackknife_out(k: int):
     bufs = (np.zeros(c), np.zeros((2, c, 3)), np.zeros((c, 3)))
     o = N.ob_jackknife_out()
     o.capacity = c
-    o.point, o.sums, o.stats = (b.ctypes.data_as(C.POINTER(C.c_double)) for b in bufs)
+    o.point, o.sums, o.stats = (N.dp(b) for b in bufs)
     return o, bufs
 
 
@@ -596,7 +594,7 @@ def _results_from_c(handle, jackknife: bool = False) -> OaxacaResults:
         ptr = C.POINTER(C.c_double)()
         n = C.c_int64()
         N.check(lib.ob_results_vector(handle, w, C.byref(ptr), C.byref(n)))
-        return np.ctypeslib.as_array(ptr, shape=(n.value,)).copy() if n.value else np.zeros(0)
+        return N.array_copy(ptr, (n.value,))
 
     try:
         nc = int(lib.ob_results_n_clusters(handle))
@@ -612,6 +610,31 @@ def _results_from_c(handle, jackknife: bool = False) -> OaxacaResults:
             jackknife=jack() if jackknife else None)
     finally:
         lib.ob_results_free(handle)
+
+
+def _remedy_result(handle, info, contributions: bool, defensible: bool = False) -> OptimizationResult:
+    """The adjustments and the fair-wage model of a remediation handle (``ob_remedy_results_get`` / ``_model``);
+    ``info`` is its ``ob_remedy_info`` or ``ob_defend_info``. ``defensible``: the handle carries the defensibility
+    flags, and every adjustment gets its verdict and message."""
+    lib = N.lib()
+    pi, pf = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
+    pd = [C.POINTER(C.c_double)() for _ in range(6)]
+    N.check(lib.ob_remedy_results_get(handle, C.byref(pi), *[C.byref(p) for p in pd], None, None))
+    if defensible:
+        N.check(lib.ob_remedy_results_defensible(handle, C.byref(pf)))
+    k, pn = C.c_int32(), C.POINTER(C.c_char_p)()
+    pb, pc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+    N.check(lib.ob_remedy_results_model(handle, C.byref(k), C.byref(pn), C.byref(pb), C.byref(pc)))
+    names = [pn[j].decode() for j in range(k.value)]
+    adjustments = []
+    for i in range(int(info.n_adjustments)):
+        con = [Contribution(names[j], pc[i * k.value + j]) for j in range(k.value)] if contributions and pc else []
+        verdict = (bool(pf[i]), defensibility_message(bool(pf[i]), pd[2][i], pd[4][i])) if defensible else ()
+        adjustments.append(Adjustment(int(pi[i]), *[p[i] for p in pd], con, *verdict))
+    return OptimizationResult(
+        adjustments=adjustments, total_cost=info.total_cost, original_gap=info.original_gap, new_gap=info.new_gap,
+        original_unexplained_gap=info.original_unexplained_gap, new_unexplained_gap=info.new_unexplained_gap,
+        required_budget=info.required_budget, model_coefficients=[Contribution(names[j], pb[j]) for j in range(k.value)])
 
 
 def parse_formula(formula: str):
@@ -639,9 +662,46 @@ def parse_formula(formula: str):
     return outcome, preds, cats
 
 
-def _strs(names):
-    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
-    return C.cast(arr, C.POINTER(C.c_char_p)), arr
+def _set_names(cfg, field: str, names):
+    """``cfg.<field>`` = the names as a ``char**`` and ``cfg.n_<field>`` = their number -> the array behind the
+    pointer, which goes into ``_frame_call``'s ``keep``."""
+    ptr, arr = N.strs(names)
+    setattr(cfg, field, ptr)
+    setattr(cfg, "n_" + field, len(names))
+    return arr
+
+
+# How an entry point that takes a frame gets its context (DESIGN.md §5.21). The policy is part of a method's
+# behaviour on a machine without a GPU: which error comes first.
+CONTEXT_FIRST = "context-first"      # N.context(device) before the call: the missing device is the first error
+ARGUMENTS_FIRST = "arguments-first"  # engine.with_context: the call's argument errors come before the missing device
+HOST_ONLY = "host-only"              # the entry point takes no context
+
+
+def _frame_call(symbol: str, frame, cfg, keep, *args, policy: str, device=None, ctx=None, handles=None):
+    """``lib.<symbol>(ctx, cols, n_cols, n_rows, &cfg, *args, &handle)``, checked -> the handle.
+    ``keep``: the arrays behind the ``char**`` fields of ``cfg`` and of ``args``; they are held here until the call
+    has returned. ``cfg`` None: an entry point without a config struct. ``policy``: see above; an explicit ``ctx``
+    (a rank context) is used as it is under either policy. ``handles`` = n: the entry point fills an array of n
+    handles, returned as a list; 0: it returns none."""
+    from .engine import with_context
+
+    fn = getattr(N.lib(), symbol)
+    cols, ncol, nrow = frame.as_c()
+    hs = (C.c_void_p * (1 if handles is None else handles))()
+    tail = (() if cfg is None else (C.byref(cfg),)) + args + ((C.cast(hs, C.POINTER(C.c_void_p)),) if len(hs) else ())
+    if policy == HOST_ONLY:
+        N.check(fn(cols, ncol, nrow, *tail))
+    elif ctx is not None:
+        N.check(fn(ctx, cols, ncol, nrow, *tail))
+    elif policy == ARGUMENTS_FIRST:
+        with_context(lambda c: fn(c, cols, ncol, nrow, *tail), device)
+    else:
+        assert policy == CONTEXT_FIRST, policy
+        N.check(fn(N.context(device), cols, ncol, nrow, *tail))
+    del keep  # held until here
+    out = [C.c_void_p(h) for h in hs]
+    return out[0] if handles is None else out
 
 
 class OaxacaBuilder:
@@ -730,37 +790,38 @@ class OaxacaBuilder:
         return self
 
     def _config(self):
-        keep = []
+        """(ob_builder_config, the arrays its ``char**`` fields point into)."""
         cfg = N.ob_builder_config()
         cfg.outcome, cfg.group, cfg.reference_group = (self.outcome.encode(), self.group.encode(),
                                                        self.reference_group.encode())
-        for attr, names in (("predictors", self._predictors), ("categorical", self._categorical),
-                            ("normalize", self._normalize)):
-            ptr, arr = _strs(names)
-            keep.append(arr)
-            setattr(cfg, attr, ptr)
-            setattr(cfg, "n_" + attr if attr != "categorical" else "n_categorical", len(names))
-        cfg.n_predictors = len(self._predictors)
-        cfg.n_normalize = len(self._normalize)
+        keep = [_set_names(cfg, field, names) for field, names in (
+            ("predictors", self._predictors), ("categorical", self._categorical), ("normalize", self._normalize),
+            ("selection_predictors", self._selection_predictors))]
         cfg.weights = self._weights.encode() if self._weights else None
         cfg.selection_outcome = self._selection.encode() if self._selection else None
-        ptr, arr = _strs(self._selection_predictors)
-        keep.append(arr)
-        cfg.selection_predictors = ptr
-        cfg.n_selection_predictors = len(self._selection_predictors)
         cfg.bootstrap_reps = self._bootstrap_reps
         cfg.reference_coeffs = int(self._ref)
         cfg.has_seed = 0 if self._seed is None else 1
         cfg.seed = 0 if self._seed is None else self._seed
         return cfg, keep
 
+    def _call(self, symbol: str, *args, policy: str, ctx=None, handles=None, keep=(), clustered: bool = False):
+        """``_frame_call`` on this builder's frame, configuration and device. ``clustered``: the entry point takes the
+        cluster configuration after the builder's. ``keep``: arrays behind ``char**`` arguments of ``args``."""
+        cfg, held = self._config()
+        if clustered:
+            cc = self._cluster_config()
+            args = (C.byref(cc),) + args
+        return _frame_call(symbol, self._frame, cfg, (held, keep), *args, policy=policy, device=self._device, ctx=ctx,
+                           handles=handles)
+
+    def _prepared(self, handle) -> "PreparedRun":
+        return PreparedRun(handle, self._bootstrap_reps, N.resolve_device(self._device))
+
     def get_data_matrices(self):
         """builder.rs:252-291 -> (X_A, y_A, X_B, y_B, names); X includes the intercept column."""
         lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-        N.check(lib.ob_builder_data_matrices(cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+        h = self._call("ob_builder_data_matrices", policy=HOST_ONLY)
         try:
             na, nb, k = C.c_int64(), C.c_int64(), C.c_int32()
             N.check(lib.ob_matrices_dims(h, C.byref(na), C.byref(nb), C.byref(k)))
@@ -773,8 +834,7 @@ class OaxacaBuilder:
                 return np.ctypeslib.as_array(p, shape=(kk, n)).T.copy()
 
             xa, xb = mat(ptrs[0], na.value, k.value), mat(ptrs[2], nb.value, k.value)
-            ya = np.ctypeslib.as_array(ptrs[1], shape=(na.value,)).copy() if na.value else np.zeros(0)
-            yb = np.ctypeslib.as_array(ptrs[3], shape=(nb.value,)).copy() if nb.value else np.zeros(0)
+            ya, yb = N.array_copy(ptrs[1], (na.value,)), N.array_copy(ptrs[3], (nb.value,))
             names = [lib.ob_matrices_name(h, i).decode() for i in range(k.value)]
             return xa, ya, xb, yb, names
         finally:
@@ -804,49 +864,18 @@ class OaxacaBuilder:
         if target not in N.OB_REMEDY_TARGETS or strategy not in N.OB_REMEDY_STRATEGIES \
                 or range_target not in N.OB_REMEDY_RANGE_TARGETS:
             raise ValueError("target: reference|pooled, strategy: greedy|equitable, range_target: midpoint|lower|upper")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
         rq = N.ob_remedy_request(float(budget), float(min_gap_pct), float(confidence_level),
                                  N.OB_REMEDY_STRATEGIES[strategy], N.OB_REMEDY_RANGE_TARGETS[range_target],
                                  int(bool(forensic_mode)), int(bool(adjust_both_groups)))
-        h = C.c_void_p()
-
-        def call(ctx):
-            return lib.ob_remedy_run(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(rq), N.OB_REMEDY_TARGETS[target],
-                                     int(bool(contributions)), C.byref(h))
-
-        try:
-            ctx = N.context(self._device)
-        except (N.OaxacaError, ImportError):
-            rc = call(None)  # the argument errors come before the device, as in ob_vif_run
-            if not (rc == N.OB_E_INVALID and b"null pointer" in lib.ob_last_error()):
-                N.check(rc)
-            raise  # the arguments are good: the missing device is the error
-        N.check(call(ctx))
+        h = self._call("ob_remedy_run", C.byref(rq), N.OB_REMEDY_TARGETS[target], int(bool(contributions)),
+                       policy=ARGUMENTS_FIRST)
         try:
             info = N.ob_remedy_info()
-            N.check(lib.ob_remedy_results_info(h, C.byref(info)))
-            m = int(info.n_adjustments)
-            pi = C.POINTER(C.c_int64)()
-            pd = [C.POINTER(C.c_double)() for _ in range(6)]
-            N.check(lib.ob_remedy_results_get(h, C.byref(pi), *[C.byref(p) for p in pd], None, None))
-            k, pn = C.c_int32(), C.POINTER(C.c_char_p)()
-            pb, pc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
-            N.check(lib.ob_remedy_results_model(h, C.byref(k), C.byref(pn), C.byref(pb), C.byref(pc)))
-            names = [pn[j].decode() for j in range(k.value)]
-            adjustments = []
-            for i in range(m):
-                con = [Contribution(names[j], pc[i * k.value + j]) for j in range(k.value)] if contributions and pc else []
-                adjustments.append(Adjustment(int(pi[i]), *[p[i] for p in pd], con))
-            self.last_remedy_info = {name: getattr(info, name) for name, _ in info._fields_}
-            return OptimizationResult(
-                adjustments=adjustments, total_cost=info.total_cost, original_gap=info.original_gap,
-                new_gap=info.new_gap, original_unexplained_gap=info.original_unexplained_gap,
-                new_unexplained_gap=info.new_unexplained_gap, required_budget=info.required_budget,
-                model_coefficients=[Contribution(names[j], pb[j]) for j in range(k.value)])
+            N.check(N.lib().ob_remedy_results_info(h, C.byref(info)))
+            self.last_remedy_info = N.struct_dict(info)
+            return _remedy_result(h, info, contributions)
         finally:
-            lib.ob_remedy_results_free(h)
+            N.lib().ob_remedy_results_free(h)
 
     def efficient_frontier(self, steps: int = 50, max_budget: float | None = None) -> list:
         """engine/src/analysis.rs:871-1153 (calculate_efficient_frontier_inner) on the MI355X engine
@@ -854,16 +883,11 @@ class OaxacaBuilder:
         dummy's t statistic in the pooled regression after the greedy raises that budget pays for.
         ``max_budget`` defaults to 1.1 times the total need. ``last_frontier_ms`` keeps the HIP-event ms of the
         two passes (X'Y, rss)."""
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
         s = max(int(steps), 0) + 1
         b, t, p, ms = np.zeros(s), np.zeros(s), np.zeros(s), np.zeros(2)
         sig = np.zeros(s, dtype=np.int32)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
-        N.check(lib.ob_remedy_frontier(N.context(self._device), cols, ncol, nrow, C.byref(cfg), int(steps),
-                                       float("nan") if max_budget is None else float(max_budget), dp(b), dp(t), dp(p),
-                                       sig.ctypes.data_as(C.POINTER(C.c_int32)), dp(ms)))
+        self._call("ob_remedy_frontier", int(steps), float("nan") if max_budget is None else float(max_budget),
+                   N.dp(b), N.dp(t), N.dp(p), N.i32p(sig), N.dp(ms), policy=CONTEXT_FIRST, handles=0)
         self.last_frontier_ms = {"xty_ms": float(ms[0]), "rss_ms": float(ms[1])}
         return [FrontierPoint(float(b[i]), float(t[i]), float(p[i]), bool(sig[i])) for i in range(s)]
 
@@ -881,60 +905,22 @@ class OaxacaBuilder:
         An index outside the frame is skipped (``last_defend_info["n_skipped"]``). The reference
         hard-wires ``confidence_level`` 0.95. ``last_defend_info`` keeps the call's ``ob_defend_info``."""
         prop = _proposed(adjustments)
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
         m = len(prop)
         idx = np.array([p[0] for p in prop], dtype=np.int64)
         val = np.array([p[1] for p in prop], dtype=np.float64)
         flat = [(j, name, v) for j, p in enumerate(prop) for name, v in p[2].items()]
         opos = np.array([f[0] for f in flat], dtype=np.int64)
         oval = np.array([f[2] for f in flat], dtype=np.float64)
-        onames, keep_names = _strs([f[1] for f in flat])
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
-        h = C.c_void_p()
-
-        def call(ctx):
-            return lib.ob_remedy_defend(ctx, cols, ncol, nrow, C.byref(cfg), ip(idx), dp(val), m, ip(opos), onames,
-                                        dp(oval), len(flat), float(confidence_level), int(bool(contributions)),
-                                        C.byref(h))
-
-        try:
-            ctx = N.context(self._device)
-        except (N.OaxacaError, ImportError):
-            rc = call(None)  # the argument errors come before the device, as in optimize()
-            if not (rc == N.OB_E_INVALID and b"null pointer" in lib.ob_last_error()):
-                N.check(rc)
-            raise
-        N.check(call(ctx))
+        onames, keep_names = N.strs([f[1] for f in flat])
+        h = self._call("ob_remedy_defend", N.i64p(idx), N.dp(val), m, N.i64p(opos), onames, N.dp(oval), len(flat),
+                       float(confidence_level), int(bool(contributions)), policy=ARGUMENTS_FIRST, keep=keep_names)
         try:
             info = N.ob_defend_info()
-            N.check(lib.ob_remedy_results_defend_info(h, C.byref(info)))
-            kept = int(info.n_adjustments)
-            pi, pf = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
-            pd = [C.POINTER(C.c_double)() for _ in range(6)]
-            N.check(lib.ob_remedy_results_get(h, C.byref(pi), *[C.byref(p) for p in pd], None, None))
-            N.check(lib.ob_remedy_results_defensible(h, C.byref(pf)))
-            k, pn = C.c_int32(), C.POINTER(C.c_char_p)()
-            pb, pc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
-            N.check(lib.ob_remedy_results_model(h, C.byref(k), C.byref(pn), C.byref(pb), C.byref(pc)))
-            names = [pn[j].decode() for j in range(k.value)]
-            out = []
-            for i in range(kept):
-                con = [Contribution(names[j], pc[i * k.value + j]) for j in range(k.value)] if contributions and pc else []
-                ok = bool(pf[i])
-                out.append(Adjustment(int(pi[i]), *[p[i] for p in pd], con, ok,
-                                      defensibility_message(ok, pd[2][i], pd[4][i])))
-            self.last_defend_info = {name: (list(getattr(info, name)) if name == "sums" else getattr(info, name))
-                                     for name, _ in info._fields_}
-            return OptimizationResult(
-                adjustments=out, total_cost=info.total_cost, original_gap=info.original_gap, new_gap=info.new_gap,
-                original_unexplained_gap=info.original_unexplained_gap,
-                new_unexplained_gap=info.new_unexplained_gap, required_budget=info.required_budget,
-                model_coefficients=[Contribution(names[j], pb[j]) for j in range(k.value)])
+            N.check(N.lib().ob_remedy_results_defend_info(h, C.byref(info)))
+            self.last_defend_info = {**N.struct_dict(info), "sums": list(info.sums)}
+            return _remedy_result(h, info, contributions, defensible=True)
         finally:
-            lib.ob_remedy_results_free(h)
+            N.lib().ob_remedy_results_free(h)
 
     def verify_adjustments(self, adjustments, three_fold: bool = False) -> "DecompositionResult":
         """engine/src/analysis.rs:40-96 (verify_inner) on the MI355X engine (``ob_remedy_verify``): the
@@ -947,26 +933,9 @@ class OaxacaBuilder:
         from .engine import remedy_apply_adjustments
 
         prop = _proposed(adjustments)
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
         idx = np.array([p[0] for p in prop], dtype=np.int64)
         val = np.array([p[1] for p in prop], dtype=np.float64)
-        h = C.c_void_p()
-
-        def call(ctx):
-            return lib.ob_remedy_verify(ctx, cols, ncol, nrow, C.byref(cfg), idx.ctypes.data_as(C.POINTER(C.c_int64)),
-                                        val.ctypes.data_as(C.POINTER(C.c_double)), len(prop), C.byref(h))
-
-        try:
-            ctx = N.context(self._device)
-        except (N.OaxacaError, ImportError):
-            rc = call(None)  # the argument errors come before the device
-            if not (rc == N.OB_E_INVALID and b"null pointer" in lib.ob_last_error()):
-                N.check(rc)
-            raise
-        N.check(call(ctx))
-        res = _results_from_c(h)
+        res = _results_from_c(self._call("ob_remedy_verify", N.i64p(idx), N.dp(val), len(prop), policy=ARGUMENTS_FIRST))
         # run_decomposition_on_df's summary (analysis.rs:102-140) of the adjusted wages
         kind, wage, valid = self._frame.columns[self.outcome]
         adjusted = remedy_apply_adjustments(wage, idx, val, valid)
@@ -1003,17 +972,9 @@ class OaxacaBuilder:
 
     def run(self) -> OaxacaResults:
         """builder.rs:787-951 on the MI355X engine."""
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
         if self._cluster is not None:
-            cc = self._cluster_config()
-            N.check(lib.ob_builder_run_clustered(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(cc),
-                                                 C.byref(h)))
-            return _results_from_c(h)
-        N.check(lib.ob_builder_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
-        return _results_from_c(h)
+            return _results_from_c(self._call("ob_builder_run_clustered", policy=CONTEXT_FIRST, clustered=True))
+        return _results_from_c(self._call("ob_builder_run", policy=CONTEXT_FIRST))
 
     def run_bca(self, confidence_level: float = 0.95) -> OaxacaResults:
         """``run()`` with every component's interval replaced by the bias-corrected and accelerated (BCa)
@@ -1021,22 +982,14 @@ class OaxacaBuilder:
         standard errors and p-values are those of ``run()`` with the same seed; ``.jackknife`` holds, per
         (table, name), the acceleration, the jackknife standard error and bias, z0 and the BCa flag."""
         self._refuse_clustered("run_bca")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-        N.check(lib.ob_builder_run_bca(N.context(self._device), cols, ncol, nrow, C.byref(cfg),
-                                       float(confidence_level), C.byref(h)))
+        h = self._call("ob_builder_run_bca", float(confidence_level), policy=CONTEXT_FIRST)
         return _results_from_c(h, jackknife=True)
 
     def jackknife(self) -> "JackknifeResult":
         """The leave-one-out pass alone: acceleration, jackknife standard error and bias of every component."""
         self._refuse_clustered("jackknife")
-        pr = self.prepare()
-        try:
+        with self.prepare() as pr:
             return pr.jackknife()
-        finally:
-            pr.close()
 
     def _require_clustered(self, what: str):
         if self._cluster is None:
@@ -1048,13 +1001,7 @@ class OaxacaBuilder:
         standard errors and p-values are those of ``run()`` with the same seed; ``.jackknife`` holds, per
         (table, name), the acceleration, the cluster jackknife standard error and bias, z0 and the BCa flag."""
         self._require_clustered("run_cluster_bca")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        cc = self._cluster_config()
-        h = C.c_void_p()
-        N.check(lib.ob_builder_run_clustered_bca(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(cc),
-                                                 float(confidence_level), C.byref(h)))
+        h = self._call("ob_builder_run_clustered_bca", float(confidence_level), policy=CONTEXT_FIRST, clustered=True)
         return _results_from_c(h, jackknife=True)
 
     def cluster_jackknife(self) -> "JackknifeResult":
@@ -1062,51 +1009,33 @@ class OaxacaBuilder:
         jackknife standard error and bias of every component. ``n_used`` / ``n_dropped`` count clusters per
         stratum: all clusters as stratum 0 in joint mode, A's and B's clusters in stratified mode."""
         self._require_clustered("cluster_jackknife")
-        pr = self.prepare()
-        try:
+        with self.prepare() as pr:
             return pr.cluster_jackknife()
-        finally:
-            pr.close()
 
     def decompose_quantile(self, quantile: float, refit: bool = False) -> OaxacaResults:
         """builder.rs:711-757: RIF-regression decomposition at ``quantile``. ``refit=True``: see
         ``decompose_quantiles``."""
         if refit:
             return self.decompose_quantiles([float(quantile)], refit=True)[0]
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
         if self._cluster is not None:
             return self.decompose_quantiles([float(quantile)])[0]
-        N.check(lib.ob_builder_decompose_quantile(N.context(self._device), cols, ncol, nrow, C.byref(cfg),
-                                                  float(quantile), C.byref(h)))
-        return _results_from_c(h)
+        return _results_from_c(self._call("ob_builder_decompose_quantile", float(quantile), policy=CONTEXT_FIRST))
 
     def prepare_quantiles_refit(self, quantiles) -> "PreparedRun":
         """ob_builder_prepare_quantiles_refit: a handle whose replicates refit the quantile, the bandwidth, the
         density and so the RIF on every resample. ``boot`` returns rows (T, n_reps, row_len) and
         ok (T, n_reps); ``point_row()`` is (T * row_len,). Each group's rows stand in stable ascending order of y,
         so the same seed draws other rows than the fixed-RIF run."""
-        from .engine import with_context
-
         taus = np.ascontiguousarray(quantiles, dtype=np.float64)
         if taus.ndim != 1 or taus.size == 0:
             raise ValueError("quantiles must be a non-empty 1-D sequence")
         if self._cluster is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED, "quantile refit: the cluster bootstrap is outside its scope")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-        tp = taus.ctypes.data_as(C.POINTER(C.c_double))
-        with_context(lambda ctx: lib.ob_builder_prepare_quantiles_refit(ctx, cols, ncol, nrow, C.byref(cfg), tp,
-                                                                        int(taus.size), C.byref(h)), self._device)
-        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+        return self._prepared(self._call("ob_builder_prepare_quantiles_refit", N.dp(taus), int(taus.size),
+                                         policy=ARGUMENTS_FIRST))
 
     def _decompose_quantiles_refit(self, quantiles) -> list:
-        pr = self.prepare_quantiles_refit(quantiles)
-        try:
+        with self.prepare_quantiles_refit(quantiles) as pr:
             rows, ok = pr.boot(0, pr.bootstrap_reps)
             info = pr.rifq_info()
             out = []
@@ -1117,8 +1046,6 @@ class OaxacaBuilder:
                 r.n_density_floored = info["n_density_floored"]
                 out.append(r)
             return out
-        finally:
-            pr.close()
 
     def decompose_quantiles(self, quantiles, refit: bool = False) -> list:
         """RIF decompositions at several quantiles in one run: one panel
@@ -1129,23 +1056,13 @@ class OaxacaBuilder:
         ``density_values`` and ``n_density_floored``. Unweighted, no ``normalize``, Heckman or ``cluster``."""
         if refit:
             return self._decompose_quantiles_refit(quantiles)
-        lib = N.lib()
         taus = np.ascontiguousarray(quantiles, dtype=np.float64)
         if taus.ndim != 1 or taus.size == 0:
             raise ValueError("quantiles must be a non-empty 1-D sequence")
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        hs = (C.c_void_p * taus.size)()
-        if self._cluster is not None:
-            cc = self._cluster_config()
-            N.check(lib.ob_builder_decompose_quantiles_clustered(
-                N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(cc),
-                taus.ctypes.data_as(C.POINTER(C.c_double)), int(taus.size), C.cast(hs, C.POINTER(C.c_void_p))))
-            return [_results_from_c(C.c_void_p(h)) for h in hs]
-        N.check(lib.ob_builder_decompose_quantiles(N.context(self._device), cols, ncol, nrow, C.byref(cfg),
-                                                   taus.ctypes.data_as(C.POINTER(C.c_double)), int(taus.size),
-                                                   C.cast(hs, C.POINTER(C.c_void_p))))
-        return [_results_from_c(C.c_void_p(h)) for h in hs]
+        clustered = self._cluster is not None
+        hs = self._call("ob_builder_decompose_quantiles" + ("_clustered" if clustered else ""), N.dp(taus),
+                        int(taus.size), policy=CONTEXT_FIRST, handles=int(taus.size), clustered=clustered)
+        return [_results_from_c(h) for h in hs]
 
     def decompose_statistic(self, stat, refit: bool = False, **params) -> OaxacaResults:
         """RIF-regression decomposition of the gap in a distributional statistic (Firpo, Fortin, Lemieux):
@@ -1163,24 +1080,18 @@ class OaxacaBuilder:
         is (S * row_len,). Row-order convention of §5.18: each group's rows stand in stable ascending order of y and
         OBRS-3 position i is the i-th row in that order, so the same seed draws other rows than the fixed-RIF
         run."""
-        from .engine import _rif_specs, with_context
+        from .engine import _rif_specs
 
         specs, parsed = _rif_specs(stats)
         if not parsed:
             raise ValueError("statistics must be a non-empty sequence")
         if self._cluster is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED, "statistics refit: the cluster bootstrap is outside its scope")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-        with_context(lambda ctx: lib.ob_builder_prepare_statistics_refit(ctx, cols, ncol, nrow, C.byref(cfg), specs,
-                                                                         len(parsed), C.byref(h)), self._device)
-        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+        return self._prepared(self._call("ob_builder_prepare_statistics_refit", specs, len(parsed),
+                                         policy=ARGUMENTS_FIRST))
 
     def _decompose_statistics_refit(self, stats) -> list:
-        pr = self.prepare_statistics_refit(stats)
-        try:
+        with self.prepare_statistics_refit(stats) as pr:
             rows, ok = pr.boot(0, pr.bootstrap_reps)
             info = pr.rifs_info()
             out = []
@@ -1191,8 +1102,6 @@ class OaxacaBuilder:
                     r.n_density_floored = info["n_density_floored"]
                 out.append(r)
             return out
-        finally:
-            pr.close()
 
     def decompose_statistics(self, stats, refit: bool = False) -> list:
         """Several statistics in one run: one panel whose outcomes are the RIF columns, so every replicate's
@@ -1202,7 +1111,7 @@ class OaxacaBuilder:
         ``refit=True``: every replicate refits the statistic on its own resample, so the standard
         errors carry its sampling error; the results gain ``statistic_values`` and, for a range,
         ``n_density_floored``. Unweighted, no ``normalize``, Heckman or ``cluster``."""
-        from .engine import parse_rif_statistic, with_context
+        from .engine import parse_rif_statistic
 
         stats = list(stats)
         parsed = [s if isinstance(s, tuple) and len(s) == 3 else parse_rif_statistic(s) for s in stats]
@@ -1211,38 +1120,18 @@ class OaxacaBuilder:
         if refit:
             return self._decompose_statistics_refit(parsed)
         specs = (N.ob_rif_spec * len(parsed))(*[N.ob_rif_spec(*p) for p in parsed])
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        hs = (C.c_void_p * len(parsed))()
-        out = C.cast(hs, C.POINTER(C.c_void_p))
-        if self._cluster is not None:
-            cc = self._cluster_config()
-            with_context(lambda ctx: lib.ob_builder_decompose_statistics_clustered(
-                ctx, cols, ncol, nrow, C.byref(cfg), C.byref(cc), specs, len(parsed), out), self._device)
-        else:
-            with_context(lambda ctx: lib.ob_builder_decompose_statistics(
-                ctx, cols, ncol, nrow, C.byref(cfg), specs, len(parsed), out), self._device)
-        return [_results_from_c(C.c_void_p(h)) for h in hs]
+        clustered = self._cluster is not None
+        hs = self._call("ob_builder_decompose_statistics" + ("_clustered" if clustered else ""), specs, len(parsed),
+                        policy=ARGUMENTS_FIRST, handles=len(parsed), clustered=clustered)
+        return [_results_from_c(h) for h in hs]
 
     def prepare_binary(self, model: str = "probit") -> "PreparedRun":
-        from .engine import with_context
-
         if model not in N.OB_BINARY_MODELS:
             raise ValueError(f"unknown binary model {model!r}: 'probit' (or 'logit', which is refused)")
         if self._cluster is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED, "binary decomposition: the cluster bootstrap is outside its scope")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-        code = N.OB_BINARY_MODELS[model]
-        if self._ctx is not None:
-            N.check(lib.ob_builder_prepare_binary(self._ctx, cols, ncol, nrow, C.byref(cfg), code, C.byref(h)))
-        else:
-            with_context(lambda ctx: lib.ob_builder_prepare_binary(ctx, cols, ncol, nrow, C.byref(cfg), code,
-                                                                   C.byref(h)), self._device)
-        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+        return self._prepared(self._call("ob_builder_prepare_binary", N.OB_BINARY_MODELS[model], policy=ARGUMENTS_FIRST,
+                                         ctx=self._ctx))
 
     def decompose_binary(self, model: str = "probit") -> "BinaryDecompositionResults":
         """Extension (no counterpart in the reference crate): the nonlinear decomposition of a gap in a 0/1
@@ -1251,13 +1140,10 @@ class OaxacaBuilder:
         detailed terms, bootstrapped like ``run()``. Reference coefficients GroupA, GroupB, Weighted or Cotton.
         Refused (``OB_E_UNSUPPORTED``): ``model="logit"``, weights, ``normalize``, ``cluster``, Heckman settings,
         Pooled / Neumark, more than 32 design columns."""
-        pr = self.prepare_binary(model)
-        try:
+        with self.prepare_binary(model) as pr:
             rows, ok = pr.boot(0, self._bootstrap_reps)
             res = pr.finish(rows, ok)
             point = pr.point_row()
-        finally:
-            pr.close()
         k = (len(point) - 14) // 7
         tail = point[6 + 2 * k:]
         names = [c.name for c in res.two_fold.detailed_explained]
@@ -1276,7 +1162,7 @@ class OaxacaBuilder:
         """The handle of ``decompose_reweighted``. ``statistic`` (with its parameters, as
         ``parse_weighted_rif_statistic`` takes them) makes it the decomposition of that statistic; ``None`` is
         the mean."""
-        from .engine import parse_weighted_rif_statistic, with_context
+        from .engine import parse_weighted_rif_statistic
 
         if statistic is None and params:
             raise ValueError(f"unexpected parameter(s) {', '.join(sorted(params))} without a statistic")
@@ -1284,28 +1170,18 @@ class OaxacaBuilder:
         if self._cluster is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED,
                                 "reweighted decomposition: the cluster bootstrap is outside its scope")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-
-        def call(ctx):
-            if spec is None:
-                return lib.ob_builder_prepare_reweighted(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h))
-            return lib.ob_builder_prepare_reweighted_statistic(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(spec),
-                                                               C.byref(h))
-
-        if self._ctx is not None:
-            N.check(call(self._ctx))
+        if spec is None:
+            h = self._call("ob_builder_prepare_reweighted", policy=ARGUMENTS_FIRST, ctx=self._ctx)
         else:
-            with_context(call, self._device)
-        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+            h = self._call("ob_builder_prepare_reweighted_statistic", C.byref(spec), policy=ARGUMENTS_FIRST,
+                           ctx=self._ctx)
+        return self._prepared(h)
 
     def decompose_reweighted_statistics(self, stats) -> list:
         """Several statistics in one reweighted run (``ob_builder_run_reweighted_statistics``): every replicate's
         resample and logit fit serve all of them. ``stats``: names, ``(name, params)`` pairs or dicts with a
         ``stat`` key, at most 16. Element t equals ``decompose_reweighted`` of element t bitwise (same seed)."""
-        from .engine import parse_weighted_rif_statistic, weighted_rif_name, with_context
+        from .engine import parse_weighted_rif_statistic, weighted_rif_name
 
         parsed = [parse_weighted_rif_statistic(s) for s in stats]
         if not parsed:
@@ -1313,22 +1189,14 @@ class OaxacaBuilder:
         if self._cluster is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED,
                                 "reweighted decomposition: the cluster bootstrap is outside its scope")
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
         specs = (N.ob_rif_spec * len(parsed))(*[N.ob_rif_spec(*p) for p in parsed])
-        hs = (C.c_void_p * len(parsed))()
-        out = C.cast(hs, C.POINTER(C.c_void_p))
-        with_context(lambda ctx: lib.ob_builder_run_reweighted_statistics(ctx, cols, ncol, nrow, C.byref(cfg), specs,
-                                                                          len(parsed), out), self._device)
-        results = [_results_from_c(C.c_void_p(h)) for h in hs]
+        hs = self._call("ob_builder_run_reweighted_statistics", specs, len(parsed), policy=ARGUMENTS_FIRST,
+                        handles=len(parsed))
+        results = [_results_from_c(h) for h in hs]
         outs = []
         for p, res in zip(parsed, results):  # the tables came from the one run; a handle gives the point row and nu
-            pr = self.prepare_reweighted(weighted_rif_name(p))
-            try:
+            with self.prepare_reweighted(weighted_rif_name(p)) as pr:
                 outs.append(_reweighted_results(res, pr.point_row(), weighted_rif_name(p), pr.reweight_statistics()))
-            finally:
-                pr.close()
         return outs
 
     def decompose_reweighted(self, statistic=None, **params) -> "ReweightedDecompositionResults":
@@ -1348,14 +1216,11 @@ class OaxacaBuilder:
         exactly as before."""
         from .engine import parse_weighted_rif_statistic, weighted_rif_name
 
-        pr = self.prepare_reweighted(statistic, **params)
-        try:
+        with self.prepare_reweighted(statistic, **params) as pr:
             rows, ok = pr.boot(0, self._bootstrap_reps)
             res = pr.finish(rows, ok)
             point = pr.point_row()
             nu = None if statistic is None else pr.reweight_statistics()
-        finally:
-            pr.close()
         name = None if statistic is None else weighted_rif_name(parse_weighted_rif_statistic(statistic, **params))
         return _reweighted_results(res, point, name, nu)
 
@@ -1363,39 +1228,24 @@ class OaxacaBuilder:
                              hi=0.95) -> "PreparedRun":
         """The handle of ``decompose_distribution`` (``ob_builder_prepare_dr``): the thresholds are fixed and the
         point pass has run; ``boot`` / ``boot_device`` / ``finish`` / ``point_row`` / ``dr_info`` work on it."""
-        from .engine import with_context
-
         if self._cluster is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED,
                                 "distribution regression: the cluster bootstrap is outside its scope")
         taus = np.ascontiguousarray(np.atleast_1d(quantiles), dtype=np.float64)
         if taus.ndim != 1:
             raise ValueError("quantiles must be a 1-D sequence")
-        dp = C.POINTER(C.c_double)
         dr = N.ob_dr_config()
         thr = None
         if thresholds is not None:
             thr = np.ascontiguousarray(thresholds, dtype=np.float64)
             if thr.ndim != 1:
                 raise ValueError("thresholds must be a 1-D sequence")
-            dr.thresholds, dr.n_thresholds = thr.ctypes.data_as(dp), len(thr)
+            dr.thresholds, dr.n_thresholds = N.dp(thr), len(thr)
         else:
             dr.thresholds, dr.n_thresholds = None, int(n_thresholds)
         dr.lo, dr.hi = float(lo), float(hi)
-        dr.quantiles, dr.n_quantiles = taus.ctypes.data_as(dp), len(taus)
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-
-        def call(ctx):
-            return lib.ob_builder_prepare_dr(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(dr), C.byref(h))
-
-        if self._ctx is not None:
-            N.check(call(self._ctx))
-        else:
-            with_context(call, self._device)
-        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+        dr.quantiles, dr.n_quantiles = N.dp(taus), len(taus)
+        return self._prepared(self._call("ob_builder_prepare_dr", C.byref(dr), policy=ARGUMENTS_FIRST, ctx=self._ctx))
 
     def decompose_distribution(self, quantiles=(0.1, 0.25, 0.5, 0.75, 0.9), thresholds=None, n_thresholds=50, lo=0.05,
                                hi=0.95) -> "DistributionDecompositionResults":
@@ -1411,17 +1261,13 @@ class OaxacaBuilder:
         64 thresholds or 32 quantiles. Warns when a tau lies outside the range the threshold grid covers."""
         import warnings
 
-        pr = self.prepare_distribution(quantiles, thresholds, n_thresholds, lo, hi)
-        try:
+        with self.prepare_distribution(quantiles, thresholds, n_thresholds, lo, hi) as pr:
             rows, ok = pr.boot(0, self._bootstrap_reps)
-            h = C.c_void_p()
-            N.check(N.lib().ob_prepared_finish(pr._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                               ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
+            h = C.c_void_p()  # not finish(): the four tables of this handle are read by _dr_tables
+            N.check(N.lib().ob_prepared_finish(pr._h, N.dp(rows), N.u8p(ok), len(ok), C.byref(h)))
             qe, qv, de, cdf, n_failed, n_a, n_b = _dr_tables(h)
             info = pr.dr_info()
             point = pr.point_row()
-        finally:
-            pr.close()
         from .engine import dr_quantiles
 
         T, nq = len(info["thresholds"]), len(info["quantiles"])
@@ -1488,17 +1334,9 @@ class OaxacaBuilder:
     def prepare(self) -> "PreparedRun":
         """clean/dummies/split/upload/point estimate once; replicate ranges run separately
         (the multi-GPU path in ``distributed.py``)."""
-        lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
-        cfg, keep = self._config()
-        h = C.c_void_p()
-        ctx = self._ctx if self._ctx is not None else N.context(self._device)
-        if self._cluster is not None:
-            cc = self._cluster_config()
-            N.check(lib.ob_builder_prepare_clustered(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(cc), C.byref(h)))
-        else:
-            N.check(lib.ob_builder_prepare(ctx, cols, ncol, nrow, C.byref(cfg), C.byref(h)))
-        return PreparedRun(h, self._bootstrap_reps, N.resolve_device(self._device))
+        clustered = self._cluster is not None
+        return self._prepared(self._call("ob_builder_prepare" + ("_clustered" if clustered else ""), policy=CONTEXT_FIRST,
+                                         ctx=self._ctx, clustered=clustered))
 
 
 class PreparedRun:
@@ -1513,7 +1351,7 @@ class PreparedRun:
         info = N.ob_cluster_info()
         self.cluster_info = None  # a clustered run: n_clusters, n_clusters_a, n_clusters_b, max_cluster_rows, stratified
         if N.lib().ob_prepared_cluster_info(handle, C.byref(info)) == N.OB_OK:
-            self.cluster_info = {f: int(getattr(info, f)) for f, _ in N.ob_cluster_info._fields_}
+            self.cluster_info = {f: int(v) for f, v in N.struct_dict(info).items()}
         # a refit handle (prepare_quantiles_refit): its quantiles; boot then returns (n_taus, n_reps, ...) blocks
         rq = N.ob_rifq_info()
         self.n_taus = int(rq.n_taus) if N.lib().ob_prepared_rifq_info(handle, C.byref(rq)) == N.OB_OK else 0
@@ -1526,9 +1364,7 @@ class PreparedRun:
         rows = np.empty(shape + (self.row_len,), dtype=np.float64)
         ok = np.zeros(shape, dtype=np.uint8)
         if n_reps:
-            N.check(N.lib().ob_prepared_boot(self._h, first_rep, n_reps,
-                                             rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                             ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+            N.check(N.lib().ob_prepared_boot(self._h, first_rep, n_reps, N.dp(rows), N.u8p(ok)))
         return rows, ok
 
     def boot_sharded(self, first_rep: int, n_reps: int):
@@ -1537,9 +1373,7 @@ class PreparedRun:
         rows = np.empty((n_reps, self.row_len), dtype=np.float64)
         ok = np.zeros(n_reps, dtype=np.uint8)
         if n_reps:
-            N.check(N.lib().ob_prepared_boot_sharded(self._h, first_rep, n_reps,
-                                                     rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                                     ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+            N.check(N.lib().ob_prepared_boot_sharded(self._h, first_rep, n_reps, N.dp(rows), N.u8p(ok)))
         return rows, ok
 
     def boot_device(self, first_rep: int, n_reps: int, rows_ptr: int, ok_ptr: int, stream: int | None):
@@ -1552,12 +1386,12 @@ class PreparedRun:
         ptr = C.POINTER(C.c_double)()
         n = C.c_int64()
         N.check(N.lib().ob_prepared_point_row(self._h, C.byref(ptr), C.byref(n)))
-        return np.ctypeslib.as_array(ptr, shape=(n.value,)).copy() if n.value else np.zeros(0)
+        return N.array_copy(ptr, (n.value,))
 
     def reweight_statistics(self) -> tuple:
         """ob_prepared_reweight_statistics: (nu_A, nu_B, nu_C) of a reweighted statistic's handle."""
         out = np.zeros(3)
-        N.check(N.lib().ob_prepared_reweight_statistics(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        N.check(N.lib().ob_prepared_reweight_statistics(self._h, N.dp(out)))
         return tuple(float(v) for v in out)
 
     def dr_info(self) -> dict:
@@ -1566,10 +1400,7 @@ class PreparedRun:
         o = N.ob_dr_info()
         N.check(N.lib().ob_prepared_dr_info(self._h, C.byref(o)))
         T, nq, k = o.n_thresholds, o.n_quantiles, o.k
-
-        def arr(ptr, shape):
-            return np.ctypeslib.as_array(ptr, shape=shape).copy()
-
+        arr = N.array_copy
         return {"thresholds": arr(o.thresholds, (T,)), "quantiles": arr(o.quantiles, (nq,)),
                 "beta": arr(o.beta, (2, T, k)), "passes": arr(o.passes, (2, T)),
                 "out_of_range": arr(o.out_of_range, (3, nq)), "n_out_of_range": int(o.n_out_of_range),
@@ -1581,10 +1412,7 @@ class PreparedRun:
         o = N.ob_rifq_info()
         N.check(N.lib().ob_prepared_rifq_info(self._h, C.byref(o)))
         T = o.n_taus
-
-        def arr(ptr, shape):
-            return np.ctypeslib.as_array(ptr, shape=shape).copy()
-
+        arr = N.array_copy
         return {"taus": arr(o.taus, (T,)), "k": int(o.k), "perm_a": arr(o.perm_a, (o.n_a,)),
                 "perm_b": arr(o.perm_b, (o.n_b,)), "q": arr(o.q, (2, T)), "f": arr(o.f, (2, T)),
                 "n_density_floored": int(o.n_density_floored)}
@@ -1595,10 +1423,7 @@ class PreparedRun:
         o = N.ob_rifs_info()
         N.check(N.lib().ob_prepared_rifs_info(self._h, C.byref(o)))
         S = o.n_specs
-
-        def arr(ptr, shape):
-            return np.ctypeslib.as_array(ptr, shape=shape).copy()
-
+        arr = N.array_copy
         return {"specs": [(int(o.specs[t].stat), float(o.specs[t].p0), float(o.specs[t].p1)) for t in range(S)],
                 "k": int(o.k), "perm_a": arr(o.perm_a, (o.n_a,)), "perm_b": arr(o.perm_b, (o.n_b,)),
                 "nu": arr(o.nu, (2, S)), "n_density_floored": int(o.n_density_floored)}
@@ -1606,11 +1431,7 @@ class PreparedRun:
     def finish_tau(self, t: int, rows: np.ndarray, ok: np.ndarray) -> OaxacaResults:
         """ob_prepared_finish_tau: ``finish`` for quantile t of a refit handle, or statistic t of a statistics refit
         handle (rows / ok: its block)."""
-        rows, ok = self._flat_block(rows, ok)
-        h = C.c_void_p()
-        N.check(N.lib().ob_prepared_finish_tau(self._h, int(t), rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                               ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
-        return _results_from_c(h)
+        return self._finish("ob_prepared_finish_tau", rows, ok, tau=int(t))
 
     def sync(self):
         N.check(N.lib().ob_panel_sync(N.lib().ob_prepared_panel(self._h)))
@@ -1618,7 +1439,7 @@ class PreparedRun:
     def timing(self) -> dict:
         t = N.ob_timing()
         N.check(N.lib().ob_panel_last_timing(N.lib().ob_prepared_panel(self._h), C.byref(t)))
-        return {f: getattr(t, f) for f, _ in N.ob_timing._fields_}
+        return N.struct_dict(t)
 
     def _flat_block(self, rows, ok):
         """rows (n_reps, row_len) and ok (n_reps,) of one outcome: a refit handle's (T, n_reps, ...) blocks go
@@ -1630,12 +1451,20 @@ class PreparedRun:
                              "handle's boot to finish_tau")
         return rows, ok
 
-    def finish(self, rows: np.ndarray, ok: np.ndarray) -> OaxacaResults:
-        rows, ok = self._flat_block(rows, ok)
+    def _finish(self, symbol: str, rows, ok, *extra, jackknife: bool = False, tau=None, flat: bool = True):
+        """``lib.<symbol>(handle[, tau], rows, ok, n_reps, *extra, &results)`` -> OaxacaResults. ``flat`` False skips
+        ``_flat_block``'s shape check."""
+        if flat:
+            rows, ok = self._flat_block(rows, ok)
+        else:
+            rows, ok = np.ascontiguousarray(rows, dtype=np.float64), np.ascontiguousarray(ok, dtype=np.uint8)
         h = C.c_void_p()
-        N.check(N.lib().ob_prepared_finish(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                           ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), C.byref(h)))
-        return _results_from_c(h)
+        first = () if tau is None else (tau,)
+        N.check(getattr(N.lib(), symbol)(self._h, *first, N.dp(rows), N.u8p(ok), len(ok), *extra, C.byref(h)))
+        return _results_from_c(h, jackknife=jackknife)
+
+    def finish(self, rows: np.ndarray, ok: np.ndarray) -> OaxacaResults:
+        return self._finish("ob_prepared_finish", rows, ok)
 
     def jackknife(self) -> "JackknifeResult":
         """ob_prepared_jackknife: the leave-one-out pass over the resident panel (kept in the handle)."""
@@ -1646,12 +1475,7 @@ class PreparedRun:
 
     def finish_bca(self, rows: np.ndarray, ok: np.ndarray, confidence_level: float = 0.95) -> OaxacaResults:
         """``finish`` with BCa intervals (ob_prepared_finish_bca); rows of ``boot`` or ``boot_sharded``."""
-        rows, ok = self._flat_block(rows, ok)
-        h = C.c_void_p()
-        N.check(N.lib().ob_prepared_finish_bca(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                               ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok),
-                                               float(confidence_level), C.byref(h)))
-        return _results_from_c(h, jackknife=True)
+        return self._finish("ob_prepared_finish_bca", rows, ok, float(confidence_level), jackknife=True)
 
     def cluster_jackknife(self) -> "JackknifeResult":
         """ob_prepared_cluster_jackknife: the delete-one-cluster pass over the resident per-cluster Grams (kept in
@@ -1674,27 +1498,25 @@ class PreparedRun:
         kept = np.zeros(nc, dtype=np.uint8)
         dev = np.empty((nc, 6 + 2 * k), dtype=np.float64) if deviations else None
         nd = (C.c_int64 * 2)()
-        dp = C.POINTER(C.c_double)
-        N.check(N.lib().ob_prepared_cluster_jackknife_rows(self._h, theta.ctypes.data_as(dp),
-                                                           kept.ctypes.data_as(C.POINTER(C.c_uint8)), nd,
-                                                           dev.ctypes.data_as(dp) if deviations else None))
+        N.check(N.lib().ob_prepared_cluster_jackknife_rows(self._h, N.dp(theta), N.u8p(kept), nd, N.dp(dev)))
         out = ((theta if full else theta[:, :6 + 2 * k].copy()), kept.astype(bool), (int(nd[0]), int(nd[1])))
         return out + (dev,) if deviations else out
 
     def finish_cluster_bca(self, rows: np.ndarray, ok: np.ndarray, confidence_level: float = 0.95) -> OaxacaResults:
         """``finish`` with BCa intervals from the delete-one-cluster accelerations (ob_prepared_finish_cluster_bca)."""
-        rows = np.ascontiguousarray(rows, dtype=np.float64)
-        ok = np.ascontiguousarray(ok, dtype=np.uint8)
-        h = C.c_void_p()
-        N.check(N.lib().ob_prepared_finish_cluster_bca(self._h, rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                                       ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok),
-                                                       float(confidence_level), C.byref(h)))
-        return _results_from_c(h, jackknife=True)
+        return self._finish("ob_prepared_finish_cluster_bca", rows, ok, float(confidence_level), jackknife=True,
+                            flat=False)
 
     def close(self):
         if self._h:
             N.lib().ob_prepared_destroy(self._h)
             self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
@@ -1853,22 +1675,17 @@ class QuantileDecompositionBuilder:
         if getattr(self, "_cluster", None) is not None:
             raise N.OaxacaError(N.OB_E_UNSUPPORTED, "cluster bootstrap: Machado-Mata is outside its scope")
         lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
         cfg = N.ob_qd_config()
         cfg.outcome, cfg.group, cfg.reference_group = (self.outcome.encode(), self.group.encode(),
                                                        self.reference_group.encode())
-        pp, pa = _strs(self._predictors)
-        cp, ca = _strs(self._categorical)
+        keep = [_set_names(cfg, "predictors", self._predictors), _set_names(cfg, "categorical", self._categorical)]
         qs = np.ascontiguousarray(self._quantiles, dtype=np.float64)
-        cfg.predictors, cfg.n_predictors = pp, len(self._predictors)
-        cfg.categorical, cfg.n_categorical = cp, len(self._categorical)
-        cfg.quantiles, cfg.n_quantiles = qs.ctypes.data_as(C.POINTER(C.c_double)), int(qs.size)
+        cfg.quantiles, cfg.n_quantiles = N.dp(qs), int(qs.size)
         cfg.simulations, cfg.bootstrap_reps = self._simulations, self._bootstrap_reps
         cfg.has_seed = 0 if self._seed is None else 1
         cfg.seed = 0 if self._seed is None else self._seed
-        h = C.c_void_p()
-        N.check(lib.ob_quantile_decomposition_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg),
-                                                  C.byref(h)))
+        h = _frame_call("ob_quantile_decomposition_run", self._frame, cfg, keep, policy=CONTEXT_FIRST,
+                        device=self._device)
         try:
             n, na, nb = C.c_int32(), C.c_int64(), C.c_int64()
             N.check(lib.ob_qd_results_dims(h, C.byref(n), C.byref(na), C.byref(nb)))
@@ -1884,7 +1701,6 @@ class QuantileDecompositionBuilder:
                                                 int(lib.ob_qd_results_n_failed(h)))
         finally:
             lib.ob_qd_results_free(h)
-            del pa, ca
 
 
 @dataclass
@@ -1933,19 +1749,16 @@ def run_dfl(dataframe, outcome: str, group: str, reference_group: str, predictor
     takes; ``grid_size`` 0 is the reference's 100 points."""
     lib = N.lib()
     frame = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
-    cols, ncol, nrow = frame.as_c()
-    predictors = [str(p) for p in predictors]
     cfg = N.ob_dfl_config()
     cfg.outcome, cfg.group, cfg.reference_group = outcome.encode(), group.encode(), reference_group.encode()
-    pp, pa = _strs(predictors)
-    cfg.predictors, cfg.n_predictors, cfg.grid_size = pp, len(predictors), int(grid_size)
-    h = C.c_void_p()
-    N.check(lib.ob_dfl_run(N.context(device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+    keep = _set_names(cfg, "predictors", [str(p) for p in predictors])
+    cfg.grid_size = int(grid_size)
+    h = _frame_call("ob_dfl_run", frame, cfg, keep, policy=CONTEXT_FIRST, device=device)
     try:
         ng = C.c_int64()
         ptrs = [C.POINTER(C.c_double)() for _ in range(4)]
         N.check(lib.ob_dfl_results_get(h, C.byref(ng), *[C.byref(p) for p in ptrs]))
-        arrs = [np.ctypeslib.as_array(p, shape=(ng.value,)).copy() if ng.value else np.zeros(0) for p in ptrs]
+        arrs = [N.array_copy(p, (ng.value,)) for p in ptrs]
         info = N.ob_dfl_info()
         N.check(lib.ob_dfl_results_info(h, C.byref(info)))
         return DflResult(*arrs, n_a=int(info.n_a), n_b=int(info.n_b), group_a=info.group_a.decode(),
@@ -1954,7 +1767,6 @@ def run_dfl(dataframe, outcome: str, group: str, reference_group: str, predictor
                          kde_ms=info.kde_ms)
     finally:
         lib.ob_dfl_results_free(h)
-        del pa
 
 
 def run_dfl_from_csv(csv_path, outcome: str, group: str, reference_group: str, predictors,
@@ -1998,35 +1810,27 @@ class MatchingEngine:
 
     def run(self, k: int, method: int) -> MatchResult:
         lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
         cfg = N.ob_match_config()
         cfg.treatment, cfg.outcome = self._treatment.encode(), self._outcome.encode()
-        pp, pa = _strs(self._covariates)
-        cfg.covariates, cfg.n_covariates, cfg.k, cfg.method = pp, len(self._covariates), int(k), int(method)
-        h = C.c_void_p()
-        N.check(lib.ob_match_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+        keep = _set_names(cfg, "covariates", self._covariates)
+        cfg.k, cfg.method = int(k), int(method)
+        h = _frame_call("ob_match_run", self._frame, cfg, keep, policy=CONTEXT_FIRST, device=self._device)
         try:
             n, nt, kk = C.c_int64(), C.c_int64(), C.c_int32()
             w, d2 = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
             tr, nb = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)()
             N.check(lib.ob_match_results_get(h, C.byref(n), C.byref(w), C.byref(nt), C.byref(kk), C.byref(tr),
                                              C.byref(nb), C.byref(d2)))
-
-            def arr(p, shape, dtype):
-                size = int(np.prod(shape))
-                return np.ctypeslib.as_array(p, shape=(size,)).copy().reshape(shape) if size else np.zeros(shape, dtype)
-
             info = N.ob_match_info()
             N.check(lib.ob_match_results_info(h, C.byref(info)))
-            return MatchResult(arr(w, (n.value,), np.float64), arr(tr, (nt.value,), np.int64),
-                               arr(nb, (nt.value, kk.value), np.int64), arr(d2, (nt.value, kk.value), np.float64),
+            return MatchResult(N.array_copy(w, (n.value,)), N.array_copy(tr, (nt.value,)),
+                               N.array_copy(nb, (nt.value, kk.value)), N.array_copy(d2, (nt.value, kk.value)),
                                n_treated=int(info.n_treated), n_control=int(info.n_control),
                                logistic_iterations=int(info.logistic_iterations),
                                logistic_converged=bool(info.logistic_converged), knn_ms=info.knn_ms,
                                prep_ms=info.prep_ms)
         finally:
             lib.ob_match_results_free(h)
-            del pa
 
     def run_matching(self, k: int, use_mahalanobis: bool = False) -> list:
         """engine.rs:113-229: the weight of every row."""
@@ -2097,14 +1901,11 @@ class AkmBuilder:
 
     def run(self) -> AkmResult:
         lib = N.lib()
-        cols, ncol, nrow = self._frame.as_c()
         cfg = N.ob_akm_config()
         cfg.outcome, cfg.worker_col, cfg.firm_col = self._outcome.encode(), self._worker.encode(), self._firm.encode()
-        pp, pa = _strs(self._controls)
-        cfg.controls, cfg.n_controls = pp, len(self._controls)
+        keep = _set_names(cfg, "controls", self._controls)
         cfg.tolerance, cfg.max_iters = self._tolerance, self._max_iters
-        h = C.c_void_p()
-        N.check(lib.ob_akm_run(N.context(self._device), cols, ncol, nrow, C.byref(cfg), C.byref(h)))
+        h = _frame_call("ob_akm_run", self._frame, cfg, keep, policy=CONTEXT_FIRST, device=self._device)
         try:
             k, nw, nf, r2 = C.c_int32(), C.c_int64(), C.c_int64(), C.c_double()
             beta, alpha, psi = (C.POINTER(C.c_double)() for _ in range(3))
@@ -2125,7 +1926,6 @@ class AkmBuilder:
                  "ols_ms": info.ols_ms, "recover_ms": info.recover_ms})
         finally:
             lib.ob_akm_results_free(h)
-            del pa
 
 
 def estimate_akm(csv_path, outcome: str, worker_col: str, firm_col: str, controls=None, tolerance: float = 1e-8,
@@ -2150,15 +1950,9 @@ def calculate_vif(dataframe, predictor_names, device: int | None = None) -> list
     failure of any auxiliary fit (perfect multicollinearity) and too few rows raise as the reference
     returns its errors; a null in a named column raises OB_E_INVALID (the reference would read it as
     0.0 in the regressand and as missing in the regressors)."""
-    lib = N.lib()
     frame = dataframe if isinstance(dataframe, Frame) else Frame(dataframe)
-    cols, ncol, nrow = frame.as_c()
     names = [str(p) for p in predictor_names]
-    pp, pa = _strs(names)
+    pp, keep = N.strs(names)
     out = np.empty(len(names))
-    try:
-        N.check(lib.ob_vif_run(N.context(device), cols, ncol, nrow, pp, len(names),
-                               out.ctypes.data_as(C.POINTER(C.c_double))))
-    finally:
-        del pa
+    _frame_call("ob_vif_run", frame, None, keep, pp, len(names), N.dp(out), policy=CONTEXT_FIRST, device=device, handles=0)
     return [VifResult(nm, float(s)) for nm, s in zip(names, out)]

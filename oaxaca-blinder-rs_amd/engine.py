@@ -23,14 +23,6 @@ def row_layout(k: int, n_base: int = 0) -> dict:
             "len": t + 5 * k}
 
 
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
 class Panel:
     """Two-group design (predictors only; intercept implicit) copied into HBM.
 
@@ -68,15 +60,15 @@ class Panel:
         d.n_num = self.p if n_num is None else int(n_num)
         d.weighted = 1 if weighted else 0
         d.n_y = self.n_y
-        d.a = N.ob_group_desc(xa.shape[0], _dp(self._xa), max(xa.shape[0], 1), _dp(self._ya), _dp(self._wa))
-        d.b = N.ob_group_desc(xb.shape[0], _dp(self._xb), max(xb.shape[0], 1), _dp(self._yb), _dp(self._wb))
+        d.a = N.ob_group_desc(xa.shape[0], N.dp(self._xa), max(xa.shape[0], 1), N.dp(self._ya), N.dp(self._wa))
+        d.b = N.ob_group_desc(xb.shape[0], N.dp(self._xb), max(xb.shape[0], 1), N.dp(self._yb), N.dp(self._wb))
         self._norm_keep = []
         if norm:
             arrs = [np.ascontiguousarray(norm[k], dtype=np.int32)
                     for k in ("start", "idx", "m", "pstart", "pidx", "has_base")]
             self._norm_keep = arrs
             d.n_norm = len(arrs[2])
-            (d.norm_start, d.norm_idx, d.norm_m, d.pooled_start, d.pooled_idx, d.has_base) = [_ip(a) for a in arrs]
+            (d.norm_start, d.norm_idx, d.norm_m, d.pooled_start, d.pooled_idx, d.has_base) = [N.i32p(a) for a in arrs]
         self._h = C.c_void_p()
         self._ctx = ctx if ctx is not None else N.context(device)
         N.check(N.lib().ob_panel_create(self._ctx, C.byref(d), C.byref(self._h)))
@@ -89,7 +81,7 @@ class Panel:
     def point_estimate(self, ref=ReferenceCoefficients.GroupA, residuals=False):
         row = np.empty((self.n_y, self.row_len))
         res = np.empty((self.n_y, self.n_b)) if residuals else None
-        N.check(N.lib().ob_point_estimate(self._h, int(ref), _dp(row), _dp(res)))
+        N.check(N.lib().ob_point_estimate(self._h, int(ref), N.dp(row), N.dp(res)))
         if self.n_y == 1:
             row = row[0]
             res = None if res is None else res[0]
@@ -109,15 +101,15 @@ class Panel:
         theta = np.empty((self.n_a + self.n_b, c))
         kept = np.zeros(self.n_a + self.n_b, dtype=np.uint8)
         nd = (C.c_int64 * 2)()
-        N.check(N.lib().ob_jackknife_rows(self._h, int(ref), _dp(theta), kept.ctypes.data_as(C.POINTER(C.c_uint8)), nd))
+        N.check(N.lib().ob_jackknife_rows(self._h, int(ref), N.dp(theta), N.u8p(kept), nd))
         return theta, kept, (int(nd[0]), int(nd[1]))
 
     def boot(self, seed: int, first_rep: int, n_reps: int, ref=ReferenceCoefficients.GroupA):
         rows = np.empty((self.n_y, n_reps, self.row_len))
         ok = np.zeros((self.n_y, n_reps), dtype=np.uint8)
         if n_reps:
-            N.check(N.lib().ob_boot_run(self._h, seed & ((1 << 64) - 1), first_rep, n_reps, int(ref), _dp(rows),
-                                        ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+            N.check(N.lib().ob_boot_run(self._h, seed & ((1 << 64) - 1), first_rep, n_reps, int(ref), N.dp(rows),
+                                        N.u8p(ok)))
         return (rows[0], ok[0]) if self.n_y == 1 else (rows, ok)
 
     def mm(self, seed: int, simulations: int, quantiles, first_rep: int = 0, n_reps: int = 0, with_point=True):
@@ -127,8 +119,8 @@ class Panel:
         m = int(bool(with_point)) + n_reps
         rows = np.empty((m, 3 * q.size))
         ok = np.zeros(m, dtype=np.uint8)
-        N.check(N.lib().ob_mm_run(self._h, seed & ((1 << 64) - 1), int(simulations), _dp(q), int(q.size), first_rep,
-                                  n_reps, int(bool(with_point)), _dp(rows), ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+        N.check(N.lib().ob_mm_run(self._h, seed & ((1 << 64) - 1), int(simulations), N.dp(q), int(q.size), first_rep,
+                                  n_reps, int(bool(with_point)), N.dp(rows), N.u8p(ok)))
         return rows, ok
 
     def debug_mm_betas(self, seed: int, simulations: int, rep: int):
@@ -136,14 +128,14 @@ class Panel:
         OB_MM_POINT_REP = 2^32 - 1 for the point pass): (betas [2, S, K], converged [2, S])."""
         b = np.empty((2, int(simulations), self.k))
         done = np.zeros((2, int(simulations)), dtype=np.uint8)
-        N.check(N.lib().ob_debug_mm_betas(self._h, seed & ((1 << 64) - 1), int(simulations), int(rep), _dp(b),
-                                          done.ctypes.data_as(C.POINTER(C.c_uint8))))
+        N.check(N.lib().ob_debug_mm_betas(self._h, seed & ((1 << 64) - 1), int(simulations), int(rep), N.dp(b),
+                                          N.u8p(done)))
         return b, done
 
     def debug_mm_fail(self, mask=None):
         """ob_debug_mm_fail: mask[g][s] bit (rep & 7) forces fit (g, s) of pass rep to fail."""
         m = np.ascontiguousarray(np.zeros((2, 0)) if mask is None else mask, dtype=np.uint8)
-        N.check(N.lib().ob_debug_mm_fail(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), m.shape[1]))
+        N.check(N.lib().ob_debug_mm_fail(self._h, N.u8p(m), m.shape[1]))
 
     def boot_device(self, seed: int, first_rep: int, n_reps: int, rows_ptr: int, ok_ptr: int,
                     ref=ReferenceCoefficients.GroupA, stream: int | None = None):
@@ -156,8 +148,8 @@ class Panel:
         rows = np.empty((self.n_y, n_reps, self.row_len))
         ok = np.zeros((self.n_y, n_reps), dtype=np.uint8)
         if n_reps:
-            N.check(N.lib().ob_boot_run_sharded(self._h, seed & ((1 << 64) - 1), first_rep, n_reps, int(ref), _dp(rows),
-                                                ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+            N.check(N.lib().ob_boot_run_sharded(self._h, seed & ((1 << 64) - 1), first_rep, n_reps, int(ref), N.dp(rows),
+                                                N.u8p(ok)))
         return (rows[0], ok[0]) if self.n_y == 1 else (rows, ok)
 
     def boot_sharded_device(self, seed: int, first_rep: int, n_reps: int, rows_ptr: int, ok_ptr: int,
@@ -173,8 +165,8 @@ class Panel:
         l1 = np.zeros((n_reps, tiles), dtype=np.uint32)
         rc = np.zeros((n_reps, ng), dtype=np.uint8)
         N.check(N.lib().ob_debug_counts(self._h, seed & ((1 << 64) - 1), first_rep, n_reps, group,
-                                        l1.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                        rc.ctypes.data_as(C.POINTER(C.c_uint8))))
+                                        N.u32p(l1),
+                                        N.u8p(rc)))
         return l1, rc
 
     def debug_gram(self, seed: int, first_rep: int, n_reps: int, path: int = 0):
@@ -182,7 +174,7 @@ class Panel:
         2 = exact integer-sliced i8 MFMA, 0 = the engine's default."""
         e_pad = -(-((self.k + self.n_y) * (self.k + self.n_y + 1) // 2) // 16) * 16
         g = np.empty((n_reps, 2, e_pad))
-        N.check(N.lib().ob_debug_gram(self._h, int(path), seed & ((1 << 64) - 1), first_rep, n_reps, _dp(g)))
+        N.check(N.lib().ob_debug_gram(self._h, int(path), seed & ((1 << 64) - 1), first_rep, n_reps, N.dp(g)))
         return g
 
     def debug_chunks(self):
@@ -190,13 +182,13 @@ class Panel:
         n = C.c_int32(0)
         N.check(N.lib().ob_debug_chunks(self._h, None, 0, C.byref(n)))
         t = np.zeros(3 * n.value, dtype=np.uint32)
-        N.check(N.lib().ob_debug_chunks(self._h, t.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)))
+        N.check(N.lib().ob_debug_chunks(self._h, N.u32p(t), n.value, C.byref(n)))
         return [tuple(int(v) for v in t[3 * c: 3 * c + 3]) for c in range(n.value)]
 
     def set_gather_columns(self, cols=None):
         """Row columns the sharded entry points gather (ob_panel_set_gather_columns); None = all."""
         c = np.ascontiguousarray([] if cols is None else cols, dtype=np.int32)
-        N.check(N.lib().ob_panel_set_gather_columns(self._h, _ip(c), len(c)))
+        N.check(N.lib().ob_panel_set_gather_columns(self._h, N.i32p(c), len(c)))
 
     def component_columns(self):
         """The row columns the aggregation reads: two-fold, three-fold, total gap, detailed."""
@@ -210,7 +202,7 @@ class Panel:
         ok = np.zeros((self.n_y, n_reps), dtype=np.uint8)
         if n_reps:
             N.check(N.lib().ob_debug_shard_sim(self._h, world, self_rank, seed & ((1 << 64) - 1), first_rep, n_reps,
-                                               int(ref), _dp(rows), ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+                                               int(ref), N.dp(rows), N.u8p(ok)))
         return (rows[0], ok[0]) if self.n_y == 1 else (rows, ok)
 
     def debug_gram_exceptions(self):
@@ -218,7 +210,7 @@ class Panel:
         bits, n = C.c_int32(0), C.c_int32(0)
         buf = np.zeros(4096, dtype=np.uint32)
         N.check(N.lib().ob_debug_gram_exceptions(self._h, C.byref(bits), C.byref(n),
-                                                 buf.ctypes.data_as(C.POINTER(C.c_uint32)), len(buf)))
+                                                 N.u32p(buf), len(buf)))
         ent = buf[: n.value]
         return bits.value, [(int(e >> 31), int(e & 0x7FFFFFFF)) for e in ent]
 
@@ -228,7 +220,7 @@ class Panel:
     def timing(self) -> dict:
         t = N.ob_timing()
         N.check(N.lib().ob_panel_last_timing(self._h, C.byref(t)))
-        return {f: getattr(t, f) for f, _ in N.ob_timing._fields_}
+        return N.struct_dict(t)
 
     def close(self):
         if self._h:
@@ -251,7 +243,7 @@ def boot_multi(panels, seed: int, first_rep: int, n_reps: int, ref=ReferenceCoef
     hs = (C.c_void_p * len(panels))(*[p._h for p in panels])
     if n_reps:
         N.check(N.lib().ob_boot_run_multi(hs, len(panels), seed & ((1 << 64) - 1), first_rep, n_reps, int(ref),
-                                          _dp(rows), ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+                                          N.dp(rows), N.u8p(ok)))
     return (rows[0], ok[0]) if p0.n_y == 1 else (rows, ok)
 
 
@@ -259,7 +251,7 @@ def bootstrap_stats(values, point_estimate: float = 0.0):
     """inference.rs:4-34 -> (std_err, p_value, (ci_lower, ci_upper)) via the native routine."""
     v = np.ascontiguousarray(values, dtype=np.float64)
     out = np.empty(4)
-    N.check(N.lib().ob_bootstrap_stats(_dp(v), len(v), float(point_estimate), _dp(out)))
+    N.check(N.lib().ob_bootstrap_stats(N.dp(v), len(v), float(point_estimate), N.dp(out)))
     return out[0], out[1], (out[2], out[3])
 
 
@@ -270,8 +262,8 @@ def aggregate(rows, ok, cols):
     ok = np.ascontiguousarray(ok, dtype=np.uint8)
     cols = np.ascontiguousarray(cols, dtype=np.int32)
     out = np.empty((len(cols), 4))
-    N.check(N.lib().ob_aggregate(_dp(rows), ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), rows.shape[1],
-                                 _ip(cols), len(cols), _dp(out)))
+    N.check(N.lib().ob_aggregate(N.dp(rows), N.u8p(ok), len(ok), rows.shape[1],
+                                 N.i32p(cols), len(cols), N.dp(out)))
     return out
 
 
@@ -303,7 +295,7 @@ def jackknife_finish(sums, n_used):
         raise ValueError("sums must be (2, C, 3)")
     m = (C.c_int64 * 2)(int(n_used[0]), int(n_used[1]))
     out = np.zeros((sums.shape[1], 3))
-    N.check(N.lib().ob_jackknife_finish(_dp(sums), m, sums.shape[1], _dp(out)))
+    N.check(N.lib().ob_jackknife_finish(N.dp(sums), m, sums.shape[1], N.dp(out)))
     return out
 
 
@@ -311,7 +303,7 @@ def bca_stats(estimates, point: float, accel: float, level: float = 0.95) -> dic
     """ob_bca_stats -> dict(ci_lower, ci_upper, z0, alpha_lo, alpha_hi, flag)."""
     v = np.ascontiguousarray(estimates, dtype=np.float64)
     out = np.zeros(6)
-    N.check(N.lib().ob_bca_stats(_dp(v), len(v), float(point), float(accel), float(level), _dp(out)))
+    N.check(N.lib().ob_bca_stats(N.dp(v), len(v), float(point), float(accel), float(level), N.dp(out)))
     return {"ci_lower": out[0], "ci_upper": out[1], "z0": out[2], "alpha_lo": out[3], "alpha_hi": out[4],
             "flag": int(out[5])}
 
@@ -324,8 +316,8 @@ def aggregate_bca(rows, ok, cols, point, accel, level: float = 0.95):
     point = np.ascontiguousarray(point, dtype=np.float64)
     accel = np.ascontiguousarray(accel, dtype=np.float64)
     out = np.zeros((len(cols), 6))
-    N.check(N.lib().ob_aggregate_bca(_dp(rows), ok.ctypes.data_as(C.POINTER(C.c_uint8)), len(ok), rows.shape[1],
-                                     _ip(cols), len(cols), _dp(point), _dp(accel), float(level), _dp(out)))
+    N.check(N.lib().ob_aggregate_bca(N.dp(rows), N.u8p(ok), len(ok), rows.shape[1],
+                                     N.i32p(cols), len(cols), N.dp(point), N.dp(accel), float(level), N.dp(out)))
     return out
 
 
@@ -333,7 +325,7 @@ def rif(y, quantile: float):
     """math/rif.rs:14-88 via the native routine."""
     y = np.ascontiguousarray(y, dtype=np.float64)
     out = np.empty_like(y)
-    N.check(N.lib().ob_rif(_dp(y), len(y), float(quantile), _dp(out)))
+    N.check(N.lib().ob_rif(N.dp(y), len(y), float(quantile), N.dp(out)))
     return out
 
 
@@ -409,6 +401,45 @@ def with_context(call, device: int | None = None):
     N.check(call(ctx))
 
 
+def _last_timing(symbol: str, struct) -> dict:
+    """This thread's last timing record of one estimator: ``symbol`` fills a ``struct``."""
+    t = struct()
+    N.check(getattr(N.lib(), symbol)(C.byref(t)))
+    return N.struct_dict(t)
+
+
+# One group's rows as the array entry points take them. Each check raises ValueError(what).
+def _design(x, what="x must be (n, k)"):
+    """A design matrix: float64, column-major -> (array, n, k)."""
+    xf = np.asfortranarray(x, dtype=np.float64)
+    if xf.ndim != 2:
+        raise ValueError(what)
+    return (xf,) + xf.shape
+
+
+def _per_row(v, n: int, what: str, optional: bool = False):
+    """One float64 per row; an ``optional`` vector (weights) may be ``None`` and stays so."""
+    if v is None and optional:
+        return None
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.shape != (n,):
+        raise ValueError(what)
+    return v
+
+
+def _counts_u8(counts, n: int, by_rep: bool = False):
+    """Resample counts in [0, 255] as the kernels read them: uint8 (n,), or ``by_rep`` (n_reps, n) with a plain
+    vector taken as one replicate; ``None`` (every row once) stays ``None``."""
+    if counts is None:
+        return None
+    c = np.ascontiguousarray(counts)
+    if by_rep:
+        c = np.atleast_2d(c)
+    if c.shape[1 if by_rep else 0:] != (n,) or (c < 0).any() or (c > 255).any():
+        raise ValueError(f"counts must be {'(n_reps, n)' if by_rep else 'n'} integers in [0, 255]")
+    return np.ascontiguousarray(c.astype(np.uint8))
+
+
 def rif_statistic(y, stat, device: int | None = None, **params):
     """``ob_rif_stat``: the recentred influence function of ``stat`` ("variance", "gini", "iqr" with ``upper`` /
     ``lower``) over ``y`` on the GPU -> (rif in y's order, the statistic). Unweighted; n >= 2."""
@@ -417,7 +448,7 @@ def rif_statistic(y, stat, device: int | None = None, **params):
         raise ValueError("y must be one-dimensional")
     spec = N.ob_rif_spec(*parse_rif_statistic(stat, **params))
     out, value = np.empty_like(y), C.c_double()
-    with_context(lambda ctx: N.lib().ob_rif_stat(ctx, _dp(y), len(y), C.byref(spec), _dp(out), C.byref(value)), device)
+    with_context(lambda ctx: N.lib().ob_rif_stat(ctx, N.dp(y), len(y), C.byref(spec), N.dp(out), C.byref(value)), device)
     return out, value.value
 
 
@@ -431,7 +462,7 @@ def rif_statistic_weighted(y, w, stat, device: int | None = None, **params):
         raise ValueError("y and w must be one-dimensional and of one length")
     spec = N.ob_rif_spec(*parse_weighted_rif_statistic(stat, **params))
     out, value = np.empty_like(y), C.c_double()
-    with_context(lambda ctx: N.lib().ob_rif_stat_weighted(ctx, _dp(y), _dp(w), len(y), C.byref(spec), _dp(out),
+    with_context(lambda ctx: N.lib().ob_rif_stat_weighted(ctx, N.dp(y), N.dp(w), len(y), C.byref(spec), N.dp(out),
                                                           C.byref(value)), device)
     return out, value.value
 
@@ -443,9 +474,7 @@ def rif_scan_block() -> int:
 
 def rif_last_timing() -> dict:
     """ob_rif_last_timing: sort / scan / kde / scatter ms of this thread's last RIF statistics call."""
-    t = N.ob_rif_timing()
-    N.check(N.lib().ob_rif_last_timing(C.byref(t)))
-    return {f: getattr(t, f) for f, _ in N.ob_rif_timing._fields_}
+    return _last_timing("ob_rif_last_timing", N.ob_rif_timing)
 
 
 def logit(y, x, max_iter: int = 100, tol: float = 1e-6, device: int | None = None):
@@ -453,17 +482,12 @@ def logit(y, x, max_iter: int = 100, tol: float = 1e-6, device: int | None = Non
     intercept column included, ``k <= OB_LOGIT_MAX_K``. Returns (coefficients, predicted_probs,
     converged, iterations); on convergence the probabilities are those of the last iteration's
     start, as in the reference."""
-    xf = np.asfortranarray(x, dtype=np.float64)
-    if xf.ndim != 2:
-        raise ValueError("x must be (n, k)")
-    n, k = xf.shape
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    if y.shape != (n,):
-        raise ValueError("y must have one entry per row of x")
+    xf, n, k = _design(x)
+    y = _per_row(y, n, "y must have one entry per row of x")
     beta, probs = np.empty(k), np.empty(n)
     conv, iters = C.c_int32(0), C.c_int32(0)
-    N.check(N.lib().ob_logit(N.context(device), _dp(xf), max(n, 1), _dp(y), n, k, int(max_iter), float(tol),
-                             _dp(beta), _dp(probs), C.byref(conv), C.byref(iters)))
+    N.check(N.lib().ob_logit(N.context(device), N.dp(xf), max(n, 1), N.dp(y), n, k, int(max_iter), float(tol),
+                             N.dp(beta), N.dp(probs), C.byref(conv), C.byref(iters)))
     return beta, probs, bool(conv.value), int(iters.value)
 
 
@@ -471,17 +495,12 @@ def probit(x, y, max_iter: int = 100, tol: float = 1e-6, device: int | None = No
     """math/probit.rs::probit with the Fisher-scoring passes on the GPU (``ob_probit``). ``x``: (n, k)
     with the intercept (all ones) as column 0, ``k <= 32``; ``y``: the 0/1 outcome. Returns
     (coefficients, converged, iterations); running out of iterations is not an error."""
-    xf = np.asfortranarray(x, dtype=np.float64)
-    if xf.ndim != 2:
-        raise ValueError("x must be (n, k)")
-    n, k = xf.shape
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    if y.shape != (n,):
-        raise ValueError("y must have one entry per row of x")
+    xf, n, k = _design(x)
+    y = _per_row(y, n, "y must have one entry per row of x")
     beta = np.empty(k)
     conv, iters = C.c_int32(0), C.c_int32(0)
-    N.check(N.lib().ob_probit(N.context(device), _dp(xf), max(n, 1), _dp(y), n, k, int(max_iter), float(tol),
-                              _dp(beta), C.byref(conv), C.byref(iters)))
+    N.check(N.lib().ob_probit(N.context(device), N.dp(xf), max(n, 1), N.dp(y), n, k, int(max_iter), float(tol),
+                              N.dp(beta), C.byref(conv), C.byref(iters)))
     return beta, bool(conv.value), int(iters.value)
 
 
@@ -490,23 +509,16 @@ def binary_means(x, y, betas, counts=None, device: int | None = None) -> dict:
     ``x``: (n, k) with the intercept (all ones) as column 0, ``k <= 32``; ``y``: the outcome; ``betas``: (3, k);
     ``counts``: n resample counts below 256 (``None``: every row once). Returns ``probabilities`` (the three
     count-weighted means of Phi(x'beta)), ``y_mean``, ``n`` (the counts' sum) and ``x_mean`` (k)."""
-    xf = np.asfortranarray(x, dtype=np.float64)
-    if xf.ndim != 2:
-        raise ValueError("x must be (n, k)")
-    n, k = xf.shape
-    y = np.ascontiguousarray(y, dtype=np.float64)
+    xf, n, k = _design(x)
+    what = "y must have one entry per row of x and betas must be (3, k)"
+    y = _per_row(y, n, what)
     b = np.ascontiguousarray(betas, dtype=np.float64)
-    if y.shape != (n,) or b.shape != (3, k):
-        raise ValueError("y must have one entry per row of x and betas must be (3, k)")
-    cp = None
-    if counts is not None:
-        c = np.ascontiguousarray(counts)
-        if c.shape != (n,) or (c < 0).any() or (c > 255).any():
-            raise ValueError("counts must be n integers in [0, 255]")
-        c8 = c.astype(np.uint8)
-        cp = c8.ctypes.data_as(C.POINTER(C.c_uint8))
+    if b.shape != (3, k):
+        raise ValueError(what)
+    c8 = _counts_u8(counts, n)
     out = np.empty(5 + k)
-    with_context(lambda ctx: N.lib().ob_binary_means(ctx, _dp(xf), max(n, 1), _dp(y), n, k, cp, _dp(b), _dp(out)), device)
+    with_context(lambda ctx: N.lib().ob_binary_means(ctx, N.dp(xf), max(n, 1), N.dp(y), n, k, N.u8p(c8), N.dp(b),
+                                                     N.dp(out)), device)
     return {"probabilities": out[:3].copy(), "y_mean": float(out[3]), "n": float(out[4]), "x_mean": out[5:].copy()}
 
 
@@ -522,9 +534,21 @@ def binary_row_len(k: int) -> int:
 
 def binary_last_timing() -> dict:
     """ob_binary_last_timing: HIP-event ms of this thread's last binary boot (probit, means pass, rows)."""
-    t = N.ob_binary_timing()
-    N.check(N.lib().ob_binary_last_timing(C.byref(t)))
-    return {f: getattr(t, f) for f, _ in N.ob_binary_timing._fields_}
+    return _last_timing("ob_binary_last_timing", N.ob_binary_timing)
+
+
+def _refit_pass_args(n: int, counts, x):
+    """What ``rifq_pass`` and ``rifs_pass`` share: the optional (n, p) predictors and the (n_reps, n) counts of the n
+    sorted rows -> (x column-major or None, p, uint8 counts or None, n_reps)."""
+    xf, p = None, 0
+    if x is not None:
+        xf, rows, p = _design(x, "x must be (n, p)")
+        if rows != n:
+            raise ValueError("x must be (n, p)")
+        if p == 0:
+            xf = None
+    c8 = _counts_u8(counts, n, by_rep=True)
+    return xf, p, c8, 1 if c8 is None else len(c8)
 
 
 def rifq_pass(y_sorted, taus, counts=None, x=None, device: int | None = None) -> dict:
@@ -539,34 +563,20 @@ def rifq_pass(y_sorted, taus, counts=None, x=None, device: int | None = None) ->
     if y.ndim != 1 or tq.ndim != 1:
         raise ValueError("y_sorted and taus must be one-dimensional")
     n, nt = len(y), len(tq)
-    xf, p = None, 0
-    if x is not None:
-        xf = np.asfortranarray(x, dtype=np.float64)
-        if xf.ndim != 2 or xf.shape[0] != n:
-            raise ValueError("x must be (n, p)")
-        p = xf.shape[1]
-        if p == 0:
-            xf = None
-    cp, reps = None, 1
-    if counts is not None:
-        c = np.atleast_2d(np.ascontiguousarray(counts))
-        if c.ndim != 2 or c.shape[1] != n or (c < 0).any() or (c > 255).any():
-            raise ValueError("counts must be (n_reps, n) integers in [0, 255]")
-        c8 = np.ascontiguousarray(c.astype(np.uint8))
-        cp, reps = c8.ctypes.data_as(C.POINTER(C.c_uint8)), c.shape[0]
+    xf, p, c8, reps = _refit_pass_args(n, counts, x)
     q, f, nle = np.empty((reps, nt)), np.empty((reps, nt)), np.empty((reps, nt))
     bw, t, gy = np.empty(reps), np.empty((reps, nt, p + 1)), np.empty((reps, nt, p + 2))
     fl = np.zeros((reps, nt), dtype=np.uint8)
-    with_context(lambda ctx: N.lib().ob_rifq_pass(ctx, _dp(y), n, cp, reps, _dp(tq), nt, _dp(xf), max(n, 1), p, _dp(q),
-                                                  _dp(bw), _dp(f), _dp(nle), _dp(t), _dp(gy),
-                                                  fl.ctypes.data_as(C.POINTER(C.c_uint8))), device)
+    with_context(lambda ctx: N.lib().ob_rifq_pass(ctx, N.dp(y), n, N.u8p(c8), reps, N.dp(tq), nt, N.dp(xf), max(n, 1), p,
+                                                  N.dp(q), N.dp(bw), N.dp(f), N.dp(nle), N.dp(t), N.dp(gy), N.u8p(fl)),
+                 device)
     return {"q": q, "bw": bw, "f": f, "n_le": nle, "t": t, "gy": gy, "floored": fl.astype(bool)}
 
 
 def rifq_check_shape(k: int, taus, n_a: int, n_b: int) -> None:
     """ob_rifq_check_shape: raises OaxacaError where a refitted quantile decomposition would (host only)."""
     tq = np.ascontiguousarray(np.atleast_1d(taus), dtype=np.float64)
-    N.check(N.lib().ob_rifq_check_shape(int(k), len(tq), _dp(tq), int(n_a), int(n_b)))
+    N.check(N.lib().ob_rifq_check_shape(int(k), len(tq), N.dp(tq), int(n_a), int(n_b)))
 
 
 def rifq_row_len(k: int, n_base: int = 0) -> int:
@@ -577,9 +587,7 @@ def rifq_row_len(k: int, n_base: int = 0) -> int:
 def rifq_last_timing() -> dict:
     """ob_rifq_last_timing: HIP-event ms of this thread's last rifq_pass, or prepare / boot of a refit handle: search,
     density, patch, and for a handle gram (resample, f64 Gram, reduce) and solve (y-pairs, solves, rows)."""
-    t = N.ob_rifq_timing()
-    N.check(N.lib().ob_rifq_last_timing(C.byref(t)))
-    return {f: getattr(t, f) for f, _ in N.ob_rifq_timing._fields_}
+    return _last_timing("ob_rifq_last_timing", N.ob_rifq_timing)
 
 
 def _rif_specs(stats):
@@ -603,26 +611,11 @@ def rifs_pass(y_sorted, stats, counts=None, x=None, device: int | None = None) -
         raise ValueError("y_sorted must be one-dimensional")
     specs, parsed = _rif_specs(stats)
     n, ns = len(y), len(parsed)
-    xf, p = None, 0
-    if x is not None:
-        xf = np.asfortranarray(x, dtype=np.float64)
-        if xf.ndim != 2 or xf.shape[0] != n:
-            raise ValueError("x must be (n, p)")
-        p = xf.shape[1]
-        if p == 0:
-            xf = None
-    cp, reps = None, 1
-    if counts is not None:
-        c = np.atleast_2d(np.ascontiguousarray(counts))
-        if c.ndim != 2 or c.shape[1] != n or (c < 0).any() or (c > 255).any():
-            raise ValueError("counts must be (n_reps, n) integers in [0, 255]")
-        c8 = np.ascontiguousarray(c.astype(np.uint8))
-        cp, reps = c8.ctypes.data_as(C.POINTER(C.c_uint8)), c.shape[0]
+    xf, p, c8, reps = _refit_pass_args(n, counts, x)
     nu, gy = np.empty((reps, ns)), np.empty((reps, ns, p + 2))
     fl, ok = np.zeros((reps, ns), dtype=np.uint8), np.zeros((reps, ns), dtype=np.uint8)
-    with_context(lambda ctx: N.lib().ob_rifs_pass(ctx, _dp(y), n, cp, reps, specs, ns, _dp(xf), max(n, 1), p, _dp(nu),
-                                                  _dp(gy), fl.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  ok.ctypes.data_as(C.POINTER(C.c_uint8))), device)
+    with_context(lambda ctx: N.lib().ob_rifs_pass(ctx, N.dp(y), n, N.u8p(c8), reps, specs, ns, N.dp(xf), max(n, 1), p,
+                                                  N.dp(nu), N.dp(gy), N.u8p(fl), N.u8p(ok)), device)
     return {"nu": nu, "gy": gy, "floored": fl.astype(bool), "ok": ok.astype(bool)}
 
 
@@ -640,33 +633,25 @@ def rifs_row_len(k: int, n_base: int = 0) -> int:
 def rifs_last_timing() -> dict:
     """ob_rifs_last_timing: HIP-event ms of this thread's last rifs_pass, or prepare / boot of a statistics refit
     handle: moment, scan, gini, tie, finish, rifq (the ranges' quantile pass), and for a handle gram and solve."""
-    t = N.ob_rifs_timing()
-    N.check(N.lib().ob_rifs_last_timing(C.byref(t)))
-    return {f: getattr(t, f) for f, _ in N.ob_rifs_timing._fields_}
+    return _last_timing("ob_rifs_last_timing", N.ob_rifs_timing)
+
+
+def _coefficient_rows(coefs, k: int, what: str):
+    """(m, k) coefficient vectors; a plain vector is one row."""
+    c = np.ascontiguousarray(np.atleast_2d(coefs), dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != k:
+        raise ValueError(what)
+    return c
 
 
 def _reweight_args(x, second, w, counts, gammas):
     """The arrays of the two reweighting pieces as the C ABI takes them."""
-    xf = np.asfortranarray(x, dtype=np.float64)
-    if xf.ndim != 2:
-        raise ValueError("x must be (n, k)")
-    n, k = xf.shape
-    second = np.ascontiguousarray(second, dtype=np.float64)
-    g = np.ascontiguousarray(np.atleast_2d(gammas), dtype=np.float64)
-    if second.shape != (n,) or g.ndim != 2 or g.shape[1] != k:
-        raise ValueError("d / y must have one entry per row of x and gammas must be (R, k)")
-    wv = None
-    if w is not None:
-        wv = np.ascontiguousarray(w, dtype=np.float64)
-        if wv.shape != (n,):
-            raise ValueError("w must have one entry per row of x")
-    c8 = None
-    if counts is not None:
-        c = np.ascontiguousarray(counts)
-        if c.shape != (n,) or (c < 0).any() or (c > 255).any():
-            raise ValueError("counts must be n integers in [0, 255]")
-        c8 = c.astype(np.uint8)
-    return xf, second, wv, c8, g, n, k
+    what = "d / y must have one entry per row of x and gammas must be (R, k)"
+    xf, n, k = _design(x)
+    second = _per_row(second, n, what)
+    g = _coefficient_rows(gammas, k, what)
+    wv = _per_row(w, n, "w must have one entry per row of x", optional=True)
+    return xf, second, wv, _counts_u8(counts, n), g, n, k
 
 
 def reweight_logit_pass(x, d, gammas, w=None, counts=None, device: int | None = None):
@@ -677,9 +662,8 @@ def reweight_logit_pass(x, d, gammas, w=None, counts=None, device: int | None = 
     c w (d - p) x, p the sigmoid of x'gamma clamped to [1e-10, 1 - 1e-10]."""
     xf, dv, wv, c8, g, n, k = _reweight_args(x, d, w, counts, gammas)
     info, grad = np.empty((len(g), k, k)), np.empty((len(g), k))
-    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
-    with_context(lambda ctx: N.lib().ob_reweight_logit_pass(ctx, _dp(xf), max(n, 1), _dp(dv), _dp(wv), cp, n, k, _dp(g),
-                                                           len(g), _dp(info), _dp(grad)), device)
+    with_context(lambda ctx: N.lib().ob_reweight_logit_pass(ctx, N.dp(xf), max(n, 1), N.dp(dv), N.dp(wv), N.u8p(c8), n, k,
+                                                           N.dp(g), len(g), N.dp(info), N.dp(grad)), device)
     return info, grad
 
 
@@ -690,9 +674,8 @@ def reweight_gram(x, y, gammas, w=None, counts=None, device: int | None = None):
     ``reweight_logit_pass``."""
     xf, yv, wv, c8, g, n, k = _reweight_args(x, y, w, counts, gammas)
     gram, den = np.empty((len(g), k + 1, k + 1)), np.empty(len(g))
-    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
-    with_context(lambda ctx: N.lib().ob_reweight_gram(ctx, _dp(xf), max(n, 1), _dp(yv), _dp(wv), cp, n, k, _dp(g), len(g),
-                                                     _dp(gram), _dp(den)), device)
+    with_context(lambda ctx: N.lib().ob_reweight_gram(ctx, N.dp(xf), max(n, 1), N.dp(yv), N.dp(wv), N.u8p(c8), n, k,
+                                                     N.dp(g), len(g), N.dp(gram), N.dp(den)), device)
     return gram, den
 
 
@@ -709,32 +692,15 @@ def reweight_row_len(k: int) -> int:
 def reweight_last_timing() -> dict:
     """ob_reweight_last_timing: logit passes and HIP-event ms (logit passes, Grams, rows) of this thread's last
     reweighted boot."""
-    t = N.ob_reweight_timing()
-    N.check(N.lib().ob_reweight_last_timing(C.byref(t)))
-    return {f: getattr(t, f) for f, _ in N.ob_reweight_timing._fields_}
+    return _last_timing("ob_reweight_last_timing", N.ob_reweight_timing)
 
 
 def _dr_args(x, w, counts, betas):
     """The arrays of the two distribution-regression pieces as the C ABI takes them."""
-    xf = np.asfortranarray(x, dtype=np.float64)
-    if xf.ndim != 2:
-        raise ValueError("x must be (n, k)")
-    n, k = xf.shape
-    b = np.ascontiguousarray(np.atleast_2d(betas), dtype=np.float64)
-    if b.ndim != 2 or b.shape[1] != k:
-        raise ValueError("betas must be (m, k)")
-    wv = None
-    if w is not None:
-        wv = np.ascontiguousarray(w, dtype=np.float64)
-        if wv.shape != (n,):
-            raise ValueError("w must have one entry per row of x")
-    c8 = None
-    if counts is not None:
-        c = np.ascontiguousarray(counts)
-        if c.shape != (n,) or (c < 0).any() or (c > 255).any():
-            raise ValueError("counts must be n integers in [0, 255]")
-        c8 = c.astype(np.uint8)
-    return xf, wv, c8, b, n, k
+    xf, n, k = _design(x)
+    b = _coefficient_rows(betas, k, "betas must be (m, k)")
+    wv = _per_row(w, n, "w must have one entry per row of x", optional=True)
+    return xf, wv, _counts_u8(counts, n), b, n, k
 
 
 def dr_logit_pass(x, y, thresholds, betas, w=None, counts=None, device: int | None = None):
@@ -749,9 +715,8 @@ def dr_logit_pass(x, y, thresholds, betas, w=None, counts=None, device: int | No
     if yv.shape != (n,) or thr.ndim != 1 or len(thr) != len(b):
         raise ValueError("y must have one entry per row of x and betas one row per threshold")
     info, grad = np.empty((len(b), k, k)), np.empty((len(b), k))
-    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
-    with_context(lambda ctx: N.lib().ob_dr_logit_pass(ctx, _dp(xf), max(n, 1), _dp(yv), _dp(wv), cp, n, k, _dp(thr),
-                                                     len(thr), _dp(b), _dp(info), _dp(grad)), device)
+    with_context(lambda ctx: N.lib().ob_dr_logit_pass(ctx, N.dp(xf), max(n, 1), N.dp(yv), N.dp(wv), N.u8p(c8), n, k,
+                                                     N.dp(thr), len(thr), N.dp(b), N.dp(info), N.dp(grad)), device)
     return info, grad
 
 
@@ -760,9 +725,8 @@ def dr_cdf(x, betas, w=None, counts=None, device: int | None = None):
     (m, k) ``betas``, m <= 128, L the clamped sigmoid, and wsum = sum c w. Arguments as ``dr_logit_pass``."""
     xf, wv, c8, b, n, k = _dr_args(x, w, counts, betas)
     sums, wsum = np.empty(len(b)), np.empty(1)
-    cp = None if c8 is None else c8.ctypes.data_as(C.POINTER(C.c_uint8))
-    with_context(lambda ctx: N.lib().ob_dr_cdf(ctx, _dp(xf), max(n, 1), _dp(wv), cp, n, k, _dp(b), len(b), _dp(sums),
-                                              _dp(wsum)), device)
+    with_context(lambda ctx: N.lib().ob_dr_cdf(ctx, N.dp(xf), max(n, 1), N.dp(wv), N.u8p(c8), n, k, N.dp(b), len(b),
+                                              N.dp(sums), N.dp(wsum)), device)
     return sums, float(wsum[0])
 
 
@@ -772,7 +736,7 @@ def dr_thresholds(y, n_thresholds: int = 50, lo: float = 0.05, hi: float = 0.95)
     yv = np.ascontiguousarray(y, dtype=np.float64).ravel()
     out = np.empty(max(int(n_thresholds), 1))
     kept = C.c_int32()
-    N.check(N.lib().ob_dr_thresholds(_dp(yv), len(yv), int(n_thresholds), float(lo), float(hi), _dp(out), C.byref(kept)))
+    N.check(N.lib().ob_dr_thresholds(N.dp(yv), len(yv), int(n_thresholds), float(lo), float(hi), N.dp(out), C.byref(kept)))
     return out[:kept.value].copy()
 
 
@@ -785,8 +749,8 @@ def dr_quantiles(f, thresholds, taus):
     if fv.ndim != 1 or fv.shape != thr.shape or tv.ndim != 1:
         raise ValueError("f and thresholds must be 1-D of one length and taus 1-D")
     q, re, edge = np.empty(len(tv)), np.empty(len(fv)), np.zeros(len(tv), dtype=np.uint8)
-    N.check(N.lib().ob_dr_quantiles(_dp(fv), _dp(thr), len(fv), _dp(tv), len(tv), _dp(q), _dp(re),
-                                    edge.ctypes.data_as(C.POINTER(C.c_uint8))))
+    N.check(N.lib().ob_dr_quantiles(N.dp(fv), N.dp(thr), len(fv), N.dp(tv), len(tv), N.dp(q), N.dp(re),
+                                    N.u8p(edge)))
     return q, re, edge
 
 
@@ -803,9 +767,7 @@ def dr_row_len(n_thresholds: int, n_quantiles: int) -> int:
 def dr_last_timing() -> dict:
     """ob_dr_last_timing: Newton passes and HIP-event ms (logit passes, distribution pass, rows) of this thread's
     last distribution-regression boot."""
-    t = N.ob_dr_timing()
-    N.check(N.lib().ob_dr_last_timing(C.byref(t)))
-    return {f: getattr(t, f) for f, _ in N.ob_dr_timing._fields_}
+    return _last_timing("ob_dr_last_timing", N.ob_dr_timing)
 
 
 def knn(queries, controls, k: int, device: int | None = None):
@@ -818,8 +780,8 @@ def knn(queries, controls, k: int, device: int | None = None):
         raise ValueError("queries and controls must be (n, d) with the same d")
     (n_q, d), n_c, k = q.shape, c.shape[0], int(k)
     idx, dist2 = np.empty((n_q, max(k, 0)), dtype=np.int64), np.empty((n_q, max(k, 0)))
-    N.check(N.lib().ob_knn(N.context(device), _dp(q), max(n_q, 1), n_q, _dp(c), max(n_c, 1), n_c, d, k,
-                           idx.ctypes.data_as(C.POINTER(C.c_int64)), _dp(dist2)))
+    N.check(N.lib().ob_knn(N.context(device), N.dp(q), max(n_q, 1), n_q, N.dp(c), max(n_c, 1), n_c, d, k,
+                           N.i64p(idx), N.dp(dist2)))
     return idx, dist2
 
 
@@ -827,17 +789,12 @@ def match_logistic(x, y, max_iter: int = 100, tol: float = 1e-6, device: int | N
     """matching/logistic.rs:31-113 with the Newton passes on the GPU (``ob_match_logistic``): no
     probability clamp, a 1e-6 ridge, an LU solve. ``x``: (n, k) with the intercept column included.
     Returns (coefficients, scores at the final coefficients, converged, iterations)."""
-    xf = np.asfortranarray(x, dtype=np.float64)
-    if xf.ndim != 2:
-        raise ValueError("x must be (n, k)")
-    n, k = xf.shape
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    if y.shape != (n,):
-        raise ValueError("y must have one entry per row of x")
+    xf, n, k = _design(x)
+    y = _per_row(y, n, "y must have one entry per row of x")
     beta, probs = np.empty(k), np.empty(n)
     conv, iters = C.c_int32(0), C.c_int32(0)
-    N.check(N.lib().ob_match_logistic(N.context(device), _dp(xf), max(n, 1), _dp(y), n, k, int(max_iter), float(tol),
-                                      _dp(beta), _dp(probs), C.byref(conv), C.byref(iters)))
+    N.check(N.lib().ob_match_logistic(N.context(device), N.dp(xf), max(n, 1), N.dp(y), n, k, int(max_iter), float(tol),
+                                      N.dp(beta), N.dp(probs), C.byref(conv), C.byref(iters)))
     return beta, probs, bool(conv.value), int(iters.value)
 
 
@@ -850,8 +807,8 @@ def kde(data, grid, bandwidth: float, weights=None, device: int | None = None):
     if w is not None and w.shape != data.shape:
         raise ValueError("weights must match data")
     out = np.empty(len(grid))
-    N.check(N.lib().ob_kde(N.context(device), _dp(data), _dp(w), len(data), _dp(grid), len(grid), float(bandwidth),
-                           _dp(out)))
+    N.check(N.lib().ob_kde(N.context(device), N.dp(data), N.dp(w), len(data), N.dp(grid), len(grid), float(bandwidth),
+                           N.dp(out)))
     return out
 
 
@@ -859,12 +816,8 @@ def silverman_bandwidth(data) -> float:
     """math/kde.rs:44-59 via the native host routine (not the RIF bandwidth of math/rif.rs)."""
     data = np.ascontiguousarray(data, dtype=np.float64)
     out = C.c_double()
-    N.check(N.lib().ob_silverman_bandwidth(_dp(data), len(data), C.byref(out)))
+    N.check(N.lib().ob_silverman_bandwidth(N.dp(data), len(data), C.byref(out)))
     return out.value
-
-
-def _i32(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def akm_connected_set(dataframe, worker_col: str, firm_col: str) -> dict:
@@ -886,12 +839,8 @@ def akm_connected_set(dataframe, worker_col: str, firm_col: str) -> dict:
         wi, fi = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
         N.check(lib.ob_akm_set_get(h, C.byref(n), C.byref(keep), C.byref(kept), C.byref(wi), C.byref(fi),
                                    C.byref(nw), C.byref(nf), C.byref(comps)))
-
-        def arr(p, m, dtype):
-            return np.ctypeslib.as_array(p, shape=(m,)).astype(dtype) if m else np.zeros(0, dtype)
-
-        return {"keep": arr(keep, n.value, bool), "worker_idx": arr(wi, kept.value, np.int32),
-                "firm_idx": arr(fi, kept.value, np.int32),
+        return {"keep": N.array_copy(keep, (n.value,)).astype(bool), "worker_idx": N.array_copy(wi, (kept.value,)),
+                "firm_idx": N.array_copy(fi, (kept.value,)),
                 "worker_ids": [lib.ob_akm_set_id(h, 0, i).decode() for i in range(nw.value)],
                 "firm_ids": [lib.ob_akm_set_id(h, 1, i).decode() for i in range(nf.value)],
                 "n_components": int(comps.value)}
@@ -919,8 +868,8 @@ def akm_demean(v, worker_idx, firm_idx, n_workers: int, n_firms: int, tol: float
         raise ValueError("one worker and one firm index per row")
     out = np.full((c, ldv), np.nan).T[:n]  # the same leading dimension; the padding is never written
     iters, conv = np.zeros(c, np.int32), np.zeros(c, np.int32)
-    N.check(N.lib().ob_akm_demean(N.context(device), _dp(v2), ldv, n, c, _i32(wi), _i32(fi), int(n_workers),
-                                  int(n_firms), float(tol), int(max_iters), _dp(out), _i32(iters), _i32(conv)))
+    N.check(N.lib().ob_akm_demean(N.context(device), N.dp(v2), ldv, n, c, N.i32p(wi), N.i32p(fi), int(n_workers),
+                                  int(n_firms), float(tol), int(max_iters), N.dp(out), N.i32p(iters), N.i32p(conv)))
     return (out[:, 0] if one else out), iters, conv.astype(bool)
 
 
@@ -936,8 +885,8 @@ def akm_recover_fe(r, worker_idx, firm_idx, n_workers: int, n_firms: int, tol: f
         raise ValueError("one worker and one firm index per row")
     alpha, psi = np.zeros(int(n_workers)), np.zeros(int(n_firms))
     iters, conv = C.c_int32(0), C.c_int32(0)
-    N.check(N.lib().ob_akm_recover_fe(N.context(device), _dp(r), n, _i32(wi), _i32(fi), int(n_workers), int(n_firms),
-                                      float(tol), int(max_iters), _dp(alpha), _dp(psi), C.byref(iters), C.byref(conv)))
+    N.check(N.lib().ob_akm_recover_fe(N.context(device), N.dp(r), n, N.i32p(wi), N.i32p(fi), int(n_workers), int(n_firms),
+                                      float(tol), int(max_iters), N.dp(alpha), N.dp(psi), C.byref(iters), C.byref(conv)))
     return alpha, psi, int(iters.value), bool(conv.value)
 
 
@@ -959,7 +908,7 @@ def vif_gram(x, device: int | None = None):
     (K + 1, K + 1) with both triangles filled; row and column K are the intercept's."""
     x, ldx, n, k = _vif_x(x)
     g = np.empty((k + 1, k + 1), order="F")
-    N.check(N.lib().ob_vif_gram(N.context(device), _dp(x), ldx, n, k, _dp(g)))
+    N.check(N.lib().ob_vif_gram(N.context(device), N.dp(x), ldx, n, k, N.dp(g)))
     return g
 
 
@@ -972,7 +921,7 @@ def vif_solve(gram, n: int):
         raise ValueError("gram must be (K + 1, K + 1)")
     k = g.shape[0] - 1
     b = np.empty((k + 1, max(k, 0)), order="F")
-    N.check(N.lib().ob_vif_solve(_dp(g), int(n), k, _dp(b)))
+    N.check(N.lib().ob_vif_solve(N.dp(g), int(n), k, N.dp(b)))
     return b
 
 
@@ -986,7 +935,7 @@ def vif_sums(x, coef, means, device: int | None = None):
     if b.shape != (k + 1, k) or m.shape != (k,):
         raise ValueError("coef must be (K + 1, K) and means (K,)")
     ss_res, ss_tot = np.empty(k), np.empty(k)
-    N.check(N.lib().ob_vif_sums(N.context(device), _dp(x), ldx, n, k, _dp(b), _dp(m), _dp(ss_res), _dp(ss_tot)))
+    N.check(N.lib().ob_vif_sums(N.context(device), N.dp(x), ldx, n, k, N.dp(b), N.dp(m), N.dp(ss_res), N.dp(ss_tot)))
     return ss_res, ss_tot
 
 
@@ -996,7 +945,7 @@ def vif(x, device: int | None = None):
     auxiliary fit raises OB_E_LINALG for the whole call, as in the reference."""
     x, ldx, n, k = _vif_x(x)
     out = np.empty(k)
-    N.check(N.lib().ob_vif(N.context(device), _dp(x), ldx, n, k, _dp(out)))
+    N.check(N.lib().ob_vif(N.context(device), N.dp(x), ldx, n, k, N.dp(out)))
     return out
 
 
@@ -1030,7 +979,7 @@ def remedy_solve(gram_a, gram_fit=None):
         if gf.shape != ga.shape:
             raise ValueError("gram_fit must have gram_a's shape")
     beta, cov = np.empty(k), np.empty((k, k), order="F")
-    N.check(N.lib().ob_remedy_solve(_dp(ga), _dp(gf), k, _dp(beta), _dp(cov)))
+    N.check(N.lib().ob_remedy_solve(N.dp(ga), N.dp(gf), k, N.dp(beta), N.dp(cov)))
     return beta, cov
 
 
@@ -1051,8 +1000,8 @@ def remedy_score(x, beta, cov, y=None, contributions: bool = False, device: int 
         raise ValueError("y must be 1-D with at most n entries")
     fair, lev, rss = np.empty(n), np.empty(n), C.c_double(0.0)
     con = np.empty((n, k), order="F") if contributions else None
-    N.check(N.lib().ob_remedy_score(N.context(device), _dp(x), ldx, _dp(yv), n, n_rss, k, _dp(b), _dp(c), _dp(fair),
-                                    _dp(lev), C.byref(rss), _dp(con)))
+    N.check(N.lib().ob_remedy_score(N.context(device), N.dp(x), ldx, N.dp(yv), n, n_rss, k, N.dp(b), N.dp(c), N.dp(fair),
+                                    N.dp(lev), C.byref(rss), N.dp(con)))
     return (fair, lev, rss.value, con) if contributions else (fair, lev, rss.value)
 
 
@@ -1080,9 +1029,8 @@ def remedy_allocate(y, fair, leverage, n_a: int, sigma_squared: float, budget: f
                              int(bool(forensic_mode)), int(bool(adjust_both_groups)))
     lib = N.lib()
     h = C.c_void_p()
-    N.check(lib.ob_remedy_allocate(N.context(device), _dp(yv), _dp(fv), _dp(hv), int(n_a), n - int(n_a),
-                                   None if iv is None else iv.ctypes.data_as(C.POINTER(C.c_int64)),
-                                   float(sigma_squared), C.byref(rq), C.byref(h)))
+    N.check(lib.ob_remedy_allocate(N.context(device), N.dp(yv), N.dp(fv), N.dp(hv), int(n_a), n - int(n_a),
+                                   N.i64p(iv), float(sigma_squared), C.byref(rq), C.byref(h)))
     try:
         info = N.ob_remedy_info()
         N.check(lib.ob_remedy_results_info(h, C.byref(info)))
@@ -1091,22 +1039,12 @@ def remedy_allocate(y, fair, leverage, n_a: int, sigma_squared: float, budget: f
         pg = C.POINTER(C.c_int32)()
         pd = [C.POINTER(C.c_double)() for _ in range(6)]
         N.check(lib.ob_remedy_results_get(h, C.byref(pi), *[C.byref(p) for p in pd], C.byref(pg), C.byref(pr)))
-
-        def arr(p, dtype):
-            return np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, dtype=dtype)
-
-        out = {"index": arr(pi, np.int64), "group": arr(pg, np.int32), "row": arr(pr, np.int64)}
+        out = {"index": N.array_copy(pi, (m,)), "group": N.array_copy(pg, (m,)), "row": N.array_copy(pr, (m,))}
         for name, p in zip(("adjustment", "current_wage", "new_wage", "fair_wage", "lower", "upper"), pd):
-            out[name] = arr(p, np.float64)
-        for name, _ in info._fields_:
-            out[name] = getattr(info, name)
-        return out
+            out[name] = N.array_copy(p, (m,))
+        return {**out, **N.struct_dict(info)}
     finally:
         lib.ob_remedy_results_free(h)
-
-
-def _i64p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
 def remedy_defend_rows(y, fair, leverage, n_a: int, sigma_squared: float, rows, values, confidence_level: float = 0.95,
@@ -1128,8 +1066,8 @@ def remedy_defend_rows(y, fair, leverage, n_a: int, sigma_squared: float, rows, 
     m = int(rv.shape[0])
     lib = N.lib()
     h = C.c_void_p()
-    N.check(lib.ob_remedy_defend_rows(N.context(device), _dp(yv), _dp(fv), _dp(hv), int(n_a), n - int(n_a), _i64p(rv),
-                                      _dp(vv), m, float(sigma_squared), float(confidence_level), C.byref(h)))
+    N.check(lib.ob_remedy_defend_rows(N.context(device), N.dp(yv), N.dp(fv), N.dp(hv), int(n_a), n - int(n_a), N.i64p(rv),
+                                      N.dp(vv), m, float(sigma_squared), float(confidence_level), C.byref(h)))
     try:
         info = N.ob_defend_info()
         N.check(lib.ob_remedy_results_defend_info(h, C.byref(info)))
@@ -1137,16 +1075,10 @@ def remedy_defend_rows(y, fair, leverage, n_a: int, sigma_squared: float, rows, 
         pd = [C.POINTER(C.c_double)() for _ in range(6)]
         N.check(lib.ob_remedy_results_get(h, None, *[C.byref(p) for p in pd], None, C.byref(pr)))
         N.check(lib.ob_remedy_results_defensible(h, C.byref(pf)))
-
-        def arr(p, dtype):
-            return np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, dtype=dtype)
-
-        out = {"row": arr(pr, np.int64), "is_defensible": arr(pf, np.int32).astype(bool)}
+        out = {"row": N.array_copy(pr, (m,)), "is_defensible": N.array_copy(pf, (m,)).astype(bool)}
         for name, p in zip(("adjustment", "current_wage", "new_wage", "fair_wage", "lower", "upper"), pd):
-            out[name] = arr(p, np.float64)
-        for name, _ in info._fields_:
-            out[name] = np.array(info.sums) if name == "sums" else getattr(info, name)
-        return out
+            out[name] = N.array_copy(p, (m,))
+        return {**out, **N.struct_dict(info), "sums": np.array(info.sums)}
     finally:
         lib.ob_remedy_results_free(h)
 
@@ -1161,14 +1093,15 @@ def remedy_resolve_overrides(index, overrides, predictors, n_rows: int) -> list:
     ov = list(overrides)
     pos = np.array([o[0] for o in ov], dtype=np.int64)
     val = np.array([o[2] for o in ov], dtype=np.float64)
-    names = (C.c_char_p * max(len(ov), 1))(*[str(o[1]).encode() for o in ov])
+    names, keep_names = N.strs([str(o[1]) for o in ov])
     preds = [str(p) for p in predictors]
-    pn = (C.c_char_p * max(len(preds), 1))(*[p.encode() for p in preds])
+    pn, keep_preds = N.strs(preds)
     cap = max(len(ov), 1)
     orow, opred, oval, n_out = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap), C.c_int64(0)
-    N.check(N.lib().ob_remedy_resolve_overrides(_i64p(iv), int(iv.shape[0]), _i64p(pos), C.cast(names, C.POINTER(C.c_char_p)),
-                                                _dp(val), len(ov), C.cast(pn, C.POINTER(C.c_char_p)), len(preds),
-                                                int(n_rows), _i64p(orow), _ip(opred), _dp(oval), C.byref(n_out)))
+    N.check(N.lib().ob_remedy_resolve_overrides(N.i64p(iv), int(iv.shape[0]), N.i64p(pos), names, N.dp(val), len(ov),
+                                                pn, len(preds), int(n_rows), N.i64p(orow), N.i32p(opred), N.dp(oval),
+                                                C.byref(n_out)))
+    del keep_names, keep_preds  # held until the call has returned
     return [(int(orow[i]), preds[opred[i]], float(oval[i])) for i in range(n_out.value)]
 
 
@@ -1184,8 +1117,8 @@ def remedy_apply_adjustments(wage, index, value, valid=None):
         raise ValueError("wage must be 1-D, index and value 1-D of one length")
     ok = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
     out = np.empty_like(wv)
-    N.check(N.lib().ob_remedy_apply_adjustments(_dp(wv), None if ok is None else ok.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                int(wv.shape[0]), _i64p(iv), _dp(vv), int(iv.shape[0]), _dp(out)))
+    N.check(N.lib().ob_remedy_apply_adjustments(N.dp(wv), N.u8p(ok),
+                                                int(wv.shape[0]), N.i64p(iv), N.dp(vv), int(iv.shape[0]), N.dp(out)))
     return out
 
 
@@ -1211,9 +1144,8 @@ def cluster_index(ids, group, stratified: bool = False) -> dict:
     perm = [np.zeros(max(n, 1), dtype=np.int64) for _ in range(2)]
     off = [np.zeros(n + 1, dtype=np.int64) for _ in range(2)]
     info = N.ob_cluster_info()
-    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-    N.check(N.lib().ob_cluster_index(cols, _ip(grp), n, int(bool(stratified)), _ip(dense), lp(perm[0]), lp(perm[1]),
-                                     lp(off[0]), lp(off[1]), C.byref(info)))
+    N.check(N.lib().ob_cluster_index(cols, N.i32p(grp), n, int(bool(stratified)), N.i32p(dense), N.i64p(perm[0]), N.i64p(perm[1]),
+                                     N.i64p(off[0]), N.i64p(off[1]), C.byref(info)))
     nc = int(info.n_clusters)
     kept = [int(((grp == g) & (dense >= 0)).sum()) for g in (0, 1)]
     return {"dense": dense, "perm_a": perm[0][:kept[0]].copy(), "perm_b": perm[1][:kept[1]].copy(),
@@ -1238,9 +1170,8 @@ def cluster_gram(x, y, w, perm, off, device=None):
     e_pad = (e + 15) // 16 * 16
     q = np.zeros((nc, e_pad))
     rows = np.zeros(nc, dtype=np.uint32)
-    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-    N.check(N.lib().ob_cluster_gram(N.context(device), _dp(x), n, max(n, 1), p, _dp(y), None if w is None else _dp(w),
-                                    lp(perm), lp(off), nc, _dp(q), rows.ctypes.data_as(C.POINTER(C.c_uint32))))
+    N.check(N.lib().ob_cluster_gram(N.context(device), N.dp(x), n, max(n, 1), p, N.dp(y), N.dp(w),
+                                    N.i64p(perm), N.i64p(off), nc, N.dp(q), N.u32p(rows)))
     return q[:, :e].copy(), rows
 
 
@@ -1251,7 +1182,7 @@ def cluster_counts(seed: int, first_rep: int, n_reps: int, n_clusters_a: int, n_
     out = np.zeros((n_reps, max(nc, 0)), dtype=np.uint32)
     N.check(N.lib().ob_cluster_counts(N.context(device), int(seed) & (2 ** 64 - 1), int(first_rep), int(n_reps),
                                       int(n_clusters_a), int(n_clusters_b), int(bool(stratified)),
-                                      out.ctypes.data_as(C.POINTER(C.c_uint32))))
+                                      N.u32p(out)))
     return out
 
 
@@ -1267,16 +1198,14 @@ def cluster_apply(counts, q, device=None):
     qp = np.zeros((q.shape[0], w_pad))
     qp[:, :w] = q
     out = np.zeros((counts.shape[0], w_pad))
-    N.check(N.lib().ob_cluster_apply(N.context(device), counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.shape[0],
-                                     counts.shape[1], _dp(qp), w_pad, _dp(out)))
+    N.check(N.lib().ob_cluster_apply(N.context(device), N.u32p(counts), counts.shape[0],
+                                     counts.shape[1], N.dp(qp), w_pad, N.dp(out)))
     return out[:, :w].copy()
 
 
 def cluster_last_timing() -> dict:
     """ob_cluster_last_timing: gram / counts / apply / solve ms of this thread's last clustered host boot."""
-    t = N.ob_cluster_timing()
-    N.check(N.lib().ob_cluster_last_timing(C.byref(t)))
-    return {f: getattr(t, f) for f, _ in N.ob_cluster_timing._fields_}
+    return _last_timing("ob_cluster_last_timing", N.ob_cluster_timing)
 
 
 # ---- delete-one-cluster jackknife (DESIGN.md §5.17) ---------------------------------------------
@@ -1327,10 +1256,10 @@ def cluster_jackknife(q_a, q_b, rows_a, rows_b, tail, n_a: int, n_b: int, weight
     if tail.size != 5 * (k1 - 1):
         raise ValueError("cluster_jackknife: tail holds 5 K values")
     o, bufs = _jackknife_out(k1 - 1)
-    N.check(N.lib().ob_cluster_jackknife(N.context(device), _dp(q), rows.ctypes.data_as(C.POINTER(C.c_uint32)), len(q),
+    N.check(N.lib().ob_cluster_jackknife(N.context(device), N.dp(q), N.u32p(rows), len(q),
                                          len(q) if n_clusters_a is None else int(n_clusters_a),
                                          0 if n_clusters_a is None else 1, k1 - 2, int(bool(weighted)), int(n_a), int(n_b),
-                                         _dp(np.ascontiguousarray(g)), _dp(tail), int(ref_mode), C.byref(o)))
+                                         N.dp(np.ascontiguousarray(g)), N.dp(tail), int(ref_mode), C.byref(o)))
     return _jackknife_result(o, bufs, None)
 
 
@@ -1345,9 +1274,9 @@ def cluster_jackknife_rows(panel, q_a, q_b, rows_a, rows_b, ref_mode=ReferenceCo
     kept = np.zeros(nc, dtype=np.uint8)
     dev = np.empty((nc, 6 + 2 * k), dtype=np.float64) if deviations else None
     nd = (C.c_int64 * 2)()
-    N.check(lib.ob_cluster_jackknife_rows(panel._h, _dp(q), rows.ctypes.data_as(C.POINTER(C.c_uint32)), nc,
+    N.check(lib.ob_cluster_jackknife_rows(panel._h, N.dp(q), N.u32p(rows), nc,
                                           nc if n_clusters_a is None else int(n_clusters_a),
-                                          0 if n_clusters_a is None else 1, int(ref_mode), _dp(theta),
-                                          kept.ctypes.data_as(C.POINTER(C.c_uint8)), nd, _dp(dev) if deviations else None))
+                                          0 if n_clusters_a is None else 1, int(ref_mode), N.dp(theta),
+                                          N.u8p(kept), nd, N.dp(dev)))
     out = (theta, kept.astype(bool), (int(nd[0]), int(nd[1])))
     return out + (dev,) if deviations else out
