@@ -1665,6 +1665,91 @@ int ob_builder_decompose_statistics_refit(ob_ctx* ctx, const ob_column* cols, in
    handle of another kind. */
 int ob_prepared_rifs_info(const ob_prepared* prep, ob_rifs_info* out);
 
+/* ---- Nopo's exact-matching decomposition with a bootstrapped common support --------------------
+ * Nopo (2008), "Matching as a tool to decompose wage gaps"; Stata's `nopomatch`. No counterpart in the reference
+ * crate. Every other decomposition here extrapolates one group's fitted structure to rows of the other group that
+ * have no counterpart there; this one compares like with like and reports what the rows without a counterpart owe:
+ *     D = D_X + D_0 + D_A + D_B.
+ *   Groups and rows: A is the non-reference group, B cfg->reference_group; total_gap = ybar_A - ybar_B. Row i has
+ *   outcome y_i, weight w_i (1 without cfg->weights) and resample count c_i (1 in the point pass).
+ *   Cells: a cell x is one distinct combination of the values of all matching columns, cfg->predictors then
+ *   cfg->categorical. Numeric columns match on exact value (-0.0 = 0.0; i64 columns as integers), categorical columns
+ *   on their string bytes. Ids number the distinct key tuples of the rows of A and B in lexicographic order, numeric
+ *   columns ascending, categorical columns by bytes; a row of a third group level has id -1.
+ *   Row order: each group's rows stand in stable ascending order of cell id, and OBRS-3 position i of a group is its
+ *   i-th row in that order (as in the refits: the same seed draws other rows than ob_builder_run does).
+ *   Per-cell sums, per group g and cell x, over the group's rows of the cell in that order:
+ *     N_g(x) = sum c w, S_g(x) = sum c (w y). A cell's rows are one run of the order; where a chunk boundary of the
+ *     panel's chunk table cuts the run, the pieces (fragments) are summed each on its own and added in chunk order.
+ *   Support: a cell is in the support S of a replicate iff N_A(x) > 0 and N_B(x) > 0 in that replicate: the common
+ *   support is decided again in every replicate.
+ *   Aggregates, each accumulated over the cells in id order: N_g, S_g over all cells; N_g^S, S_g^S over support
+ *   cells; N_g^out, S_g^out over the others (sums of their own, not differences);
+ *     CF = sum_{x in S} N_B(x) (S_A(x) / N_A(x)) / N_B^S.
+ *   Terms: D_X = S_A^S / N_A^S - CF; D_0 = CF - S_B^S / N_B^S;
+ *     D_A = (N_A^out / N_A) (S_A^out / N_A^out - S_A^S / N_A^S), exactly 0.0 when N_A^out = 0;
+ *     D_B = (N_B^out / N_B) (S_B^S / N_B^S - S_B^out / N_B^out), exactly 0.0 when N_B^out = 0;
+ *     D = S_A / N_A - S_B / N_B.
+ * Row of a replicate, ob_nopo_row_len() = 13 doubles:
+ *     D, D_X, D_0, D_A, D_B | ybar_A, ybar_B, E_A[y|S], E_B[y|S], CF | N_A^S / N_A, N_B^S / N_B (the matched shares)
+ *     | the number of support cells.
+ * A replicate with an empty support, or with N_A = 0 or N_B = 0, has ok = 0 and a NaN row, which ob_prepared_finish
+ * drops and counts. Every sum is f64 in a fixed order without atomics: a replicate's row has the same bytes alone, in
+ * any batch and at any first_rep. Option "hk_batch" caps a batch at n 64-replicate blocks (default: as many
+ * replicates as keep the fragment table within 1 GiB).
+ * Errors of the frame entry points, all before any device work and before the context is read: normalize, Heckman
+ * settings, more than OB_NOPO_MAX_CELLS cells, a group of 2^31 rows or more: OB_E_UNSUPPORTED; no matching column, a
+ * null or non-finite value in a named column, a negative weight: OB_E_INVALID; a group without rows or without
+ * positive weight, a point pass with an empty support ("no common support"): OB_E_INSUFFICIENT.
+ * cfg->reference_coeffs is ignored. The cluster bootstrap is not served. On a handle prepared here ob_prepared_boot,
+ * ob_prepared_boot_device, ob_prepared_finish and ob_prepared_point_row work; ob_prepared_boot_sharded,
+ * ob_prepared_jackknife and ob_prepared_finish_bca are OB_E_UNSUPPORTED.
+ * Results of ob_prepared_finish / ob_builder_run_nopo: table 0 holds total_gap, composition (D_X), unexplained (D_0),
+ * unmatched_a (D_A), unmatched_b (D_B), matched_share_a and matched_share_b, each with the point row's estimate and
+ * the standard error, percentile interval and p of ob_bootstrap_stats over the ok replicates. */
+/* (2^20 - 4096) / 2: a 64-replicate block's fragment table within 1 GiB at the worst fragment count (ob_nopo.hpp) */
+#define OB_NOPO_MAX_CELLS 522240
+typedef struct {
+  double cell_ms;   /* the per-cell sums */
+  double row_ms;    /* the rows */
+  double counts_ms; /* the resample: the segments' count images */
+} ob_nopo_timing;
+typedef struct {
+  int32_t n_cells, n_support_cells;
+  int64_t n_rows, n_a, n_b;     /* rows of the frame, of A, of B */
+  const int64_t* n_cell_a;      /* [n_cells] rows of A in the cell */
+  const int64_t* n_cell_b;
+  const double* w_a;            /* [n_cells] N_A(x) of the point pass */
+  const double* w_b;
+  const double* mean_a;         /* [n_cells] S_A(x) / N_A(x) of the point pass, NaN where N_A(x) = 0 */
+  const double* mean_b;
+  const uint8_t* in_support;    /* [n_cells] */
+  const int32_t* row_cell;      /* [n_rows] the cell of every row of the frame, -1 for a row of neither group */
+} ob_nopo_info;
+int ob_nopo_row_len(void);
+/* The shape limits above on their own (host only). */
+int ob_nopo_check_shape(int64_t n_cells, int64_t n_a, int64_t n_b);
+/* Host only: the cell of every row of the frame (row_cell [n_rows]) and the number of cells. The refusals above
+   apply; the groups' sizes, the weights' sums and the support are not looked at. */
+int ob_nopo_cells(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, int32_t* row_cell,
+                  int32_t* n_cells);
+/* The cell pass alone over one group of rows in ascending order of cell: y (n), w (n weights or NULL for 1), cell (n
+   ids in [0, n_cells), ascending), counts [n_reps][n] bytes (NULL: the point pass, n_reps = 1). n_sums and s_sums
+   [n_reps][n_cells]: N(x) and S(x), a cell's fragments added in chunk order; a cell without rows gives 0. */
+int ob_nopo_sums(ob_ctx* ctx, const double* y, const double* w, const int32_t* cell, int64_t n, int32_t n_cells,
+                 const uint8_t* counts, int32_t n_reps, double* n_sums, double* s_sums);
+/* Host only: the aggregation of ob_prepared_finish on rows of ob_nopo_row_len() doubles and their point row. */
+int ob_nopo_finish_rows(const double* point_row, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out);
+/* HIP-event ms of the calling thread's last matching-decomposition boot (or prepare: the point pass) or ob_nopo_sums. */
+int ob_nopo_last_timing(ob_nopo_timing* out);
+int ob_builder_prepare_nopo(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                            const ob_builder_config* cfg, ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish. */
+int ob_builder_run_nopo(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                        ob_results** out);
+/* The point pass's cell table and every row's cell (owned by the handle). OB_E_INVALID on a handle of another kind. */
+int ob_prepared_nopo_info(const ob_prepared* prep, ob_nopo_info* out);
+
 #ifdef __cplusplus
 }
 #endif

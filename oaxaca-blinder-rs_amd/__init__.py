@@ -11,7 +11,7 @@ from .api import (Adjustment, AkmBuilder, AkmResult, BinaryDecompositionResults,
                   OaxacaResults, OptimizationResult, PreparedRun,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
                   ReferenceCoefficients, ReweightedDecompositionResults, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
-                  parse_formula, run_dfl, run_dfl_from_csv)
+                  parse_formula, run_dfl, run_dfl_from_csv, NopoDecompositionResults, nopo_cells, nopo_finish_rows)
 from .engine import (binary_check_shape, binary_last_timing, binary_means, binary_row_len, cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
                      cluster_last_timing, cluster_jackknife, cluster_jackknife_rows, cluster_jackknife_check_shape, cluster_jackknife_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
@@ -23,6 +23,7 @@ from .engine import (binary_check_shape, binary_last_timing, binary_means, binar
                      dr_cdf, dr_check_shape, dr_last_timing, dr_logit_pass, dr_quantiles, dr_row_len, dr_thresholds,
                      rifq_check_shape, rifq_last_timing, rifq_pass, rifq_row_len,
                      rifs_check_shape, rifs_last_timing, rifs_pass, rifs_row_len,
+                     nopo_check_shape, nopo_last_timing, nopo_row_len, nopo_sums,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
@@ -51,4 +52,6 @@ __all__ = [
     "dr_check_shape", "dr_row_len", "dr_finish_rows",
     "rifq_pass", "rifq_check_shape", "rifq_row_len", "rifq_last_timing",
     "rifs_pass", "rifs_check_shape", "rifs_row_len", "rifs_last_timing",
+    "NopoDecompositionResults", "nopo_cells", "nopo_sums", "nopo_check_shape", "nopo_row_len", "nopo_last_timing",
+    "nopo_finish_rows",
 ]

@@ -263,6 +263,18 @@ class ob_dr_info(C.Structure):
                 ("passes", C.POINTER(C.c_int32)), ("out_of_range", C.POINTER(C.c_uint8))]
 
 
+class ob_nopo_timing(C.Structure):
+    _fields_ = [("cell_ms", C.c_double), ("row_ms", C.c_double), ("counts_ms", C.c_double)]
+
+
+class ob_nopo_info(C.Structure):
+    _fields_ = [("n_cells", C.c_int32), ("n_support_cells", C.c_int32), ("n_rows", C.c_int64), ("n_a", C.c_int64),
+                ("n_b", C.c_int64), ("n_cell_a", C.POINTER(C.c_int64)), ("n_cell_b", C.POINTER(C.c_int64)),
+                ("w_a", C.POINTER(C.c_double)), ("w_b", C.POINTER(C.c_double)), ("mean_a", C.POINTER(C.c_double)),
+                ("mean_b", C.POINTER(C.c_double)), ("in_support", C.POINTER(C.c_uint8)),
+                ("row_cell", C.POINTER(C.c_int32))]
+
+
 class ob_component(C.Structure):
     _fields_ = [("name", C.c_char_p), ("estimate", C.c_double), ("std_err", C.c_double),
                 ("t_stat", C.c_double), ("p_value", C.c_double), ("ci_lower", C.c_double),
@@ -512,6 +524,15 @@ _SIGS = {
     "ob_builder_prepare_statistics_refit": (C.c_int, _FRAME_CFG + [_SPEC, C.c_int32, _H]),
     "ob_builder_decompose_statistics_refit": (C.c_int, _FRAME_CFG + [_SPEC, C.c_int32, _H]),
     "ob_prepared_rifs_info": (C.c_int, [_P, C.POINTER(ob_rifs_info)]),
+    "ob_nopo_row_len": (C.c_int, []),
+    "ob_nopo_check_shape": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
+    "ob_nopo_cells": (C.c_int, _FRAME_CFG[1:] + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ob_nopo_sums": (C.c_int, [_P, _D, _D, C.POINTER(C.c_int32), C.c_int64, C.c_int32, _U8, C.c_int32, _D, _D]),
+    "ob_nopo_finish_rows": (C.c_int, [_D, _D, _U8, C.c_uint64, C.POINTER(_P)]),
+    "ob_nopo_last_timing": (C.c_int, [C.POINTER(ob_nopo_timing)]),
+    "ob_builder_prepare_nopo": (C.c_int, _FRAME_CFG + [_H]),
+    "ob_builder_run_nopo": (C.c_int, _FRAME_CFG + [_H]),
+    "ob_prepared_nopo_info": (C.c_int, [_P, C.POINTER(ob_nopo_info)]),
 }
 
 # Every exported entry point of include/oaxaca_boot.h (tests/test_capi_host.py checks both ways).

@@ -541,6 +541,108 @@ def dr_finish_rows(point_row, thresholds, quantiles, rows, ok) -> DistributionDe
         n_failed=n_failed, n_out_of_range=int((edge != 0).sum()))
 
 
+NOPO_COMPONENTS = ("total_gap", "composition", "unexplained", "unmatched_a", "unmatched_b", "matched_share_a",
+                   "matched_share_b")
+
+
+@dataclass
+class NopoDecompositionResults:
+    """``OaxacaBuilder.decompose_nopo``: Nopo's (2008) exact-matching decomposition, ``total_gap = composition +
+    unexplained + unmatched_a + unmatched_b``. ``components`` holds the four terms, the gap and the two matched
+    shares (the weight of a group that lies in the common support), each with its point estimate and the standard
+    error, percentile interval and p-value over the bootstrap, in which the support is decided again per replicate.
+    ``cells``: one dict per cell (``key``: the tuple of matching values, ``n_a``, ``n_b``, ``mean_a``, ``mean_b``,
+    ``in_support``) in id order; ``row_cell``: the cell of every row of the frame (-1 outside A and B).
+    ``relative``: with ``relative=True`` the five terms over ybar_B, computed per replicate."""
+    components: dict
+    cells: list = field(repr=False, default_factory=list)
+    row_cell: np.ndarray = field(repr=False, default=None)
+    relative: dict = field(default_factory=dict)
+    n_cells: int = 0
+    n_support_cells: int = 0
+    n_a: int = 0
+    n_b: int = 0
+    n_failed: int = 0
+
+    def __getattr__(self, name):  # the seven components by name
+        if name in NOPO_COMPONENTS:
+            return self.__dict__["components"][name]
+        raise AttributeError(name)
+
+    def to_json(self) -> str:
+        def fix(v):  # serde_json writes non-finite floats as null
+            if isinstance(v, (bytes, np.bytes_)):
+                return v.decode("utf-8", "replace")
+            if isinstance(v, (str, bool)):
+                return v
+            if isinstance(v, (int, np.integer)):
+                return int(v)
+            return float(v) if np.isfinite(v) else None
+
+        def comps(d):
+            return {key: {k: fix(v) for k, v in c.__dict__.items()} for key, c in d.items()}
+
+        return json.dumps({
+            "components": comps(self.components), "relative": comps(self.relative),
+            "cells": [{**{k: fix(v) for k, v in c.items() if k != "key"}, "key": [fix(v) for v in c["key"]]}
+                      for c in self.cells],
+            "row_cell": [] if self.row_cell is None else [int(v) for v in self.row_cell], "n_cells": self.n_cells,
+            "n_support_cells": self.n_support_cells, "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed})
+
+
+def _nopo_components(handle):
+    """Table 0 of a matching decomposition's finish() -> (components by name, n_failed, n_a, n_b); frees the
+    handle."""
+    lib = N.lib()
+    try:
+        out = {}
+        for i in range(lib.ob_results_count(handle, 0)):
+            c = N.ob_component()
+            N.check(lib.ob_results_component(handle, 0, i, C.byref(c)))
+            out[c.name.decode()] = ComponentResult(c.name.decode(), c.estimate, c.std_err, c.t_stat, c.p_value,
+                                                   c.ci_lower, c.ci_upper)
+        return out, int(lib.ob_results_n_failed(handle)), int(lib.ob_results_n_a(handle)), int(lib.ob_results_n_b(handle))
+    finally:
+        lib.ob_results_free(handle)
+
+
+def _nopo_relative(point, rows, ok) -> dict:
+    """The five terms over ybar_B (row entry 6), per replicate, through ``ob_bootstrap_stats``."""
+    from .engine import bootstrap_stats
+
+    rows = np.asarray(rows)[np.asarray(ok).astype(bool)]
+    out = {}
+    for i, name in enumerate(NOPO_COMPONENTS[:5]):
+        est = float(point[i] / point[6])
+        se, p, (lo, hi) = bootstrap_stats(rows[:, i] / rows[:, 6], est)
+        out[name] = ComponentResult(name, est, se, (est / se if abs(se) > 1e-9 else 0.0), p, lo, hi)
+    return out
+
+
+def nopo_finish_rows(point_row, rows, ok) -> NopoDecompositionResults:
+    """ob_nopo_finish_rows (host only): the aggregation of ``decompose_nopo`` on given replicate rows (each
+    ``nopo_row_len()`` doubles) and their point row."""
+    point = np.ascontiguousarray(point_row, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    rl = N.lib().ob_nopo_row_len()
+    if point.shape != (rl,) or rows.shape != (len(ok), rl):
+        raise ValueError(f"point_row and rows must have {rl} entries per row")
+    h = C.c_void_p()
+    N.check(N.lib().ob_nopo_finish_rows(N.dp(point), N.dp(rows), N.u8p(ok), len(ok), C.byref(h)))
+    comps, n_failed, n_a, n_b = _nopo_components(h)
+    return NopoDecompositionResults(components=comps, n_support_cells=int(point[12]), n_a=n_a, n_b=n_b,
+                                    n_failed=n_failed)
+
+
+def nopo_cells(dataframe, outcome: str, group: str, reference_group: str, predictors=(), categorical_predictors=(),
+               bins=None):
+    """ob_nopo_cells (host only): (row_cell, n_cells) of ``decompose_nopo`` over the frame: the cell id of every row
+    (-1 for a row of neither group), ids numbering the distinct tuples of matching values in lexicographic order."""
+    b = OaxacaBuilder(dataframe, outcome, group, reference_group).predictors(predictors)
+    return b.categorical_predictors(categorical_predictors)._nopo_binned(bins)._nopo_cells()
+
+
 def _jackknife_out(k: int):
     c = 6 + 2 * k
     bufs = (np.zeros(c), np.zeros((2, c, 3)), np.zeros((c, 3)))
@@ -1285,6 +1387,80 @@ class OaxacaBuilder:
             n_failed=n_failed, n_out_of_range=info["n_out_of_range"],
             n_thresholds_requested=info["n_thresholds_requested"])
 
+    def _nopo_binned(self, bins) -> "OaxacaBuilder":
+        """This builder, or with ``bins`` a copy whose frame has each named numeric matching column replaced by its
+        ``numpy.digitize`` index (host side, a convenience only)."""
+        if not bins:
+            return self
+        frame = self._frame
+        for name, edges in bins.items():
+            if name not in self._predictors:
+                raise ValueError(f"bins: `{name}` is not a numeric matching column (predictors)")
+            if name not in frame.columns:
+                raise N.OaxacaError(N.OB_E_COLUMN, f"Column not found: {name}")
+            kind, values, valid = frame.columns[name]
+            if kind == N.OB_COL_STR:
+                raise ValueError(f"bins: `{name}` is a string column")
+            idx = np.digitize(np.asarray(values, dtype=np.float64), np.asarray(edges, dtype=np.float64))
+            out = Frame({})
+            out.nrows, out.columns = frame.nrows, dict(frame.columns)
+            out.columns[name] = (N.OB_COL_I64, np.ascontiguousarray(idx, dtype=np.int64), valid)
+            frame = out
+        b = OaxacaBuilder(frame, self.outcome, self.group, self.reference_group)
+        for attr in ("_predictors", "_categorical", "_normalize", "_selection_predictors"):
+            setattr(b, attr, list(getattr(self, attr)))
+        for attr in ("_bootstrap_reps", "_ref", "_weights", "_selection", "_seed", "_device", "_ctx", "_cluster",
+                     "_cluster_stratified"):
+            setattr(b, attr, getattr(self, attr))
+        return b
+
+    def _nopo_cells(self):
+        row_cell, n_cells = np.empty(self._frame.nrows, dtype=np.int32), C.c_int32()
+        self._call("ob_nopo_cells", N.i32p(row_cell), C.byref(n_cells), policy=HOST_ONLY, handles=0)
+        return row_cell, int(n_cells.value)
+
+    def prepare_nopo(self, bins=None) -> "PreparedRun":
+        """The handle of ``decompose_nopo`` (``ob_builder_prepare_nopo``): the cells are fixed and the point pass has
+        run; ``boot`` / ``boot_device`` / ``finish`` / ``point_row`` / ``nopo_info`` work on it."""
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, "matching decomposition: the cluster bootstrap is outside its scope")
+        b = self._nopo_binned(bins)
+        return b._prepared(b._call("ob_builder_prepare_nopo", policy=ARGUMENTS_FIRST, ctx=self._ctx))
+
+    def decompose_nopo(self, bins=None, relative: bool = False) -> "NopoDecompositionResults":
+        """Extension (no counterpart in the reference crate): Nopo's (2008) exact-matching decomposition, Stata's
+        ``nopomatch``. Rows are matched on the exact values of all ``predictors`` and ``categorical_predictors`` (a
+        cell is one combination); the gap splits into ``composition`` and ``unexplained`` inside the common support
+        and ``unmatched_a`` / ``unmatched_b``, what each group's rows without a counterpart owe. Every bootstrap
+        replicate decides the support again on the GPU, so the intervals carry the matching step. ``bins``:
+        ``{"age": [20, 30, 40]}`` matches a numeric column on its ``numpy.digitize`` index instead of its value.
+        ``relative=True`` adds the terms over ybar_B. Sample weights are served; ``reference_coefficients`` is
+        ignored. Refused (``OB_E_UNSUPPORTED``): ``normalize``, ``cluster``, Heckman settings, more than 522240
+        cells."""
+        b = self._nopo_binned(bins)
+        with b.prepare_nopo() as pr:
+            rows, ok = pr.boot(0, self._bootstrap_reps)
+            h = C.c_void_p()  # not finish(): table 0 of this handle is read by _nopo_components
+            N.check(N.lib().ob_prepared_finish(pr._h, N.dp(rows), N.u8p(ok), len(ok), C.byref(h)))
+            comps, n_failed, n_a, n_b = _nopo_components(h)
+            info = pr.nopo_info()
+            point = pr.point_row()
+        row_cell = info["row_cell"]
+        first = np.full(info["n_cells"], -1, dtype=np.int64)  # a cell's key: the matching values of its first row
+        used = np.flatnonzero(row_cell >= 0)[::-1]
+        first[row_cell[used]] = used
+        keycols = [b._frame.columns[name][1] for name in (*b._predictors, *b._categorical)]
+        def value(v):
+            return v.decode() if isinstance(v, bytes) else (v.item() if hasattr(v, "item") else v)
+
+        cells = [{"key": tuple(value(col[r]) for col in keycols),
+                  "n_a": int(info["n_cell_a"][x]), "n_b": int(info["n_cell_b"][x]), "mean_a": float(info["mean_a"][x]),
+                  "mean_b": float(info["mean_b"][x]), "in_support": bool(info["in_support"][x])}
+                 for x, r in enumerate(first)]
+        return NopoDecompositionResults(
+            components=comps, cells=cells, row_cell=row_cell, relative=_nopo_relative(point, rows, ok) if relative else {},
+            n_cells=info["n_cells"], n_support_cells=info["n_support_cells"], n_a=n_a, n_b=n_b, n_failed=n_failed)
+
     def statistic_builder(self, stat, **params) -> "OaxacaBuilder":
         """A fresh builder over this frame with the outcome replaced by the statistic's RIF of each group's
         outcome (the rows ``run()`` would keep, group by group, as ``decompose_statistic`` forms it), so that
@@ -1405,6 +1581,17 @@ class PreparedRun:
                 "beta": arr(o.beta, (2, T, k)), "passes": arr(o.passes, (2, T)),
                 "out_of_range": arr(o.out_of_range, (3, nq)), "n_out_of_range": int(o.n_out_of_range),
                 "n_thresholds_requested": int(o.n_requested)}
+
+    def nopo_info(self) -> dict:
+        """ob_prepared_nopo_info: the point pass's cell table (per cell the rows of A and B, N_A(x), N_B(x), the cell
+        means and the support flag) and the cell of every row of the frame."""
+        o = N.ob_nopo_info()
+        N.check(N.lib().ob_prepared_nopo_info(self._h, C.byref(o)))
+        nc, arr = o.n_cells, N.array_copy
+        return {"n_cells": int(nc), "n_support_cells": int(o.n_support_cells), "n_cell_a": arr(o.n_cell_a, (nc,)),
+                "n_cell_b": arr(o.n_cell_b, (nc,)), "w_a": arr(o.w_a, (nc,)), "w_b": arr(o.w_b, (nc,)),
+                "mean_a": arr(o.mean_a, (nc,)), "mean_b": arr(o.mean_b, (nc,)),
+                "in_support": arr(o.in_support, (nc,)).astype(bool), "row_cell": arr(o.row_cell, (o.n_rows,))}
 
     def rifq_info(self) -> dict:
         """ob_prepared_rifq_info: the quantiles, each group's sort permutation, the point q and f (2, T: A then B)

@@ -30,6 +30,7 @@
 #include "ob_cluster.hpp"
 #include "ob_mm.hpp"
 #include "ob_model.hpp"
+#include "ob_nopo.hpp"
 #include "ob_rif.hpp"
 #include "ob_spec.h"
 
@@ -639,9 +640,208 @@ int dr_finish_rows(const double* point, int T, int nq, const double* rows, const
   return OB_OK;
 }
 
+// ---- Nopo's matching decomposition: the host side (ob_nopo.hpp, include/oaxaca_boot.h) -----------
+
+int nopo_check_shape(int64_t n_cells, int64_t n_a, int64_t n_b) {
+  if (n_cells < 0 || n_a < 0 || n_b < 0)
+    return fail(OB_E_INVALID, "matching decomposition: bad shape (n_cells = %lld, n_a = %lld, n_b = %lld)",
+                (long long)n_cells, (long long)n_a, (long long)n_b);
+  if (n_a >= ((int64_t)1 << 31) || n_b >= ((int64_t)1 << 31))
+    return fail(OB_E_UNSUPPORTED, "matching decomposition: groups take fewer than 2^31 rows");
+  if (n_cells > kNopoMaxCells)
+    return fail(OB_E_UNSUPPORTED, "matching decomposition: at most %lld cells, got %lld (coarsen a matching column)",
+                (long long)kNopoMaxCells, (long long)n_cells);
+  for (int64_t n : {n_a, n_b})
+    if (n == 0)
+      return fail(OB_E_INSUFFICIENT, "%smatching decomposition: a group has no rows", error_prefix(OB_E_INSUFFICIENT));
+  if (n_cells == 0)
+    return fail(OB_E_INSUFFICIENT, "%smatching decomposition: no cells", error_prefix(OB_E_INSUFFICIENT));
+  return OB_OK;
+}
+
+int nopo_stage(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, Config& c,
+               NopoStaged& out, bool cells_only) {
+  const char* label = model_name(kModelNopo).label;
+  OB_TRY(config_from(cfg, c));
+  if (!c.normalize.empty()) return model_refuse(kModelNopo, "normalized categoricals are");
+  if (c.has_selection || !c.selection_predictors.empty()) return model_refuse(kModelNopo, "Heckman selection settings are");
+  if (c.predictors.empty() && c.categorical.empty()) return fail(OB_E_INVALID, "%s: no matching column", label);
+  Frame f;
+  OB_TRY(load_frame(cols, n_cols, n_rows, f));
+  std::vector<std::string> named = {c.outcome, c.group};
+  named.insert(named.end(), c.predictors.begin(), c.predictors.end());
+  named.insert(named.end(), c.categorical.begin(), c.categorical.end());
+  if (c.has_weights) named.push_back(c.weights);
+  for (const std::string& name : named) {
+    const int i = f.find(name);
+    if (i < 0) return fail(OB_E_COLUMN, "%s%s", error_prefix(OB_E_COLUMN), name.c_str());
+    const Col& col = f.cols[i];
+    for (int64_t r = 0; r < f.nrows; ++r) {
+      if (!col.valid[r])
+        return fail(OB_E_INVALID, "%s: column `%s` has a null in row %lld", label, name.c_str(), (long long)r);
+      if (col.kind == OB_COL_F64 && !std::isfinite(col.f[r]))
+        return fail(OB_E_INVALID, "%s: column `%s` has a non-finite value in row %lld", label, name.c_str(), (long long)r);
+    }
+  }
+  const Col& ycol = f.cols[f.find(c.outcome)];
+  const Col* wcol = c.has_weights ? &f.cols[f.find(c.weights)] : nullptr;
+  for (const Col* col : {&ycol, wcol})
+    if (col && col->kind != OB_COL_F64)
+      return fail(OB_E_POLARS, "%sinvalid series dtype: expected `Float64`, got `%s` for `%s`", error_prefix(OB_E_POLARS),
+                  dtype_name(col->kind), col->name.c_str());
+  if (wcol)
+    for (int64_t r = 0; r < f.nrows; ++r)
+      if (wcol->f[r] < 0.0) return fail(OB_E_INVALID, "%s: weight %g in row %lld is negative", label, wcol->f[r], (long long)r);
+  // the key columns: predictors by value (-0.0 = 0.0: the comparison of doubles), categoricals by their bytes
+  std::vector<const Col*> keys;
+  for (const auto& name : c.predictors) {
+    const Col* col = &f.cols[f.find(name)];
+    double v;
+    if (col->kind == OB_COL_STR) return numeric_value(*col, 0, v);
+    keys.push_back(col);
+  }
+  for (const auto& name : c.categorical) {
+    const Col* col = &f.cols[f.find(name)];
+    OB_TRY(expect_str(*col));
+    keys.push_back(col);
+  }
+  Split sp;
+  OB_TRY(split_groups(f, c, sp));
+  // every column's values to their dense ranks, then the rows of A and B in lexicographic order of the rank tuples
+  const size_t nk = keys.size();
+  std::vector<int64_t> used(sp.a);
+  used.insert(used.end(), sp.b.begin(), sp.b.end());
+  std::vector<int32_t> code(used.size() * nk);  // [row of used][key]
+  for (size_t j = 0; j < nk; ++j) {
+    const Col& col = *keys[j];
+    std::vector<size_t> ord(used.size());
+    for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
+    auto num = [&](size_t i) { return col.kind == OB_COL_F64 ? col.f[used[i]] : (double)col.i[used[i]]; };
+    const bool str = col.kind == OB_COL_STR, i64 = col.kind == OB_COL_I64;  // i64 keys compare as integers
+    auto less = [&](size_t a, size_t b) {
+      if (str) return col.s[used[a]] < col.s[used[b]];
+      if (i64) return col.i[used[a]] < col.i[used[b]];
+      return num(a) < num(b);
+    };
+    std::sort(ord.begin(), ord.end(), less);
+    int32_t rank = 0;
+    for (size_t i = 0; i < ord.size(); ++i) {
+      if (i && less(ord[i - 1], ord[i])) ++rank;
+      code[ord[i] * nk + j] = rank;
+    }
+  }
+  std::vector<size_t> ord(used.size());
+  for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
+  auto tuple_less = [&](size_t a, size_t b) {
+    return std::lexicographical_compare(code.begin() + a * nk, code.begin() + (a + 1) * nk, code.begin() + b * nk,
+                                        code.begin() + (b + 1) * nk);
+  };
+  std::sort(ord.begin(), ord.end(), tuple_less);
+  out.row_cell.assign((size_t)f.nrows, -1);
+  int64_t n_cells = 0;
+  for (size_t i = 0; i < ord.size(); ++i) {
+    if (i == 0 || tuple_less(ord[i - 1], ord[i])) ++n_cells;
+    if (n_cells > kNopoMaxCells) return nopo_check_shape(n_cells, (int64_t)sp.a.size(), (int64_t)sp.b.size());
+    out.row_cell[(size_t)used[ord[i]]] = (int32_t)(n_cells - 1);
+  }
+  out.n_cells = (int32_t)n_cells;
+  if (cells_only) return OB_OK;
+  OB_TRY(nopo_check_shape(n_cells, (int64_t)sp.a.size(), (int64_t)sp.b.size()));
+  // each group's rows in stable ascending order of cell id: a counting sort over the frame's row order
+  std::vector<uint8_t> has[2];
+  for (int g = 0; g < 2; ++g) {
+    const std::vector<int64_t>& rows = g ? sp.b : sp.a;
+    NopoGroup& ng = out.g[g];
+    std::vector<size_t> first((size_t)n_cells + 1, 0);
+    for (int64_t r : rows) ++first[(size_t)out.row_cell[(size_t)r] + 1];
+    for (int64_t x = 0; x < n_cells; ++x) first[(size_t)x + 1] += first[(size_t)x];
+    ng.row.resize(rows.size());
+    for (int64_t r : rows) ng.row[first[(size_t)out.row_cell[(size_t)r]]++] = r;
+    ng.cell.resize(rows.size());
+    ng.y.resize(rows.size());
+    ng.w.clear();
+    if (wcol) ng.w.resize(rows.size());
+    has[g].assign((size_t)n_cells, 0);
+    bool positive = false;
+    for (size_t i = 0; i < rows.size(); ++i) {
+      const int64_t r = ng.row[i];
+      ng.cell[i] = out.row_cell[(size_t)r];
+      ng.y[i] = ycol.f[(size_t)r];
+      if (wcol) ng.w[i] = wcol->f[(size_t)r];
+      if (!wcol || wcol->f[(size_t)r] > 0.0) has[g][(size_t)ng.cell[i]] = 1, positive = true;
+    }
+    if (!positive)
+      return fail(OB_E_INSUFFICIENT, "%s%s: group %c has no positive weight", error_prefix(OB_E_INSUFFICIENT), label,
+                  g ? 'B' : 'A');
+  }
+  bool support = false;
+  for (int64_t x = 0; x < n_cells && !support; ++x) support = has[0][(size_t)x] && has[1][(size_t)x];
+  if (!support)
+    return fail(OB_E_INSUFFICIENT, "%s%s: no common support (no cell holds weight of both groups)",
+                error_prefix(OB_E_INSUFFICIENT), label);
+  return OB_OK;
+}
+
+void nopo_fragments(const std::vector<int32_t>& cell_sorted, int32_t n_cells, const uint32_t* chunks, int n_chunks,
+                    uint32_t group, NopoFrags& out) {
+  const uint64_t n = cell_sorted.size();
+  out = NopoFrags();
+  out.cell_first.assign((size_t)n_cells + 1, 0);
+  for (int c = 0; c < n_chunks; ++c) {
+    if (chunks[3 * c] != group) continue;
+    const uint64_t r0 = (uint64_t)chunks[3 * c + 1] * OB_TILE_ROWS, r1 = std::min<uint64_t>((uint64_t)chunks[3 * c + 2] * OB_TILE_ROWS, n);
+    out.chunk_first.push_back((uint32_t)out.cell.size());
+    for (uint64_t i = r0; i < r1; ++i) {
+      if (i == r0 || cell_sorted[i] != cell_sorted[i - 1]) {
+        if (i > r0) out.end.push_back((uint32_t)i);
+        out.cell.push_back((uint32_t)cell_sorted[i]);
+      }
+    }
+    if (r1 > r0) out.end.push_back((uint32_t)r1);
+  }
+  out.end.push_back(0xFFFFFFFFu);  // never reached: the kernel reads one entry past a chunk's last fragment
+  // the cells' fragment ranges: a cell's fragments are consecutive, in chunk order
+  for (uint32_t x : out.cell) ++out.cell_first[(size_t)x + 1];
+  for (int32_t x = 0; x < n_cells; ++x) out.cell_first[(size_t)x + 1] += out.cell_first[(size_t)x];
+}
+
+int nopo_finish_rows(const double* point, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
+  uint64_t ng = 0;
+  for (uint64_t r = 0; r < n_reps; ++r) ng += ok[r] ? 1 : 0;
+  if (ng < n_reps)
+    fprintf(stderr,
+            "Warning: %llu out of %llu bootstrap replications failed and were discarded. The analysis is based on "
+            "%llu successful replications.\n",
+            (unsigned long long)(n_reps - ng), (unsigned long long)n_reps, (unsigned long long)ng);
+  ob_results* res = new ob_results();
+  res->total_gap = point[0];
+  res->n_failed = (int64_t)(n_reps - ng);
+  static const char* names[7] = {"total_gap", "composition", "unexplained", "unmatched_a", "unmatched_b",
+                                 "matched_share_a", "matched_share_b"};
+  static const int col[7] = {0, 1, 2, 3, 4, 10, 11};
+  std::vector<std::vector<int>> groups;
+  for (int i = 0; i < 7; ++i) groups.push_back({col[i]});
+  std::vector<double> st(4 * groups.size());
+  aggregate(rows, ok, n_reps, kNopoRowLen, groups, st.data());
+  for (int i = 0; i < 7; ++i) {
+    const double* s4 = st.data() + 4 * i;
+    const double pt = point[col[i]];
+    const double t = std::fabs(s4[0]) > 1e-9 ? pt / s4[0] : 0.0;  // as finish()
+    res->tables[0].push_back({names[i], pt, s4[0], t, s4[1], s4[2], s4[3]});
+  }
+  *out = res;
+  return OB_OK;
+}
+
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block).
 int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
   if (pr->model_kind == kModelReweight) return reweight_finish(pr, rows, ok, n_reps, out);
+  if (pr->model_kind == kModelNopo) {
+    OB_TRY(nopo_finish_rows(pr->point_row.data(), rows, ok, n_reps, out));
+    (*out)->n_a = pr->n_a;
+    (*out)->n_b = pr->n_b;
+    return OB_OK;
+  }
   if (pr->model_kind == kModelDr) {
     OB_TRY(dr_finish_rows(pr->point_row.data(), (int)pr->dr_info.thresholds.size(), (int)pr->dr_info.taus.size(), rows, ok,
                           n_reps, out));
@@ -993,6 +1193,27 @@ int ob_dr_finish_rows(const double* point_row, int32_t n_thresholds, int32_t n_q
   if (n_thresholds < 2 || n_thresholds > OB_DR_MAX_T || n_q < 1 || n_q > OB_DR_MAX_Q)
     return ob::fail(OB_E_INVALID, "ob_dr_finish_rows: bad shape (T = %d, n_q = %d)", n_thresholds, n_q);
   return ob::dr_finish_rows(point_row, n_thresholds, n_q, rows, ok, n_reps, out);
+}
+
+int ob_nopo_row_len(void) { return ob::kNopoRowLen; }
+
+int ob_nopo_check_shape(int64_t n_cells, int64_t n_a, int64_t n_b) { return ob::nopo_check_shape(n_cells, n_a, n_b); }
+
+int ob_nopo_cells(const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg, int32_t* row_cell,
+                  int32_t* n_cells) {
+  if (!n_cells || (n_rows > 0 && !row_cell)) return ob::fail(OB_E_INVALID, "null pointer");
+  ob::Config c;
+  ob::NopoStaged st;
+  OB_TRY(ob::nopo_stage(cols, n_cols, n_rows, cfg, c, st, true));
+  std::copy(st.row_cell.begin(), st.row_cell.end(), row_cell);
+  *n_cells = st.n_cells;
+  return OB_OK;
+}
+
+int ob_nopo_finish_rows(const double* point_row, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
+  if (!point_row || !out || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  return ob::nopo_finish_rows(point_row, rows, ok, n_reps, out);
 }
 
 int ob_prepared_row_len(const ob_prepared* p) { return p ? p->row_len : 0; }

@@ -770,6 +770,44 @@ def dr_last_timing() -> dict:
     return _last_timing("ob_dr_last_timing", N.ob_dr_timing)
 
 
+def nopo_sums(y, cell, n_cells: int, w=None, counts=None, device: int | None = None):
+    """The cell pass of the matching decomposition alone (``ob_nopo_sums``) over one group of rows in ascending
+    order of ``cell`` (ids in [0, n_cells)). ``w``: weights or ``None`` for 1; ``counts``: (n_reps, n) resample
+    counts below 256 (``None``: the point pass, one replicate). Returns (N, S), each (n_reps, n_cells): sum c w and
+    sum c (w y) per cell."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 1:
+        raise ValueError("y must be one-dimensional")
+    n = len(y)
+    what = "cell and w must have one entry per entry of y"
+    wv = _per_row(w, n, what, optional=True)
+    cv = np.ascontiguousarray(cell, dtype=np.int32)
+    if cv.shape != (n,):
+        raise ValueError(what)
+    c8 = _counts_u8(counts, n, by_rep=True)
+    reps = 1 if c8 is None else len(c8)
+    ns, ss = np.empty((reps, max(int(n_cells), 0))), np.empty((reps, max(int(n_cells), 0)))
+    with_context(lambda ctx: N.lib().ob_nopo_sums(ctx, N.dp(y), N.dp(wv), N.i32p(cv), n, int(n_cells), N.u8p(c8), reps,
+                                                 N.dp(ns), N.dp(ss)), device)
+    return ns, ss
+
+
+def nopo_check_shape(n_cells: int, n_a: int, n_b: int) -> None:
+    """ob_nopo_check_shape: raises OaxacaError where a matching decomposition would (host only)."""
+    N.check(N.lib().ob_nopo_check_shape(int(n_cells), int(n_a), int(n_b)))
+
+
+def nopo_row_len() -> int:
+    """ob_nopo_row_len: 13 doubles per replicate of a matching decomposition."""
+    return int(N.lib().ob_nopo_row_len())
+
+
+def nopo_last_timing() -> dict:
+    """ob_nopo_last_timing: HIP-event ms of the cell pass, the rows and the resample of this thread's last matching
+    decomposition boot (or prepare, or ``nopo_sums``)."""
+    return _last_timing("ob_nopo_last_timing", N.ob_nopo_timing)
+
+
 def knn(queries, controls, k: int, device: int | None = None):
     """The min(k, n_c) nearest controls of each query (``ob_knn``): squared Euclidean distance summed
     in covariate order without FMA, ties by control position. ``queries``: (n_q, d), ``controls``:
