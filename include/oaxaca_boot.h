@@ -1750,6 +1750,98 @@ int ob_builder_run_nopo(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int6
 /* The point pass's cell table and every row's cell (owned by the handle). OB_E_INVALID on a handle of another kind. */
 int ob_prepared_nopo_info(const ob_prepared* prep, ob_nopo_info* out);
 
+/* ---- Bootstrapped DFL density decomposition with confidence bands ------------------------------
+ * DiNardo, Fortin and Lemieux (1996): the densities of the outcome in A, in B and in B reweighted to A's covariates
+ * (the counterfactual C), on a grid, with the propensity logit refitted in every bootstrap replicate. ob_dfl_run
+ * gives the three curves of the reference crate; this is the same picture under the builder's conventions, with
+ * sample weights and with inference. A is the non-reference group, B cfg->reference_group; x the design row with the
+ * intercept in column 0 (K <= OB_REWEIGHT_MAX_K columns); w the sample weight (1 without cfg->weights); c the
+ * replicate's OBRS-3 count of the row (1 in the point pass): all exactly as in the reweighted decomposition above.
+ *   Grid g_0 < .. < g_{G-1}, 2 <= G <= OB_DENSITY_MAX_GRID: given (finite and strictly increasing), or
+ *   (ob_density_config.grid == NULL) g_j = min + j (max - min) / G over the outcomes of A and B together, the rule of
+ *   dfl.rs:164-172 (the product j * step is rounded before the sum); grid_size 0 is 100.
+ *   Bandwidths h_A, h_B: given (finite and > 0), or (0) ob_silverman_bandwidth of each group's outcome, unweighted
+ *   (dfl.rs:174-175). They are fixed at prepare time: a replicate does not move them. f_C uses h_B (dfl.rs:178).
+ *   Per replicate: gamma is the propensity logit of the reweighted decomposition, unchanged (Newton from 0, the
+ *   clamp of p to [1e-10, 1 - 1e-10], the stopping rule, the failure flags); psi_i = p_i / (1 - p_i) on B's rows;
+ *   with phi(u) = exp(-u^2 / 2) / sqrt(2 pi)
+ *     f_A(g) = sum_A c w phi((g - y) / h_A) / (h_A sum_A c w)
+ *     f_B(g) = sum_B c w phi((g - y) / h_B) / (h_B sum_B c w)
+ *     f_C(g) = sum_B c w psi phi((g - y) / h_B) / (h_B sum_B c w psi).
+ *   The factor P(B) / P(A) of dfl.rs:116 cancels in f_C.
+ * Row of a replicate, ob_density_row_len(K, G) = 6 G + K + 2 doubles:
+ *     f_A | f_B | f_C | total = f_A - f_B | composition = f_C - f_B | structure = f_A - f_C (G each) | gamma (K) |
+ *     the effective sample size (sum c w psi)^2 / sum c (w psi)^2 | the replicate's logit passes.
+ * A replicate whose logit fails or does not converge, or one of whose groups has sum c w = 0, has ok = 0 and a NaN
+ * row; in the point pass that is OB_E_LINALG for the whole call. Every sum is f64, over a chunk's rows in row order
+ * and over the chunks in chunk order, without atomics: a replicate's row has the same bytes alone, in any batch and at
+ * any first_rep. Option "hk_batch" caps a batch at n 64-replicate blocks.
+ * Errors of the frame entry points, all before any device work and before the context is read: normalize, Heckman
+ * settings, K > OB_REWEIGHT_MAX_K, G > OB_DENSITY_MAX_GRID: OB_E_UNSUPPORTED; a null or non-finite value in a named
+ * column, a negative weight, G < 2, a grid that is not finite and strictly increasing, a bandwidth that is not finite
+ * and > 0 (0 asks for the default): OB_E_INVALID; a group with rows <= K or without positive weight:
+ * OB_E_INSUFFICIENT. cfg->reference_coeffs is ignored. The cluster bootstrap is not served. On a handle prepared
+ * here ob_prepared_boot, ob_prepared_boot_device, ob_prepared_finish and ob_prepared_point_row work;
+ * ob_prepared_boot_sharded, ob_prepared_jackknife and ob_prepared_finish_bca are OB_E_UNSUPPORTED.
+ * Results of ob_prepared_finish / ob_builder_run_density / ob_density_finish_rows: table OB_DENSITY_TABLE_CURVES
+ * holds the 6 G entries of the curves in row order, each through the aggregation of the other runs (estimate = the
+ * point row's, standard error, percentile interval, p); names are "<curve>@<j>" with curve one of density_a,
+ * density_b, density_counterfactual, total, composition, structure. Table OB_DENSITY_TABLE_BANDS holds, under the
+ * same names, the uniform 95 % band of each curve: over the replicates kept and the grid points with se_j > 0,
+ * t_r = max_j |v_rj - point_j| / se_j; crit is the ascending-sorted t at index min(R - 1, floor(0.95 R)), R the
+ * replicates kept; ci_lower / ci_upper = point_j -+ crit se_j (the point itself where se_j = 0), estimate = point_j,
+ * std_err = se_j, t_stat = crit (the same for every entry of a curve), p_value = NaN. A curve without a kept replicate
+ * or without a grid point of positive se has crit = NaN. */
+#define OB_DENSITY_MAX_GRID 256
+#define OB_DENSITY_MAX_VECTORS 64
+#define OB_DENSITY_TABLE_CURVES 0
+#define OB_DENSITY_TABLE_BANDS 1
+typedef struct {
+  int32_t grid_size;  /* 0: 100 */
+  const double* grid; /* grid_size points, or NULL: the rule above */
+  double bandwidth_a; /* 0: ob_silverman_bandwidth of A's outcome */
+  double bandwidth_b; /* 0: of B's */
+} ob_density_config; /* a NULL configuration is every default */
+typedef struct {
+  int32_t logit_passes;   /* the longest batch's Newton rounds */
+  int32_t logit_launches; /* logit pass kernels over all batches */
+  double logit_ms;        /* the logit pass kernels (the Newton steps not included) */
+  double density_ms;      /* the density pass */
+  double finish_ms;       /* the rows */
+} ob_density_timing;
+typedef struct {
+  int32_t grid_size, k;
+  const double* grid; /* [grid_size] */
+  double bandwidth_a, bandwidth_b;
+  int64_t n_a, n_b;
+} ob_density_info;
+/* 6 G + K + 2, or 0 for k < 1 or G outside [2, OB_DENSITY_MAX_GRID]. */
+int ob_density_row_len(int32_t k, int32_t grid_size);
+/* The shape limits above on their own (host only). k: design columns with the intercept. */
+int ob_density_check_shape(int32_t k, int64_t n_a, int64_t n_b, int32_t grid_size);
+/* HIP-event ms of the calling thread's last density boot (or prepare: the point pass) or ob_density_pass. */
+int ob_density_last_timing(ob_density_timing* out);
+/* Host only: the default grid of grid_size points (0: 100) over y (n finite values). out [grid_size]. */
+int ob_density_grid(const double* y, int64_t n, int32_t grid_size, double* out);
+/* The density pass alone over one group of rows: x (n x k, column-major, ldx >= n, column 0 all ones), y (n), w (n
+   weights or NULL for 1), counts (n bytes or NULL for every row once), gammas [m][k], 1 <= m <= OB_DENSITY_MAX_VECTORS
+   (NULL: psi = 1 and m = 1), grid [grid_size] (any finite values), h > 0. With v = w psi: num [m][grid_size] =
+   sum c v phi((g_j - y) / h), den [m] = sum c v, den2 [m] = sum c v^2; the chunk partials are added in chunk order. */
+int ob_density_pass(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, const double* w, const uint8_t* counts,
+                    int64_t n, int32_t k, const double* gammas, int32_t m, const double* grid, int32_t grid_size, double h,
+                    double* num, double* den, double* den2);
+/* Host only: the aggregation of ob_prepared_finish on rows of ob_density_row_len(k, grid_size) doubles and their
+   point row. */
+int ob_density_finish_rows(const double* point_row, int32_t k, int32_t grid_size, const double* rows, const uint8_t* ok,
+                           uint64_t n_reps, ob_results** out);
+int ob_builder_prepare_density(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                               const ob_builder_config* cfg, const ob_density_config* dc, ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish. */
+int ob_builder_run_density(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                           const ob_builder_config* cfg, const ob_density_config* dc, ob_results** out);
+/* The grid and bandwidths a handle was prepared with; the pointer lives as long as the handle. */
+int ob_prepared_density_info(const ob_prepared* prep, ob_density_info* out);
+
 #ifdef __cplusplus
 }
 #endif

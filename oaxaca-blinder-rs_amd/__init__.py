@@ -11,7 +11,8 @@ from .api import (Adjustment, AkmBuilder, AkmResult, BinaryDecompositionResults,
                   OaxacaResults, OptimizationResult, PreparedRun,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
                   ReferenceCoefficients, ReweightedDecompositionResults, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
-                  parse_formula, run_dfl, run_dfl_from_csv, NopoDecompositionResults, nopo_cells, nopo_finish_rows)
+                  parse_formula, run_dfl, run_dfl_from_csv, NopoDecompositionResults, nopo_cells, nopo_finish_rows,
+                  DensityCurve, DensityDecompositionResults, density_finish_rows)
 from .engine import (binary_check_shape, binary_last_timing, binary_means, binary_row_len, cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
                      cluster_last_timing, cluster_jackknife, cluster_jackknife_rows, cluster_jackknife_check_shape, cluster_jackknife_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
@@ -24,6 +25,7 @@ from .engine import (binary_check_shape, binary_last_timing, binary_means, binar
                      rifq_check_shape, rifq_last_timing, rifq_pass, rifq_row_len,
                      rifs_check_shape, rifs_last_timing, rifs_pass, rifs_row_len,
                      nopo_check_shape, nopo_last_timing, nopo_row_len, nopo_sums,
+                     density_check_shape, density_grid, density_last_timing, density_pass, density_row_len,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
@@ -54,4 +56,6 @@ __all__ = [
     "rifs_pass", "rifs_check_shape", "rifs_row_len", "rifs_last_timing",
     "NopoDecompositionResults", "nopo_cells", "nopo_sums", "nopo_check_shape", "nopo_row_len", "nopo_last_timing",
     "nopo_finish_rows",
+    "DensityDecompositionResults", "DensityCurve", "density_pass", "density_grid", "density_check_shape",
+    "density_row_len", "density_last_timing", "density_finish_rows",
 ]

@@ -56,6 +56,8 @@ OB_RW_TABLE_AGGREGATE, OB_RW_TABLE_PURE_EXPLAINED, OB_RW_TABLE_SPECIFICATION_ERR
 OB_RW_TABLE_PURE_UNEXPLAINED, OB_RW_TABLE_REWEIGHTING_ERROR = 3, 4
 OB_DR_MAX_K, OB_DR_MAX_T, OB_DR_MAX_Q, OB_DR_MAX_VECTORS = 32, 64, 32, 128
 OB_DR_TABLE_QUANTILE_EFFECTS, OB_DR_TABLE_QUANTILES, OB_DR_TABLE_DISTRIBUTION_EFFECTS, OB_DR_TABLE_CDF = 0, 1, 2, 3
+OB_DENSITY_MAX_GRID, OB_DENSITY_MAX_VECTORS = 256, 64
+OB_DENSITY_TABLE_CURVES, OB_DENSITY_TABLE_BANDS = 0, 1
 
 
 class OaxacaError(RuntimeError):
@@ -273,6 +275,21 @@ class ob_nopo_info(C.Structure):
                 ("w_a", C.POINTER(C.c_double)), ("w_b", C.POINTER(C.c_double)), ("mean_a", C.POINTER(C.c_double)),
                 ("mean_b", C.POINTER(C.c_double)), ("in_support", C.POINTER(C.c_uint8)),
                 ("row_cell", C.POINTER(C.c_int32))]
+
+
+class ob_density_config(C.Structure):
+    _fields_ = [("grid_size", C.c_int32), ("grid", C.POINTER(C.c_double)), ("bandwidth_a", C.c_double),
+                ("bandwidth_b", C.c_double)]
+
+
+class ob_density_timing(C.Structure):
+    _fields_ = [("logit_passes", C.c_int32), ("logit_launches", C.c_int32), ("logit_ms", C.c_double),
+                ("density_ms", C.c_double), ("finish_ms", C.c_double)]
+
+
+class ob_density_info(C.Structure):
+    _fields_ = [("grid_size", C.c_int32), ("k", C.c_int32), ("grid", C.POINTER(C.c_double)),
+                ("bandwidth_a", C.c_double), ("bandwidth_b", C.c_double), ("n_a", C.c_int64), ("n_b", C.c_int64)]
 
 
 class ob_component(C.Structure):
@@ -533,6 +550,16 @@ _SIGS = {
     "ob_builder_prepare_nopo": (C.c_int, _FRAME_CFG + [_H]),
     "ob_builder_run_nopo": (C.c_int, _FRAME_CFG + [_H]),
     "ob_prepared_nopo_info": (C.c_int, [_P, C.POINTER(ob_nopo_info)]),
+    "ob_density_row_len": (C.c_int, [C.c_int32, C.c_int32]),
+    "ob_density_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "ob_density_last_timing": (C.c_int, [C.POINTER(ob_density_timing)]),
+    "ob_density_grid": (C.c_int, [_D, C.c_int64, C.c_int32, _D]),
+    "ob_density_pass": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _D, C.c_int32, _D, C.c_int32,
+                                  C.c_double, _D, _D, _D]),
+    "ob_density_finish_rows": (C.c_int, [_D, C.c_int32, C.c_int32, _D, _U8, C.c_uint64, C.POINTER(_P)]),
+    "ob_builder_prepare_density": (C.c_int, _FRAME_CFG + [C.POINTER(ob_density_config), _H]),
+    "ob_builder_run_density": (C.c_int, _FRAME_CFG + [C.POINTER(ob_density_config), _H]),
+    "ob_prepared_density_info": (C.c_int, [_P, C.POINTER(ob_density_info)]),
 }
 
 # Every exported entry point of include/oaxaca_boot.h (tests/test_capi_host.py checks both ways).

@@ -541,6 +541,129 @@ def dr_finish_rows(point_row, thresholds, quantiles, rows, ok) -> DistributionDe
         n_failed=n_failed, n_out_of_range=int((edge != 0).sum()))
 
 
+DENSITY_CURVES = ("density_a", "density_b", "density_counterfactual", "total", "composition", "structure")
+
+
+@dataclass
+class DensityCurve:
+    """One curve of ``DensityDecompositionResults`` on its grid: per grid point the point estimate, the bootstrap
+    standard error, the pointwise percentile interval and p-value, and the uniform 95 % band ``estimate -+
+    band_critical * std_err`` (the band covers the whole curve at once; ``band_critical`` is the 95 % point of the
+    replicates' largest standardised deviation over the grid)."""
+    estimate: np.ndarray
+    std_err: np.ndarray
+    ci_lower: np.ndarray
+    ci_upper: np.ndarray
+    p_value: np.ndarray
+    band_lower: np.ndarray
+    band_upper: np.ndarray
+    band_critical: float = float("nan")
+
+
+@dataclass
+class DensityDecompositionResults:
+    """``OaxacaBuilder.decompose_density``: the DFL density decomposition (DiNardo, Fortin and Lemieux 1996) with
+    bootstrap inference. ``density_a``, ``density_b`` and ``density_counterfactual`` (B reweighted to A's covariates)
+    are the kernel densities on ``grid``; ``total`` = f_A - f_B, ``composition`` = f_C - f_B and ``structure`` =
+    f_A - f_C their differences. Each is a ``DensityCurve``. ``gamma``: the point logit; ``effective_sample_size``:
+    that of the reweighting factor on B's rows."""
+    grid: np.ndarray
+    bandwidth_a: float
+    bandwidth_b: float
+    density_a: DensityCurve
+    density_b: DensityCurve
+    density_counterfactual: DensityCurve
+    total: DensityCurve
+    composition: DensityCurve
+    structure: DensityCurve
+    gamma: np.ndarray = field(repr=False, default=None)
+    effective_sample_size: float = float("nan")
+    logit_passes: int = 0
+    names: list = field(default_factory=list, repr=False)
+    n_a: int = 0
+    n_b: int = 0
+    n_failed: int = 0
+
+    def to_json(self) -> str:
+        def vec(a):  # serde_json writes non-finite floats as null
+            return [float(v) if np.isfinite(v) else None for v in np.asarray(a, dtype=np.float64).ravel()]
+
+        def curve(c):
+            d = {key: vec(v) for key, v in c.__dict__.items() if key != "band_critical"}
+            d["band_critical"] = vec([c.band_critical])[0]
+            return d
+
+        out = {"grid": vec(self.grid), "bandwidth_a": self.bandwidth_a, "bandwidth_b": self.bandwidth_b}
+        out.update({name: curve(getattr(self, name)) for name in DENSITY_CURVES})
+        out.update({"gamma": vec(self.gamma), "effective_sample_size": vec([self.effective_sample_size])[0],
+                    "logit_passes": self.logit_passes, "names": list(self.names), "n_a": self.n_a, "n_b": self.n_b,
+                    "n_failed": self.n_failed})
+        return json.dumps(out)
+
+    def plot(self):
+        """The three densities with their uniform bands on one matplotlib figure (returned), in the manner of
+        ``DflResult.plot``."""
+        try:
+            import matplotlib.pyplot as plt
+        except ImportError as e:
+            raise ImportError("DensityDecompositionResults.plot() needs matplotlib, which is not installed") from e
+        fig = plt.figure()
+        ax = fig.gca()
+        for c, label in ((self.density_a, "Group A"), (self.density_b, "Group B"),
+                         (self.density_counterfactual, "Group B (Counterfactual)")):
+            ax.plot(self.grid, c.estimate, label=label)
+            ax.fill_between(self.grid, c.band_lower, c.band_upper, alpha=0.2)
+        ax.legend()
+        ax.set_title("DFL Decomposition: Density Estimates (uniform 95 % bands)")
+        return fig
+
+
+def _density_results(handle, grid, bandwidth_a, bandwidth_b, point, k, names=()) -> DensityDecompositionResults:
+    """The two tables of a density finish() and the tail of the point row; frees the handle."""
+    lib = N.lib()
+    G = len(grid)
+
+    def table(t):
+        c = N.ob_component()
+        rows = []
+        for i in range(lib.ob_results_count(handle, t)):
+            N.check(lib.ob_results_component(handle, t, i, C.byref(c)))
+            rows.append((c.estimate, c.std_err, c.t_stat, c.p_value, c.ci_lower, c.ci_upper))
+        return np.array(rows, dtype=np.float64).reshape(6, G, 6)
+
+    try:
+        cv, bd = table(N.OB_DENSITY_TABLE_CURVES), table(N.OB_DENSITY_TABLE_BANDS)
+        n_failed, n_a, n_b = (int(lib.ob_results_n_failed(handle)), int(lib.ob_results_n_a(handle)),
+                              int(lib.ob_results_n_b(handle)))
+    finally:
+        lib.ob_results_free(handle)
+    curves = {name: DensityCurve(estimate=cv[i, :, 0].copy(), std_err=cv[i, :, 1].copy(), ci_lower=cv[i, :, 4].copy(),
+                                 ci_upper=cv[i, :, 5].copy(), p_value=cv[i, :, 3].copy(), band_lower=bd[i, :, 4].copy(),
+                                 band_upper=bd[i, :, 5].copy(), band_critical=float(bd[i, 0, 2]))
+              for i, name in enumerate(DENSITY_CURVES)}
+    return DensityDecompositionResults(
+        grid=np.array(grid, dtype=np.float64), bandwidth_a=float(bandwidth_a), bandwidth_b=float(bandwidth_b),
+        gamma=np.array(point[6 * G:6 * G + k]), effective_sample_size=float(point[6 * G + k]),
+        logit_passes=int(point[6 * G + k + 1]) if np.isfinite(point[6 * G + k + 1]) else 0, names=list(names),
+        n_a=n_a, n_b=n_b, n_failed=n_failed, **curves)
+
+
+def density_finish_rows(point_row, k: int, grid, rows, ok, bandwidth_a: float = float("nan"),
+                        bandwidth_b: float = float("nan")) -> DensityDecompositionResults:
+    """ob_density_finish_rows (host only): the aggregation of ``decompose_density`` on given replicate rows (each
+    ``density_row_len(k, G)`` doubles) and their point row."""
+    point = np.ascontiguousarray(point_row, dtype=np.float64)
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    G = len(grid)
+    if point.shape != (6 * G + int(k) + 2,) or rows.shape != (len(ok), len(point)):
+        raise ValueError("point_row and rows must have 6 G + k + 2 entries per row")
+    h = C.c_void_p()
+    N.check(N.lib().ob_density_finish_rows(N.dp(point), int(k), G, N.dp(rows), N.u8p(ok), len(ok), C.byref(h)))
+    return _density_results(h, grid, bandwidth_a, bandwidth_b, point, int(k))
+
+
 NOPO_COMPONENTS = ("total_gap", "composition", "unexplained", "unmatched_a", "unmatched_b", "matched_share_a",
                    "matched_share_b")
 
@@ -1387,6 +1510,54 @@ class OaxacaBuilder:
             n_failed=n_failed, n_out_of_range=info["n_out_of_range"],
             n_thresholds_requested=info["n_thresholds_requested"])
 
+    def prepare_density(self, grid_size=100, grid=None, bandwidth=None) -> "PreparedRun":
+        """The handle of ``decompose_density`` (``ob_builder_prepare_density``): the grid and the bandwidths are fixed
+        and the point pass has run; ``boot`` / ``boot_device`` / ``finish`` / ``point_row`` / ``density_info`` work on
+        it."""
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, "density decomposition: the cluster bootstrap is outside its scope")
+        dc = N.ob_density_config()
+        gr = None
+        if grid is not None:
+            gr = np.ascontiguousarray(grid, dtype=np.float64)
+            if gr.ndim != 1:
+                raise ValueError("grid must be a 1-D sequence")
+            dc.grid, dc.grid_size = N.dp(gr), len(gr)
+        else:
+            dc.grid, dc.grid_size = None, int(grid_size)
+        if bandwidth is None:
+            dc.bandwidth_a = dc.bandwidth_b = 0.0
+        else:
+            bw = np.atleast_1d(np.asarray(bandwidth, dtype=np.float64))
+            if bw.shape not in ((1,), (2,)):
+                raise ValueError("bandwidth must be one value or (bandwidth_a, bandwidth_b)")
+            if (bw == 0.0).any():
+                raise ValueError("a bandwidth of 0 is not a bandwidth; pass None for Silverman's")
+            dc.bandwidth_a, dc.bandwidth_b = float(bw[0]), float(bw[-1])
+        return self._prepared(self._call("ob_builder_prepare_density", C.byref(dc), policy=ARGUMENTS_FIRST,
+                                         ctx=self._ctx, keep=(gr,)))
+
+    def decompose_density(self, grid_size=100, grid=None, bandwidth=None) -> "DensityDecompositionResults":
+        """Extension: the density decomposition of DiNardo, Fortin and Lemieux (1996) with bootstrap inference --
+        ``run_dfl``'s picture under this builder's conventions, with sample weights and with bands. The kernel
+        densities of the outcome in A, in the reference group B and in B reweighted to A's covariates (the
+        counterfactual C, psi = p / (1 - p) of the reweighted decomposition's propensity logit) on a grid of
+        ``grid_size`` points over the pooled outcome (dfl.rs's rule) or on ``grid``; the bandwidths are Silverman's
+        per group at the point estimate (``bandwidth``: one value or a pair overrides them) and stay fixed. Every
+        bootstrap replicate refits the logit and recomputes the three curves on the GPU. Each curve and each
+        difference (total = f_A - f_B, composition = f_C - f_B, structure = f_A - f_C) comes with standard errors,
+        pointwise percentile intervals and a uniform 95 % band. Sample weights are served;
+        ``reference_coefficients`` is ignored. Refused (``OB_E_UNSUPPORTED``): ``normalize``, ``cluster``, Heckman
+        settings, more than 32 design columns or 256 grid points."""
+        with self.prepare_density(grid_size, grid, bandwidth) as pr:
+            rows, ok = pr.boot(0, self._bootstrap_reps)
+            h = C.c_void_p()  # not finish(): the two tables of this handle are read by _density_results
+            N.check(N.lib().ob_prepared_finish(pr._h, N.dp(rows), N.u8p(ok), len(ok), C.byref(h)))
+            info = pr.density_info()
+            point = pr.point_row()
+        names = self.get_data_matrices()[4]
+        return _density_results(h, info["grid"], info["bandwidth_a"], info["bandwidth_b"], point, info["k"], names)
+
     def _nopo_binned(self, bins) -> "OaxacaBuilder":
         """This builder, or with ``bins`` a copy whose frame has each named numeric matching column replaced by its
         ``numpy.digitize`` index (host side, a convenience only)."""
@@ -1592,6 +1763,14 @@ class PreparedRun:
                 "n_cell_b": arr(o.n_cell_b, (nc,)), "w_a": arr(o.w_a, (nc,)), "w_b": arr(o.w_b, (nc,)),
                 "mean_a": arr(o.mean_a, (nc,)), "mean_b": arr(o.mean_b, (nc,)),
                 "in_support": arr(o.in_support, (nc,)).astype(bool), "row_cell": arr(o.row_cell, (o.n_rows,))}
+
+    def density_info(self) -> dict:
+        """ob_prepared_density_info: the grid, the two bandwidths, the design columns and the groups' rows of a
+        density handle."""
+        o = N.ob_density_info()
+        N.check(N.lib().ob_prepared_density_info(self._h, C.byref(o)))
+        return {"grid": N.array_copy(o.grid, (o.grid_size,)), "bandwidth_a": float(o.bandwidth_a),
+                "bandwidth_b": float(o.bandwidth_b), "k": int(o.k), "n_a": int(o.n_a), "n_b": int(o.n_b)}
 
     def rifq_info(self) -> dict:
         """ob_prepared_rifq_info: the quantiles, each group's sort permutation, the point q and f (2, T: A then B)

@@ -28,6 +28,7 @@
 #include "ob_host.hpp"
 #include "ob_builder.hpp"
 #include "ob_cluster.hpp"
+#include "ob_density.hpp"
 #include "ob_mm.hpp"
 #include "ob_model.hpp"
 #include "ob_nopo.hpp"
@@ -640,6 +641,63 @@ int dr_finish_rows(const double* point, int T, int nq, const double* rows, const
   return OB_OK;
 }
 
+// finish() for rows of the density decomposition (ob_density.hpp's row, include/oaxaca_boot.h): the 6 G entries of
+// the curves through the same aggregate() as an OLS row's, then per curve the uniform band from the sup-t statistic
+// of the kept replicates.
+int density_finish_rows(const double* point, int k, int G, const double* rows, const uint8_t* ok, uint64_t n_reps,
+                        ob_results** out) {
+  const int rl = density_row_len(k, G);
+  uint64_t ng = 0;
+  for (uint64_t r = 0; r < n_reps; ++r) ng += ok[r] ? 1 : 0;
+  if (ng < n_reps)
+    fprintf(stderr,
+            "Warning: %llu out of %llu bootstrap replications failed and were discarded. The analysis is based on "
+            "%llu successful replications.\n",
+            (unsigned long long)(n_reps - ng), (unsigned long long)n_reps, (unsigned long long)ng);
+  ob_results* res = new ob_results();
+  res->n_failed = (int64_t)(n_reps - ng);
+  static const char* curves[6] = {"density_a", "density_b", "density_counterfactual", "total", "composition", "structure"};
+  std::vector<std::vector<int>> groups;
+  for (int e = 0; e < 6 * G; ++e) groups.push_back({e});
+  std::vector<double> st(4 * groups.size());
+  aggregate(rows, ok, n_reps, rl, groups, st.data());
+  std::vector<double> t;
+  for (int c = 0; c < 6; ++c) {
+    t.clear();
+    bool any_se = false;
+    for (int j = 0; j < G; ++j) any_se = any_se || st[4 * (size_t)(c * G + j)] > 0.0;
+    for (uint64_t r = 0; r < n_reps && any_se; ++r) {
+      if (!ok[r]) continue;
+      double m = 0.0;
+      for (int j = 0; j < G; ++j) {
+        const int e = c * G + j;
+        const double se = st[4 * (size_t)e];
+        if (se > 0.0) m = std::fmax(m, std::fabs(rows[(size_t)r * rl + e] - point[e]) / se);
+      }
+      t.push_back(m);
+    }
+    double crit = NAN;
+    if (!t.empty()) {
+      std::sort(t.begin(), t.end());
+      const size_t R = t.size();
+      crit = t[std::min(R - 1, (size_t)std::floor(0.95 * (double)R))];
+    }
+    for (int j = 0; j < G; ++j) {
+      const int e = c * G + j;
+      const double* s4 = st.data() + 4 * (size_t)e;
+      const double pt = point[e];
+      const std::string name = std::string(curves[c]) + "@" + std::to_string(j);
+      const double ts = std::fabs(s4[0]) > 1e-9 ? pt / s4[0] : 0.0;  // as finish()
+      res->tables[OB_DENSITY_TABLE_CURVES].push_back({name, pt, s4[0], ts, s4[1], s4[2], s4[3]});
+      const bool flat = !(s4[0] > 0.0);
+      res->tables[OB_DENSITY_TABLE_BANDS].push_back(
+          {name, pt, s4[0], crit, NAN, flat ? pt : pt - crit * s4[0], flat ? pt : pt + crit * s4[0]});
+    }
+  }
+  *out = res;
+  return OB_OK;
+}
+
 // ---- Nopo's matching decomposition: the host side (ob_nopo.hpp, include/oaxaca_boot.h) -----------
 
 int nopo_check_shape(int64_t n_cells, int64_t n_a, int64_t n_b) {
@@ -838,6 +896,13 @@ int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* 
   if (pr->model_kind == kModelReweight) return reweight_finish(pr, rows, ok, n_reps, out);
   if (pr->model_kind == kModelNopo) {
     OB_TRY(nopo_finish_rows(pr->point_row.data(), rows, ok, n_reps, out));
+    (*out)->n_a = pr->n_a;
+    (*out)->n_b = pr->n_b;
+    return OB_OK;
+  }
+  if (pr->model_kind == kModelDensity) {
+    const int G = (pr->row_len - pr->k - 2) / 6;
+    OB_TRY(density_finish_rows(pr->point_row.data(), pr->k, G, rows, ok, n_reps, out));
     (*out)->n_a = pr->n_a;
     (*out)->n_b = pr->n_b;
     return OB_OK;
@@ -1193,6 +1258,15 @@ int ob_dr_finish_rows(const double* point_row, int32_t n_thresholds, int32_t n_q
   if (n_thresholds < 2 || n_thresholds > OB_DR_MAX_T || n_q < 1 || n_q > OB_DR_MAX_Q)
     return ob::fail(OB_E_INVALID, "ob_dr_finish_rows: bad shape (T = %d, n_q = %d)", n_thresholds, n_q);
   return ob::dr_finish_rows(point_row, n_thresholds, n_q, rows, ok, n_reps, out);
+}
+
+int ob_density_finish_rows(const double* point_row, int32_t k, int32_t grid_size, const double* rows, const uint8_t* ok,
+                           uint64_t n_reps, ob_results** out) {
+  if (!point_row || !out || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (k < 1 || k > OB_REWEIGHT_MAX_K || grid_size < 2 || grid_size > OB_DENSITY_MAX_GRID)
+    return ob::fail(OB_E_INVALID, "ob_density_finish_rows: bad shape (k = %d, G = %d)", k, grid_size);
+  return ob::density_finish_rows(point_row, k, grid_size, rows, ok, n_reps, out);
 }
 
 int ob_nopo_row_len(void) { return ob::kNopoRowLen; }

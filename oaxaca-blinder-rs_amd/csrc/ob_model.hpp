@@ -1,7 +1,8 @@
 // ob_model.hpp -- what the model front ends on top of the engine's resampler share: the hooks
 // through which ob_builder.cpp routes a prepared handle, the segmented boot driver, the staging of a frame entry
 // point, the host side of the two refits, and the count images of the array entry points. The front ends are
-// ob_binary.hip, ob_reweight.hip, ob_dr.hip, ob_rifq.hip, ob_rifs.hip and ob_nopo.hip; ob_model.hip holds the rest.
+// ob_binary.hip, ob_reweight.hip, ob_dr.hip, ob_rifq.hip, ob_rifs.hip, ob_nopo.hip and ob_density.hip; ob_model.hip holds
+// the rest.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,8 @@
 
 namespace ob {
 
-enum ModelKind : int { kModelNone = 0, kModelBinary, kModelReweight, kModelDr, kModelRifq, kModelRifs, kModelNopo, kModelKinds };
+enum ModelKind : int { kModelNone = 0, kModelBinary, kModelReweight, kModelDr, kModelRifq, kModelRifs, kModelNopo, kModelDensity,
+                 kModelKinds };
 
 // ob_builder.cpp reaches a front end through these hooks only, so that it links without the front end's file,
 // which installs them when the library loads. state: the front end's own struct behind ob_prepared::model.
@@ -47,6 +49,7 @@ inline const ModelName& model_name(int kind) {
       {"quantile refit", "refitted quantile decompositions"},
       {"statistics refit", "refitted statistic decompositions"},
       {"matching decomposition", "matching decompositions"},
+      {"density decomposition", "density decompositions"},
   };
   return names[kind];
 }

@@ -55,7 +55,7 @@ constexpr int kRS = 65;      // doubles per staged column: a tile's 16 column re
 constexpr int kRReps = 16;   // replicates per block
 constexpr int kRMaxU = 9;    // column tiles per wave: 36 tiles at K = 32 (561 pairs of the extended Gram)
 constexpr int kRMaxK = ob::kReweightMaxK;
-constexpr uint32_t kRwDone = 1u, kRwFailed = 2u;
+constexpr uint32_t kRwDone = ob::kLogitDoneBit, kRwFailed = ob::kLogitFailedBit;
 constexpr int kModeLogit = 0, kModeGram = 1, kModeGramPsi = 2;
 
 struct RwArgs {
@@ -446,13 +446,12 @@ hipError_t launch_pass(const RwArgs& a, int mode, hipStream_t s) {
 thread_local ob_reweight_timing g_timing = {};
 constexpr int kRwMaxPasses = 100;
 
-// The stages over one batch (or the point pass): the Newton loop, each replicate stopping on its own, then per
-// statistic (once for the mean, n_stats = 0) the Grams and the rows. rows / ok: one destination per statistic
-// (NULL: a's own).
-int rw_batch(const RwArgs& a, hipStream_t s, int n_stats = 0, double* const* rows = nullptr,
-             uint8_t* const* ok = nullptr) {
+// The Newton loop of one batch (or of the point pass), every replicate stopping on its own: gamma from 0, one
+// logit pass and one step per round until no replicate is left iterating, at most kRwMaxPasses rounds. Shared with
+// ob_density.hip through ob::reweight_logit_batch.
+int rw_logit_loop(const RwArgs& a, hipStream_t s, ob::LogitTimes* t) {
   if (a.k < 1 || a.k > kRMaxK || a.n_reps < 1 || a.part_pad < a.n_reps) return ob::fail(OB_E_INVALID, "reweight batch: bad shape");
-  Events<5> ev;
+  Events<2> ev;
   OB_HIP(ev.create());
   OB_HIP(hipMemsetAsync(a.gamma, 0, sizeof(double) * (size_t)a.n_reps * a.k, s));
   OB_HIP(hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * a.n_reps, s));
@@ -471,11 +470,25 @@ int rw_batch(const RwArgs& a, hipStream_t s, int n_stats = 0, double* const* row
     OB_HIP(hipStreamSynchronize(s));
     float ms = 0.f;
     OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    g_timing.logit_ms += ms;
-    g_timing.logit_launches += 1;
+    t->ms += ms;
+    t->launches += 1;
     if (active == 0) break;
   }
-  g_timing.logit_passes = std::max(g_timing.logit_passes, (int32_t)it);
+  t->passes = std::max(t->passes, (int32_t)it);
+  return OB_OK;
+}
+
+// The stages over one batch (or the point pass): the Newton loop, then per statistic (once for the mean,
+// n_stats = 0) the Grams and the rows. rows / ok: one destination per statistic (NULL: a's own).
+int rw_batch(const RwArgs& a, hipStream_t s, int n_stats = 0, double* const* rows = nullptr,
+             uint8_t* const* ok = nullptr) {
+  ob::LogitTimes lt;
+  OB_TRY(rw_logit_loop(a, s, &lt));
+  g_timing.logit_ms += lt.ms;
+  g_timing.logit_launches += lt.launches;
+  g_timing.logit_passes = std::max(g_timing.logit_passes, lt.passes);
+  Events<5> ev;
+  OB_HIP(ev.create());
   for (int t = 0; t < std::max(n_stats, 1); ++t) {
     RwArgs b = a;
     if (n_stats > 0) {
@@ -528,6 +541,32 @@ int reweight_check_shape(int k, int64_t n_a, int64_t n_b) {
                   "%sreweighted decomposition: a group's rows (%lld) must exceed the design columns (%d)",
                   error_prefix(OB_E_INSUFFICIENT), (long long)n, k);
   return OB_OK;
+}
+
+size_t reweight_logit_vals(int k) { return (size_t)rw_nv(k, kModeLogit); }
+
+int reweight_logit_batch(const LogitBatch& b, hipStream_t s, LogitTimes* t) {
+  RwArgs h{};
+  for (int g = 0; g < 2; ++g) {
+    h.cols[g] = b.cols[g];
+    h.ld[g] = b.ld[g];
+    h.n[g] = b.n[g];
+  }
+  h.tiles0 = b.tiles0;
+  h.k = b.k;
+  h.counts = b.counts;
+  h.nb_rep = b.nb_rep;
+  h.chunks = b.chunks;
+  h.n_chunks = b.n_chunks;
+  h.n_reps = b.n_reps;
+  h.part_pad = b.part_pad;
+  h.gamma = b.gamma;
+  h.flags = b.flags;
+  h.passes = b.passes;
+  h.active = b.active;
+  h.partial = b.partial;
+  h.tol = 1e-6;
+  return rw_logit_loop(h, s, t);
 }
 
 // Device side of a prepared reweighted run. The handle's ob_panel (no predictors, the outcome alone) is the

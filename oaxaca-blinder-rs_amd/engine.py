@@ -770,6 +770,52 @@ def dr_last_timing() -> dict:
     return _last_timing("ob_dr_last_timing", N.ob_dr_timing)
 
 
+def density_pass(x, y, grid, bandwidth: float, gammas=None, w=None, counts=None, device: int | None = None):
+    """The density pass of ``decompose_density`` alone (``ob_density_pass``) over one group's rows. ``x``: (n, k) with
+    the intercept (all ones) as column 0, ``k <= 32``; ``y``: n outcomes; ``grid``: 2 to 256 finite points;
+    ``gammas``: (m, k) logit coefficients, ``m <= 64``, or ``None`` (psi = 1, m = 1); ``w``: n weights (``None``: 1);
+    ``counts``: n resample counts below 256 (``None``: every row once). With v = w psi, psi = p / (1 - p) of the
+    clamped sigmoid of x'gamma, returns ``(num, den, den2)``: (m, G) sums c v phi((g_j - y) / h), (m) sums c v and
+    (m) sums c v^2."""
+    xf, n, k = _design(x)
+    yv = _per_row(y, n, "y must have one entry per row of x")
+    wv = _per_row(w, n, "w must have one entry per row of x", optional=True)
+    g = None if gammas is None else _coefficient_rows(gammas, k, "gammas must be (m, k)")
+    gr = np.ascontiguousarray(grid, dtype=np.float64)
+    if gr.ndim != 1:
+        raise ValueError("grid must be a 1-D sequence")
+    m = 1 if g is None else len(g)
+    num, den, den2 = np.empty((m, len(gr))), np.empty(m), np.empty(m)
+    with_context(lambda ctx: N.lib().ob_density_pass(ctx, N.dp(xf), max(n, 1), N.dp(yv), N.dp(wv),
+                                                    N.u8p(_counts_u8(counts, n)), n, k, N.dp(g), m, N.dp(gr), len(gr),
+                                                    float(bandwidth), N.dp(num), N.dp(den), N.dp(den2)), device)
+    return num, den, den2
+
+
+def density_grid(y, grid_size: int = 100) -> np.ndarray:
+    """ob_density_grid (host only): the default grid, g_j = min + j (max - min) / grid_size (dfl.rs:164-172)."""
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    out = np.empty(max(int(grid_size) or 100, 0))
+    N.check(N.lib().ob_density_grid(N.dp(yv), len(yv), int(grid_size), N.dp(out)))
+    return out
+
+
+def density_check_shape(k: int, n_a: int, n_b: int, grid_size: int) -> None:
+    """ob_density_check_shape: raises OaxacaError where a density decomposition would (host only)."""
+    N.check(N.lib().ob_density_check_shape(int(k), int(n_a), int(n_b), int(grid_size)))
+
+
+def density_row_len(k: int, grid_size: int) -> int:
+    """ob_density_row_len: 6 G + k + 2 doubles per replicate of a density decomposition (0 outside the limits)."""
+    return int(N.lib().ob_density_row_len(int(k), int(grid_size)))
+
+
+def density_last_timing() -> dict:
+    """ob_density_last_timing: logit passes and HIP-event ms (logit passes, the density pass, the rows) of this
+    thread's last density boot."""
+    return _last_timing("ob_density_last_timing", N.ob_density_timing)
+
+
 def nopo_sums(y, cell, n_cells: int, w=None, counts=None, device: int | None = None):
     """The cell pass of the matching decomposition alone (``ob_nopo_sums``) over one group of rows in ascending
     order of ``cell`` (ids in [0, n_cells)). ``w``: weights or ``None`` for 1; ``counts``: (n_reps, n) resample
