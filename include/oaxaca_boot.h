@@ -1842,6 +1842,122 @@ int ob_builder_run_density(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, i
 /* The grid and bandwidths a handle was prepared with; the pointer lives as long as the handle. */
 int ob_prepared_density_info(const ob_prepared* prep, ob_density_info* out);
 
+/* ---- Bootstrapped Tobit decomposition of a censored outcome --------------------------------------
+ * Bauer and Sinning (2008, 2010), Stata's `nldecompose ..., tobit`: the decomposition of a gap in an outcome that is
+ * observed as y = max(lower, min(upper, y*)), y* = x'beta + sigma eps, eps ~ N(0, 1), with either limit optional
+ * (none: the Gaussian MLE). No counterpart in the reference crate. A is the non-reference group, B
+ * cfg->reference_group; x the design row with the intercept in column 0 (K <= OB_TOBIT_MAX_K columns); w the sample
+ * weight (1 without cfg->weights); c the replicate's OBRS-3 count of the row (1 in the point pass). A row is
+ * left-censored if y == lower, right-censored if y == upper, else uncensored.
+ *   Fit, per group and replicate, in Olsen's parameters eta = [delta; theta], delta = beta / sigma, theta = 1 / sigma,
+ *   by Newton's method on the concave log-likelihood. With v = [x; -y], u = theta y - x'delta and lambda = phi / Phi:
+ *     gradient = sum c w s v + (N_unc / theta) e_theta,   s = u | -lambda(u) | +lambda(-u)  (uncensored | left | right)
+ *     -Hessian = sum c w h v v' + (N_unc / theta^2) e_theta e_theta',   h = 1 | lambda(u) (lambda(u) + u) |
+ *     lambda(-u) (lambda(-u) - u);   N_unc = sum c w over the uncensored rows.
+ *   The step is the Cholesky solve of -Hessian; while theta + d theta <= 0 the whole step is halved, at most 30 times
+ *   (a step still outside, or not finite, fails the fit); the fit stops when the norm of the step taken is below 1e-6,
+ *   and fails when it has not after OB_TOBIT_MAX_PASSES passes. The point fit starts from the group's (weighted) least
+ *   squares on all rows: delta = beta_ols / s, theta = 1 / s, s^2 = sum w r^2 / sum w; every replicate starts from its
+ *   group's point fit. A fit whose resample holds an uncensored count sum (sum c) of at most K is dropped before its
+ *   first step: OB_TOBIT_FAILED with eta at its start and no pass counted.
+ *   lambda is evaluated without the quotient below z = -0.46875 sqrt 2: finite for every finite z.
+ *   The conditional mean m(xb, sigma) = lower Phi(z_a) + upper (1 - Phi(z_b)) + (Phi(z_b) - Phi(z_a)) xb
+ *   + sigma (phi(z_a) - phi(z_b)), z_a = (lower - xb) / sigma, z_b = (upper - xb) / sigma, the terms of an absent limit
+ *   dropped; M[g][h] = sum_g c w m(x'beta_h, sigma_h) / sum_g c w.
+ * Row of a replicate, ob_tobit_row_len(K) = 6 + 7K + 17 doubles (beta* = beta_A under OB_REF_GROUP_A, M[g][*] alike):
+ *     explained = M[A][*] - M[B][*], unexplained = total - explained, endowments = M[A][B] - M[B][B],
+ *     coefficients = M[B][A] - M[B][B], interaction = total - endowments - coefficients, total = M[A][A] - M[B][B]
+ *     | explained_j (K) | unexplained_j (K): Yun's terms as in the binary row, a part with a zero denominator 0.0
+ *     | beta_A, beta_B, xbar_A, xbar_B, beta* (K each)
+ *     | the latent terms (xbar_A - xbar_B)'beta*, xbar_A'(beta_A - beta*) + xbar_B'(beta* - beta_B), their sum
+ *     | M[A][A], M[A][B], M[B][A], M[B][B] | ybar_A, ybar_B | sigma_A, sigma_B
+ *     | the censored shares (of sum c w): left A, right A, left B, right B | the passes of A's and B's fit.
+ * A replicate one of whose fits failed, or one of whose groups has sum c w = 0, has ok = 0 and a NaN row, which
+ * ob_prepared_finish drops and counts. Every sum is f64, over a chunk's rows in row order and over the chunks in chunk
+ * order, without atomics: a replicate's row has the same bytes alone, in any batch and at any first_rep. Option
+ * "hk_batch" caps a batch at n 64-replicate blocks.
+ * Errors of the frame entry points, all before any device work and before the context is read: normalize, Heckman
+ * settings, reference coefficients other than OB_REF_GROUP_A / OB_REF_GROUP_B (sigma* has no agreed definition for
+ * them), K > OB_TOBIT_MAX_K: OB_E_UNSUPPORTED; a null or non-finite value in a named column, a negative weight, a
+ * non-finite limit, lower >= upper, an outcome below lower or above upper: OB_E_INVALID; a group whose uncensored rows
+ * are at most K: OB_E_INSUFFICIENT; a start or point fit that fails: OB_E_LINALG. The cluster bootstrap is not served.
+ * On a handle prepared here ob_prepared_boot, ob_prepared_boot_device, ob_prepared_finish, ob_prepared_point_row and
+ * ob_prepared_tobit_info work; ob_prepared_boot_sharded, ob_prepared_jackknife and ob_prepared_finish_bca are
+ * OB_E_UNSUPPORTED. Not built: the split of the unexplained part into a beta share and a sigma share.
+ * Results of ob_prepared_finish / ob_builder_run_tobit / ob_tobit_finish_rows: OB_TABLE_TWO_FOLD, OB_TABLE_THREE_FOLD,
+ * OB_TABLE_DETAILED_EXPLAINED and OB_TABLE_DETAILED_UNEXPLAINED as ob_builder_run fills them, and
+ * OB_TOBIT_TABLE_LATENT with explained, unexplained and total_gap of the latent outcome; ob_results_total_gap is the
+ * row's total. */
+#define OB_TOBIT_MAX_K 31
+#define OB_TOBIT_MAX_PASSES 100
+#define OB_TOBIT_MAX_ARRAY_REPS 1024
+#define OB_TOBIT_DONE 1u
+#define OB_TOBIT_FAILED 2u
+#define OB_TOBIT_TABLE_LATENT 3
+typedef struct {
+  double lower, upper;           /* read only where the flag beside it is set */
+  int32_t has_lower, has_upper;
+} ob_tobit_config; /* a NULL configuration is no limit */
+typedef struct {
+  int32_t passes;        /* the longest batch's Newton rounds */
+  int32_t pass_launches; /* pass kernels over all batches */
+  double pass_ms;        /* the pass kernels (the Newton steps not included) */
+  double means_ms;       /* the means pass */
+  double row_ms;         /* the rows */
+} ob_tobit_timing;
+typedef struct {
+  int32_t k, has_lower, has_upper, passes_a, passes_b;
+  double lower, upper;
+  int64_t n_a, n_b, n_left_a, n_right_a, n_left_b, n_right_b; /* rows, and rows at the limits */
+  const double* eta; /* [2][k + 1] the point fits of A and B (owned by the handle) */
+} ob_tobit_info;
+/* 6 + 7K + 17, or 0 for k < 1. */
+int ob_tobit_row_len(int32_t k);
+/* The shape limits above on their own (host only). k: design columns with the intercept; n_a, n_b: uncensored rows. */
+int ob_tobit_check_shape(int32_t k, int64_t n_a, int64_t n_b);
+/* HIP-event ms of the calling thread's last Tobit boot (or prepare: the point pass), ob_tobit_fit or ob_tobit_rows. */
+int ob_tobit_last_timing(ob_tobit_timing* out);
+/* Host only: out[i] = lambda(z[i]) by the branches the kernels take. */
+int ob_tobit_lambda(const double* z, int64_t n, double* out);
+/* One pass alone over one group of rows: x (n x k, column-major, ldx >= n, column 0 all ones), y (n, within the
+   limits), w (n weights or NULL for 1), counts (n bytes or NULL for every row once), etas [m][k + 1], 1 <= m <= 64,
+   theta > 0. info [m][k + 1][k + 1] = -Hessian and grad [m][k + 1] = the gradient above (the N_unc terms added on the
+   host), n_unc [m]; the chunk partials are added in chunk order. */
+int ob_tobit_pass(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, const double* w, const uint8_t* counts,
+                  int64_t n, int32_t k, const ob_tobit_config* tc, const double* etas, int32_t m, double* info,
+                  double* grad, double* n_unc);
+/* The fits alone over one group of rows: counts [n_reps][n] bytes (NULL: n_reps fits of every row once), 1 <= n_reps
+   <= OB_TOBIT_MAX_ARRAY_REPS, eta0 [k + 1] the start of every fit (NULL: the least-squares start above). eta
+   [n_reps][k + 1], flags [n_reps] (OB_TOBIT_DONE | OB_TOBIT_FAILED; a fit without OB_TOBIT_DONE did not converge),
+   passes [n_reps]. */
+int ob_tobit_fit(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, const double* w, int64_t n, int32_t k,
+                 const ob_tobit_config* tc, const uint8_t* counts, int32_t n_reps, const double* eta0, double* eta,
+                 uint32_t* flags, uint32_t* passes);
+/* The means pass alone over one group of rows and one replicate's counts (n bytes or NULL): etas [2][k + 1] the fits
+   whose parameters are applied. out [6 + k] = M under etas[0], M under etas[1], ybar, sum c w, the left and the right
+   censored share, xbar (k). */
+int ob_tobit_means(ob_ctx* ctx, const double* x, int64_t ldx, const double* y, const double* w, const uint8_t* counts,
+                   int64_t n, int32_t k, const ob_tobit_config* tc, const double* etas, double* out);
+/* Fits (from each group's least-squares start), means and rows over two groups of rows: counts_a [n_reps][n_a] and
+   counts_b [n_reps][n_b] bytes (both NULL: the point pass, n_reps = 1). rows [n_reps][ob_tobit_row_len(k)], ok
+   [n_reps]. */
+int ob_tobit_rows(ob_ctx* ctx, int32_t k, const ob_tobit_config* tc, int32_t reference_coeffs, const double* xa, int64_t ldxa,
+                  const double* ya, const double* wa, int64_t na, const uint8_t* counts_a, const double* xb, int64_t ldxb,
+                  const double* yb, const double* wb, int64_t nb, const uint8_t* counts_b, int32_t n_reps, double* rows,
+                  uint8_t* ok);
+/* Host only: the aggregation of ob_prepared_finish on rows of ob_tobit_row_len(k) doubles and their point row; the
+   detailed components are named "x0" .. "x<k-1>". */
+int ob_tobit_finish_rows(const double* point_row, int32_t k, const double* rows, const uint8_t* ok, uint64_t n_reps,
+                         ob_results** out);
+int ob_builder_prepare_tobit(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows,
+                             const ob_builder_config* cfg, const ob_tobit_config* tc, ob_prepared** out);
+/* prepare + cfg->bootstrap_reps replicates + finish. */
+int ob_builder_run_tobit(ob_ctx* ctx, const ob_column* cols, int32_t n_cols, int64_t n_rows, const ob_builder_config* cfg,
+                         const ob_tobit_config* tc, ob_results** out);
+/* The limits, the rows at them and the point fits a handle was prepared with. OB_E_INVALID on a handle of another
+   kind. */
+int ob_prepared_tobit_info(const ob_prepared* prep, ob_tobit_info* out);
+
 #ifdef __cplusplus
 }
 #endif

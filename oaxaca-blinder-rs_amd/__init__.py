@@ -12,7 +12,8 @@ from .api import (Adjustment, AkmBuilder, AkmResult, BinaryDecompositionResults,
                   QuantileDecompositionBuilder, QuantileDecompositionDetail, QuantileDecompositionResults,
                   ReferenceCoefficients, ReweightedDecompositionResults, TwoFoldResults, VifResult, calculate_vif, estimate_akm, match_units,
                   parse_formula, run_dfl, run_dfl_from_csv, NopoDecompositionResults, nopo_cells, nopo_finish_rows,
-                  DensityCurve, DensityDecompositionResults, density_finish_rows)
+                  DensityCurve, DensityDecompositionResults, density_finish_rows, TobitDecompositionResults,
+                  tobit_finish_rows)
 from .engine import (binary_check_shape, binary_last_timing, binary_means, binary_row_len, cluster_apply, cluster_check_shape, cluster_counts, cluster_gram, cluster_index,
                      cluster_last_timing, cluster_jackknife, cluster_jackknife_rows, cluster_jackknife_check_shape, cluster_jackknife_last_timing, Panel, aggregate, aggregate_bca, bca_stats, jackknife_check_shape, jackknife_finish,
                      jackknife_last_timing, jackknife_rows, akm_connected_set, akm_demean, akm_recover_fe, boot_multi, bootstrap_stats, kde,
@@ -26,6 +27,8 @@ from .engine import (binary_check_shape, binary_last_timing, binary_means, binar
                      rifs_check_shape, rifs_last_timing, rifs_pass, rifs_row_len,
                      nopo_check_shape, nopo_last_timing, nopo_row_len, nopo_sums,
                      density_check_shape, density_grid, density_last_timing, density_pass, density_row_len,
+                     tobit, tobit_check_shape, tobit_fit, tobit_lambda, tobit_last_timing, tobit_means, tobit_pass,
+                     tobit_row_len, tobit_rows,
                      row_layout, silverman_bandwidth, vif, vif_gram, vif_last_timing, vif_solve, vif_sums)
 from .frame import Frame, read_csv
 
@@ -58,4 +61,6 @@ __all__ = [
     "nopo_finish_rows",
     "DensityDecompositionResults", "DensityCurve", "density_pass", "density_grid", "density_check_shape",
     "density_row_len", "density_last_timing", "density_finish_rows",
+    "TobitDecompositionResults", "tobit", "tobit_pass", "tobit_fit", "tobit_means", "tobit_rows", "tobit_lambda",
+    "tobit_check_shape", "tobit_row_len", "tobit_last_timing", "tobit_finish_rows",
 ]

@@ -58,6 +58,9 @@ OB_DR_MAX_K, OB_DR_MAX_T, OB_DR_MAX_Q, OB_DR_MAX_VECTORS = 32, 64, 32, 128
 OB_DR_TABLE_QUANTILE_EFFECTS, OB_DR_TABLE_QUANTILES, OB_DR_TABLE_DISTRIBUTION_EFFECTS, OB_DR_TABLE_CDF = 0, 1, 2, 3
 OB_DENSITY_MAX_GRID, OB_DENSITY_MAX_VECTORS = 256, 64
 OB_DENSITY_TABLE_CURVES, OB_DENSITY_TABLE_BANDS = 0, 1
+OB_TOBIT_MAX_K, OB_TOBIT_MAX_PASSES, OB_TOBIT_MAX_ARRAY_REPS = 31, 100, 1024
+OB_TOBIT_DONE, OB_TOBIT_FAILED = 1, 2
+OB_TOBIT_TABLE_LATENT = 3
 
 
 class OaxacaError(RuntimeError):
@@ -292,6 +295,22 @@ class ob_density_info(C.Structure):
                 ("bandwidth_a", C.c_double), ("bandwidth_b", C.c_double), ("n_a", C.c_int64), ("n_b", C.c_int64)]
 
 
+class ob_tobit_config(C.Structure):
+    _fields_ = [("lower", C.c_double), ("upper", C.c_double), ("has_lower", C.c_int32), ("has_upper", C.c_int32)]
+
+
+class ob_tobit_timing(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("pass_launches", C.c_int32), ("pass_ms", C.c_double),
+                ("means_ms", C.c_double), ("row_ms", C.c_double)]
+
+
+class ob_tobit_info(C.Structure):
+    _fields_ = [("k", C.c_int32), ("has_lower", C.c_int32), ("has_upper", C.c_int32), ("passes_a", C.c_int32),
+                ("passes_b", C.c_int32), ("lower", C.c_double), ("upper", C.c_double), ("n_a", C.c_int64),
+                ("n_b", C.c_int64), ("n_left_a", C.c_int64), ("n_right_a", C.c_int64), ("n_left_b", C.c_int64),
+                ("n_right_b", C.c_int64), ("eta", C.POINTER(C.c_double))]
+
+
 class ob_component(C.Structure):
     _fields_ = [("name", C.c_char_p), ("estimate", C.c_double), ("std_err", C.c_double),
                 ("t_stat", C.c_double), ("p_value", C.c_double), ("ci_lower", C.c_double),
@@ -305,6 +324,7 @@ _H = C.POINTER(_P)  # a handle out parameter
 # the prefix of every entry point that takes a frame: ctx, cols, n_cols, n_rows (then the builder's config)
 _FRAME = [_P, C.POINTER(ob_column), C.c_int32, C.c_int64]
 _FRAME_CFG = _FRAME + [C.POINTER(ob_builder_config)]
+_TOBIT = C.POINTER(ob_tobit_config)
 _CLUSTER = C.POINTER(ob_cluster_config)
 _SPEC = C.POINTER(ob_rif_spec)
 _SIGS = {
@@ -560,6 +580,21 @@ _SIGS = {
     "ob_builder_prepare_density": (C.c_int, _FRAME_CFG + [C.POINTER(ob_density_config), _H]),
     "ob_builder_run_density": (C.c_int, _FRAME_CFG + [C.POINTER(ob_density_config), _H]),
     "ob_prepared_density_info": (C.c_int, [_P, C.POINTER(ob_density_info)]),
+    "ob_tobit_row_len": (C.c_int, [C.c_int32]),
+    "ob_tobit_check_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64]),
+    "ob_tobit_last_timing": (C.c_int, [C.POINTER(ob_tobit_timing)]),
+    "ob_tobit_lambda": (C.c_int, [_D, C.c_int64, _D]),
+    "ob_tobit_pass": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _TOBIT, _D, C.c_int32, _D, _D,
+                                _D]),
+    "ob_tobit_fit": (C.c_int, [_P, _D, C.c_int64, _D, _D, C.c_int64, C.c_int32, _TOBIT, _U8, C.c_int32, _D, _D,
+                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ob_tobit_means": (C.c_int, [_P, _D, C.c_int64, _D, _D, _U8, C.c_int64, C.c_int32, _TOBIT, _D, _D]),
+    "ob_tobit_rows": (C.c_int, [_P, C.c_int32, _TOBIT, C.c_int32, _D, C.c_int64, _D, _D, C.c_int64, _U8, _D, C.c_int64,
+                                _D, _D, C.c_int64, _U8, C.c_int32, _D, _U8]),
+    "ob_tobit_finish_rows": (C.c_int, [_D, C.c_int32, _D, _U8, C.c_uint64, C.POINTER(_P)]),
+    "ob_builder_prepare_tobit": (C.c_int, _FRAME_CFG + [_TOBIT, _H]),
+    "ob_builder_run_tobit": (C.c_int, _FRAME_CFG + [_TOBIT, _H]),
+    "ob_prepared_tobit_info": (C.c_int, [_P, C.POINTER(ob_tobit_info)]),
 }
 
 # Every exported entry point of include/oaxaca_boot.h (tests/test_capi_host.py checks both ways).

@@ -766,6 +766,91 @@ def nopo_cells(dataframe, outcome: str, group: str, reference_group: str, predic
     return b.categorical_predictors(categorical_predictors)._nopo_binned(bins)._nopo_cells()
 
 
+@dataclass
+class TobitDecompositionResults:
+    """``OaxacaBuilder.decompose_tobit``: the Tobit decomposition of a censored outcome (Bauer and Sinning 2008,
+    2010). The component objects are ``OaxacaResults``' (estimate, standard error, percentile interval, p-value over
+    the bootstrap, in which both censored-normal fits are redone per replicate). ``total_gap`` is the predicted gap
+    M[A][A] - M[B][B] in the conditional means of the observed (censored) outcome, ``raw_gap`` the gap in the groups'
+    observed means; ``expected_values`` maps (group, coefficients) to the four M; ``latent`` decomposes the gap in
+    the uncensored outcome x'beta (explained, unexplained, total_gap): what the gap would be without the limits.
+    ``censored_share`` maps (group, side) to the weighted share of rows at a limit."""
+    total_gap: float
+    raw_gap: float
+    two_fold: list
+    three_fold: list
+    latent: list
+    detailed_explained: list
+    detailed_unexplained: list
+    expected_values: dict
+    censored_share: dict
+    beta_a: np.ndarray = field(repr=False)
+    beta_b: np.ndarray = field(repr=False)
+    sigma_a: float = 0.0
+    sigma_b: float = 0.0
+    xa_mean: np.ndarray = field(repr=False, default=None)
+    xb_mean: np.ndarray = field(repr=False, default=None)
+    names: list = field(repr=False, default_factory=list)
+    lower: float | None = None
+    upper: float | None = None
+    passes: tuple = (0, 0)
+    n_a: int = 0
+    n_b: int = 0
+    n_failed: int = 0
+
+    def to_json(self) -> str:
+        def fix(v):  # serde_json writes non-finite floats as null
+            return v if v is None or isinstance(v, str) or np.isfinite(v) else None
+
+        def comps(cs):
+            return [{k: fix(v) for k, v in c.__dict__.items()} for c in cs]
+
+        return json.dumps({
+            "total_gap": fix(self.total_gap), "raw_gap": fix(self.raw_gap), "two_fold": comps(self.two_fold),
+            "three_fold": comps(self.three_fold), "latent": comps(self.latent),
+            "detailed_explained": comps(self.detailed_explained),
+            "detailed_unexplained": comps(self.detailed_unexplained),
+            "expected_values": {f"{g}|{b}": fix(v) for (g, b), v in self.expected_values.items()},
+            "censored_share": {f"{g}|{side}": fix(v) for (g, side), v in self.censored_share.items()},
+            "names": list(self.names), "beta_a": [fix(float(v)) for v in self.beta_a],
+            "beta_b": [fix(float(v)) for v in self.beta_b], "sigma_a": fix(self.sigma_a), "sigma_b": fix(self.sigma_b),
+            "lower": fix(self.lower), "upper": fix(self.upper), "passes": [int(v) for v in self.passes],
+            "n_a": self.n_a, "n_b": self.n_b, "n_failed": self.n_failed})
+
+
+def _tobit_results(res, point, lower=None, upper=None) -> TobitDecompositionResults:
+    """The results of a Tobit run from finish()'s tables (``res``: an ``OaxacaResults`` whose selection table holds
+    the latent terms) and the point row."""
+    k = (len(point) - 23) // 7
+    tail = point[6 + 2 * k:]
+    sc = tail[5 * k:]
+    keys = [(g, b) for g in ("A", "B") for b in ("beta_a", "beta_b")]
+    sides = [(g, side) for g in ("A", "B") for side in ("left", "right")]
+    return TobitDecompositionResults(
+        total_gap=float(point[5]), raw_gap=float(sc[7] - sc[8]), two_fold=res.two_fold.aggregate,
+        three_fold=res.three_fold.aggregate, latent=res.two_fold.detailed_selection,
+        detailed_explained=res.two_fold.detailed_explained, detailed_unexplained=res.two_fold.detailed_unexplained,
+        expected_values={key: float(v) for key, v in zip(keys, sc[3:7])},
+        censored_share={key: float(v) for key, v in zip(sides, sc[11:15])},
+        beta_a=tail[:k].copy(), beta_b=tail[k:2 * k].copy(), sigma_a=float(sc[9]), sigma_b=float(sc[10]),
+        xa_mean=tail[2 * k:3 * k].copy(), xb_mean=tail[3 * k:4 * k].copy(),
+        names=[c.name for c in res.two_fold.detailed_explained], lower=lower, upper=upper,
+        passes=(int(sc[15]), int(sc[16])), n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed)
+
+
+def tobit_finish_rows(point_row, k: int, rows, ok) -> TobitDecompositionResults:
+    """ob_tobit_finish_rows (host only): the aggregation of ``decompose_tobit`` on given replicate rows (each
+    ``tobit_row_len(k)`` doubles) and their point row; the detailed components are named x0 .. x<k-1>."""
+    point = np.ascontiguousarray(point_row, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    ok = np.ascontiguousarray(ok, dtype=np.uint8)
+    if point.shape != (6 + 7 * int(k) + 17,) or rows.shape != (len(ok), len(point)):
+        raise ValueError("point_row and rows must have 6 + 7 k + 17 entries per row")
+    h = C.c_void_p()
+    N.check(N.lib().ob_tobit_finish_rows(N.dp(point), int(k), N.dp(rows), N.u8p(ok), len(ok), C.byref(h)))
+    return _tobit_results(_results_from_c(h), point)
+
+
 def _jackknife_out(k: int):
     c = 6 + 2 * k
     bufs = (np.zeros(c), np.zeros((2, c, 3)), np.zeros((c, 3)))
@@ -1383,6 +1468,32 @@ class OaxacaBuilder:
             xa_mean=tail[2 * k:3 * k].copy(), xb_mean=tail[3 * k:4 * k].copy(), names=names,
             n_a=res.n_a, n_b=res.n_b, n_failed=res.n_failed)
 
+    def prepare_tobit(self, lower=None, upper=None) -> "PreparedRun":
+        """The handle of ``decompose_tobit`` (``ob_builder_prepare_tobit``): the limits are fixed and the point fits
+        have run; ``boot`` / ``boot_device`` / ``finish`` / ``point_row`` / ``tobit_info`` work on it."""
+        if self._cluster is not None:
+            raise N.OaxacaError(N.OB_E_UNSUPPORTED, "tobit decomposition: the cluster bootstrap is outside its scope")
+        from .engine import _tobit_config
+
+        tc = _tobit_config(lower, upper)
+        return self._prepared(self._call("ob_builder_prepare_tobit", C.byref(tc), policy=ARGUMENTS_FIRST, ctx=self._ctx))
+
+    def decompose_tobit(self, lower=None, upper=None) -> "TobitDecompositionResults":
+        """Extension (no counterpart in the reference crate): the decomposition of a gap in a censored outcome
+        (Bauer and Sinning 2008, 2010; Stata's ``nldecompose ..., tobit``) -- top-coded earnings, or a bonus that is
+        zero for many. The outcome is read as max(``lower``, min(``upper``, x'beta + sigma eps)); a row at a limit
+        is censored, either limit may be ``None``. A censored-normal fit per group and replicate on the GPU, the
+        conditional means of the censored outcome under own and other coefficients, two-fold and three-fold terms
+        from them, Yun's detailed terms and the decomposition of the latent gap, bootstrapped like ``run()``.
+        Sample weights are served. Reference coefficients GroupA or GroupB. Refused (``OB_E_UNSUPPORTED``):
+        Weighted, Cotton, Pooled and Neumark coefficients, ``normalize``, ``cluster``, Heckman settings, more than
+        31 design columns; ``boot_sharded``, the jackknife and BCa on its handle."""
+        with self.prepare_tobit(lower, upper) as pr:
+            rows, ok = pr.boot(0, self._bootstrap_reps)
+            res = pr.finish(rows, ok)
+            point = pr.point_row()
+        return _tobit_results(res, point, lower, upper)
+
     def prepare_reweighted(self, statistic=None, **params) -> "PreparedRun":
         """The handle of ``decompose_reweighted``. ``statistic`` (with its parameters, as
         ``parse_weighted_rif_statistic`` takes them) makes it the decomposition of that statistic; ``None`` is
@@ -1771,6 +1882,19 @@ class PreparedRun:
         N.check(N.lib().ob_prepared_density_info(self._h, C.byref(o)))
         return {"grid": N.array_copy(o.grid, (o.grid_size,)), "bandwidth_a": float(o.bandwidth_a),
                 "bandwidth_b": float(o.bandwidth_b), "k": int(o.k), "n_a": int(o.n_a), "n_b": int(o.n_b)}
+
+    def tobit_info(self) -> dict:
+        """ob_prepared_tobit_info: the limits (``None`` where absent), the groups' rows and rows at each limit and the
+        point fits of a Tobit handle: ``eta`` (2, k + 1: A then B, [delta; theta]), ``beta`` (2, k), ``sigma`` (2)."""
+        o = N.ob_tobit_info()
+        N.check(N.lib().ob_prepared_tobit_info(self._h, C.byref(o)))
+        eta = N.array_copy(o.eta, (2, o.k + 1))
+        return {"k": int(o.k), "lower": float(o.lower) if o.has_lower else None,
+                "upper": float(o.upper) if o.has_upper else None, "n_a": int(o.n_a), "n_b": int(o.n_b),
+                "n_censored": {("A", "left"): int(o.n_left_a), ("A", "right"): int(o.n_right_a),
+                               ("B", "left"): int(o.n_left_b), ("B", "right"): int(o.n_right_b)},
+                "eta": eta, "beta": eta[:, :-1] / eta[:, -1:], "sigma": 1.0 / eta[:, -1],
+                "passes": (int(o.passes_a), int(o.passes_b))}
 
     def rifq_info(self) -> dict:
         """ob_prepared_rifq_info: the quantiles, each group's sort permutation, the point q and f (2, T: A then B)

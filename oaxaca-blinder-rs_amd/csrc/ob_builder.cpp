@@ -34,6 +34,7 @@
 #include "ob_nopo.hpp"
 #include "ob_rif.hpp"
 #include "ob_spec.h"
+#include "ob_tobit.hpp"
 
 namespace ob {
 
@@ -891,6 +892,63 @@ int nopo_finish_rows(const double* point, const double* rows, const uint8_t* ok,
   return OB_OK;
 }
 
+// finish() for rows of the Tobit decomposition (ob_tobit.hpp's row, include/oaxaca_boot.h): the tables of an OLS row
+// (the detailed estimates merged by variable name, builder.rs:963-971) and the three latent terms, through the same
+// aggregate().
+int tobit_finish_rows(const double* point, int k, const char* const* names, const double* rows, const uint8_t* ok,
+                      uint64_t n_reps, ob_results** out) {
+  const int rl = tobit_row_len(k);
+  uint64_t ng = 0;
+  for (uint64_t r = 0; r < n_reps; ++r) ng += ok[r] ? 1 : 0;
+  if (ng < n_reps)
+    fprintf(stderr,
+            "Warning: %llu out of %llu bootstrap replications failed and were discarded. The analysis is based on "
+            "%llu successful replications.\n",
+            (unsigned long long)(n_reps - ng), (unsigned long long)n_reps, (unsigned long long)ng);
+  ob_results* res = new ob_results();
+  res->total_gap = point[OB_ROW_TOTAL_GAP];
+  res->n_failed = (int64_t)(n_reps - ng);
+  const double* tail = point + 6 + 2 * k;
+  res->xa_mean.assign(tail + 2 * k, tail + 3 * k);
+  res->xb_mean.assign(tail + 3 * k, tail + 4 * k);
+  res->beta_star.assign(tail + 4 * k, tail + 5 * k);
+  std::vector<std::string> nm((size_t)k);
+  for (int j = 0; j < k; ++j) nm[(size_t)j] = names ? names[j] : "x" + std::to_string(j);
+  std::vector<int> table, pcol;  // a component's table and the row entry of its estimate
+  std::vector<std::string> label;
+  std::vector<std::vector<int>> groups;
+  auto job = [&](int tb, const std::string& name, int at, std::vector<int> cols) {
+    table.push_back(tb);
+    pcol.push_back(at);
+    label.push_back(name);
+    groups.push_back(std::move(cols));
+  };
+  static const char* two[2] = {"explained", "unexplained"};
+  static const char* three[3] = {"endowments", "coefficients", "interaction"};
+  static const char* latent[3] = {"explained", "unexplained", "total_gap"};
+  for (int i = 0; i < 2; ++i) job(OB_TABLE_TWO_FOLD, two[i], i, {i});
+  for (int i = 0; i < 3; ++i) job(OB_TABLE_THREE_FOLD, three[i], 2 + i, {2 + i});
+  for (int t = 0; t < 2; ++t)
+    for (int i = 0; i < k; ++i) {
+      std::vector<int> cols;
+      for (int q = 0; q < k; ++q)
+        if (nm[(size_t)q] == nm[(size_t)i]) cols.push_back(6 + t * k + q);
+      job(t == 0 ? OB_TABLE_DETAILED_EXPLAINED : OB_TABLE_DETAILED_UNEXPLAINED, nm[(size_t)i], 6 + t * k + i,
+          std::move(cols));
+    }
+  for (int i = 0; i < 3; ++i) job(OB_TOBIT_TABLE_LATENT, latent[i], 6 + 7 * k + i, {6 + 7 * k + i});
+  std::vector<double> st(4 * groups.size());
+  aggregate(rows, ok, n_reps, rl, groups, st.data());
+  for (size_t ji = 0; ji < groups.size(); ++ji) {
+    const double* s4 = st.data() + 4 * ji;
+    const double pt = point[pcol[ji]];
+    const double t = std::fabs(s4[0]) > 1e-9 ? pt / s4[0] : 0.0;  // as finish()
+    res->tables[table[ji]].push_back({label[ji], pt, s4[0], t, s4[1], s4[2], s4[3]});
+  }
+  *out = res;
+  return OB_OK;
+}
+
 // builder.rs:841-950 over successful rows in replicate order, for outcome t (rows/ok: its block).
 int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* ok, uint64_t n_reps, ob_results** out) {
   if (pr->model_kind == kModelReweight) return reweight_finish(pr, rows, ok, n_reps, out);
@@ -903,6 +961,14 @@ int finish(const ob_prepared* pr, int t_out, const double* rows, const uint8_t* 
   if (pr->model_kind == kModelDensity) {
     const int G = (pr->row_len - pr->k - 2) / 6;
     OB_TRY(density_finish_rows(pr->point_row.data(), pr->k, G, rows, ok, n_reps, out));
+    (*out)->n_a = pr->n_a;
+    (*out)->n_b = pr->n_b;
+    return OB_OK;
+  }
+  if (pr->model_kind == kModelTobit) {
+    std::vector<const char*> names;
+    for (const std::string& n : pr->detail_names) names.push_back(n.c_str());
+    OB_TRY(tobit_finish_rows(pr->point_row.data(), pr->k, names.data(), rows, ok, n_reps, out));
     (*out)->n_a = pr->n_a;
     (*out)->n_b = pr->n_b;
     return OB_OK;
@@ -1267,6 +1333,14 @@ int ob_density_finish_rows(const double* point_row, int32_t k, int32_t grid_size
   if (k < 1 || k > OB_REWEIGHT_MAX_K || grid_size < 2 || grid_size > OB_DENSITY_MAX_GRID)
     return ob::fail(OB_E_INVALID, "ob_density_finish_rows: bad shape (k = %d, G = %d)", k, grid_size);
   return ob::density_finish_rows(point_row, k, grid_size, rows, ok, n_reps, out);
+}
+
+int ob_tobit_finish_rows(const double* point_row, int32_t k, const double* rows, const uint8_t* ok, uint64_t n_reps,
+                         ob_results** out) {
+  if (!point_row || !out || (n_reps && (!rows || !ok))) return ob::fail(OB_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (k < 1 || k > OB_TOBIT_MAX_K) return ob::fail(OB_E_INVALID, "ob_tobit_finish_rows: bad shape (k = %d)", k);
+  return ob::tobit_finish_rows(point_row, k, nullptr, rows, ok, n_reps, out);
 }
 
 int ob_nopo_row_len(void) { return ob::kNopoRowLen; }

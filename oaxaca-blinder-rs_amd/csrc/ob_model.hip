@@ -79,7 +79,7 @@ int Matrices::load(const ob_column* cols, int32_t n_cols, int64_t n_rows, const 
 }
 
 int stage_named(const ob_column* cols, int32_t n_cols, int64_t n_rows, const Config& c, int kind, bool weights,
-                bool finite) {
+                bool finite, bool weights_nonneg) {
   Frame f;
   OB_TRY(load_frame(cols, n_cols, n_rows, f));
   std::vector<std::string> named = {c.outcome, c.group};
@@ -97,6 +97,12 @@ int stage_named(const ob_column* cols, int32_t n_cols, int64_t n_rows, const Con
       if (finite && col.kind == OB_COL_F64 && !std::isfinite(col.f[r]))
         return fail(OB_E_INVALID, "%s: column `%s` has a non-finite value in row %lld", label, name.c_str(), (long long)r);
     }
+  }
+  if (weights && weights_nonneg && c.has_weights) {
+    const Col& wc = f.cols[f.find(c.weights)];
+    for (int64_t r = 0; r < f.nrows; ++r)
+      if ((wc.kind == OB_COL_F64 && wc.f[r] < 0.0) || (wc.kind == OB_COL_I64 && wc.i[r] < 0))
+        return fail(OB_E_INVALID, "%s: column `%s` has a negative weight in row %lld", label, c.weights.c_str(), (long long)r);
   }
   return OB_OK;
 }

@@ -1,7 +1,7 @@
 // ob_model.hpp -- what the model front ends on top of the engine's resampler share: the hooks
 // through which ob_builder.cpp routes a prepared handle, the segmented boot driver, the staging of a frame entry
 // point, the host side of the two refits, and the count images of the array entry points. The front ends are
-// ob_binary.hip, ob_reweight.hip, ob_dr.hip, ob_rifq.hip, ob_rifs.hip, ob_nopo.hip and ob_density.hip; ob_model.hip holds
+// ob_binary.hip, ob_reweight.hip, ob_dr.hip, ob_rifq.hip, ob_rifs.hip, ob_nopo.hip, ob_density.hip and ob_tobit.hip; ob_model.hip holds
 // the rest.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,7 +20,7 @@
 namespace ob {
 
 enum ModelKind : int { kModelNone = 0, kModelBinary, kModelReweight, kModelDr, kModelRifq, kModelRifs, kModelNopo, kModelDensity,
-                 kModelKinds };
+                 kModelTobit, kModelKinds };
 
 // ob_builder.cpp reaches a front end through these hooks only, so that it links without the front end's file,
 // which installs them when the library loads. state: the front end's own struct behind ob_prepared::model.
@@ -50,6 +50,7 @@ inline const ModelName& model_name(int kind) {
       {"statistics refit", "refitted statistic decompositions"},
       {"matching decomposition", "matching decompositions"},
       {"density decomposition", "density decompositions"},
+      {"tobit decomposition", "tobit decompositions"},
   };
   return names[kind];
 }
@@ -121,9 +122,10 @@ struct Matrices {
 };
 
 // The frame, then every named column (outcome, group, predictors, categoricals, the weights where `weights`): it
-// exists, holds no null and, where `finite`, no non-finite f64.
+// exists, holds no null and, where `finite`, no non-finite f64; where `weights_nonneg`, no negative weight either
+// (OB_E_INVALID here, before the design's own check of the weights answers OB_E_GROUP).
 int stage_named(const ob_column* cols, int32_t n_cols, int64_t n_rows, const Config& c, int kind, bool weights,
-                bool finite);
+                bool finite, bool weights_nonneg = false);
 
 // A handle of `kind` over m with the common fields set (the seed drawn where the configuration has none); it owns
 // `state` from here on.

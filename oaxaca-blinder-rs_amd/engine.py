@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .api import ReferenceCoefficients
+from .api import ReferenceCoefficients, tobit_finish_rows  # noqa: F401 (tobit_finish_rows is served from here too)
 
 
 def row_layout(k: int, n_base: int = 0) -> dict:
@@ -535,6 +535,128 @@ def binary_row_len(k: int) -> int:
 def binary_last_timing() -> dict:
     """ob_binary_last_timing: HIP-event ms of this thread's last binary boot (probit, means pass, rows)."""
     return _last_timing("ob_binary_last_timing", N.ob_binary_timing)
+
+
+def _tobit_config(lower, upper):
+    """ob_tobit_config of two optional limits."""
+    tc = N.ob_tobit_config()
+    tc.has_lower, tc.has_upper = int(lower is not None), int(upper is not None)
+    tc.lower, tc.upper = float(lower or 0.0), float(upper or 0.0)
+    return tc
+
+
+def _tobit_group(x, y, w):
+    """(x column-major, n, k, y, w) of one group for the Tobit array entry points."""
+    xf, n, k = _design(x)
+    what = "y (and w) must have one entry per row of x"
+    return xf, n, k, _per_row(y, n, what), _per_row(w, n, what, optional=True)
+
+
+def tobit_pass(x, y, etas, lower=None, upper=None, w=None, counts=None, device: int | None = None):
+    """One Newton pass of the Tobit fit alone (``ob_tobit_pass``) over one group. ``x``: (n, k) with the intercept
+    (all ones) as column 0, ``k <= 31``; ``y``: the censored outcome; ``etas``: (m, k + 1) parameter vectors
+    [delta; theta], m <= 64; ``counts``: n resample counts below 256 (``None``: every row once). Returns
+    (-Hessian (m, k + 1, k + 1), gradient (m, k + 1), N_unc (m,))."""
+    xf, n, k, y, w = _tobit_group(x, y, w)
+    e = np.ascontiguousarray(np.atleast_2d(np.asarray(etas, dtype=np.float64)))
+    if e.shape[1:] != (k + 1,):
+        raise ValueError("etas must be (m, k + 1)")
+    c8, tc, m = _counts_u8(counts, n), _tobit_config(lower, upper), len(e)
+    info, grad, nunc = np.empty((m, k + 1, k + 1)), np.empty((m, k + 1)), np.empty(m)
+    with_context(lambda ctx: N.lib().ob_tobit_pass(ctx, N.dp(xf), max(n, 1), N.dp(y), N.dp(w), N.u8p(c8), n, k,
+                                                   C.byref(tc), N.dp(e), m, N.dp(info), N.dp(grad), N.dp(nunc)), device)
+    return info, grad, nunc
+
+
+def tobit_fit(x, y, lower=None, upper=None, w=None, counts=None, n_reps: int = 1, eta0=None,
+              device: int | None = None):
+    """The Tobit fits alone (``ob_tobit_fit``) over one group: ``counts`` (n_reps, n) resample counts (``None``:
+    ``n_reps`` fits of every row once), ``eta0`` (k + 1) the start of every fit (``None``: the least-squares start).
+    Returns (eta (n_reps, k + 1), flags (n_reps) of ``OB_TOBIT_DONE | OB_TOBIT_FAILED``, passes (n_reps))."""
+    xf, n, k, y, w = _tobit_group(x, y, w)
+    c8 = _counts_u8(counts, n, by_rep=True)
+    reps = int(n_reps) if c8 is None else len(c8)
+    e0 = None if eta0 is None else np.ascontiguousarray(eta0, dtype=np.float64)
+    if e0 is not None and e0.shape != (k + 1,):
+        raise ValueError("eta0 must be (k + 1,)")
+    tc = _tobit_config(lower, upper)
+    eta = np.empty((max(reps, 0), k + 1))
+    flags, passes = np.zeros(max(reps, 0), dtype=np.uint32), np.zeros(max(reps, 0), dtype=np.uint32)
+    with_context(lambda ctx: N.lib().ob_tobit_fit(ctx, N.dp(xf), max(n, 1), N.dp(y), N.dp(w), n, k, C.byref(tc),
+                                                  N.u8p(c8), reps, N.dp(e0), N.dp(eta), N.u32p(flags),
+                                                  N.u32p(passes)), device)
+    return eta, flags, passes
+
+
+def tobit(x, y, lower=None, upper=None, w=None, device: int | None = None) -> dict:
+    """The censored-normal (Tobit) maximum-likelihood fit of ``y`` on ``x`` on the GPU: ``tobit_fit`` of every row
+    once from the least-squares start. Returns ``beta`` (k), ``sigma``, ``eta`` (k + 1), ``converged`` and
+    ``passes``."""
+    eta, flags, passes = tobit_fit(x, y, lower, upper, w, device=device)
+    e = eta[0]
+    return {"beta": e[:-1] / e[-1], "sigma": float(1.0 / e[-1]), "eta": e.copy(),
+            "converged": int(flags[0]) == N.OB_TOBIT_DONE, "passes": int(passes[0])}
+
+
+def tobit_means(x, y, etas, lower=None, upper=None, w=None, counts=None, device: int | None = None) -> dict:
+    """The conditional-mean pass of the Tobit decomposition alone (``ob_tobit_means``) over one group and one
+    replicate's ``counts``: ``etas`` (2, k + 1) the two fits whose parameters are applied. Returns ``means`` (2),
+    ``y_mean``, ``n`` (sum c w), ``censored_share`` (left, right) and ``x_mean`` (k)."""
+    xf, n, k, y, w = _tobit_group(x, y, w)
+    e = np.ascontiguousarray(etas, dtype=np.float64)
+    if e.shape != (2, k + 1):
+        raise ValueError("etas must be (2, k + 1)")
+    c8, tc = _counts_u8(counts, n), _tobit_config(lower, upper)
+    out = np.empty(6 + k)
+    with_context(lambda ctx: N.lib().ob_tobit_means(ctx, N.dp(xf), max(n, 1), N.dp(y), N.dp(w), N.u8p(c8), n, k,
+                                                    C.byref(tc), N.dp(e), N.dp(out)), device)
+    return {"means": out[:2].copy(), "y_mean": float(out[2]), "n": float(out[3]),
+            "censored_share": (float(out[4]), float(out[5])), "x_mean": out[6:].copy()}
+
+
+def tobit_rows(xa, ya, xb, yb, lower=None, upper=None, wa=None, wb=None, counts_a=None, counts_b=None,
+               reference_coefficients=ReferenceCoefficients.GroupA, device: int | None = None):
+    """Fits, means and rows of the Tobit decomposition over two groups of rows with given resample counts
+    (``ob_tobit_rows``): ``counts_a`` (n_reps, n_a) and ``counts_b`` (n_reps, n_b), or both ``None`` for the point
+    pass. Returns (rows (n_reps, tobit_row_len(k)), ok (n_reps))."""
+    xfa, na, k, ya, wa = _tobit_group(xa, ya, wa)
+    xfb, nb, kb, yb, wb = _tobit_group(xb, yb, wb)
+    if kb != k:
+        raise ValueError("xa and xb must have the same columns")
+    ca, cb = _counts_u8(counts_a, na, by_rep=True), _counts_u8(counts_b, nb, by_rep=True)
+    if (ca is None) != (cb is None) or (ca is not None and len(ca) != len(cb)):
+        raise ValueError("counts_a and counts_b must be given together, for the same replicates")
+    reps, tc = 1 if ca is None else len(ca), _tobit_config(lower, upper)
+    rows, ok = np.empty((reps, tobit_row_len(k))), np.zeros(reps, dtype=np.uint8)
+    with_context(lambda ctx: N.lib().ob_tobit_rows(
+        ctx, k, C.byref(tc), int(reference_coefficients), N.dp(xfa), max(na, 1), N.dp(ya), N.dp(wa), na, N.u8p(ca),
+        N.dp(xfb), max(nb, 1), N.dp(yb), N.dp(wb), nb, N.u8p(cb), reps, N.dp(rows), N.u8p(ok)), device)
+    return rows, ok
+
+
+def tobit_lambda(z) -> np.ndarray:
+    """ob_tobit_lambda (host only): the inverse Mills ratio phi(z) / Phi(z) by the branches the kernels take."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    out = np.empty_like(z)
+    N.check(N.lib().ob_tobit_lambda(N.dp(z.ravel()), z.size, N.dp(out.ravel())))
+    return out
+
+
+def tobit_check_shape(k: int, n_a: int, n_b: int) -> None:
+    """ob_tobit_check_shape: raises OaxacaError where a Tobit decomposition would (host only); ``n_a`` and ``n_b``
+    are the groups' uncensored rows."""
+    N.check(N.lib().ob_tobit_check_shape(int(k), int(n_a), int(n_b)))
+
+
+def tobit_row_len(k: int) -> int:
+    """ob_tobit_row_len: 6 + 7k + 17 doubles per replicate of a Tobit decomposition."""
+    return int(N.lib().ob_tobit_row_len(int(k)))
+
+
+def tobit_last_timing() -> dict:
+    """ob_tobit_last_timing: the Newton rounds and the HIP-event ms of the pass kernels, the means pass and the rows
+    of this thread's last Tobit boot (or prepare, ``tobit_fit`` or ``tobit_rows``)."""
+    return _last_timing("ob_tobit_last_timing", N.ob_tobit_timing)
 
 
 def _refit_pass_args(n: int, counts, x):
