@@ -32,6 +32,7 @@
 #include "ob_hip.hpp"
 #include "ob_model.hpp"
 #include "ob_options.hpp"
+#include "ob_pairpass.hpp"
 #include "ob_spec.h"
 
 namespace {
@@ -74,14 +75,6 @@ struct DrArgs {
 };
 
 __host__ __device__ inline int dr_nv(int k) { return k * (k + 1) / 2 + k; }
-
-// Row j of the packed lower triangle that holds entry e = j (j + 1) / 2 + i, i <= j.
-__device__ __forceinline__ int dr_tri_row(int e) {
-  int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-  while ((j + 1) * (j + 2) / 2 <= e) ++j;
-  while (j * (j + 1) / 2 > e) --j;
-  return j;
-}
 
 __device__ __forceinline__ double dr_sigmoid(double z) {
   double p = 1.0 / (1.0 + exp(-z));
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(kDB) void ob_dr_kernel(const DrArgs a) {
     if (c < nt0) {
       const int idx = 16 * c + e16;
       if (idx < NP) {
-        const int j = dr_tri_row(idx), i = idx - j * (j + 1) / 2;
+        const int j = tri_row(idx), i = idx - j * (j + 1) / 2;
         oa[u] = j == 0 ? ones : j * kDS;
         ob2[u] = i == 0 ? ones : i * kDS;
         dst[u] = idx;
@@ -237,22 +230,12 @@ __global__ __launch_bounds__(kDB) void ob_dr_kernel(const DrArgs a) {
 // fit that has converged keeps its beta and its pass count while the batch runs on.
 __global__ __launch_bounds__(64) void ob_dr_step_kernel(const DrArgs a) {
   __shared__ double m[kDMaxK * kDMaxK], step[kDMaxK];
-  const int lane = threadIdx.x, k = a.k, T = a.T, NH = k * (k + 1) / 2, NP = NH + k;
+  const int lane = threadIdx.x, k = a.k, T = a.T;
   const size_t fit = blockIdx.x;
   if (a.flags[fit] & kDrDone) return;
   const uint32_t t = (uint32_t)(fit % T), g = (uint32_t)((fit / T) & 1), rep = (uint32_t)(fit / (2 * (size_t)T));
-  for (int e = lane; e < NP; e += 64) {
-    double v = 0.0;
-    for (int c = 0; c < a.n_chunks; ++c)
-      if (a.chunks[3 * c] == g) v += a.partial[(((size_t)c * a.part_pad + rep) * T + t) * NP + e];
-    if (e < NH) {
-      const int j = dr_tri_row(e), i = e - j * (j + 1) / 2;
-      m[j + i * k] = v;
-      m[i + j * k] = v;
-    } else {
-      step[e - NH] = v;
-    }
-  }
+  gather_partials(a.partial, (size_t)a.part_pad * T, (size_t)rep * T + t, dr_nv(k), a.chunks, a.n_chunks, (int)g, k, lane, m,
+                  step);
   __syncthreads();
   const bool chol = wave_cholesky(m, k, lane);
   __syncthreads();
@@ -483,41 +466,34 @@ constexpr uint32_t kDrMaxBatch = 32768;  // replicates of a batch: the grid's z 
 int dr_batch(const DrArgs& a, hipStream_t s) {
   if (a.k < 1 || a.k > kDMaxK || a.T < 2 || a.T > kDMaxT || a.n_reps < 1 || a.part_pad < a.n_reps || a.n_reps > kDrMaxBatch)
     return ob::fail(OB_E_INVALID, "distribution regression batch: bad shape");
-  Events<5> ev;
+  Events<3> ev;
   OB_HIP(ev.create());
   const size_t fits = (size_t)a.n_reps * 2 * a.T;
   OB_HIP(hipMemsetAsync(a.beta, 0, sizeof(double) * fits * a.k, s));
   OB_HIP(hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * fits, s));
   OB_HIP(hipMemsetAsync(a.passes, 0, sizeof(uint32_t) * fits, s));
   int it = 0;
-  while (it < kDrMaxPasses) {
-    OB_HIP(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
-    OB_HIP(hipEventRecord(ev.e[0], s));
-    OB_HIP(launch_pass(a, s));
-    OB_HIP(hipEventRecord(ev.e[1], s));
-    hipLaunchKernelGGL(ob_dr_step_kernel, dim3((unsigned)fits), dim3(64), 0, s, a);
-    OB_HIP(hipGetLastError());
-    ++it;
-    uint32_t active = 0;
-    OB_HIP(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OB_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    g_timing.pass_ms += ms;
-    g_timing.launches += 1;
-    if (active == 0) break;
-  }
+  float ms = 0.f;
+  OB_TRY(newton_rounds(
+      a.active, kDrMaxPasses, s, [&] { return launch_pass(a, s); },
+      [&] {
+        hipLaunchKernelGGL(ob_dr_step_kernel, dim3((unsigned)fits), dim3(64), 0, s, a);
+        return hipGetLastError();
+      },
+      &it, &ms));
+  g_timing.pass_ms += ms;
+  g_timing.launches += it;
   g_timing.passes = std::max(g_timing.passes, (int32_t)it);
-  OB_HIP(hipEventRecord(ev.e[2], s));
+  OB_HIP(hipEventRecord(ev.e[0], s));
   OB_HIP(launch_cdf(a, s));
-  OB_HIP(hipEventRecord(ev.e[3], s));
+  OB_HIP(hipEventRecord(ev.e[1], s));
   hipLaunchKernelGGL(ob_dr_row_kernel, dim3(a.n_reps), dim3(64), 0, s, a);
   OB_HIP(hipGetLastError());
-  OB_HIP(hipEventRecord(ev.e[4], s));
-  OB_HIP(hipEventSynchronize(ev.e[4]));
+  OB_HIP(hipEventRecord(ev.e[2], s));
+  OB_HIP(hipEventSynchronize(ev.e[2]));
   float m0 = 0.f, m1 = 0.f;
-  OB_HIP(hipEventElapsedTime(&m0, ev.e[2], ev.e[3]));
-  OB_HIP(hipEventElapsedTime(&m1, ev.e[3], ev.e[4]));
+  OB_HIP(hipEventElapsedTime(&m0, ev.e[0], ev.e[1]));
+  OB_HIP(hipEventElapsedTime(&m1, ev.e[1], ev.e[2]));
   g_timing.cdf_ms += m0;
   g_timing.row_ms += m1;
   return OB_OK;

@@ -34,6 +34,7 @@
 #include "ob_normal.hpp"
 #include "ob_heckman.hpp"
 #include "ob_options.hpp"
+#include "ob_pairpass.hpp"
 #include "ob_spec.h"
 
 namespace {
@@ -590,14 +591,6 @@ inline size_t wide_lds(const ob_heck_seg& a, bool sums) {
   return sizeof(double) * ((size_t)(ncol + 1) * kWS + 2 * 64 * kWReps + (size_t)kWReps * (a.ks | 1) + (sums ? 512 : 0));
 }
 
-// Row j of the packed lower triangle that holds entry e = j (j + 1) / 2 + k, k <= j.
-__device__ __forceinline__ int tri_row(int e) {
-  int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-  while ((j + 1) * (j + 2) / 2 <= e) ++j;
-  while (j * (j + 1) / 2 > e) --j;
-  return j;
-}
-
 template <bool SUMS, bool CODY>
 __global__ __launch_bounds__(kHB) void ob_heck_wide_kernel(const ob_heck_seg a) {
   extern __shared__ __attribute__((aligned(16))) double wsm[];
@@ -846,27 +839,18 @@ __global__ __launch_bounds__(64) void ob_probit_wide_step_kernel(const ob_heck_s
   __shared__ double m[M * M], l[M * M], b[M], step[M], x[M];
   __shared__ int perm[M];
   __shared__ int solved;
-  const int lane = threadIdx.x, ks = a.ks, NH = ks * (ks + 1) / 2, NP = NH + ks;
+  const int lane = threadIdx.x, ks = a.ks;
   const uint32_t rep = blockIdx.x, g = blockIdx.y;
   const size_t st = (size_t)g * a.rep_pad + rep;
   if (a.hflags[st] & kDone) return;
-  for (int e = lane; e < NP; e += 64) {
-    double v = 0.0;
-    for (int c = 0; c < a.n_chunks; ++c)
-      if (a.chunks[3 * c] == g) v += a.partial[((size_t)c * a.part_pad + rep) * NP + e];
-    // -H = sum c w z z' + 1e-9 I (probit.rs:95-118), g = sum c lambda z
-    if (e < NH) {
-      const int j = tri_row(e), k = e - j * (j + 1) / 2;
-      if (j == k) v += 1e-9;
-      m[j + k * ks] = v;
-      m[k + j * ks] = v;
-      l[j + k * ks] = v;
-      l[k + j * ks] = v;
-    } else {
-      b[e - NH] = v;
-      step[e - NH] = v;
-    }
+  gather_partials(a.partial, a.part_pad, rep, ks * (ks + 1) / 2 + ks, a.chunks, a.n_chunks, (int)g, ks, lane, m, step);
+  __syncthreads();
+  // -H = sum c w z z' + 1e-9 I (probit.rs:95-118), g = sum c lambda z; Cholesky factors the copy l, the LU fallback takes m and b
+  for (int i = lane; i < ks * ks; i += 64) {
+    if (i % (ks + 1) == 0) m[i] += 1e-9;
+    l[i] = m[i];
   }
+  for (int i = lane; i < ks; i += 64) b[i] = step[i];
   __syncthreads();
   const bool chol = wave_cholesky(l, ks, lane);
   __syncthreads();

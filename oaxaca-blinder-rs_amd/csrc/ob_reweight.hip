@@ -43,6 +43,7 @@
 #include "ob_hip.hpp"
 #include "ob_model.hpp"
 #include "ob_options.hpp"
+#include "ob_pairpass.hpp"
 #include "ob_reweight.hpp"
 #include "ob_rif.hpp"
 #include "ob_spec.h"
@@ -89,14 +90,6 @@ struct RwArgs {
 __host__ __device__ inline int rw_nv(int k, int mode) {
   if (mode == kModeLogit) return k * (k + 1) / 2 + k;
   return (k + 1) * (k + 2) / 2 + (mode == kModeGramPsi ? 1 : 0);
-}
-
-// Row j of the packed lower triangle that holds entry e = j (j + 1) / 2 + i, i <= j.
-__device__ __forceinline__ int rw_tri_row(int e) {
-  int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-  while ((j + 1) * (j + 2) / 2 <= e) ++j;
-  while (j * (j + 1) / 2 > e) --j;
-  return j;
 }
 
 inline size_t rw_lds(int k) {
@@ -157,7 +150,7 @@ __global__ __launch_bounds__(kRB) void ob_rw_kernel(const RwArgs a) {
     if (c < nt0) {
       const int idx = 16 * c + e16;
       if (idx < NP) {
-        const int j = rw_tri_row(idx), i = idx - j * (j + 1) / 2;
+        const int j = tri_row(idx), i = idx - j * (j + 1) / 2;
         oa[u] = j == 0 ? ones : (j < k ? j * kRS : 0);
         ob2[u] = i == 0 ? ones : (i < k ? i * kRS : 0);
         dst[u] = idx;
@@ -286,20 +279,10 @@ __global__ __launch_bounds__(kRB) void ob_rw_psi_kernel(const double* X, int64_t
 // converged keeps its gamma and its pass count while the batch runs on.
 __global__ __launch_bounds__(64) void ob_rw_step_kernel(const RwArgs a) {
   __shared__ double m[kRMaxK * kRMaxK], step[kRMaxK];
-  const int lane = threadIdx.x, k = a.k, NH = k * (k + 1) / 2, NP = NH + k;
+  const int lane = threadIdx.x, k = a.k;
   const uint32_t rep = blockIdx.x;
   if (a.flags[rep] & kRwDone) return;
-  for (int e = lane; e < NP; e += 64) {
-    double v = 0.0;
-    for (int c = 0; c < a.n_chunks; ++c) v += a.partial[((size_t)c * a.part_pad + rep) * NP + e];
-    if (e < NH) {
-      const int j = rw_tri_row(e), i = e - j * (j + 1) / 2;
-      m[j + i * k] = v;
-      m[i + j * k] = v;
-    } else {
-      step[e - NH] = v;
-    }
-  }
+  gather_partials(a.partial, a.part_pad, rep, rw_nv(k, kModeLogit), a.chunks, a.n_chunks, -1, k, lane, m, step);
   __syncthreads();
   const bool chol = wave_cholesky(m, k, lane);
   __syncthreads();
@@ -361,7 +344,7 @@ __global__ __launch_bounds__(64) void ob_rw_row_kernel(const RwArgs a) {
     for (int f = 0; f < 3 && !failed; ++f) {
       const double* Gf = G[f];
       for (int e = lane; e < k * (k + 1) / 2; e += 64) {
-        const int j = rw_tri_row(e), i = e - j * (j + 1) / 2;
+        const int j = tri_row(e), i = e - j * (j + 1) / 2;
         m[j + i * k] = Gf[e];
         m[i + j * k] = Gf[e];
       }
@@ -451,29 +434,20 @@ constexpr int kRwMaxPasses = 100;
 // ob_density.hip through ob::reweight_logit_batch.
 int rw_logit_loop(const RwArgs& a, hipStream_t s, ob::LogitTimes* t) {
   if (a.k < 1 || a.k > kRMaxK || a.n_reps < 1 || a.part_pad < a.n_reps) return ob::fail(OB_E_INVALID, "reweight batch: bad shape");
-  Events<2> ev;
-  OB_HIP(ev.create());
   OB_HIP(hipMemsetAsync(a.gamma, 0, sizeof(double) * (size_t)a.n_reps * a.k, s));
   OB_HIP(hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * a.n_reps, s));
   OB_HIP(hipMemsetAsync(a.passes, 0, sizeof(uint32_t) * a.n_reps, s));
   int it = 0;
-  while (it < kRwMaxPasses) {
-    OB_HIP(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
-    OB_HIP(hipEventRecord(ev.e[0], s));
-    OB_HIP(launch_pass(a, kModeLogit, s));
-    OB_HIP(hipEventRecord(ev.e[1], s));
-    hipLaunchKernelGGL(ob_rw_step_kernel, dim3(a.n_reps), dim3(64), 0, s, a);
-    OB_HIP(hipGetLastError());
-    ++it;
-    uint32_t active = 0;
-    OB_HIP(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OB_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    t->ms += ms;
-    t->launches += 1;
-    if (active == 0) break;
-  }
+  float ms = 0.f;
+  OB_TRY(newton_rounds(
+      a.active, kRwMaxPasses, s, [&] { return launch_pass(a, kModeLogit, s); },
+      [&] {
+        hipLaunchKernelGGL(ob_rw_step_kernel, dim3(a.n_reps), dim3(64), 0, s, a);
+        return hipGetLastError();
+      },
+      &it, &ms));
+  t->ms += ms;
+  t->launches += it;
   t->passes = std::max(t->passes, (int32_t)it);
   return OB_OK;
 }

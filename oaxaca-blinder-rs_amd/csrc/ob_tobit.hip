@@ -35,6 +35,7 @@
 #include "ob_model.hpp"
 #include "ob_normal.hpp"
 #include "ob_options.hpp"
+#include "ob_pairpass.hpp"
 #include "ob_spec.h"
 #include "ob_tobit.hpp"
 
@@ -82,13 +83,6 @@ __host__ __device__ inline int tb_nv(int k) { return (k + 1) * (k + 2) / 2 + (k 
 // Of the means pass: sum c w m under A's and B's parameters, sum c w y, sum c w, the left and right censored
 // sum c w, sum c w x_j for 1 <= j < k.
 __host__ __device__ inline int tb_mv(int k) { return 5 + k; }
-
-__device__ __forceinline__ int tb_tri_row(int e) {
-  int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-  while ((j + 1) * (j + 2) / 2 <= e) ++j;
-  while (j * (j + 1) / 2 > e) --j;
-  return j;
-}
 
 __device__ __forceinline__ double tb_lambda(double z) {
   return ob::tobit_lambda_with(z, [](double v) { return nd_rcp(v); });
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(kTB, 2) void ob_tobit_kernel(const TbArgs a) {
     if (c < nt0) {
       const int idx = 16 * c + e16;
       if (idx < NP) {
-        const int j = tb_tri_row(idx), i = idx - j * (j + 1) / 2;
+        const int j = tri_row(idx), i = idx - j * (j + 1) / 2;
         o0 = vcol(j);
         o1 = vcol(i);
       }
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(kTB, 2) void ob_tobit_kernel(const TbArgs a) {
     if (c < nt0) {
       const int idx = 16 * c + e16;
       if (idx < NP) {
-        const int j = tb_tri_row(idx), i = idx - j * (j + 1) / 2;
+        const int j = tri_row(idx), i = idx - j * (j + 1) / 2;
         dst = idx;
         neg = (j == k) != (i == k);
       }
@@ -300,22 +294,11 @@ __global__ __launch_bounds__(64) void ob_tobit_init_kernel(const TbArgs a, const
 // has converged keeps its eta and its pass count while the batch runs on.
 __global__ __launch_bounds__(64) void ob_tobit_step_kernel(const TbArgs a) {
   __shared__ double m[kTMaxD * kTMaxD], step[kTMaxD + 2];
-  const int lane = threadIdx.x, k = a.k, D = k + 1, NH = D * (D + 1) / 2, NP = NH + D + 2;
+  const int lane = threadIdx.x, k = a.k, D = k + 1;
   const uint32_t rep = blockIdx.x, g = blockIdx.y;
   const size_t fit = (size_t)g * a.part_pad + rep;
   if (a.flags[fit] & kTbDone) return;
-  for (int e = lane; e < NP; e += 64) {
-    double v = 0.0;
-    for (int c = 0; c < a.n_chunks; ++c)
-      if (a.chunks[3 * c] == g) v += a.partial[((size_t)c * a.part_pad + rep) * NP + e];
-    if (e < NH) {
-      const int j = tb_tri_row(e), i = e - j * (j + 1) / 2;
-      m[j + i * D] = v;
-      m[i + j * D] = v;
-    } else {
-      step[e - NH] = v;
-    }
-  }
+  gather_partials(a.partial, a.part_pad, rep, tb_nv(k), a.chunks, a.n_chunks, (int)g, D, lane, m, step);
   __syncthreads();
   const double nunc = step[D], cunc = step[D + 1];
   if (!(cunc > (double)k)) {
@@ -630,28 +613,19 @@ bool tb_args_ok(const TbArgs& a) {
 // round (the count of fits still iterating).
 int tb_fit_loop(const TbArgs& a, const double* start, int n_groups, hipStream_t s) {
   if (!tb_args_ok(a)) return ob::fail(OB_E_INVALID, "tobit batch: bad shape");
-  Events<2> ev;
-  OB_HIP(ev.create());
   hipLaunchKernelGGL(ob_tobit_init_kernel, dim3((a.n_reps + 63) / 64), dim3(64), 0, s, a, start, n_groups);
   OB_HIP(hipGetLastError());
   int it = 0;
-  while (it < kTbMaxPasses) {
-    OB_HIP(hipMemsetAsync(a.active, 0, sizeof(uint32_t), s));
-    OB_HIP(hipEventRecord(ev.e[0], s));
-    OB_HIP(launch_pass(a, s));
-    OB_HIP(hipEventRecord(ev.e[1], s));
-    hipLaunchKernelGGL(ob_tobit_step_kernel, dim3(a.n_reps, n_groups), dim3(64), 0, s, a);
-    OB_HIP(hipGetLastError());
-    ++it;
-    uint32_t active = 0;
-    OB_HIP(hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OB_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    OB_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    g_timing.pass_ms += ms;
-    g_timing.pass_launches += 1;
-    if (active == 0) break;
-  }
+  float ms = 0.f;
+  OB_TRY(newton_rounds(
+      a.active, kTbMaxPasses, s, [&] { return launch_pass(a, s); },
+      [&] {
+        hipLaunchKernelGGL(ob_tobit_step_kernel, dim3(a.n_reps, n_groups), dim3(64), 0, s, a);
+        return hipGetLastError();
+      },
+      &it, &ms));
+  g_timing.pass_ms += ms;
+  g_timing.pass_launches += it;
   g_timing.passes = std::max(g_timing.passes, (int32_t)it);
   return OB_OK;
 }

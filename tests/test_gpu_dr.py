@@ -381,3 +381,33 @@ def test_older_paths_keep_their_bytes(ob, N):
     after = rows()
     assert before[0] == after[0]
     assert before[1] == after[1]
+
+
+@pytest.mark.parametrize("n", [65, 257])
+@pytest.mark.parametrize("k", [1, 5, 6, 11, 31, 32])
+def test_pass_edges_match_numpy(ob, k, n):
+    """The pass kernel's edges under the tolerance of test_pieces_match_numpy: one pair tile with
+    three idle waves (k = 1), 15 and 21 pairs either side of the first tile boundary, a wave's second pair tile
+    (k = 11), 496 and 528 pairs without a padding lane and all 9 tiles of a wave (k = 32); a one-row last sub-tile
+    (n = 65) and a one-row second tile (n = 257); 17 thresholds: a partly filled block of 16."""
+    rng = np.random.default_rng(1000 * n + k)
+    T = 17
+    x = np.column_stack([np.ones(n), rng.normal(size=(n, k - 1))])
+    y = rng.normal(size=n)
+    w = rng.uniform(0.5, 2.0, n)
+    c = rng.integers(0, 4, n).astype(np.uint8)
+    cw = c * w
+    thr = np.linspace(np.quantile(y, 0.1), np.quantile(y, 0.9), T)
+    betas = rng.normal(size=(T, k)) * 0.4 / np.sqrt(k)
+    L = np.longdouble
+    info, grad = ob.dr_logit_pass(x, y, thr, betas, w=w, counts=c)
+    i64, g64 = D.logit_pass(x, y, cw, thr, betas)
+    iL, gL = D.logit_pass(x, y, cw, thr, betas, dtype=L)
+    E = dev = 0.0
+    for t in range(T):
+        gscale = np.maximum(np.sqrt(np.abs(np.diag(iL[t])) * np.sum(cw)), np.abs(gL[t]))
+        E = max(E, rel_err(i64[t].astype(L), iL[t]), float(np.max(np.abs(g64[t] - gL[t]) / gscale)))
+        dev = max(dev, rel_err(info[t].astype(L), iL[t]), float(np.max(np.abs(grad[t] - gL[t]) / gscale)))
+        assert np.array_equal(info[t], info[t].T)
+    print(f"k={k} n={n}: E {E:.2e} dev {dev:.2e}")
+    assert E > 0.0 and dev <= 8 * E

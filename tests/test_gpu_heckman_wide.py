@@ -185,6 +185,10 @@ def test_wide_limits(ob, N):
 # oracle.probit converges on each in fewer than 100 iterations (6, 6, 7, 9 and 7; run on the CPU),
 # so neither (63, 3) nor (257, 12) separates and no shape had to move.
 PROBIT_SHAPES = [(63, 3), (1000, 8), (1000, 9), (257, 12), (3001, 32)]
+# the edges of the wide pass kernel: a one-row last sub-tile at the first wide width,
+# a one-row second tile where a wave owns two pair tiles (66 pairs), and 496 pairs without a padding lane; 10, 7 and
+# 7 iterations of oracle.probit (run on the CPU)
+PROBIT_SHAPES += [(65, 9), (257, 11), (2049, 31)]
 
 
 def probit_xy(n, k):

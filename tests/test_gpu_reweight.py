@@ -288,3 +288,46 @@ def test_refusals_on_a_reweighted_handle(ob, N):
         assert e.value.code == N.OB_E_UNSUPPORTED
     finally:
         pr.close()
+
+
+def edge_inputs(n, k):
+    """n stacked rows of k columns (intercept first), 0/1 group flags, weights, counts below 4 with zeros, and 17
+    coefficient vectors of fitted size: a partly filled block of 16."""
+    rng = np.random.default_rng(1000 * n + k)
+    x = np.column_stack([np.ones(n), rng.normal(size=(n, k - 1))])
+    y = rng.normal(size=n)
+    d = (rng.random(n) < 0.5).astype(float)
+    d[:2] = [0.0, 1.0]
+    w = rng.uniform(0.5, 2.0, n)
+    c = rng.integers(0, 4, n).astype(np.uint8)
+    gammas = rng.normal(size=(17, k)) * 0.4 / np.sqrt(k)
+    return x, y, d, w, c, gammas
+
+
+@pytest.mark.parametrize("n", [65, 257])
+@pytest.mark.parametrize("k", [1, 5, 6, 11, 31, 32])
+def test_pass_edges_match_numpy(ob, k, n):
+    """The pass kernel's edges under the tolerance of test_pieces_match_numpy: one pair tile with
+    three idle waves (k = 1), 15 and 21 pairs either side of the first tile boundary, a wave's second pair tile
+    (k = 11), 496 and 528 pairs without a padding lane and all 9 tiles of a wave (k = 32: 561 pairs of the extended
+    Gram); a one-row last sub-tile (n = 65) and a one-row second tile (n = 257); 17 replicates."""
+    x, y, d, w, c, gammas = edge_inputs(n, k)
+    L = np.longdouble
+    cf = c.astype(float)
+    cw = cf * w
+    info, grad = ob.reweight_logit_pass(x, d, gammas, w=w, counts=c)
+    b = d == 0
+    gram, den = ob.reweight_gram(x[b], y[b], gammas, w=w[b], counts=c[b])
+    for i, g in enumerate(gammas):
+        i64, g64 = R.logit_pass(x, d, cw, g)
+        iL, gL = R.logit_pass(x, d, cw, g, dtype=L)
+        gscale = np.maximum(np.sqrt(np.abs(np.diag(iL)) * np.sum(cw)), np.abs(gL))
+        m64, s64 = R.psi_gram(x[b], y[b], cw[b], w[b], cf[b], g)
+        mL, sL = R.psi_gram(x[b], y[b], cw[b], w[b], cf[b], g, dtype=L)
+        E = max(rel_err(i64.astype(L), iL), float(np.max(np.abs(g64 - gL) / gscale)), rel_err(m64.astype(L), mL),
+                float(abs(s64 - sL) / sL))
+        dev = max(rel_err(info[i].astype(L), iL), float(np.max(np.abs(grad[i] - gL) / gscale)),
+                  rel_err(gram[i].astype(L), mL), float(abs(den[i] - sL) / sL))
+        print(f"k={k} n={n} gamma#{i}: E {E:.2e} dev {dev:.2e}")
+        assert E > 0.0 and dev <= 8 * E
+        assert np.array_equal(info[i], info[i].T) and np.array_equal(gram[i], gram[i].T)

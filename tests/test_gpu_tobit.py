@@ -253,3 +253,30 @@ def test_decompose_tobit_end_to_end(ob, O, N):
     assert back["expected_values"]["A|beta_a"] == res.expected_values[("A", "beta_a")]
     t = ob.tobit_last_timing()
     assert 1 <= t["passes"] <= N.OB_TOBIT_MAX_PASSES and t["pass_launches"] >= 1
+
+
+@pytest.mark.parametrize("n", [65, 257])
+@pytest.mark.parametrize("k", [1, 5, 6, 11, 30, 31])
+def test_pass_edges_match_numpy(ob, O, k, n):
+    """The pass's edges at dimension D = k + 1 under the bound of test_pass_and_means_match_numpy: three pairs in one
+    tile (k = 1), 21 and 28 pairs either side of a tile boundary, a wave's second pair tile (k = 11), 496 and 528
+    pairs without a padding lane and all 9 tiles of a wave (k = 31); a one-row last sub-tile (n = 65) and a one-row
+    second tile (n = 257); 17 parameter vectors: a partly filled block of 16."""
+    rng = np.random.default_rng(1000 * n + k)
+    x = np.column_stack([np.ones(n), rng.normal(size=(n, k - 1))])
+    ystar = 0.5 + x[:, 1:] @ (0.5 / np.sqrt(max(k - 1, 1)) * np.ones(k - 1)) + rng.normal(size=n)
+    lower, upper = 0.0, float(np.round(np.quantile(ystar, 0.9), 2))
+    y = np.clip(ystar, lower, upper)
+    w = rng.uniform(0.5, 2.0, n)
+    c = rng.integers(0, 4, n).astype(np.uint8)
+    start = R.ols_start(x, y, w)
+    etas = start[None, :] * rng.uniform(0.8, 1.25, size=(17, k + 1))
+    info, grad, nunc = ob.tobit_pass(x, y, etas, lower, upper, w=w, counts=c)
+    for i, eta in enumerate(etas):
+        want_info, want_grad, want_nunc = R.tobit_pass(O, x, y, c * w, eta, lower, upper)
+        _, sc, _ = R.score_weights(O, x, y, eta, lower, upper)
+        terms = np.abs(np.column_stack([x, -y]) * (c * w * sc)[:, None]).sum(0).max() + want_nunc / eta[k]
+        e_info, e_grad = rel_err(info[i], want_info), float(np.max(np.abs(grad[i] - want_grad)) / terms)
+        print(f"k={k} n={n} eta#{i}: info {e_info:.2e} grad {e_grad:.2e}")
+        assert e_info <= 1e-11 and e_grad <= 1e-11 and abs(nunc[i] - want_nunc) <= 1e-11 * want_nunc
+        assert np.array_equal(info[i], info[i].T)
