@@ -1,13 +1,16 @@
-"""The segment loop of the boot driver the five model front ends share (csrc/ob_model.hip): a boot of
-one segment and three replicates against its two halves and against a short boot, byte for byte, per front end; and the
-refusals that the builder answers for a handle of each kind through one dispatch.
+"""The segment loop of the boot driver the eight model front ends share (csrc/ob_model.hip): a boot of
+one segment and three replicates against its two halves and against a short boot, byte for byte, for seven of them
+(the density decomposition's boundary test lives in test_gpu_density.py); and the refusals that the builder answers
+for a handle of each kind through one dispatch.
 
 FIT_SEG and REFIT_SEG are the front ends' segment lengths, the `seg_reps` of its boot plan in csrc/ob_model.hpp: kRefitSegReps = 2048 for
-the two refits, kFitSegReps = 4096 for binary, reweight and dr. On these frames (groups of 130 and 257 rows, three
+the two refits, kFitSegReps = 4096 for binary, reweight, dr, tobit and nopo. On these frames (groups of 130 and 257 rows, three
 tiles) the count-image budget allows far more, so seg_reps is the segment. Frames and K = 3 are those of the front
 ends' own determinism tests; the refits run three outputs, so that the [T][n_total] stride of the row blocks is
-crossed at s0 > 0; reweight and dr also run with hk_batch = 1 (batches of 64), so that a batch ends inside the second
-segment's three replicates."""
+crossed at s0 > 0; reweight, dr, tobit and nopo also run with hk_batch = 1 (batches of 64), so that a batch ends inside
+the second segment's three replicates. The second segment is where a Tobit boot writes rows at s0 + b0 and reads
+counts drawn at first_rep + s0; nopo draws its own counts (its plan's `draws` is false), so there the segment callback
+itself calls engine_counts(first_rep + s0)."""
 import os
 import sys
 
@@ -15,14 +18,22 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import nopo_ref as NR  # noqa: E402
 import rifq_ref as RQ  # noqa: E402
 import test_gpu_binary as TB  # noqa: E402
 import test_gpu_dr as TD  # noqa: E402
 import test_gpu_reweight as TW  # noqa: E402
 import test_gpu_rifq_decompose as TQ  # noqa: E402
 import test_gpu_rifs_decompose as TS  # noqa: E402
+import test_gpu_tobit as TT  # noqa: E402
 
 pytestmark = pytest.mark.gpu
+
+
+def _tobit(ob):
+    b, lower, upper = TT.builder(ob, 3, True, TT.R.GROUP_A)
+    return b.prepare_tobit(lower, upper)
+
 
 FIT_SEG, REFIT_SEG = 4096, 2048  # kFitSegReps, kRefitSegReps (csrc/ob_model.hpp)
 
@@ -32,8 +43,10 @@ HANDLES = {
     "dr": (FIT_SEG, lambda ob: TD.builder(ob, 3, True).prepare_distribution(TD.TAUS, n_thresholds=5, lo=0.1, hi=0.9)),
     "rifq": (REFIT_SEG, lambda ob: TQ.builder(ob, 3, "Weighted").prepare_quantiles_refit(RQ.TAUS)),
     "rifs": (REFIT_SEG, lambda ob: TS.builder(ob, 3, "Pooled").prepare_statistics_refit(TS.THREE)),
+    "tobit": (FIT_SEG, _tobit),
+    "nopo": (FIT_SEG, lambda ob: NR.panel("main", True).builder(ob).prepare_nopo()),
 }
-CASES = [(name, 0) for name in HANDLES] + [("reweight", 1), ("dr", 1)]
+CASES = [(name, 0) for name in HANDLES] + [("reweight", 1), ("dr", 1), ("tobit", 1), ("nopo", 1)]
 
 
 @pytest.mark.parametrize("name,hk_batch", CASES)
@@ -70,6 +83,8 @@ SHARDED = {
     "dr": "distribution regression: sharded runs are outside its scope",
     "rifq": "quantile refit: sharded runs are outside its scope",
     "rifs": "statistics refit: sharded runs are outside its scope",
+    "tobit": "tobit decomposition: sharded runs are outside its scope",
+    "nopo": "matching decomposition: sharded runs are outside its scope",
 }
 JACKKNIFE = {
     "binary": "jackknife: binary decompositions (BCa included) are outside its scope",
@@ -77,6 +92,8 @@ JACKKNIFE = {
     "dr": "jackknife: distribution-regression decompositions (BCa included) are outside its scope",
     "rifq": "jackknife: refitted quantile decompositions (BCa included) are outside its scope",
     "rifs": "jackknife: refitted statistic decompositions (BCa included) are outside its scope",
+    "tobit": "jackknife: tobit decompositions (BCa included) are outside its scope",
+    "nopo": "jackknife: matching decompositions (BCa included) are outside its scope",
 }
 
 

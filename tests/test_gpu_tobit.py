@@ -111,6 +111,8 @@ def test_pass_and_means_match_numpy(ob, O, k, weighted):
 
 CASES = [(k, w, ref, "both") for k in (3, 9) for w in (False, True) for ref in (R.GROUP_A, R.GROUP_B)]
 CASES += [(3, False, R.GROUP_A, "lower"), (3, True, R.GROUP_B, "none")]
+# D = 17, 18 and 32, the size of the step kernel's arrays; at K = 31 a row is 240 doubles
+CASES += [(16, True, R.GROUP_A, "both"), (17, False, R.GROUP_B, "both"), (31, True, R.GROUP_A, "both"), (31, False, R.GROUP_B, "lower")]
 
 
 @pytest.mark.parametrize("k,weighted,ref,limits", CASES)

@@ -10,6 +10,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import tobit_ref as R  # noqa: E402
+import test_gpu_tobit as TG  # noqa: E402
+import test_gpu_tobit_fit as TF  # noqa: E402
 from test_gpu_parity import RTOL, SEED, close  # noqa: E402
 
 REPS = 64 + 3
@@ -83,23 +85,95 @@ def test_lambda_is_stable(ob, O):
     assert (np.abs(ob.tobit_lambda(z) - R.lam(O, z)) <= (8.0 + 2.0 * z * z) * np.finfo(float).eps * R.lam(O, z)).all()
 
 
-@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
-@pytest.mark.parametrize("k", [3, 9])
+# the panels of test_gpu_tobit.py's test_rows_match_ref, each with the limit configurations it runs under
+PANELS = sorted({(k, w) for k, w, _, _ in TG.CASES})
+
+
+@pytest.mark.parametrize("k,weighted", PANELS, ids=[f"{k}-{'weighted' if w else 'unweighted'}" for k, w in PANELS])
 def test_gpu_panels_drop_nothing(O, k, weighted):
     """The panels of test_gpu_tobit.py: about a quarter of each group at the lower limit and a tenth at the upper,
     every replicate kept and every fit converged, under both references' shared fits."""
-    xa, ya, xb, yb, wa, wb, lower, upper = R.panel(k, weighted)
-    for y in (ya, yb):
-        assert 0.12 <= np.mean(y == lower) <= 0.40 and 0.03 <= np.mean(y == upper) <= 0.20
-    point, etas, norms = R.decompose(O, xa, ya, xb, yb, wa, wb, None, None, R.GROUP_A, lower, upper)
-    assert point is not None and max(len(v) for v in norms) <= 25
-    rows, ok, all_norms = R.boot(O, xa, ya, xb, yb, wa, wb, SEED, 0, REPS, etas, R.GROUP_A, lower, upper)
-    assert ok.all() and np.isfinite(rows).all()
-    assert max(len(v) for pair in all_norms for v in pair) <= 25
-    expl, unex, endow, coef, inter, total = point[:6]
-    eps = 64 * np.finfo(float).eps * max(1.0, abs(total))
-    assert abs(expl + unex - total) <= eps and abs(endow + coef + inter - total) <= eps
-    assert abs(point[6:6 + k].sum() - expl) <= 4 * k * eps and abs(point[6 + k:6 + 2 * k].sum() - unex) <= 4 * k * eps
+    for limits in sorted({lim for kk, w, _, lim in TG.CASES if (kk, w) == (k, weighted)}):
+        xa, ya, xb, yb, wa, wb, lower, upper = TG.panel(k, weighted, limits)
+        for y in (ya, yb):
+            assert lower is None or 0.12 <= np.mean(y == lower) <= 0.40
+            assert upper is None or 0.03 <= np.mean(y == upper) <= 0.20
+        point, etas, norms = R.decompose(O, xa, ya, xb, yb, wa, wb, None, None, R.GROUP_A, lower, upper)
+        assert point is not None and max(len(v) for v in norms) <= 25
+        rows, ok, all_norms = R.boot(O, xa, ya, xb, yb, wa, wb, SEED, 0, REPS, etas, R.GROUP_A, lower, upper)
+        assert ok.all() and np.isfinite(rows).all()
+        assert max(len(v) for pair in all_norms for v in pair) <= 25
+        expl, unex, endow, coef, inter, total = point[:6]
+        eps = 64 * np.finfo(float).eps * max(1.0, abs(total))
+        assert abs(expl + unex - total) <= eps and abs(endow + coef + inter - total) <= eps
+        assert abs(point[6:6 + k].sum() - expl) <= 4 * k * eps and abs(point[6 + k:6 + 2 * k].sum() - unex) <= 4 * k * eps
+
+
+@pytest.mark.parametrize("g", TF.GROUPS, ids=["A", "B"])
+@pytest.mark.parametrize("k", TF.DIM_KS)
+def test_fit_cases_leave_the_pass_count_decided(O, k, g):
+    """What test_gpu_tobit_fit.py's comparison at every dimension rests on: every fit of the restatement converges,
+    and at least three quarters of a case's fits take no step within a factor 10 of the stopping threshold, so that
+    their pass counts are compared exactly. The replicate ids are distinct and ascending."""
+    _, counts, point, fits, ids = TF.dim_case(O, k, g)
+    assert point[2] and all(f[2] for f in fits) and max(f[1] for f in [point] + fits) <= 25
+    assert TF.margin_share(point, fits) >= TF.MARGIN_SHARE
+    assert len(ids) == TF.REPS == len(counts) and (np.diff(ids) > 0).all()
+    assert np.array_equal(counts[-1], R.counts(O, SEED, ids[-1], g, counts.shape[1]))
+
+
+@pytest.mark.parametrize("g", TF.GROUPS, ids=["A", "B"])
+@pytest.mark.parametrize("k", TF.GUARD_KS)
+def test_guard_cases_halve(O, k, g):
+    """From theta x 20 the restatement halves two or three steps and still converges, in 10 to 14 passes; the trace
+    has one entry per pass and does not change what fit returns without it."""
+    (x, y, w, lower, upper), eta0, (eta, passes, ok, norms, halved) = TF.guard_case(O, k, g)
+    assert ok and 2 <= sum(halved) <= 3 and 10 <= passes <= 14 and len(halved) == passes == len(norms)
+    plain = R.fit(O, x, y, w, np.ones(len(y)), eta0, lower, upper)
+    assert len(plain) == 4 and np.array_equal(plain[0], eta) and plain[1:] == (passes, ok, norms)
+    if (k, g) == (1, R.GROUP_A):
+        assert (sum(halved), passes) == (2, 11)
+
+
+def test_chol_case_fails_in_its_first_pass(O):
+    """test_gpu_tobit_fit.py's failed factor: 34 counted uncensored rows (more than K), column 2 zero on every counted
+    row, so the restatement's first Cholesky has an exact zero pivot: one pass, not ok, eta at its start. The same
+    holds for the draws of the batch case that lose their even rows; its unit-count replicates converge."""
+    x, y, lower, upper, c, eta0 = TF.chol_case()
+    assert np.sum(c[R.classes(y, lower, upper) == 0]) == 34 > x.shape[1] and not x[c > 0, 2].any()
+    info = R.tobit_pass(O, x, y, c.astype(float), eta0, lower, upper)[0]
+    assert not info[2].any() and R.chol_solve(info, np.ones(4)) is None
+    eta, passes, ok, norms = R.fit(O, x, y, c.astype(float), c, eta0, lower, upper)
+    assert (passes, ok, norms) == (1, False, []) and np.array_equal(eta, eta0)
+    counts = TF.batch_counts(O)
+    got = [R.fit(O, x, y, cr.astype(float), cr, eta0, lower, upper)[1:3] for cr in counts[[0, 1, 62, 63, 64, 65, 66]]]
+    assert got[1][1] and got[1][0] >= 2 and got[4] == (0, False)
+    assert [got[i] for i in (0, 2, 3, 5, 6)] == [(1, False)] * 5
+    assert all(np.array_equal(counts[r], counts[1]) for r in range(1, 62))
+
+
+@pytest.mark.parametrize("k", [1, 17, 31])
+def test_score_hp_sees_a_wrong_eta(O, k):
+    """The relative score in mpmath at the restatement's fit (group B, weighted) is that of a maximiser found in
+    f64, below 1e-12; with its first entry moved by a relative 1e-6 it is above 1e-8: four orders over the bar
+    test_gpu_tobit_fit.py sets for the device's eta."""
+    pytest.importorskip("mpmath")
+    (x, y, w, lower, upper), _, point, _, _ = TF.dim_case(O, k, R.GROUP_B)
+    at_fit = R.score_hp(x, y, w, point[0], lower, upper)
+    moved = point[0].copy()
+    moved[0] *= 1.0 + 1e-6
+    off = R.score_hp(x, y, w, moved, lower, upper)
+    print(f"k={k}: score_hp {at_fit:.2e} at the fit, {off:.2e} beside it")
+    assert at_fit < 1e-12 and off > 1e-8
+
+
+def test_ols_cases_have_steps_to_take(O):
+    """Without censoring the restatement takes several passes from the shifted start and ends at weighted least
+    squares in long double to a few ulp."""
+    for k in TF.OLS_KS:
+        for g in TF.GROUPS:
+            _, _, ref, (beta, sigma) = TF.ols_case(O, k, g)
+            assert ref[2] and ref[1] >= 3 and TF.ols_err(ref[0], beta, sigma) <= 1e-14
 
 
 def test_row_len_and_shape(ob, N):
