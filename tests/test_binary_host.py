@@ -49,6 +49,90 @@ def test_ref_weighted_is_cotton_and_between(O):
     assert np.allclose(bs, wa * ba + (1 - wa) * bb, rtol=1e-15)
 
 
+SEED, REPS = 0x0B5EED, 64 + 3  # test_gpu_binary.py's: the properties below are those of the rows it compares
+
+
+def test_panel_defaults_are_unchanged():
+    """panel()'s new arguments leave the panels of the earlier tests as they were (first values recorded before)."""
+    xa, ya, xb, yb = R.panel(3)
+    assert xa.shape == (130, 3) and xb.shape == (257, 3)
+    assert (ya.sum(), yb.sum()) == (80.0, 126.0)
+    assert np.array_equal(R.panel(3)[0], R.panel(3, slope=1.0, x_scale=1.0, c0_shift=(0.0, 0.0), planted=())[0])
+    with pytest.raises(AssertionError):
+        R.panel(32, 1000, 2049)  # the mild band fails there (0.706), so K = 32 stays at 600 / 1025
+
+
+@pytest.mark.parametrize("k", [1, 2, 8, 16, 17, 32])
+def test_width_panels_converge_everywhere(O, k):
+    """The sizes of R.SIZES: the point fit and all 134 resampled probits converge and no replicate is dropped."""
+    point, conv, rows, ok, cv = R.case_rows(O, k, R.WEIGHTED, SEED, REPS)
+    assert conv and ok.all() and cv.all() and np.isfinite(rows).all() and np.isfinite(point).all()
+
+
+def test_k16_at_the_small_size_runs_out_of_iterations(O):
+    point, conv, rows, ok, cv = R.case_rows(O, "k16_small", R.WEIGHTED, SEED, REPS)
+    assert conv and ok.all() and np.isfinite(rows).all()
+    assert tuple(np.flatnonzero(cv == 0)) == R.K16_SMALL_UNCONVERGED
+
+
+def _clamped_in_both(O, p, row, rep=None):
+    k = p[0].shape[1]
+    tail = row[6 + 2 * k:]
+    n = []
+    for g, (x, beta) in enumerate(((p[0], tail[:k]), (p[2], tail[k:2 * k]))):
+        n.append(R.clamped_rows(x, beta, None if rep is None else R.counts(O, SEED, rep, g, len(x))))
+    return min(n)
+
+
+def test_steep_panel_reaches_the_clamp(O):
+    """From the restatement's fitted coefficients: rows beyond |z| = 6.3613 in both groups at the point fit and in at
+    least half of the replicates; every probit converges."""
+    p = R.steep_panel()
+    point, conv, rows, ok, cv = R.case_rows(O, "steep", R.WEIGHTED, SEED, REPS)
+    assert conv and ok.all() and cv.all()
+    assert _clamped_in_both(O, p, point) >= 1
+    assert sum(_clamped_in_both(O, p, rows[r], r) >= 1 for r in range(REPS)) >= (REPS + 1) // 2
+
+
+def test_outlier_panel_rows_sit_beyond_the_clamp(O):
+    """The planted rows lie beyond the clamp at the converged point fit of each group. Not every replicate converges
+    (binary_ref.outlier_panel): exactly the listed ones run out of iterations, and none is dropped."""
+    xa, ya, xb, yb = p = R.outlier_panel()
+    for x, y in ((xa, ya), (xb, yb)):
+        assert [tuple(r) for r in x[-2:, 1:]] == [(-40.0, 0.0), (40.0, 0.0)] and not y[-2:].any()
+    point, conv, rows, ok, cv = R.case_rows(O, "outliers", R.WEIGHTED, SEED, REPS)
+    assert conv and ok.all() and np.isfinite(rows).all()
+    tail = point[6 + 2 * 3:]
+    for x, beta in ((xa, tail[:3]), (xb, tail[3:6])):
+        assert np.all(np.abs(x[-2:] @ beta) > R.CLAMP_Z)
+    assert tuple(np.flatnonzero(cv == 0)) == R.OUTLIER_UNCONVERGED
+
+
+def test_lopsided_panel_bands_and_convergence(O):
+    xa, ya, xb, yb = R.lopsided_panel()
+    assert (len(ya), len(yb)) == R.LOPSIDED_SIZES
+    assert 0.02 <= ya.mean() <= 0.06 and 0.94 <= yb.mean() <= 0.98
+    point, conv, rows, ok, cv = R.case_rows(O, "lopsided", R.WEIGHTED, SEED, REPS)
+    assert conv and ok.all() and cv.all()
+
+
+def test_means_hp_agrees_with_the_restatement(O):
+    """The mpmath reference of the means pass against oracle._ncdf at mild indices (both are exact to rounding)."""
+    xa, ya, _, _ = R.panel(3)
+    betas = np.array([[0.1, 0.4, -0.3], [0.0, 0.2, 0.2], [-0.2, 0.1, 0.5]])
+    w = R.counts(O, SEED, 5, 0, len(ya))
+    got = R.means_hp(R.phi_hp(xa, betas), w)
+    want = np.array([np.sum(w * O._ncdf(xa @ b)) / w.sum() for b in betas])
+    assert np.all(np.abs(got - want) <= 1e-15)
+    # the erfc-in-fsum stand-in for very long designs, at indices out to +-40: a few ulp of the mpmath value
+    steep = betas * 60.0
+    hp, fs = R.phi_hp(xa, steep), R.phi_fsum(xa, steep)
+    assert max(abs(float(h) - f) for a, b in zip(hp, fs) for h, f in zip(a, b)) <= 1e-15
+    # relative, in the far tail: the products' rounding, 3 * 2^-53 |z|, times |z| = 40 is 5e-13
+    assert all(abs(float(h) - f) <= 1e-12 * float(h) for a, b in zip(hp, fs) for h, f in zip(a, b) if float(h) > 1e-300)
+    assert np.all(np.abs(R.means_hp(hp, w) - R.means_fsum(fs, w)) <= 1e-15)
+
+
 def test_row_len_and_shape(ob, N):
     for k in (1, 3, 9, 32):
         assert ob.binary_row_len(k) == 6 + 7 * k + 8 == R.row_len(k)
