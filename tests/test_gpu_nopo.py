@@ -9,7 +9,14 @@ its replicates have an empty support (ok = 0).
 
 Tolerance (derived): every quantity is a ratio or difference of ordered f64 sums of at most n terms, and both sides
 carry that error: |got - want| <= 16 n_max 2^-53 max|y| (Panel.tol). The matched shares and the support-cell count
-are compared with ==: the panels' weights are multiples of 1/8, so every N is exact in f64 in any order."""
+are compared with ==: the panels' weights are multiples of 1/8, so every N is exact in f64 in any order.
+
+Beside the restatement, which adds the same f64 terms in the same order and so shares the device's error, stands an
+exact reference (nopo_ref.sums_exact, terms_exact, long_sums): test_cell_pass_long_chunks (chunks of two tiles),
+test_cell_pass_counts_and_batches (every count byte in every lane, three batches, unused cell ids) and
+test_rows_match_exact (zero weights, an offset of 2^20 with weights k / 7, a cell per row, groups of exactly 1, 64,
+256 and 512 rows). Their bounds are the device's alone: per cell (m + f) 2^-53 times the absolute sum for the cell
+pass (nopo_ref.sum_bounds), Panel.tol for the rows. test_nopo_host.py proves each panel's property without a GPU."""
 import ctypes as C
 import os
 import sys
@@ -62,6 +69,138 @@ def test_cell_pass_alone(ob, O, weighted):
     assert t["cell_ms"] > 0.0 and t["row_ms"] >= 0.0
 
 
+def stack(pairs):
+    """[(N, S) per replicate] -> [N [reps][cells], S [reps][cells]]."""
+    return [np.stack(v) for v in zip(*pairs)]
+
+
+def check_sums(gr, got, want, want_abs, what):
+    """N and S of ob.nopo_sums ([reps][cells]) against the exact sums, per cell within nopo_ref.sum_bounds; want_abs:
+    the exact sums with |y| for y. Prints the worst deviation and the bound of that cell."""
+    bounds = R.sum_bounds(gr.cell, gr.n_cells, gr.chunks, *want_abs)
+    line = []
+    for i in (0, 1):
+        assert got[i].shape == want[i].shape == bounds[i].shape, what
+        dev = np.abs(got[i] - want[i])
+        r, x = np.unravel_index(np.argmax(dev), dev.shape)
+        line.append(f"{'NS'[i]} {dev[r, x]:.3e} (bound there {bounds[i][r, x]:.3e})")
+        bad = np.argwhere(dev > bounds[i])
+        assert len(bad) == 0, (what, "NS"[i], bad[:4], dev[tuple(bad[0])], bounds[i][tuple(bad[0])])
+    print(f"{what}: largest deviation {', '.join(line)}")
+
+
+def test_cell_pass_long_chunks(ob):
+    """One group of 33,025 rows: 130 tiles in 128 chunks, so chunks 63 and 127 hold two tiles and the kernel steps
+    from a chunk's first tile to its second with the next image prefetched across the step. Against math.fsum of
+    exact products (test_nopo_host.py::test_long_group_premise); bound per cell (nopo_ref.sum_bounds)."""
+    gr = R.long_group()
+    T = R.TILE
+    # restated from group_chunks (t0 = tiles * c // nc), before any device call
+    tiles = (gr.n + T - 1) // T
+    chunks = [(tiles * c // 128, tiles * (c + 1) // 128) for c in range(128)]
+    assert tiles == 130 and chunks == gr.chunks
+    two = [(t0, t1) for t0, t1 in chunks if t1 - t0 == 2]
+    assert two == [(63, 65), (128, 130)]  # at least one chunk holds two tiles
+    b0, b1 = (two[0][0] + 1) * T, (two[1][0] + 1) * T  # the tile boundaries inside them
+    assert gr.cell[b0 - 1] == gr.cell[b0]  # one cell spans the first
+    assert gr.cell[b1 - 1] != gr.cell[b1] and gr.cell[b1 - 2] == gr.cell[b1 - 1]  # another ends exactly on the second
+    assert b1 == gr.n - 1 and (gr.cell == gr.cell[-1]).sum() == 1  # the last row, alone in its tile, is its own cell
+    assert not gr.counts[3, b0:b0 + T].any()  # a replicate whose second tile of a two-tile chunk is all zeros
+    for c in (None, gr.counts):
+        got = ob.nopo_sums(gr.y, gr.cell, gr.n_cells, w=gr.w, counts=c)
+        reps = 1 if c is None else len(c)
+        assert got[0].shape == got[1].shape == (reps, gr.n_cells)
+        want = stack(R.long_sums(gr, None if c is None else c[r]) for r in range(reps))
+        want_abs = stack(R.long_sums(gr, None if c is None else c[r], absolute=True) for r in range(reps))
+        check_sums(gr, got, want, want_abs, f"long chunks, {'point' if c is None else '65 replicates'}")
+        # every product and every partial sum of a cell is exact in f64 (the host test proves it from the arrays), so
+        # no order of the sum rounds at all
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+def test_cell_pass_counts_and_batches(ob, N):
+    """257 rows, 131 replicates whose counts hold every byte value in every byte lane of a count word, against
+    sums_exact; in one batch and in three (hk_batch = 1, the last ragged), bitwise equal; and with unused cell ids
+    between the used ones and past the highest."""
+    gr = R.byte_group()
+    want = stack(R.sums_exact(gr.y, gr.w, gr.cell, gr.n_cells, c) for c in gr.counts)
+    want_abs = stack(R.sums_exact(np.abs(gr.y), gr.w, gr.cell, gr.n_cells, c) for c in gr.counts)
+    got = ob.nopo_sums(gr.y, gr.cell, gr.n_cells, w=gr.w, counts=gr.counts)
+    check_sums(gr, got, want, want_abs, "bytes, one batch")
+    assert np.array_equal(got[0], want[0])  # dyadic weights: N is exact in any order
+    with N.option("hk_batch", 1):
+        forced = ob.nopo_sums(gr.y, gr.cell, gr.n_cells, w=gr.w, counts=gr.counts)
+    check_sums(gr, forced, want, want_abs, "bytes, three batches")
+    assert forced[0].tobytes() == got[0].tobytes() and forced[1].tobytes() == got[1].tobytes()
+    # ids 3 x + 2 of 3 n_cells + 5: unused ids before, between and past the used ones
+    wide, n_wide = 3 * gr.cell + 2, 3 * gr.n_cells + 5
+    used = np.zeros(n_wide, dtype=bool)
+    used[3 * np.arange(gr.n_cells) + 2] = True
+    for batch in (None, 1):  # the default batch, and three
+        with N.option("hk_batch", batch):
+            spread = ob.nopo_sums(gr.y, wide, n_wide, w=gr.w, counts=gr.counts)
+        for i in (0, 1):
+            assert spread[i].shape == (len(gr.counts), n_wide)
+            assert spread[i][:, used].tobytes() == got[i].tobytes(), (batch, i)
+            assert np.all(spread[i][:, ~used] == 0.0) and not np.signbit(spread[i][:, ~used]).any(), (batch, i)
+
+
+def chunk_table(N, pr):
+    table = (C.c_uint32 * 96)()
+    n = C.c_int32()
+    N.check(N.lib().ob_debug_chunks(N.lib().ob_prepared_panel(pr._h), table, 32, C.byref(n)))
+    return [tuple(table[3 * i:3 * i + 3]) for i in range(n.value)]
+
+
+EXACT_CASES = [("main", False), ("main", True), ("zero_w", True), ("offset", False), ("offset", True),
+               ("singletons", False), ("singletons", True)] + [(e, wt) for e in R.EDGE_NAMES for wt in (False, True)]
+
+
+@pytest.mark.parametrize("name,weighted", EXACT_CASES, ids=[f"{n}{'_weighted' if wt else ''}" for n, wt in EXACT_CASES])
+def test_rows_match_exact(ob, O, N, name, weighted):
+    """The point row and 67 replicates against the Fraction reference (nopo_ref.terms_exact): the reference is exact,
+    so Panel.tol bounds the device alone. Unweighted zero_w is unweighted main."""
+    p = R.panel(name, weighted)
+    point, okp, rows, ok, sup = R.boot_exact(O, name, weighted)
+    assert okp and ok.all()
+    dyadic = not (name == "offset" and weighted)
+    with p.builder(ob).prepare_nopo() as pr:
+        got_point = pr.point_row()
+        got, got_ok = pr.boot(0, R.REPS)
+        info = pr.nopo_info()
+        chunks = chunk_table(N, pr)
+    for what, g, gok, w, wok in (("point", got_point, 1, point, okp), ("replicates", got, got_ok, rows, ok)):
+        g, w = np.atleast_2d(g), np.atleast_2d(w)
+        assert np.array_equal(np.atleast_1d(gok).astype(bool), np.atleast_1d(wok).astype(bool)), what
+        dev = np.abs(g - w)
+        print(f"{name} weighted={weighted} {what}: largest deviation {dev.max():.3e} (bound {p.tol:.3e})")
+        assert np.all(dev <= p.tol), (what, np.argwhere(dev > p.tol)[:4])
+        assert np.array_equal(g[:, 12], w[:, 12]), what  # the support-cell count
+        if dyadic:
+            assert np.array_equal(g[:, [10, 11]], w[:, [10, 11]]), what  # the matched shares: every N is exact
+    assert np.array_equal(info["in_support"], sup[-1]) and info["n_support_cells"] == int(point[12])
+    if name not in R.EDGE_NAMES:  # (the edges' cells are large) the support is decided again in the replicates
+        assert any(not np.array_equal(s, sup[-1]) for s in sup[:-1])
+    if name == "zero_w":
+        (na, _), (nb, _) = p.fractions()
+        by_weight = np.array([a > 0 and b > 0 for a, b in zip(na, nb)])
+        assert np.array_equal(info["in_support"].astype(bool), by_weight)
+        x = R.ZERO_A_CELL  # rows, but no weight and no mean
+        assert np.isnan(info["mean_a"][x]) and info["w_a"][x] == 0.0 and info["n_cell_a"][x] == 20
+        assert not info["in_support"][x] and info["w_b"][x] > 0.0 and np.isfinite(info["mean_b"][x])
+        assert got_point[3] == 0.0 and not np.signbit(got_point[3])  # N_A^out == 0.0 with rows present
+        zero = rows[:, 3] == 0.0
+        assert zero.any() and np.array_equal(got[:, 3] == 0.0, zero)
+    if name in R.EDGE_NAMES:
+        n_a, n_b = R.EDGE_NAMES[name]
+        ends = set((np.flatnonzero(np.diff(p.cell[1])) + 1).tolist()) | {n_b}
+        b_chunks = [c for c in chunks if c[0] == 1]
+        assert {c[2] * R.TILE for c in b_chunks if c[2] * R.TILE <= n_b} <= ends  # a fragment ends on each boundary
+        assert len(b_chunks) == (n_b + R.TILE - 1) // R.TILE and (n_b < 512 or (1, 0, 1) in b_chunks)
+        if n_a == 1:  # A's single row is drawn once in every replicate: ybar_A is its y, exactly
+            assert got_point[5] == p.y[0][0] and np.all(got[:, 5] == p.y[0][0])
+
+
 @pytest.mark.parametrize("name,weighted", CASES, ids=IDS)
 def test_rows_match_ref(ob, O, name, weighted):
     p = R.panel(name, weighted)
@@ -87,7 +226,8 @@ def test_rows_match_ref(ob, O, name, weighted):
         assert got_point[4] == 0.0 and np.all(got[keep, 4] == 0.0) and np.all(got[keep, 11] == 1.0)
 
 
-@pytest.mark.parametrize("name,weighted", [("main", True), ("tiny", False)], ids=["main_weighted", "tiny"])
+@pytest.mark.parametrize("name,weighted", [("main", True), ("tiny", False), ("zero_w", True), ("singletons", True)],
+                         ids=["main_weighted", "tiny", "zero_w", "singletons"])
 def test_bitwise_properties(ob, N, name, weighted):
     p = R.panel(name, weighted)
     with p.builder(ob).prepare_nopo() as pr:
